@@ -6,8 +6,8 @@ BASELINE metric: "LM iterations/sec + views calibrated/sec, 200-view synthetic P
   --config C4 (default)  configs[3]: synthetic 1000-scene batch, 200 views x 500 obs/view each, every scene its own seed.
                          One batch of 1000 scenes PER GPU (weak scaling: rank r solves seeds r*1000 .. r*1000+999); a "step" is
                          one pass of the hot path over that batch: every scene solved from its initial guess to Ceres-style
-                         termination (ptz_ba_batch_solve).  The line also carries configs[1] (ONE 200 x 500 rig alone, `c2_single_rig`,
-                         the configuration the 10 k it/s target is quoted on) with its per-pass critical path, configs[4]
+                         termination (ptz_ba_batch_solve).  With --full the line also carries configs[1] (ONE 200 x 500 rig alone,
+                         `c2_single_rig`, the configuration the 10 k it/s target is quoted on) with its per-pass critical path, configs[4]
                          (`c5_reloc`, a bounded sample of the relocalization queries) and the PTZ-IBA orchestration on one rig.
   --config C2            configs[1] as the headline: one rig per GPU, a step = one solve of it.
   --config C5            configs[4] as the headline: 100 000 relocalization queries x 128 matches per GPU, a step = one
@@ -17,6 +17,12 @@ BASELINE metric: "LM iterations/sec + views calibrated/sec, 200-view synthetic P
                          configs[3]: 1000 scenes over the node), dealt to the ranks in contiguous blocks.
 The line starts with a small `headline` object (the C4 figure, the single-rig figure the 10 k it/s target is quoted on, queries/s,
 views/s), and `config` repeats those scalars, so that a truncated copy of the line still shows them.
+
+A plain run sets up, warms up, times --steps steps and prints the line: headline, roofline and per-family figures of the timed
+steps themselves.  Everything that takes work of its own (the library-default pipeline, the measured peaks, the single-rig /
+relocalization / PTZ-IBA legs, the parity check, the CPU baselines) runs only with --full.  --dump-outputs DIR writes what the
+last timed step computed as .npy files (float64, a fixed seeded sample of rows where an array would not fit in 64 MB), so that two
+builds can be compared output for output on identical inputs.
 
 Inputs (observations, structure, initial state) are resident in HBM before the timed region.  N > 1: one process per GPU
 (torch.distributed, backend nccl = RCCL), every rank owns its own scenes, no data-path collective; the timed region is
@@ -422,6 +428,32 @@ def reloc_cpu_baseline_leg(pkg, n_sample=6000, budget_s=10.0):
             "sample": a["sample"] + f"; numeric-diff + QR oracle, whole queries over {a['cores']} threads", "one_thread": out.get("one_thread")}
 
 
+# ----------------------------------------------------------------------------------------------------------------- outputs
+def summary_rows(pkg, summ):
+    """LM summaries (dicts with the fields of ptz_lm_summary) -> float64 [n, 12], columns in the struct's field order."""
+    import numpy as np
+    names = [k for k, _ in pkg.api.LmSummary._fields_]
+    return np.array([[s[k] for k in names] for s in summ], dtype=np.float64).reshape(len(summ), len(names))
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy in float64, 62 MB in all (the .npy headers stay within 64 MB).  Smallest
+    first, each array takes an equal share of what is left; one over its share is replaced by a fixed seeded sample of its rows
+    (in row order: the same rows for the same shape on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    left = 62_000_000
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].nbytes)):
+        a = arrays[name]
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            rows = np.random.default_rng(0).choice(a.shape[0], size=share // (a.nbytes // a.shape[0]), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 # ------------------------------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -445,9 +477,15 @@ def main():
     ap.add_argument("--dump-gathered", default=None,
                     help="rank 0 writes the gathered result blocks (one row per scene of the whole job: 15 doubles per view, then termination, "
                          "iterations, final cost) to this .npy file -- what the multi-rank test compares with solo solves")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the library-default pipeline, the measured peaks, the single-rig / reloc / "
+                         "orchestration legs, the parity check and the CPU baselines")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed steps: no single-rig / reloc / orchestration / CPU legs, so that a rocprofv3 --stats "
-                         "summary of this command averages over the timed launch shape alone")
+                    help="only the timed steps, even with --full (what a run without --full does anyway)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float64): C4 / C2 cameras [views, 15], "
+                         "rays [rays, 3] and LM summaries [scenes, 12] of all its scenes in order; C5 cameras [queries, 15], "
+                         "summaries [queries, 12] and accepted [queries]; 64 MB in all (a fixed seeded sample of rows beyond that)")
     args = ap.parse_args()
 
     import numpy as np
@@ -477,7 +515,7 @@ def main():
                                      cache_dir=args.scene_cache or None)
         scenes = [base[i % distinct] for i in range(n_scenes)]
     rb_c5 = pkg.synth.make_reloc_queries(args.queries, 128, seed_id=1 + rank, factor_type=0) if args.config == "C5" else None
-    extras = not args.headline_only
+    extras = args.full and not args.headline_only
     c2_scene = None
     iba_scenes, iba_tables = [], []
     if extras and rank == 0:
@@ -526,6 +564,10 @@ def main():
         lm_steps = lm_steps_launch * args.steps
         units_done = float(args.queries * args.steps)
         summ = []
+        if args.dump_outputs and rank == 0:
+            rec = np.frombuffer(rr.d_sum.cpu().numpy().tobytes(), dtype=np.dtype(pkg.api.LmSummary))
+            dump_outputs(args.dump_outputs, {"cameras": rr.d_ccur.cpu().numpy(), "summaries": summary_rows(pkg, rec),
+                                             "accepted": rr.d_acc.cpu().numpy()})
     else:
         batch = pkg.api.BaBatch(scenes, device_id=local_rank)
         batch.set_state()  # observations, structure and the initial state are now resident in HBM
@@ -547,6 +589,10 @@ def main():
         elapsed = time.perf_counter() - t0
         prof = batch.get_profile()
         batch.set_profiling(False)
+        if args.dump_outputs and rank == 0:
+            cams, rays = batch.get_state()
+            dump_outputs(args.dump_outputs, {"cameras": np.concatenate(cams), "rays": np.concatenate(rays),
+                                             "summaries": summary_rows(pkg, summ)})
         units_done = float(n_scenes * args.views * args.steps)
         # results to rank 0: 15 doubles per view and a summary triple per scene (the only collective of the path)
         if dist is not None:

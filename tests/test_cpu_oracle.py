@@ -30,21 +30,22 @@ def test_tracks_match_reference_golden(orc, name):
 
 
 def test_tracks_against_live_reference_build(orc):
-    """Where oracle/_ref exists (built from /root/reference's own headers) compare on fresh random graphs."""
-    if not orc.ref_tracks_available():
-        pytest.skip("oracle/_ref/ref_tracks not built (reference tree absent)")
-    rng = np.random.default_rng(7)
-    for trial in range(20):
-        n_img = int(rng.integers(4, 20))
-        pairs = []
-        for _ in range(int(rng.integers(1, 60))):
-            i, j = rng.choice(n_img, 2, replace=False)
-            k = int(rng.integers(0, 40))
-            # mostly consistent matches (feature id = track id) plus noise
-            ms = [(int(t), int(t if rng.random() < 0.9 else rng.integers(0, 50))) for t in rng.integers(0, 50, k)]
-            pairs.append((int(i), int(j), ms))
-        ml = int(rng.integers(2, 5))
-        assert orc.tracks_build(pairs, ml) == orc.ref_tracks_build(pairs, ml)
+    """20 seeded random graphs against the reference's track builder: its outputs stored in tests/golden/ (gen_tracks_random.py),
+    and, where oracle/_ref exists (built from the reference tree's own headers), the live build as well."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_tracks_random", os.path.join(GOLD, "gen_tracks_random.py"))
+    gtr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gtr)
+    cases = json.load(open(os.path.join(GOLD, "tracks_reference_random.json")))["cases"]
+    graphs = gtr.graphs()
+    assert len(cases) == len(graphs) == 20
+    live = orc.ref_tracks_available()
+    for (pairs, ml), case in zip(graphs, cases):
+        assert gtr.graph_hash(pairs, ml) == case["graph_sha256"] and ml == case["min_track_length"]
+        want = {int(t): {int(i): f for i, f in v.items()} for t, v in case["tracks"].items()}
+        assert orc.tracks_build(pairs, ml) == want
+        if live:
+            assert orc.ref_tracks_build(pairs, ml) == want
 
 
 def test_tracks_empty_input(orc):

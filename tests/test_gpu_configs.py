@@ -237,6 +237,49 @@ def test_nccl_backend_world_size_one(pkg, tmp_path):
     assert d["parallel"]["gather_ms"] is not None and d["parallel"]["ranks_ms_per_step"] is not None
 
 
+@pytest.mark.parametrize("config", ["C4", "C5"])
+def test_bench_dump_outputs_hold_the_last_timed_step(pkg, tmp_path, config):
+    """`bench.py --dump-outputs DIR`, a plain one-process run: the files hold what the timed path computed -- a C4-shaped batch's
+    cameras, rays and LM summaries with the bits of solo solves of its scenes, C5's cameras, summaries and gate decisions with
+    the bits of the batch API on the same queries -- in float64, within 64 MB; `value` x `ms_per_step` is one step's work."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    steps = 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out)]
+    if config == "C4":
+        n_scenes, n_views, n_obs = 3, 20, 100
+        cmd += ["--scenes", str(n_scenes), "--views", str(n_views), "--obs", str(n_obs), "--scene-cache", ""]
+    else:
+        nq = 2000
+        cmd += ["--config", "C5", "--queries", str(nq)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["ms_per_step"] > 0
+    got = {f[:-len(".npy")]: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64e6
+    fields = [k for k, _ in pkg.api.LmSummary._fields_]
+    if config == "C4":
+        solo = [pkg.api.ba_solve(pkg.synth.make_scene(i, n_views, n_obs)) for i in range(n_scenes)]
+        assert sorted(got) == ["cameras", "rays", "summaries"]
+        assert np.array_equal(got["cameras"], np.concatenate([s[0] for s in solo]))
+        assert np.array_equal(got["rays"], np.concatenate([s[1] for s in solo]))
+        assert np.array_equal(got["summaries"], np.array([[s[2][k] for k in fields] for s in solo]))
+        its = sum(s[2]["num_lm_steps"] for s in solo)
+    else:
+        cam, summ, acc, _ = pkg.api.krt_solve_batch(pkg.synth.make_reloc_queries(nq, 128, seed_id=1, factor_type=0))
+        assert sorted(got) == ["accepted", "cameras", "summaries"]
+        assert np.array_equal(got["cameras"], cam) and np.array_equal(got["accepted"], acc)
+        assert np.array_equal(got["summaries"], np.array([[s[k] for k in fields] for s in summ]))
+        its = sum(s["num_lm_steps"] for s in summ)
+    assert abs(d["value"] * 1e-3 * d["ms_per_step"] - its) < 1e-6 * its
+
+
 @pytest.mark.parametrize("scaling,scenes,want_total,want_rank0", [("weak", 3, 6, 3), ("strong", 5, 5, 3)])
 def test_two_ranks_on_the_real_kernels(pkg, tmp_path, scaling, scenes, want_total, want_rank0):
     """N > 1 on the real kernels without an 8-GPU node: bench.py under torch.distributed.run with TWO ranks that share device 0

@@ -5,7 +5,7 @@
 # usage: tools/probes/probe_r5_evidence.sh <tag> [nobench] [nopmc]
 R=$GRAFT_REPO_ROOT; T=${1:-r5_evidence}; O=$R/gpurun_out/$T; mkdir -p $O; cd $R
 if [ "${2:-}" != "nobench" ]; then
-  timeout 1800 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+  timeout 1800 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
   tail -c 400 $O/bench.err
 fi
 cd /tmp && export TMPDIR=/tmp
