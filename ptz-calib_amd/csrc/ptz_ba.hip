@@ -640,13 +640,7 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
   // batch is solved once, as every bundle adjustment of the incremental pipeline is)
   const bool graph = b->use_graph && !b->profiling && !b->lookahead && b->d.chol.tmask != nullptr && b->n_solves > 0;
   ++b->n_solves;
-  // Passes per replayed graph.  Between two graph launches on a stream the device idles ~8.4 us (kernel trace of the one-rig solve:
-  // the six kernels of a pass abut, the next pass's first kernel starts 8.4-8.8 us behind the last) -- 4 % of a one-rig pass.  Launch
-  // shapes of a few scenes therefore replay graphs of SEVERAL passes (PTZ_BA_GRAPH_PASSES; the passes past a scene's end are the empty
-  // launches they always were: at most that many more of them per solve).
-  static const int graph_passes_few = [] { const char* e = getenv("PTZ_BA_GRAPH_PASSES"); return e ? std::max(1, std::min(16, atoi(e))) : 1; }();
-  auto graph_passes = [&](const PassShape& sh) { return sh.slots <= 8 ? graph_passes_few : 1; };
-  auto graph_of = [&](int g, int si) -> hipGraphExec_t {  // built on first use: one node per launch, a linear chain
+  auto graph_of = [&](int g, int si) -> hipGraphExec_t {  // built on first use: one pass, one node per launch, a linear chain
     if (b->pass_graph[g][si]) return b->pass_graph[g][si];
     GraphRecorder rec;
     bool ok = hipGraphCreate(&rec.graph, 0) == hipSuccess;
@@ -655,7 +649,7 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
       g_recorder = &rec;
       PassShape shg = b->shapes[si];
       if (si == 0) shg.slots = b->group_count[g];
-      for (int rep = 0; rep < graph_passes(shg); ++rep) enqueue_pass<TYPE>(b, b->dg[g], shg);
+      enqueue_pass<TYPE>(b, b->dg[g], shg);
       g_recorder = nullptr;
       ok = rec.ok && hipGraphInstantiate(&b->pass_graph[g][si], rec.graph, nullptr, nullptr, 0) == hipSuccess;
     }
@@ -686,11 +680,10 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
       if (enq[g] - std::max(__atomic_load_n(&b->h_ctl[4 * g], __ATOMIC_ACQUIRE), credit[g]) >= b->ahead) continue;
       const double te0 = now();
       b->stream = b->streams[g];
-      const bool last = false;
       // launch shape: the smallest one that covers the scenes last reported active (the count only ever decreases, so a stale
       // value is an upper bound); full size while more than the largest compacted shape are
       int si = 0;
-      if (b->compaction && !last) {
+      if (b->compaction) {
         const int cnt = __atomic_load_n(&b->h_ctl[4 * g + 2], __ATOMIC_ACQUIRE);
         for (int k = 1; k < (int)b->shapes.size(); ++k)
           if (b->shapes[k].slots >= cnt && b->shapes[k].slots < b->group_count[g]) { si = k; break; }
@@ -700,12 +693,11 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
       if (dbg) { if (shape_used.size() < b->shapes.size()) shape_used.resize(b->shapes.size(), 0); ++shape_used[si]; }
       // (one or two rigs: the passes are enqueued as they are -- a pass is ~200 us of device time against ~25 us of host time for its
       //  six launches, and between two REPLAYED graphs the device idles 8.4 us: 5.20 -> 5.09 ms per 25-iteration solve of the C2 rig,
-      //  A/B on one box; PTZ_BA_GRAPH_FEW=1 replays graphs there too)
-      static const bool graph_few = [] { const char* e = getenv("PTZ_BA_GRAPH_FEW"); return e && atoi(e) != 0; }();
-      hipGraphExec_t ge = (!last && graph && b->use_graph && (sh.slots > 2 || graph_few)) ? graph_of(g, si) : nullptr;
+      //  A/B on one box)
+      hipGraphExec_t ge = (graph && b->use_graph && sh.slots > 2) ? graph_of(g, si) : nullptr;
       if (ge) PTZ_HIP_TRY(hipGraphLaunch(ge, b->streams[g]));
       else { b->stream = b->streams[g]; enqueue_pass<TYPE>(b, b->dg[g], sh); }
-      enq[g] += ge ? graph_passes(sh) : 1;
+      ++enq[g];
       progressed = true;
       t_enq += now() - te0;
     }
@@ -2103,12 +2095,6 @@ static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_
   if (const char* e = getenv("PTZ_BA_AHEAD")) b->ahead = std::max(1, atoi(e));
   if (const char* e = getenv("PTZ_BA_DEBUG_STALL")) b->d.debug_stall = std::max(0, atoi(e));
   if (const char* e = getenv("PTZ_BA_DEBUG_CHAIN_SPIN")) b->d.chol.chain_spin_limit = std::max(0, atoi(e));  // tests: hand-overs that time out
-  b->d.chol.chain_ready_whole = 1;  // (Dev is zero-filled at creation)
-  b->d.chol.chain_pair = 1;
-  b->d.chol.chain_w0 = 1;
-  if (const char* e = getenv("PTZ_BA_CHAIN_W0")) b->d.chol.chain_w0 = atoi(e) != 0;
-  if (const char* e = getenv("PTZ_BA_CHAIN_PAIR")) b->d.chol.chain_pair = atoi(e) != 0;
-  if (const char* e = getenv("PTZ_BA_CHAIN_READY_WHOLE")) b->d.chol.chain_ready_whole = atoi(e) != 0;       // A/B: 0 = four block rounds also for finished columns
   if (const char* e = getenv("PTZ_BA_GRAPH")) b->use_graph = atoi(e) != 0;
   b->ctl_groups = std::max(1, std::min(b->n_group, n));
   if (b->alloc(&b->d_ctl, (size_t)4 * b->ctl_groups) != PTZ_OK ||

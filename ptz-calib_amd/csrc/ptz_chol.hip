@@ -56,23 +56,6 @@ __device__ __forceinline__ double rsqrt_nr(double d)
   return y;
 }
 
-// The same to working precision with ONE cubic step: y = y0 (1 + e / 2 + 3 e^2 / 8), e = 1 - d y0^2 -- five dependent operations
-// instead of eight; and the reciprocal likewise, r = r0 (1 + e + e^2), e = 1 - d r0, three.  For the pivot chain of the diagonal
-// tile, where every dependent operation is paid 64 times per tile.
-__device__ __forceinline__ double rsqrt_cubic(double d)
-{
-  const double y0 = __builtin_amdgcn_rsq(d);
-  const double t = d * y0;
-  const double e = fma(-t, y0, 1.0);
-  const double p = fma(0.375, e, 0.5);
-  return fma(y0, e * p, y0);
-}
-__device__ __forceinline__ double rcp_cubic(double d)
-{
-  const double r0 = __builtin_amdgcn_rcp(d);
-  const double e = fma(-d, r0, 1.0);
-  return fma(r0, fma(e, e, e), r0);
-}
 
 // coalesced 64x64 tile copy global (row stride ld) -> LDS (row stride LD); nthreads * 16 B per pass
 template <int NTHREADS, bool NEGATE>
@@ -158,8 +141,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)
 // FP64 FMA per updated column).  Everything else happens beside the chain: before a sweep the four waves bring its 16
 // columns up to date on the matrix cores (one 16-row block each, C -= X X^T over the finished column blocks); during a
 // sweep wave 1 inverts the previous 16 x 16 diagonal block (for the MFMA triangular solves of chol_trsm and the
-// back-substitution) and wave 2 stores the previous column block of L.  (That is the batch path's form, diag_factor_tile<false>;
-// the chain kernels' form, <true>, is described in front of it.)
+// back-substitution) and wave 2 stores the previous column block of L.  (That is the batch path's form, diag_factor_tile; the
+// one-launch kernels' form, diag_factor_tile_w0, is described in front of it.)
 // ---- the same sweep with DPP broadcasts (round 5; chol_chain_kernel) ----------------------------------------------------------
 // What a pivot of the sweep below pays for is the way a scalar of the pivot column reaches the other lanes: v_readlane into a
 // scalar register and from there into the multiply-add -- 30 cycles per dependent step (tools/probes/hip/dep_probe.hip: a dependent
@@ -301,7 +284,7 @@ __device__ __forceinline__ void diag_sweep_block(double* As, int b, int kbase, i
   if constexpr (DPP) {
     double ar[DB];
     {
-      // (the image's diagonal blocks are zero above the diagonal: the writers of diag_factor_tile<true> and of its callers see to it)
+      // (the image's diagonal blocks are zero above the diagonal: the callers of diag_factor_tile_w0 see to it)
       const double* src = As + (DB * b + (lane & (DB - 1))) * LD + DB * b;
 #pragma unroll
       for (int q = 0; q < DB; q += 2) {
@@ -317,11 +300,7 @@ __device__ __forceinline__ void diag_sweep_block(double* As, int b, int kbase, i
 #ifdef PTZ_CHOL_TIMELINE
     if (threadIdx.x == 0 && flag_dbg_row) flag_dbg_row[0] = wall_clock64();
 #endif
-#ifndef PTZ_TP_NO_SWEEP  // (tools/probes/hip/tile_probe.hip: the phases' costs by knock-out)
     dpp_sweep<0>(ar, a, ird, n - (kbase + DB * b), dmin, bad);
-#else
-    for (int j = 0; j < DB; ++j) ird[j] = 1.0;
-#endif
 #ifdef PTZ_CHOL_TIMELINE
     if (threadIdx.x == 0 && flag_dbg_row) flag_dbg_row[1] = wall_clock64();
 #endif
@@ -347,39 +326,8 @@ __device__ __forceinline__ void diag_sweep_block(double* As, int b, int kbase, i
   // step, the updates of the columns further right fill its latency.  The scheduling fences keep the compiler from
   // deferring those updates (it otherwise turns the sweep left-looking: a dependent chain of j products in front of
   // every pivot).
-#ifndef PTZ_SWEEP_VARIANT
-#define PTZ_SWEEP_VARIANT 0
-#endif
-#if PTZ_SWEEP_VARIANT == 2
-  // The chain d_j -> d_{j+1} through the RECIPROCAL of the pivot only: with the unscaled column u = A[:, j] and w = u / d_j the
-  // update is A[r][q] -= u_r w_q, so the next pivot waits for rcp + 3 + 2 operations; the column of L, u / sqrt(d_j), and
-  // 1 / L_jj for the block inverses are finished beside the chain.
   double d = readlane_f64(a[0], 0);
-#pragma unroll
-  for (int j = 0; j < DB; ++j) {
-    const bool live = (kbase + DB * b + j) < n;
-    dmin = fmin(dmin, live ? d : 1.0);  // NaN pivots: fmin keeps the other operand, caught by `bad`
-    bad |= (d != d) && live;
-    const double dj = d;
-    const double w = a[j] * rcp_cubic(dj);
-    if (j + 1 < DB) {
-      a[j + 1] = fma(-a[j], readlane_f64(w, j + 1), a[j + 1]);
-      d = readlane_f64(a[j + 1], j + 1);
-    }
-#pragma unroll
-    for (int q = j + 2; q < DB; ++q) a[q] = fma(-a[j], readlane_f64(w, q), a[q]);  // A[r][q] -= u_r u_q / d
-    ird[j] = rsqrt_nr(dj);
-    a[j] = a[j] * ird[j];  // lane j: sqrt(d); lanes below: L[r][j]; lanes above (diagonal block): 0
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#else
-#if PTZ_SWEEP_VARIANT == 1
-#define PTZ_SWEEP_RSQRT rsqrt_cubic
-#else
-#define PTZ_SWEEP_RSQRT rsqrt_nr
-#endif
-  double d = readlane_f64(a[0], 0);
-  ird[0] = PTZ_SWEEP_RSQRT(d);
+  ird[0] = rsqrt_nr(d);
 #pragma unroll
   for (int j = 0; j < DB; ++j) {
     const bool live = (kbase + DB * b + j) < n;
@@ -390,13 +338,12 @@ __device__ __forceinline__ void diag_sweep_block(double* As, int b, int kbase, i
     if (j + 1 < DB) {
       a[j + 1] -= l * readlane_f64(l, j + 1);
       d = readlane_f64(a[j + 1], j + 1);
-      ird[j + 1] = PTZ_SWEEP_RSQRT(d);
+      ird[j + 1] = rsqrt_nr(d);
     }
 #pragma unroll
     for (int q = j + 2; q < DB; ++q) a[q] -= l * readlane_f64(l, q);  // A[r][q] -= L[r][j] L[q][j]
     __builtin_amdgcn_sched_barrier(0);
   }
-#endif
   }
   if (lane == 0 && (!DPP || b == 0)) {  // (DPP: only block 0's inverse is still computed from the image)
 #pragma unroll
@@ -500,16 +447,7 @@ __device__ long long dft_tl[64][12];
 #else
 #define DFT_STAMP(i) do { } while (0)
 #endif
-// Fk (chol_chain_kernel only): four flags of this tile; flag b is raised with `gen` once column block b of L_kk (its rows below the
-// diagonal block) and the inverse of its diagonal block are in global memory.
-// DPP (the kernels whose critical path this is: chol_chain_kernel, chol_col_step_kernel): the sweep itself leaves the inverses of
-// blocks 1..3 (diag_sweep_block), so a block is published one phase after its sweep -- the idle fourth wave stores it while the
-// others bring the next column block up to date, and fences + flags it during the next sweep; only block 0's inverse is still a
-// wave's own work (beside sweep 1).  The last block's inverse and flag leave from the sweeping wave's registers.  A consumer that
-// chases this tile is then one block round behind the end of the last sweep, not two and the inverse.
-template <bool DPP = false>
-__device__ __forceinline__ void diag_factor_tile(double* As, double (*Dv)[DB * LDD], int* okflag_p, const CholBatch& cb, int sys, int k, int n,
-                                                 int* Fk = nullptr, int gen = 0)
+__device__ __forceinline__ void diag_factor_tile(double* As, double (*Dv)[DB * LDD], const CholBatch& cb, int sys, int k, int n)
 {
   const int np = cb.np, nt = np / NB;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -518,32 +456,12 @@ __device__ __forceinline__ void diag_factor_tile(double* As, double (*Dv)[DB * L
   double* Dg = cb.Dinv + ((size_t)sys * nt + k) * 4 * (DB * DB);
   double dmin = 1.0;
   bool bad = false;
-  if (DPP && Fk && threadIdx.x == 0) *okflag_p = 0;  // block 0 has two publishers (its rows: wave 3, its inverse: wave 1): the second one raises the flag
-  DFT_STAMP(0);
 #pragma unroll 1
   for (int b = 0; b < NB / DB; ++b) {
-    // C(ri, c) -= X(ri, m) X(c, m)^T on the matrix cores, one wave; `diag`: the finished diagonal block goes back with zeros above its diagonal
-    auto rank16 = [&](int ri, int c, int m, bool diag) {
-      double* C = As + (DB * ri) * LD + DB * c;
-      const double* Xi = As + (DB * ri) * LD + DB * m;
-      const double* Xj = As + (DB * c) * LD + DB * m;
-      d4 acc;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = C[(fq + 4 * i) * LD + fr];
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-Xi[fr * LD + 4 * ks + fq], Xj[fr * LD + 4 * ks + fq], acc, 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) C[(fq + 4 * i) * LD + fr] = (diag && fr > fq + 4 * i) ? 0.0 : acc[i];
-    };
     if (b > 0) {
       // bring column block b up to date: wave w takes the 16-row block ri = b + w:  C(ri, b) -= sum_{m < b} X(ri, m) X(b, m)^T
-      // (DPP: only m = b - 1 is left to do here -- the earlier column blocks' shares were applied beside the sweeps, see below; the
-      //  same products added in the same order, the block in LDS between them)
       const int ri = b + w;
       if (ri < NB / DB) {
-        if constexpr (DPP) rank16(ri, b, b - 1, ri == b);
-        else {
         double* C = As + (DB * ri) * LD + DB * b;
         d4 acc;
 #pragma unroll
@@ -557,57 +475,16 @@ __device__ __forceinline__ void diag_factor_tile(double* As, double (*Dv)[DB * L
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) C[(fq + 4 * i) * LD + fr] = acc[i];
-        }
-      }
-      if (DPP && w == 3) {  // (never has a row block to update) column block b - 1 and, behind block 0, its inverse on their way to global memory
-        diag_store_block(As, b - 1, Lg, Fk != nullptr);
-        if (b - 1 > 0) {
-          const double* dv = Dv[b - 1];
-          double* dg = Dg + (b - 1) * (DB * DB);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) {
-            if (Fk) st_sc1(&dg[(4 * p + fq) * DB + fr], dv[(4 * p + fq) * LDD + fr]);
-            else dg[(4 * p + fq) * DB + fr] = dv[(4 * p + fq) * LDD + fr];
-          }
-        }
       }
       __syncthreads();
     }
-    DFT_STAMP(1 + 2 * b);  // column block b is up to date
-    if constexpr (DPP) {
-      if (w == 0) {
-        const bool last = b == NB / DB - 1;
-        diag_sweep_block<true>(As, b, k * NB, n, dmin, bad, Dv[b], last ? Dg + b * (DB * DB) : nullptr, (last && Fk) ? &Fk[b] : nullptr, gen);
-      }
-      else if (w == 1 && b == 1) {
-        diag_block_inverse(As, 0, Dg, Dv[0], Fk != nullptr);
-        if (Fk) {
-          drain_stores();  // (write-through stores: once this wave's are acknowledged, the bytes are where every XCD reads them)
-          if (lane == 0 && atomicAdd(okflag_p, 1) == 1) __hip_atomic_store(&Fk[0], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      else if (w == 3 && b > 0 && Fk) {
-        drain_stores();  // this wave stored the block (and, behind block 0, its inverse) one phase ago, write-through
-        if (lane == 0 && (b - 1 > 0 || atomicAdd(okflag_p, 1) == 1)) __hip_atomic_store(&Fk[b - 1], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      else if (w == 2 && b > 0) {
-        // beside the sweep of column block b: the share of column block b - 1 in the column blocks BEHIND b, which the chain does
-        // not need yet (right-looking for them, so that what stands between two sweeps is one rank-16 update, not b of them)
-        for (int c = b + 1; c < NB / DB; ++c)
-          for (int ri = c; ri < NB / DB; ++ri) rank16(ri, c, b - 1, false);
-      }
-    }
-    else {
-      if (w == 0) diag_sweep_block<false>(As, b, k * NB, n, dmin, bad);
-      else if (w == 1 && b > 0) diag_block_inverse(As, b - 1, Dg + (b - 1) * (DB * DB), Dv[b - 1]);
-      else if (w == 2 && b > 0) diag_store_block(As, b - 1, Lg);
-    }
-    if (w == 0) DFT_STAMP(2 + 2 * b);  // the sweep of block b is done (before the barrier)
+    if (w == 0) diag_sweep_block<false>(As, b, k * NB, n, dmin, bad);
+    else if (w == 1 && b > 0) diag_block_inverse(As, b - 1, Dg + (b - 1) * (DB * DB), Dv[b - 1]);
+    else if (w == 2 && b > 0) diag_store_block(As, b - 1, Lg);
     __syncthreads();
   }
-  DFT_STAMP(9);
   if (w == 0 && lane == 0 && (bad || !(dmin > 0.0))) atomicOr(&cb.fail[sys], 1);
-  if (!DPP && w == 1) diag_block_inverse(As, NB / DB - 1, Dg + (NB / DB - 1) * (DB * DB), Dv[NB / DB - 1]);
+  if (w == 1) diag_block_inverse(As, NB / DB - 1, Dg + (NB / DB - 1) * (DB * DB), Dv[NB / DB - 1]);
   else if (w == 2) diag_store_block(As, NB / DB - 1, Lg);
   if (cb.L && cb.Linv && k == nt - 1) {
     // the last diagonal tile has no later launch whose spare workgroup could invert it
@@ -617,14 +494,14 @@ __device__ __forceinline__ void diag_factor_tile(double* As, double (*Dv)[DB * L
 }
 
 // ---- round 6: the diagonal tile of the chain kernels with ONE wave on the chain and no barrier on it ----------------------------------
-// diag_factor_tile<true> above puts, between two sweeps, a rank-16 update spread over the four waves behind a barrier and in front of
-// another: per 16-column block 0.24 us of loads + 1.1 of pivots + 0.48 of stores + 0.56 of update (stamps, NOTES_r06 1c) -- the pivots
-// are less than half of a tile's 9.3 us.  Here wave 0 alone walks the chain: it sweeps block b, stores the panel, applies block b's
-// share to column block b + 1 itself (3 - b rank-16 products on ITS matrix core, read from and written to LDS by the same wave: LDS
-// operations of one wave complete in order, no barrier), loads and sweeps block b + 1.  Beside it, synchronised through two counters in
+// With the four waves in lock step (diag_factor_tile's form, also with the DPP sweep), a rank-16 update spread over the four waves stands
+// between two sweeps, behind a barrier and in front of another: per 16-column block 0.24 us of loads + 1.1 of pivots + 0.48 of stores
+// + 0.56 of update (stamps, NOTES_r06 1c) -- the pivots are less than half of a tile's 9.3 us.  Here wave 0 alone walks the chain: it
+// sweeps block b, stores the panel, applies block b's share to column block b + 1 itself (3 - b rank-16 products on ITS matrix core,
+// read from and written to LDS by the same wave: LDS operations of one wave complete in order, no barrier), loads and sweeps block b + 1.  Beside it, synchronised through two counters in
 // LDS that the chain never waits on while they keep up: wave 2 applies block b's share to the column blocks behind b + 1 (as before),
 // wave 3 stores the finished column blocks and the inverses to global memory and raises their flags, wave 1 inverts diagonal block 0.
-// The same products in the same order per element as diag_factor_tile<true> (and therefore as every other path): same bits.
+// The same products in the same order per element as every other path (diag_factor_tile): same bits.
 // ctl: three ints in LDS -- [0] the two publishers of block 0, [1] panels stored by wave 0, [2] blocks whose far updates wave 2 has done.
 __device__ __forceinline__ void diag_factor_tile_w0(double* As, double (*Dv)[DB * LDD], int* ctl, const CholBatch& cb, int sys, int k, int n,
                                                     int* Fk = nullptr, int gen = 0)
@@ -689,14 +566,10 @@ __device__ __forceinline__ void diag_factor_tile_w0(double* As, double (*Dv)[DB 
 #pragma unroll 1
     for (int b = 0; b < NB / DB; ++b) {
       if (b > 0) {
-#ifndef PTZ_TP_NO_HELPERS
         if (b >= 2) wait_ge(2, b - 1);  // column block b holds the shares of blocks 0 .. b - 2 (wave 2)
-#endif
-#ifndef PTZ_TP_NO_NEAR
         if (b == 1) near_update(std::integral_constant<int, 3>{}, b);
         else if (b == 2) near_update(std::integral_constant<int, 2>{}, b);
         else near_update(std::integral_constant<int, 1>{}, b);
-#endif
       }
       DFT_STAMP(1 + 2 * b);  // column block b is up to date
       const bool last = b == NB / DB - 1;
@@ -707,7 +580,6 @@ __device__ __forceinline__ void diag_factor_tile_w0(double* As, double (*Dv)[DB 
     }
     if (lane == 0 && (bad || !(dmin > 0.0))) atomicOr(&cb.fail[sys], 1);
   }
-#ifndef PTZ_TP_NO_HELPERS
   else if (w == 2) {
     for (int b = 0; b + 2 < NB / DB; ++b) {  // block b's share in the column blocks behind b + 1
       wait_ge(1, b + 1);
@@ -744,7 +616,6 @@ __device__ __forceinline__ void diag_factor_tile_w0(double* As, double (*Dv)[DB 
       if (lane == 0 && atomicAdd(&ctl[0], 1) == 1) __hip_atomic_store(&Fk[0], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#endif
   __syncthreads();
   DFT_STAMP(9);
   if (cb.L && cb.Linv && k == nt - 1) tile_inverse(As, &Dv[0][0], cb.Linv + ((size_t)sys * nt + k) * (NB * NB));  // the last diagonal tile has no later launch whose spare workgroup could invert it
@@ -781,10 +652,9 @@ __global__ __launch_bounds__(256) void chol_diag_kernel(CholBatch cb, int kk)
   const double* A = cb.A + (size_t)sys * np * np;
   __shared__ __attribute__((aligned(16))) double As[NB * LD];        // A_kk, overwritten by L_kk block column by block column
   __shared__ __attribute__((aligned(16))) double Dv[4][DB * LDD];    // L_bb^-1 of the current block, one private copy per wave
-  __shared__ int okflag;
   tile_g2s<256, false>(A + (size_t)(k * NB) * np + k * NB, np, As);
   __syncthreads();
-  diag_factor_tile(As, Dv, &okflag, cb, sys, k, n);
+  diag_factor_tile(As, Dv, cb, sys, k, n);
 }
 
 // ---- trsm: X L_kk^T = A_ik for one off-diagonal tile, blocked by 16 columns, on the matrix cores --------
@@ -938,36 +808,19 @@ __global__ __launch_bounds__(256) void chol_syrk_kernel(CholBatch cb, int k, int
     // This tile is final after this update and nobody else touches it: factor it right here instead of writing it out
     // and launching the diagonal kernel for step k + 1 (saves a launch and a tile round trip per block column).
     __shared__ __attribute__((aligned(16))) double Dv[4][DB * LDD];
-    __shared__ int okflag;
     __syncthreads();  // all waves are done reading the operand tiles
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = acc[c][i];
     __syncthreads();
-    diag_factor_tile(As, Dv, &okflag, cb, sys, ti, n);
+    diag_factor_tile(As, Dv, cb, sys, ti, n);
     return;
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) C[(size_t)(fq + 4 * i) * np + 16 * c + fr] = acc[c][i];
-}
-
-// this thread's pieces of a 64 x 64 tile (row stride ld) into registers, all loads in flight together (256 threads).  The
-// buffer is ONE vector value (not an array): it is carried around the loop back-edge, and hipcc keeps arrays that are in scratch.
-typedef double d16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ d16 tile_fetch(const double* __restrict__ g, int ld)
-{
-  d16 r;
-#pragma unroll
-  for (int p = 0; p < (NB * NB / 2) / 256; ++p) {
-    const int idx = p * 256 + threadIdx.x;
-    const int row = idx >> 5, c2 = (idx & 31) * 2;
-    const double2 v = *reinterpret_cast<const double2*>(g + (size_t)row * ld + c2);
-    r[2 * p] = v.x; r[2 * p + 1] = v.y;
-  }
-  return r;
 }
 
 // ---- one launch per step (one block column, or two that do not couple) for a FEW systems: triangular solves folded into
@@ -1145,18 +998,8 @@ __device__ __forceinline__ void trsm_block_solve2(const d4 (&acc1)[4], const d4 
 }
 
 // kmin: no system factors a block column below it in this step, so only the tiles (ti, tj), ti >= tj > kmin, can have work
-#ifdef PTZ_CHOL_STAMPS  // probe builds only: where the workgroup of a step's NEXT diagonal tile spends its time (100 MHz wall clock)
-#define CS_STAMP(i) do { if (threadIdx.x == 0) cs_t[i] = wall_clock64(); } while (0)
-#else
-#define CS_STAMP(i) do { } while (0)
-#endif
 __global__ __launch_bounds__(256) void chol_col_step_kernel(CholBatch cb, int step, int kmin)
 {
-#ifdef PTZ_CHOL_STAMPS
-  long long cs_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  cs_t[0] = wall_clock64();
-  __shared__ long long cs_q[3][16];  // per column of the list: T flags seen, block 0 seen, update done
-#endif
   int bx, slot;
   xcd_remap(bx, slot);
   const int sys = chol_system_of(cb, slot);
@@ -1244,37 +1087,25 @@ __global__ __launch_bounds__(256) void chol_col_step_kernel(CholBatch cb, int st
   // The step's columns in ascending order (a tile behind both -- a separator tile -- takes both updates, always in this
   // order).  The C tile is asked for after the first triangular solve has been issued, so that its sixteen strided loads do
   // not queue up in front of the operand tiles on the critical workgroup.
-  CS_STAMP(1);
   if (nu > 0) operands(u0);
-  CS_STAMP(2);
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[c][i] = C[(size_t)(fq + 4 * i) * np + 16 * c + fr];
   if (nu > 0) update();
-  CS_STAMP(3);
   for (int u = 1; u < nu; ++u) {  // a tile behind several columns of the step (fetching the next L_kk ahead was tried: no gain)
     __syncthreads();  // all waves are done with the operand tiles of the previous column
     operands(u == 1 ? u1 : (u == 2 ? u2 : u3));
     update();
   }
-  CS_STAMP(4);
   if (next_diag) {
     __syncthreads();  // all waves are done reading the operand tiles
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = (c == w && fr > fq + 4 * i) ? 0.0 : acc[c][i];  // (diag_factor_tile<true>: zero above the diagonal)
+      for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = (c == w && fr > fq + 4 * i) ? 0.0 : acc[c][i];  // (diag_factor_tile_w0: zero above the diagonal)
     __syncthreads();
-    CS_STAMP(5);
     diag_factor_tile_w0(As, Dv, reinterpret_cast<int*>(Dv + 4), cb, sys, ti, n);  // (no static LDS: the dynamic base stays 16-byte aligned)
-#ifdef PTZ_CHOL_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    CS_STAMP(6);
-    if (threadIdx.x == 0 && slot == 0)
-      printf("chol_col_step %d tile %d updates %d | x10 ns: prologue %lld, first operands (load + solve) %lld, C + first update %lld, further columns %lld, to LDS %lld, diagonal factor %lld\n",
-             step, ti, nu, cs_t[1] - cs_t[0], cs_t[2] - cs_t[1], cs_t[3] - cs_t[2], cs_t[4] - cs_t[3], cs_t[5] - cs_t[4], cs_t[6] - cs_t[5]);
-#endif
     return;
   }
 #pragma unroll
@@ -1286,7 +1117,7 @@ __global__ __launch_bounds__(256) void chol_col_step_kernel(CholBatch cb, int st
 // ---- the whole factorisation of a FEW systems as ONE launch: workgroup = tile, tiles handed on through flags -----------------
 // The one-launch-per-step path above pays, per step of the dependent chain, the drain of a launch, the start of the next, its
 // prologue and a cold read of L_kk (~9 of the ~23 us of a step).  Here every tile (i, j), i >= j, of every system has ONE
-// workgroup for the whole factorisation, left-looking like chol_update_col_kernel: it keeps its C tile in the accumulators and
+// workgroup for the whole factorisation, left-looking like chol_update_col_h_kernel: it keeps its C tile in the accumulators and
 // walks the block columns k < j of its update list in the order of the step schedule; for each it waits until the diagonal tile
 // k is factored (flag F[k]) and the tiles (i, k), (j, k) are final (flags T[i][k], T[j][k]), solves for L_ik and L_jk in LDS as
 // chol_col_step_kernel does and applies the update.  A diagonal workgroup then factors its tile, publishes L_jj with its block
@@ -1350,7 +1181,6 @@ __global__ void chol_chain_tl_print(int nt)
 #define TL_STAMP(i) do { } while (0)
 #endif
 
-template <bool W0>  // W0: the diagonal tile with one wave on the chain (diag_factor_tile_w0); a template parameter, not a run-time switch: the kernel's code must stay inside the instruction cache
 __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, int* wg, short* klist, int ticket, int gen)
 {
   short* kstep = klist + 1024;  // step of the schedule each list entry is a column of
@@ -1378,7 +1208,7 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
   if (tm && !tm[ti * nt + tj]) return;
   int* F = cb.chain_ctl + 4 + (size_t)slot * (4 * nt + nt * nt);  // F[4 k + b]: block b of diagonal tile k factored and published
   int* T = F + 4 * nt;                                            // T[i * nt + k]: tile (i, k) final in A
-  if (threadIdx.x < 64) {  // the update list, as chol_update_col_kernel makes it (schedule order)
+  if (threadIdx.x < 64) {  // the update list, as chol_update_col_h_kernel makes it (schedule order)
     const int nq = cb.sched ? CHOL_STEP_COLS * cb.n_steps : tj;
     const int* sq = cb.sched ? cb.sched + (size_t)sys * nt * CHOL_STEP_COLS : nullptr;
     int cnt = 0;
@@ -1415,11 +1245,6 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[c][i] = C[(size_t)(fq + 4 * i) * np + 16 * c + fr];
   const double* Bop = ti == tj ? As : Bs;
-#ifdef PTZ_CHOL_STAMPS
-  long long cs_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  cs_t[0] = wall_clock64();
-  __shared__ long long cs_q[3][16];  // per column of the list: T flags seen, block 0 seen, update done
-#endif
   // TWO columns of a diagonal tile's list side by side (round 6), when their producers are columns of ONE step of the schedule --
   // the two halves of a dissected arc, the two arcs in front of the separator: they end together, and taken one after the other
   // the second costs a finished column's ~6 us behind the first on the chain.  Side by side: both columns' blocks are taken as
@@ -1427,12 +1252,8 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
   // SOLVED for (into Bs, which a diagonal tile does not otherwise use; its L blocks share the image Lk -- the block positions
   // above the diagonal, trsm_block_pre<.., true> -- and its block inverses lie in Dv, which is idle until the tile is factored),
   // and its 64 update MFMAs follow the first column's last round.  Every accumulator takes the same products in the same order
-  // as one column after the other: same bits.  PTZ_BA_CHAIN_PAIR=0: one after the other.
-#ifdef PTZ_PROBE_NO_PAIR  // probe builds: the kernel without the paired-columns path (code size experiment)
-  constexpr bool pairs_on = false;
-#else
-  const bool pairs_on = cb.chain_pair && ti == tj && cb.sched;
-#endif
+  // as one column after the other: same bits.
+  const bool pairs_on = ti == tj && cb.sched;
   for (int q = 0; q < Q; ++q) {
     const int k = klist[q];
     const bool pair = pairs_on && q + 1 < Q && kstep[q] == kstep[q + 1];
@@ -1442,16 +1263,13 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
       if (pair) ok = ok && chain_wait(&T[ti * nt + klist[q + 1]], gen, spin, &cb.fail[sys]);
       if (!ok) atomicOr(&cb.fail[sys], 2);  // bit 1: a hand-over that did not come (reported to the host: LmState::chain_timeouts)
       // is the whole column there already?  ONE thread decides for the workgroup (the waves' own looks below may differ by a flag)
-      int all = cb.chain_ready_whole && !pair;
+      int all = !pair;
       for (int c = 0; c < 4; ++c) all &= __hip_atomic_load(&F[4 * k + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen;
       wg[3] = all;
     }
     __syncthreads();
     const bool whole = wg[3] != 0;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (every load of handed-over bytes below is an sc1 load: no invalidate needed, see ld_sc1)
-#ifdef PTZ_CHOL_STAMPS
-    if (threadIdx.x == 0 && q < 16) cs_q[0][q] = wall_clock64();
-#endif
 #ifdef PTZ_CHOL_TIMELINE
     if (q < 12) { TL_STAMP(4 + 2 * q); if (threadIdx.x == 0 && tl_row) tl_row[3] |= (long long)(k & 31) << (5 * q); }
 #endif
@@ -1613,13 +1431,8 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
           pk[c < 3 ? c + 1 : 3] = __builtin_amdgcn_readfirstlane(nf);
         }
       }
-      CS_STAMP(8 + c);  // (of the last column of the list)
 #ifdef PTZ_CHOL_TIMELINE
       if (q == Q - 1) TL_STAMP(29 + c);  // block c: pre done, its flag seen, its fetch issued
-#endif
-      if (c == 3) CS_STAMP(1);
-#ifdef PTZ_CHOL_STAMPS
-      if (c == 0 && threadIdx.x == 0 && q < 16) cs_q[1][q] = wall_clock64();
 #endif
       stash(cc, rb[c]);
       __syncthreads();
@@ -1669,11 +1482,6 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
     block(std::integral_constant<int, 2>{});
     block(std::integral_constant<int, 3>{});
     }
-    CS_STAMP(2);
-    CS_STAMP(3);
-#ifdef PTZ_CHOL_STAMPS
-    if (threadIdx.x == 0 && q < 16) cs_q[2][q] = wall_clock64();
-#endif
 #ifdef PTZ_CHOL_TIMELINE
     if (q < 12) TL_STAMP(5 + 2 * q);
 #endif
@@ -1684,24 +1492,11 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = (c == w && fr > fq + 4 * i) ? 0.0 : acc[c][i];  // (diag_factor_tile<true>: zero above the diagonal)
+      for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = (c == w && fr > fq + 4 * i) ? 0.0 : acc[c][i];  // (diag_factor_tile_w0: zero above the diagonal)
     __syncthreads();
-    CS_STAMP(4);
-    if constexpr (W0) diag_factor_tile_w0(As, Dv, reinterpret_cast<int*>(Dv + 4), cb, sys, ti, n, &F[4 * ti], gen);
-    else diag_factor_tile<true>(As, Dv, reinterpret_cast<int*>(Dv + 4), cb, sys, ti, n, &F[4 * ti], gen);  // (the last tile also inverts itself there)
-    CS_STAMP(5);
+    diag_factor_tile_w0(As, Dv, reinterpret_cast<int*>(Dv + 4), cb, sys, ti, n, &F[4 * ti], gen);  // (the last tile also inverts itself there)
     TL_STAMP(2);
     // (F[4 ti + 3] was raised inside, by the sweeping wave, whose spare lanes hold the last diagonal block's inverse)
-#ifdef PTZ_CHOL_STAMPS
-    CS_STAMP(6);
-    if (threadIdx.x == 0 && slot == 0)
-      printf("chol_chain tile %d updates %d | absolute x10 ns: block flags of the last column seen %lld %lld %lld %lld, solved+updated %lld, in LDS %lld, factored %lld, posted %lld\n",
-             ti, Q, cs_t[8] % 100000000ll, cs_t[9] % 100000000ll, cs_t[10] % 100000000ll, cs_t[11] % 100000000ll, cs_t[2] % 100000000ll, cs_t[4] % 100000000ll,
-             cs_t[5] % 100000000ll, cs_t[6] % 100000000ll);
-    if (threadIdx.x == 0 && slot == 0)
-      for (int qq = 0; qq < Q && qq < 16; ++qq)
-        printf("chol_chaincol tile %d column %d: T seen %lld, block 0 seen %lld, applied %lld\n", ti, (int)klist[qq], cs_q[0][qq] % 100000000ll, cs_q[1][qq] % 100000000ll, cs_q[2][qq] % 100000000ll);
-#endif
     if (cb.Linv && ti != nt - 1) {
       __syncthreads();  // the block inverses of all four blocks are in LDS
       tile_inverse(As, &Dv[0][0], cb.Linv + ((size_t)sys * nt + ti) * (NB * NB));  // off the chain: for the back-substitution
@@ -1716,7 +1511,6 @@ __device__ __forceinline__ void chain_tile(const CholBatch& cb, double* smem, in
   TL_STAMP(2);
 }
 
-template <bool W0>
 __global__ __launch_bounds__(256) void chol_chain_kernel(CholBatch cb)
 {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1731,7 +1525,7 @@ __global__ __launch_bounds__(256) void chol_chain_kernel(CholBatch cb)
   }
   __syncthreads();
   const int ticket = wg[0], gen = wg[1];
-  chain_tile<W0>(cb, smem, wg, klist, ticket, gen);
+  chain_tile(cb, smem, wg, klist, ticket, gen);
   // the last workgroup to finish closes the launch: tickets start at zero again, the generation moves on (nobody reads
   // either any more: every workgroup has taken its ticket and read the generation before it counted itself done)
   if (threadIdx.x == 0) {
@@ -1749,122 +1543,12 @@ __global__ __launch_bounds__(256) void chol_chain_kernel(CholBatch cb)
 // L_ik and L_jk are both in the structure, so C is read and written once per column step instead of once per k (the
 // right-looking update moves 128 KB per 64^3 update, this one 64 KB), and the whole factorisation needs no trailing
 // update launches.  Same arithmetic per (i, j, k) triple as chol_syrk_kernel; the k order is ascending.
-__global__ __launch_bounds__(256) void chol_update_col_kernel(CholBatch cb, int j, int fuse_diag)
-{
-  int bx, slot;
-  xcd_remap(bx, slot);
-  const int sys = chol_system_of(cb, slot);
-  if (sys < 0 || (cb.active && !cb.active[sys])) return;
-  const int np = cb.np, nt = np / NB;
-  const int n = cb.n[sys];
-  const int ti = j + bx;
-  if (ti >= nt || ti * NB > n || j * NB > n) return;
-  const unsigned char* tm = cb.tmask ? cb.tmask + (size_t)sys * nt * nt : nullptr;
-  if (tm && !tm[ti * nt + j]) return;
-  double* A = cb.A + (size_t)sys * np * np;
-  __shared__ __attribute__((aligned(16))) double As[NB * LD];
-  __shared__ __attribute__((aligned(16))) double Bs[NB * LD];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  double* C = A + (size_t)(ti * NB + 16 * w) * np + j * NB;
-  d4 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[c][i] = C[(size_t)(fq + 4 * i) * np + 16 * c + fr];
-  const double* ap = As + (16 * w + fr) * LD + fq;
-  const double* bp = Bs + fr * LD + fq;
-  // The operand tiles of step k + 1 are fetched into registers while the matrix cores work on step k: a step then costs its 64
-  // MFMAs per wave plus one LDS hand-over, not a global-memory round trip on top (the loop used to: barrier, load, barrier, MFMA).
-  // The block columns k < j are taken in the order of the step schedule (ascending k without one): a tile then sums its
-  // updates in the order the one-launch-per-step path applies them, and a scene has the same bits on either path.
-  // The list is made once, in LDS (a system has at most a few hundred block columns).
-  __shared__ short klist[1024];
-  __shared__ int kcount;
-  if (threadIdx.x < 64) {  // wave 0: 64 candidates at a time, all their loads in flight together, compacted in order by ballot
-    const int nq = cb.sched ? CHOL_STEP_COLS * cb.n_steps : j;
-    const int* sq = cb.sched ? cb.sched + (size_t)sys * nt * CHOL_STEP_COLS : nullptr;
-    int cnt = 0;
-    for (int q0 = 0; q0 < nq; q0 += 64) {
-      const int qq = q0 + (int)threadIdx.x;
-      const int kc = qq < nq ? (sq ? sq[qq] : qq) : -1;
-      const bool in = kc >= 0 && kc < j;
-      const bool ok = in && (!tm || (tm[ti * nt + (in ? kc : 0)] && tm[j * nt + (in ? kc : 0)]));
-      const unsigned long long m = __ballot(ok);
-      const int pos = cnt + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-      if (ok && pos < 1024) klist[pos] = (short)kc;
-      cnt += __popcll(m);
-    }
-    if (threadIdx.x == 0) kcount = min(cnt, 1024);
-  }
-  __syncthreads();
-  const int Q = kcount;
-  auto col_of = [&](int q) { return (int)klist[q]; };
-  auto next_q = [&](int q) { return q; };
-  constexpr int NP = (NB * NB / 2) / 256;  // double2 pieces of one tile per thread
-  int q = 0;
-  const bool any = q < Q;
-  int k = any ? col_of(q) : 0;
-  // Two steps of operand tiles are in flight (the tiles were written by other launches, mostly on other XCDs, and come from
-  // HBM: one step of 64 MFMAs per wave does not cover that round trip).  The fetches stay unconditional: past the end of the
-  // list they re-read the last tiles.
-  auto kq = [&](int qq) { return any ? col_of(qq < Q ? qq : Q - 1) : 0; };
-  d16 ra = tile_fetch(A + (size_t)(ti * NB) * np + kq(0) * NB, np);
-  d16 rb = tile_fetch(A + (size_t)(j * NB) * np + kq(0) * NB, np);
-  d16 ra1 = tile_fetch(A + (size_t)(ti * NB) * np + kq(1) * NB, np);
-  d16 rb1 = tile_fetch(A + (size_t)(j * NB) * np + kq(1) * NB, np);
-  (void)k; (void)next_q;
-  // one step: hand the tiles in (xa, xb) over to LDS, refill the two registers sets with the tiles of step qf, multiply
-  auto step = [&](d16& xa, d16& xb, int qf) {
-    __syncthreads();  // the previous step's fragment reads are done
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int idx = p * 256 + threadIdx.x;
-      const int row = idx >> 5, c2 = (idx & 31) * 2;
-      *reinterpret_cast<double2*>(As + row * LD + c2) = make_double2(-xa[2 * p], -xa[2 * p + 1]);   // -L_ik
-      *reinterpret_cast<double2*>(Bs + row * LD + c2) = make_double2(xb[2 * p], xb[2 * p + 1]);      //  L_jk
-    }
-    __syncthreads();
-    {
-      const int kf = kq(qf);
-      xa = tile_fetch(A + (size_t)(ti * NB) * np + kf * NB, np);
-      xb = tile_fetch(A + (size_t)(j * NB) * np + kf * NB, np);
-    }
-#pragma unroll
-    for (int kk = 0; kk < NB / 4; ++kk) {
-      const double av = ap[4 * kk];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bp[(16 * c) * LD + 4 * kk], acc[c], 0, 0, 0);
-    }
-  };
-  for (; q < Q; q += 2) {  // the two register sets take turns (no copies between them)
-    step(ra, rb, q + 2);
-    if (q + 1 < Q) step(ra1, rb1, q + 3);
-  }
-  if (fuse_diag && ti == j) {
-    // the diagonal tile of this block column is complete: factor it here, no separate diagonal launch for step j
-    __shared__ __attribute__((aligned(16))) double Dv[4][DB * LDD];
-    __shared__ int okflag;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = acc[c][i];
-    __syncthreads();
-    diag_factor_tile(As, Dv, &okflag, cb, sys, j, n);
-    return;
-  }
-  if (!any) return;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) C[(size_t)(fq + 4 * i) * np + 16 * c + fr] = acc[c][i];
-}
-
-// The same update with the operand tiles in HALVES of 32 columns (PTZ_BA_CHOL_HALFK): 35 KB of LDS and two half-tile register
-// sets instead of 68 KB and two whole-tile sets, so that three workgroups share a compute unit and the ~8 us of dependent loads
-// in front of a tile's first MFMA overlap other tiles' arithmetic.  Same MFMAs per accumulator in the same order: same bits.
+// The operand tiles come in HALVES of 32 columns: 35 KB of LDS and two half-tile register sets instead of 68 KB and two whole-tile
+// sets, so that three workgroups share a compute unit and the ~8 us of dependent loads in front of a tile's first MFMA overlap other
+// tiles' arithmetic (81.5 -> 73.4 ms of column updates per C4 solve).  Same MFMAs per accumulator in the same order: same bits.
 constexpr int KH = 32, LDH = KH + 2;
+// this thread's pieces of a 64 x 32 half tile (row stride ld) into registers, all loads in flight together (256 threads).  The
+// buffer is ONE vector value (not an array): it is carried around the loop back-edge, and hipcc keeps arrays that are in scratch.
 typedef double d8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ d8 half_fetch(const double* __restrict__ g, int ld)
 {
@@ -1971,14 +1655,13 @@ __global__ __launch_bounds__(256, 3) void chol_update_col_h_kernel(CholBatch cb,
   if (fuse_diag && ti == j) {
     // the diagonal tile of this block column is complete: factor it here, no separate diagonal launch for step j
     __shared__ __attribute__((aligned(16))) double Dv[4][DB * LDD];
-    __shared__ int okflag;
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int i = 0; i < 4; ++i) As[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = acc[c][i];
     __syncthreads();
-    diag_factor_tile(Ls, Dv, &okflag, cb, sys, j, n);
+    diag_factor_tile(Ls, Dv, cb, sys, j, n);
     return;
   }
   if (!any) return;
@@ -1986,161 +1669,6 @@ __global__ __launch_bounds__(256, 3) void chol_update_col_h_kernel(CholBatch cb,
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) C[(size_t)(fq + 4 * i) * np + 16 * c + fr] = acc[c][i];
-}
-
-// ---- the same update, TWO row tiles per workgroup against one L_jk (round 6; PTZ_BA_CHOL_ROWS2) --------------------------------------
-// chol_update_col_h_kernel moves 32 KB of operand half tiles per 64 x 64 x 32 product (8 flop per byte) and was measured bound by
-// that traffic and by the latency behind it, not by the matrix cores (MFMA busy 30-34 %).  Here a workgroup takes two tiles (i0, j),
-// (i1, j) of the column's structure and multiplies both against the same L_jk: 48 KB per two products (10.7 flop per byte), twice
-// the MFMAs between two barriers, six LDS fragment reads per eight MFMAs instead of five per four.  The list of block columns is
-// the union of the two tiles' lists in schedule order with a mask per entry; each tile's accumulators take exactly the products of
-// its own list in its own order: same bits as one tile per workgroup.
-__global__ __launch_bounds__(256, 2) void chol_update_col_h2_kernel(CholBatch cb, int j, int fuse_diag)
-{
-  int bx, slot;
-  xcd_remap(bx, slot);
-  const int sys = chol_system_of(cb, slot);
-  if (sys < 0 || (cb.active && !cb.active[sys])) return;
-  const int np = cb.np, nt = np / NB;
-  const int n = cb.n[sys];
-  if (j * NB > n) return;
-  const unsigned char* tm = cb.tmask ? cb.tmask + (size_t)sys * nt * nt : nullptr;
-  // the (2 bx)-th and (2 bx + 1)-th tiles of column j's structure, top down (the diagonal tile is the first)
-  int ti0 = -1, ti1 = -1;
-  {
-    int cnt = 0;
-    for (int t = j; t < nt && t * NB <= n; ++t) {
-      if (tm && !tm[t * nt + j]) continue;
-      if (cnt == 2 * bx) ti0 = t;
-      if (cnt == 2 * bx + 1) { ti1 = t; break; }
-      ++cnt;
-    }
-  }
-  if (ti0 < 0) return;
-  const bool two = ti1 >= 0;
-  double* A = cb.A + (size_t)sys * np * np;
-  __shared__ __attribute__((aligned(16))) double Ls[3 * NB * LDH];  // -L_i0k, -L_i1k, L_jk halves; afterwards (fuse_diag) the diagonal tile at stride LD
-  static_assert(3 * NB * LDH >= NB * LD, "the diagonal tile is factored in the operand buffers");
-  double* As0 = Ls;
-  double* As1 = Ls + NB * LDH;
-  double* Bs = Ls + 2 * NB * LDH;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  double* C0 = A + (size_t)(ti0 * NB + 16 * w) * np + j * NB;
-  double* C1 = A + (size_t)((two ? ti1 : ti0) * NB + 16 * w) * np + j * NB;
-  d4 acc0[4], acc1[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { acc0[c][i] = C0[(size_t)(fq + 4 * i) * np + 16 * c + fr]; acc1[c][i] = C1[(size_t)(fq + 4 * i) * np + 16 * c + fr]; }
-  const double* ap0 = As0 + (16 * w + fr) * LDH + fq;
-  const double* ap1 = As1 + (16 * w + fr) * LDH + fq;
-  const double* bp = Bs + fr * LDH + fq;
-  __shared__ short klist[1024];
-  __shared__ unsigned char kmask[1024];  // bit 0: the entry is in tile i0's list, bit 1: in tile i1's
-  __shared__ int kcount;
-  if (threadIdx.x < 64) {
-    const int nq = cb.sched ? CHOL_STEP_COLS * cb.n_steps : j;
-    const int* sq = cb.sched ? cb.sched + (size_t)sys * nt * CHOL_STEP_COLS : nullptr;
-    int cnt = 0;
-    for (int q0 = 0; q0 < nq; q0 += 64) {
-      const int qq = q0 + (int)threadIdx.x;
-      const int kc = qq < nq ? (sq ? sq[qq] : qq) : -1;
-      const bool in = kc >= 0 && kc < j;
-      const int kk = in ? kc : 0;
-      const bool inj = in && (!tm || tm[j * nt + kk]);
-      const int m = inj ? ((!tm || tm[ti0 * nt + kk]) ? 1 : 0) | ((two && (!tm || tm[ti1 * nt + kk])) ? 2 : 0) : 0;
-      const bool ok = m != 0;
-      const unsigned long long bal = __ballot(ok);
-      const int pos = cnt + __popcll(bal & ((1ull << threadIdx.x) - 1ull));
-      if (ok && pos < 1024) { klist[pos] = (short)kc; kmask[pos] = (unsigned char)m; }
-      cnt += __popcll(bal);
-    }
-    if (threadIdx.x == 0) kcount = min(cnt, 1024);
-  }
-  __syncthreads();
-  const int Q = kcount;
-  const bool any = Q > 0;
-  auto kq = [&](int qq) { return any ? (int)klist[qq < Q ? qq : Q - 1] : 0; };
-  auto mq = [&](int qq) { return any ? (int)kmask[qq < Q ? qq : Q - 1] : 0; };
-  // unit u = half (u & 1) of the operand tiles of list entry u >> 1; a tile outside the entry's mask is not fetched (uniform branch)
-  auto fetch_a0 = [&](int u) { return half_fetch(A + (size_t)(ti0 * NB) * np + kq(u >> 1) * NB + KH * (u & 1), np); };
-  auto fetch_a1 = [&](int u) { return half_fetch(A + (size_t)((two ? ti1 : ti0) * NB) * np + kq(u >> 1) * NB + KH * (u & 1), np); };
-  auto fetch_b = [&](int u) { return half_fetch(A + (size_t)(j * NB) * np + kq(u >> 1) * NB + KH * (u & 1), np); };
-  d8 ra0 = fetch_a0(0), ra1 = fetch_a1(0), rb = fetch_b(0), sa0 = fetch_a0(1), sa1 = fetch_a1(1), sb = fetch_b(1);
-  auto step = [&](d8& xa0, d8& xa1, d8& xb, int ucur, int uf) {
-    const int m = mq(ucur >> 1);
-    __syncthreads();  // the previous step's fragment reads are done
-#pragma unroll
-    for (int p = 0; p < (NB * KH / 2) / 256; ++p) {
-      const int idx = p * 256 + threadIdx.x;
-      const int row = idx >> 4, c2 = (idx & 15) * 2;
-      *reinterpret_cast<double2*>(As0 + row * LDH + c2) = make_double2(-xa0[2 * p], -xa0[2 * p + 1]);
-      *reinterpret_cast<double2*>(As1 + row * LDH + c2) = make_double2(-xa1[2 * p], -xa1[2 * p + 1]);
-      *reinterpret_cast<double2*>(Bs + row * LDH + c2) = make_double2(xb[2 * p], xb[2 * p + 1]);
-    }
-    __syncthreads();
-    xa0 = fetch_a0(uf);
-    xa1 = fetch_a1(uf);
-    xb = fetch_b(uf);
-    if (m == 3) {
-#pragma unroll
-      for (int kk = 0; kk < KH / 4; ++kk) {
-        const double av0 = ap0[4 * kk], av1 = ap1[4 * kk];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double bv = bp[(16 * c) * LDH + 4 * kk];
-          acc0[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av0, bv, acc0[c], 0, 0, 0);
-          acc1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av1, bv, acc1[c], 0, 0, 0);
-        }
-      }
-    }
-    else if (m == 1) {
-#pragma unroll
-      for (int kk = 0; kk < KH / 4; ++kk) {
-        const double av0 = ap0[4 * kk];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc0[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av0, bp[(16 * c) * LDH + 4 * kk], acc0[c], 0, 0, 0);
-      }
-    }
-    else {
-#pragma unroll
-      for (int kk = 0; kk < KH / 4; ++kk) {
-        const double av1 = ap1[4 * kk];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc1[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av1, bp[(16 * c) * LDH + 4 * kk], acc1[c], 0, 0, 0);
-      }
-    }
-  };
-  for (int u = 0; u < 2 * Q; u += 2) {  // the two register sets take turns: first and second half of a list entry
-    step(ra0, ra1, rb, u, u + 2);
-    step(sa0, sa1, sb, u + 1, u + 3);
-  }
-  const bool diag = fuse_diag && ti0 == j;
-  if (two && any) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) C1[(size_t)(fq + 4 * i) * np + 16 * c + fr] = acc1[c][i];
-  }
-  if (diag) {
-    // the diagonal tile of this block column is complete: factor it here, no separate diagonal launch for step j
-    __shared__ __attribute__((aligned(16))) double Dv[4][DB * LDD];
-    __shared__ int okflag;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Ls[(16 * w + fq + 4 * i) * LD + 16 * c + fr] = acc0[c][i];
-    __syncthreads();
-    diag_factor_tile(Ls, Dv, &okflag, cb, sys, j, n);
-    return;
-  }
-  if (!any) return;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) C0[(size_t)(fq + 4 * i) * np + 16 * c + fr] = acc0[c][i];
 }
 
 // ---- full inverses of the factored diagonal tiles, all at once (the multi-launch paths; the one-launch-per-column path
@@ -2421,18 +1949,7 @@ void chol_syrk_launch(const CholBatch& cb, int k, hipStream_t stream, int mode, 
 void chol_update_col_launch(const CholBatch& cb, int j, hipStream_t stream, bool fuse_diag)
 {
   const int m = cb.np / NB - j;
-  // operand tiles in halves (three workgroups per compute unit): 81.5 -> 73.4 ms of column updates per C4 solve, same bits;
-  // PTZ_BA_CHOL_HALFK=0 brings the whole-tile kernel back (A/B measurements)
-  static const bool halfk = [] { const char* e = getenv("PTZ_BA_CHOL_HALFK"); return !e || atoi(e) != 0; }();
-  // two row tiles per workgroup (round 6): built, bit-identical, and SLOWER -- chol_syrk 18.3 -> 24.3 ms per 256-scene solve (A/B on one
-  // box, tools/probes/probe_r6_rows2.sh): 256 registers with 160 B of scratch and 64.5 KB of LDS leave two workgroups per compute unit
-  // with half as many workgroups in flight, and the fewer operand bytes do not pay for that.  PTZ_BA_CHOL_ROWS2=1 runs it.
-  static const bool rows2 = [] { const char* e = getenv("PTZ_BA_CHOL_ROWS2"); return e && atoi(e) != 0; }();
-  if (j > 0 && m > 0 && halfk && rows2) { launch(chol_update_col_h2_kernel, dim3((m + 1) / 2, cb.count), dim3(256), 0, stream, cb, j, fuse_diag ? 1 : 0); return; }
-  if (j > 0 && m > 0) {
-    if (halfk) launch(chol_update_col_h_kernel, dim3(m, cb.count), dim3(256), 0, stream, cb, j, fuse_diag ? 1 : 0);
-    else launch(chol_update_col_kernel, dim3(m, cb.count), dim3(256), 0, stream, cb, j, fuse_diag ? 1 : 0);
-  }
+  if (j > 0 && m > 0) launch(chol_update_col_h_kernel, dim3(m, cb.count), dim3(256), 0, stream, cb, j, fuse_diag ? 1 : 0);
 }
 void chol_col_step_launch(const CholBatch& cb, int step, hipStream_t stream)
 {
@@ -2485,13 +2002,11 @@ void chol_chain_launch(const CholBatch& cb, hipStream_t stream)
     (void)hipGetDevice(&dev);
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(done.load(std::memory_order_acquire) & bit)) {
-      (void)hipFuncSetAttribute((const void*)chol_chain_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      (void)hipFuncSetAttribute((const void*)chol_chain_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      (void)hipFuncSetAttribute((const void*)chol_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
       done.fetch_or(bit, std::memory_order_release);
     }
   }
-  if (cb.chain_w0) launch(chol_chain_kernel<true>, dim3(nt * (nt + 1) / 2 * cb.count), dim3(256), smem, stream, cb);
-  else launch(chol_chain_kernel<false>, dim3(nt * (nt + 1) / 2 * cb.count), dim3(256), smem, stream, cb);
+  launch(chol_chain_kernel, dim3(nt * (nt + 1) / 2 * cb.count), dim3(256), smem, stream, cb);
 }
 #ifdef PTZ_CHOL_TIMELINE
 void chol_chain_timeline_print(int nt) { hipLaunchKernelGGL(chol_chain_tl_print, dim3(1), dim3(1), 0, 0, nt); (void)hipDeviceSynchronize(); }
@@ -2696,7 +2211,7 @@ extern "C" int32_t ptz_chol_solve_batch(int32_t count, int32_t n, const double* 
   cb.A = dA; cb.Ldiag = dL; cb.Dinv = dD; cb.n = dn; cb.fail = dfail;
   double *dL2 = nullptr, *dLi = nullptr;
   int* dctl = nullptr;
-  if (count < 8 && !getenv("PTZ_CHOL_MULTI_LAUNCH")) {  // the path a few bundle-adjustment scenes take
+  if (count < 8) {  // the path a few bundle-adjustment scenes take
     PTZ_HIP_TRY(hipMalloc(&dL2, sizeof(double) * (size_t)count * np * np));
     PTZ_HIP_TRY(hipMemset(dL2, 0, sizeof(double) * (size_t)count * np * np));
     cb.L = dL2;
