@@ -1,7 +1,8 @@
 /*
  * ptz_calib_amd.h -- C-ABI of libptzcalib_hip.so: the MI355X (gfx950) implementation of the PTZ-Calib
  * optimisation hot path (per-observation PTZ reprojection residual/Jacobian evaluation, Levenberg-
- * Marquardt normal-equation assembly, Schur elimination, dense reduced-camera solve, LM control).
+ * Marquardt normal-equation assembly, Schur elimination, dense reduced-camera solve, LM control) and of the match table's
+ * per-pair RANSAC homographies.
  *
  * The reference (gjgjh/PTZ-Calib) has no FFI layer; its seam is the pair of C++ classes that each own
  * a ceres::Problem.  Every entry point below names the reference interface it replaces
@@ -336,6 +337,24 @@ int32_t ptz_krt_solve_batch_sharded(int32_t n_query, const int64_t* match_ptr, c
                                     const int64_t* point_ptr, const float* pts2d, const double* pts3d, const double* cam_ref,
                                     double* cam_cur, int32_t factor_type, double max_reproj_error, const int32_t* device_ids,
                                     int32_t n_devices, const ptz_lm_options* opt, ptz_lm_summary* summaries, int32_t* accepted);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pair homographies of a match table (RANSAC, batched over pairs)
+ * ------------------------------------------------------------------------------------------------ */
+/* replaces cv::findHomography(pts_i, pts_j, RANSAC, thresh) per pair of LoadMatchesInfo (data_io.cc:340-355, 384-385);
+ * pair p owns [match_ptr[p], match_ptr[p+1]), dst ~ H src; bit-identical to the host estimator (host/homography.cc).
+ * src_uv / dst_uv: float pairs [2 match_ptr[n_pair]].  found[p] = 1: H[9p .. 9p+9) row-major with h33 = 1 and, if inlier_mask
+ * is non-NULL, one byte per match of the pair; found[p] = 0 (fewer than 4 matches, no model with 4 inliers): that pair's H and
+ * mask bytes are left untouched.  PTZ_EINVAL (checked before any device work): n_pair < 0, match_ptr[0] != 0, decreasing
+ * offsets, NULL arrays with non-zero extents, a threshold that is not finite and positive; PTZ_ELIMIT: a pair of more than
+ * 2^31 - 1 matches.  n_pair = 0 is PTZ_OK.  Pairs of any size run on the device; no CPU fallback. */
+int32_t ptz_homography_ransac_batch(int32_t n_pair, const int64_t* match_ptr, const float* src_uv, const float* dst_uv,
+                                    double ransac_thresh, int32_t device_id, double* H /* [9 n_pair] */,
+                                    int32_t* found /* [n_pair] */, uint8_t* inlier_mask /* [match_ptr[n_pair]] or NULL */,
+                                    double* device_ms);
+/* Host logic only (no device): the estimator's adaptive iteration bound for cnt = 0 .. n inliers of n matches, bound[n + 1] --
+ * static_cast<int>(ceil(need)) of the host's libm, INT32_MIN where need exceeds the int range.  The kernel reads this table. */
+int32_t ptz_debug_homography_bounds(int32_t n, int32_t* bound);
 
 #ifdef __cplusplus
 }

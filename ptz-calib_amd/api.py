@@ -27,7 +27,7 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_batch_sharded", "ptz_hbm_bandwidth", "ptz_ba_batch_set_disp", "ptz_ba_batch_get_disp", "ptz_ba_solve_disp",
            "ptz_ba_plan_tile_order", "ptz_rig_create", "ptz_rig_destroy", "ptz_ba_batch_create_views", "ptz_ba_batch_set_state_pix2ray",
            "ptz_debug_batch_structure_hash", "ptz_debug_batch_initial_rays", "ptz_krt_table_create", "ptz_krt_table_destroy",
-           "ptz_krt_solve_attempts"]
+           "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds"]
 
 
 class PtzError(RuntimeError):
@@ -398,6 +398,24 @@ def chol_solve_batch(A, rhs, device_id=0):
     ms = C.c_double()
     _check(lib().ptz_chol_solve_batch(count, n, _p(A), _p(rhs), _p(x), _p(fail), device_id, C.byref(ms)), "ptz_chol_solve_batch")
     return x, fail, ms.value
+
+
+def find_homographies(match_ptr, src_uv, dst_uv, ransac_thresh=4.0, device_id=0, mask=True):
+    """RANSAC homography dst ~ H src of every pair of a match table on the device (the host estimator's bits; stands in
+    for cv::findHomography(..., RANSAC, thresh) of LoadMatchesInfo).  Pair p owns matches [match_ptr[p], match_ptr[p+1]);
+    src_uv / dst_uv: [n_match, 2].  Returns (H [n_pair, 3, 3] with h33 = 1 (zeros where not found), found [n_pair] int32,
+    inlier mask [n_match] uint8 or None, device_ms)."""
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    src = np.ascontiguousarray(src_uv, dtype=np.float32)
+    dst = np.ascontiguousarray(dst_uv, dtype=np.float32)
+    n = ptr.shape[0] - 1
+    H = np.zeros((max(n, 0), 3, 3))
+    found = np.zeros(max(n, 0), dtype=np.int32)
+    m = np.zeros(int(ptr[-1]) if n > 0 else 0, dtype=np.uint8) if mask else None
+    ms = C.c_double()
+    _check(lib().ptz_homography_ransac_batch(n, _p(ptr), _p(src), _p(dst), C.c_double(ransac_thresh), device_id, _p(H), _p(found),
+                                             _p(m), C.byref(ms)), "ptz_homography_ransac_batch")
+    return H, found, m, ms.value
 
 
 def krt_solve_batch(batch, max_reproj_error=100.0, **opt):

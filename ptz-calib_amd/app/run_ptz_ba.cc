@@ -49,6 +49,7 @@ int main(int argc, char** argv)
   parser.Add("annotation", 'a', "Annotation filepath", false);
   parser.Add("output", 'o', "Output directory", true);
   parser.AddFlag("dist", "Whether images have distortion");
+  parser.AddFlag("gpu_homography", "Compute the pair homographies of the match table on the GPU (same results)");
   parser.ParseCheck(argc, argv);
 
   std::vector<std::string> fnames;
@@ -60,7 +61,9 @@ int main(int argc, char** argv)
   }
   std::vector<MatchesInfo> matches_info;
   const std::string matches_path = parser.Get("features") + "/pairs_matches.txt";
-  if (!LoadMatchesInfo(matches_path, fnames, features, matches_info)) {
+  const bool loaded = parser.Exist("gpu_homography") ? LoadMatchesInfo(matches_path, fnames, features, matches_info, 0)
+                                                     : LoadMatchesInfo(matches_path, fnames, features, matches_info);
+  if (!loaded) {
     fprintf(stderr, "Error loading matches from %s. Exiting ...\n", matches_path.c_str());
     return -1;
   }

@@ -4,10 +4,13 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 
+#include "../../include/ptz_calib_amd.h"
 #include "homography.h"
 #include "image_size.h"
 #include "json_mini.h"
@@ -318,6 +321,70 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
     mi.src_img_idx = index_i;
     mi.dst_img_idx = index_j;
     matches_info[static_cast<size_t>(index_i) * num_images + static_cast<size_t>(index_j)] = mi;
+  }
+  return true;
+}
+
+bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                     std::vector<MatchesInfo>& matches_info, int device_id)
+{
+  std::vector<std::vector<DMatch>> pairs_matches;
+  std::vector<std::pair<std::string, std::string>> img_pairs_name;
+  ReadColmapMatches(matches_path, pairs_matches, img_pairs_name);
+  matches_info.clear();
+  const size_t num_images = fnames.size();
+  matches_info.resize(num_images * num_images);
+  // the pairs the host loader keeps, in its order, with their points packed for one device call
+  std::vector<size_t> kept;
+  std::vector<long> idx_i, idx_j;
+  std::vector<int64_t> match_ptr(1, 0);
+  std::vector<float> src_uv, dst_uv;
+  for (size_t p = 0; p < pairs_matches.size(); ++p) {
+    const long index_i = FindImgIndex(fnames, img_pairs_name[p].first);
+    const long index_j = FindImgIndex(fnames, img_pairs_name[p].second);
+    if (index_i < 0 || index_j < 0) continue;
+    const std::vector<DMatch>& ms = pairs_matches[p];
+    bool in_range = true;
+    for (const DMatch& m : ms)
+      if (m.queryIdx < 0 || m.trainIdx < 0 || static_cast<size_t>(m.queryIdx) >= features[index_i].keypoints.size() ||
+          static_cast<size_t>(m.trainIdx) >= features[index_j].keypoints.size()) { in_range = false; break; }
+    if (!in_range) continue;
+    for (const DMatch& m : ms) {
+      const Point2f& a = features[index_i].keypoints[m.queryIdx].pt;
+      const Point2f& b = features[index_j].keypoints[m.trainIdx].pt;
+      src_uv.push_back(a.x); src_uv.push_back(a.y);
+      dst_uv.push_back(b.x); dst_uv.push_back(b.y);
+    }
+    kept.push_back(p); idx_i.push_back(index_i); idx_j.push_back(index_j);
+    match_ptr.push_back(match_ptr.back() + static_cast<int64_t>(ms.size()));
+  }
+  const int n_pair = static_cast<int>(kept.size());
+  std::vector<double> H(9 * kept.size());
+  std::vector<int32_t> found(kept.size(), 0);
+  for (int q = 0; q < n_pair; ++q) {
+    const Mat33 I = Eye3();  // the H a pair without a model keeps (MatchesInfo's)
+    std::copy(I.begin(), I.end(), H.begin() + 9 * q);
+  }
+  static const double kRansacThresh = 4.0;
+  const int32_t rc = ptz_homography_ransac_batch(n_pair, match_ptr.data(), src_uv.data(), dst_uv.data(), kRansacThresh, device_id,
+                                                 H.data(), found.data(), nullptr, nullptr);
+  if (rc != PTZ_OK) {
+    fprintf(stderr, "[ptzcalib] LoadMatchesInfo: ptz_homography_ransac_batch failed (%d)\n", rc);
+    return false;
+  }
+  for (int q = 0; q < n_pair; ++q) {
+    const std::vector<DMatch>& ms = pairs_matches[kept[q]];
+    MatchesInfo mi;
+    mi.matches = ms;
+    std::copy(H.begin() + 9 * q, H.begin() + 9 * q + 9, mi.H.begin());
+    mi.H_empty = !found[q];
+    mi.inliers_mask.assign(ms.size(), 1);
+    mi.num_inliers = static_cast<int>(ms.size());
+    static const int kMaxNumMatches = 100;
+    mi.confidence = static_cast<int>(ms.size()) >= kMaxNumMatches ? 1.0f : static_cast<float>(ms.size()) / static_cast<float>(kMaxNumMatches);
+    mi.src_img_idx = idx_i[q];
+    mi.dst_img_idx = idx_j[q];
+    matches_info[static_cast<size_t>(idx_i[q]) * num_images + static_cast<size_t>(idx_j[q])] = mi;
   }
   return true;
 }

@@ -3,7 +3,8 @@
 //   * pairs_matches.txt      blocks "nameA nameB\n i j\n ...\n<blank line>"                 (data_io.cc:64-110)
 //   * camera / annotation JSON  {"cameras": {name: {name,pos,res,K,R,t,dist,distType,marker{pix,pos},version}}} (:112-295)
 //   * image directory listing with sizes read from the file headers                       (data_io.cc:294-333)
-//   * the N x N MatchesInfo table with one RANSAC homography per listed pair              (data_io.cc:336-400)
+//   * the N x N MatchesInfo table with one RANSAC homography per listed pair              (data_io.cc:336-400),
+//     on the host or, batched over the pairs, on the device
 #pragma once
 
 #include <string>
@@ -28,6 +29,10 @@ bool LoadImgsAndFeatures(const std::string& img_dir, const std::string& feature_
                          std::vector<ImageFeatures>& features, std::vector<Size>& sizes);
 bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                      std::vector<MatchesInfo>& matches_info);
+// The same table with the pair homographies computed on device `device_id` in one call (ptz_homography_ransac_batch): the same
+// pairs skipped, the same fields, the same bits.  Returns false (after a message on stderr) if the device call fails.
+bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                     std::vector<MatchesInfo>& matches_info, int device_id);
 bool LoadAnnotation(const std::string& annot_path, const std::vector<std::string>& fnames, std::vector<std::vector<Point2f>>& pixels,
                     std::vector<std::vector<Point3d>>& pts3d);
 void SaveRegisteredCam(const std::vector<Camera>& cameras, const std::unordered_set<long>& reg_image_ids,

@@ -4,7 +4,8 @@
 // transfer error against the threshold, adaptive iteration count at confidence 0.995 up to 2000 iterations, a least-squares
 // fit on the inliers (normalised DLT) followed by a few Gauss-Newton steps on the transfer error, H scaled to h33 = 1 --
 // with its own deterministic generator, so on outlier-free or clearly separated data it agrees with OpenCV's result to the
-// fit's precision, but it is not bit-identical.
+// fit's precision, but it is not bit-identical.  ptz_homography_ransac_batch (csrc/ptz_homography.{h,hip})
+// computes this estimator's results, bit for bit, for all pairs of a match table on the device.
 #pragma once
 
 #include <vector>

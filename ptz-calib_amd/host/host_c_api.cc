@@ -385,6 +385,8 @@ static char* DupText(const std::string& s)
 }
 
 // cmd = "load": a = image dir, b = feature dir  -> {ok, fnames, sizes, n_keypoints, first_keypoint, pairs:[{src,dst,n,H,H_empty,confidence}]}
+// cmd = "load_device": a = image dir, b = feature dir -> {ok, loaded, table_cells, pairs, n_pairs_found, identical}: the match table of
+//       LoadMatchesInfo(..., device 0) (pairs as for "load"), identical = every cell equal to the host loader's, H bit for bit
 // cmd = "annotation": a = annotation json, b = image dir (for the file names) -> {ok, pixels, pts3d}
 // cmd = "rewrite": a = camera json in, b = camera json out (ReadFromJson -> SaveToJson)  -> {ok, names}
 // cmd = "image_size": a = file -> {ok, width, height}
@@ -438,6 +440,44 @@ char* ptzh_io_probe(const char* cmd_c, const char* a_c, const char* b_c)
         p["first_match"] = Json::FloatArray({static_cast<double>(mi.matches[0].queryIdx), static_cast<double>(mi.matches[0].trainIdx)});
         jp.push_back(p);
       }
+    }
+    out["pairs"] = jp;
+  }
+  else if (cmd == "load_device") {
+    std::vector<std::string> fnames;
+    std::vector<ImageFeatures> features;
+    std::vector<Size> sizes;
+    const bool ok = LoadImgsAndFeatures(a, b, fnames, features, sizes);
+    out["ok"] = Json::Bool(ok);
+    Json jp = Json::Array();
+    if (ok) {
+      std::vector<MatchesInfo> host, dev;
+      LoadMatchesInfo(b + "/pairs_matches.txt", fnames, features, host);
+      const bool loaded = LoadMatchesInfo(b + "/pairs_matches.txt", fnames, features, dev, 0);
+      out["loaded"] = Json::Bool(loaded);
+      out["table_cells"] = Json::Int(static_cast<long long>(dev.size()));
+      bool same = host.size() == dev.size();
+      long long n_found = 0;
+      for (size_t c = 0; same && c < host.size(); ++c) {
+        const MatchesInfo &x = host[c], &y = dev[c];
+        same = x.src_img_idx == y.src_img_idx && x.dst_img_idx == y.dst_img_idx && x.matches.size() == y.matches.size() &&
+               x.inliers_mask == y.inliers_mask && x.num_inliers == y.num_inliers && x.H_empty == y.H_empty &&
+               memcmp(x.H.data(), y.H.data(), sizeof(double) * 9) == 0 &&
+               memcmp(&x.confidence, &y.confidence, sizeof(double)) == 0;
+        for (size_t k = 0; same && k < x.matches.size(); ++k)
+          same = x.matches[k].queryIdx == y.matches[k].queryIdx && x.matches[k].trainIdx == y.matches[k].trainIdx;
+      }
+      for (const MatchesInfo& mi : dev) {
+        if (mi.matches.empty()) continue;
+        n_found += !mi.H_empty;
+        Json p = Json::Object();
+        p["src"] = Json::Int(mi.src_img_idx); p["dst"] = Json::Int(mi.dst_img_idx); p["n"] = Json::Int(static_cast<long long>(mi.matches.size()));
+        p["H"] = Json::FloatArray(std::vector<double>(mi.H.begin(), mi.H.end()));
+        p["H_empty"] = Json::Bool(mi.H_empty);
+        jp.push_back(p);
+      }
+      out["identical"] = Json::Bool(same);
+      out["n_pairs_found"] = Json::Int(n_found);
     }
     out["pairs"] = jp;
   }
