@@ -356,6 +356,70 @@ int32_t ptz_homography_ransac_batch(int32_t n_pair, const int64_t* match_ptr, co
  * static_cast<int>(ceil(need)) of the host's libm, INT32_MIN where need exceeds the int range.  The kernel reads this table. */
 int32_t ptz_debug_homography_bounds(int32_t n, int32_t* bound);
 
+/* ------------------------------------------------------------------------------------------------
+ * RANSAC inlier gating of matches
+ * ------------------------------------------------------------------------------------------------ */
+/* puts to use what the reference drops: the mask cv::findHomography returns in LoadMatchesInfo (`matches_msk`,
+ * data_io.cc:351-352, never read) -- every listed match, wrong ones included, goes into a squared-loss LM there.
+ * GATING a CSR match set (match_ptr, uv_a, uv_b) with a threshold and min_inliers: the pair estimator of
+ * ptz_homography_ransac_batch runs with src = uv_a, dst = uv_b; pair p PASSES when found[p] = 1 and its mask has at least
+ * max(min_inliers, 4) ones; a passing pair keeps exactly its matches with mask byte 1, in their order; every other pair keeps
+ * none.  Integers and copies only: H, found and mask are the estimator's bits, the compacted CSR is what
+ * keep = mask & passes[pair_of_match] selects.
+ *
+ * ptz_match_gate owns what a launch on DEVICE-RESIDENT offsets needs: the adaptive-bound table of every pair size
+ * 5 .. max_pair_matches (about max^2 / 2 int32, computed once by host code with the host's libm; PTZ_ELIMIT above 4096, and
+ * for max_matches beyond 2^31 - 1) and the estimator's workspace for max_matches matches.  PTZ_EINVAL: out = NULL,
+ * max_pairs <= 0, a negative extent or device_id -- all checked before any device work.
+ * ptz_match_gate_run_device: every d_* is a DEVICE pointer on the gate's device; d_match_ptr [n_pair + 1], d_uv_a / d_uv_b float
+ * pairs; outputs d_found [n_pair], d_H [9 n_pair] or NULL, d_mask [n_match] or NULL, d_out_ptr [n_pair + 1], d_out_uv_a /
+ * d_out_uv_b with room for n_match float pairs, d_out_index (the kept match's index in the input arrays) likewise or NULL.
+ * Five kernels are enqueued on `hip_stream` (NULL = the default stream; it must belong to the gate's device) and the call
+ * returns without synchronising; the outputs feed ptz_krt_solve_batch_device on the same stream as they are.  A pair with more
+ * than max_pair_matches matches, or with a range outside [0, max_matches], is not served: found[p] = -1, an empty output
+ * range, nothing else written for it, and the estimator does not run on it.  d_H and the d_mask bytes of a pair whose found
+ * is not 1 are left as they were.  A pair's bits do not depend on the other pairs of the launch.  Runs on one gate are ordered
+ * by the caller (one stream, or events): they share its workspace.  PTZ_EINVAL: NULL gate / required arrays, n_pair < 0, a
+ * threshold that is not finite and positive, min_inliers < 0, a stream of another device; PTZ_ELIMIT: n_pair > max_pairs. */
+typedef struct ptz_match_gate ptz_match_gate;
+int32_t ptz_match_gate_create(int32_t max_pairs, int64_t max_matches, int32_t max_pair_matches, int32_t device_id,
+                              ptz_match_gate** out);
+void ptz_match_gate_destroy(ptz_match_gate* g);
+int32_t ptz_match_gate_run_device(ptz_match_gate* g, int32_t n_pair, const int64_t* d_match_ptr, const float* d_uv_a,
+                                  const float* d_uv_b, double ransac_thresh, int32_t min_inliers, double* d_H, int32_t* d_found,
+                                  uint8_t* d_mask, int64_t* d_out_ptr, float* d_out_uv_a, float* d_out_uv_b, int32_t* d_out_index,
+                                  void* hip_stream);
+/* The same run on HOST arrays (callers without device buffers of their own): upload, ptz_match_gate_run_device, download.
+ * out_uv_a / out_uv_b / out_index need room for match_ptr[n_pair] entries; H and mask of a pair whose found is not 1 are left
+ * untouched.  The argument list of ptz_homography_ransac_batch applies, plus min_inliers < 0 (PTZ_EINVAL) and a set larger
+ * than the gate (PTZ_ELIMIT). */
+int32_t ptz_match_gate_run(ptz_match_gate* g, int32_t n_pair, const int64_t* match_ptr, const float* uv_a, const float* uv_b,
+                           double ransac_thresh, int32_t min_inliers, double* H /* or NULL */, int32_t* found,
+                           uint8_t* mask /* or NULL */, int64_t* out_ptr, float* out_uv_a, float* out_uv_b,
+                           int32_t* out_index /* or NULL */, double* device_ms);
+
+/* Gate, then solve, in one call:
+ *   replaces the loop body of run_ptz_reloc.cc:68-118 for callers whose matches hold outliers -- upload, gate with
+ *   src = uv_ref, dst = uv_cur, the LM of ptz_krt_solve_batch on the compacted CSR (ptz_krt_solve_batch_device's launch, same
+ *   stream, no host round trip in between), download.
+ * Arguments as ptz_krt_solve_batch.  A query that does not pass is solved on no matches, i.e. gets exactly what
+ * ptz_krt_solve_batch returns for a query whose range is empty, and n_inliers = 0.  n_inliers [n_query]: kept matches;
+ * inlier_mask [n_match] or NULL: 1 for every kept match, 0 for every other (all of a query that does not pass);
+ * H [9 n_query] or NULL: the estimator's H, untouched where it found none; device_ms [2] or NULL: gate, LM.
+ * The offsets are read on the host, so the bound tables are built per distinct size and no pair size limit applies.
+ * PTZ_EINVAL, before any device work: the list of ptz_homography_ransac_batch, min_inliers < 0, NULL cameras / summaries /
+ * accepted / n_inliers with n_query > 0; PTZ_EUNSUPPORTED: factor_type.  n_query = 0 is PTZ_OK. */
+int32_t ptz_krt_solve_batch_gated(int32_t n_query, const int64_t* match_ptr, const float* uv_ref, const float* uv_cur,
+                                  const double* cam_ref, double* cam_cur, int32_t factor_type, double max_reproj_error,
+                                  double ransac_thresh, int32_t min_inliers, const ptz_lm_options* opt, ptz_lm_summary* summaries,
+                                  int32_t* accepted, int32_t* n_inliers /* [n_query] */,
+                                  uint8_t* inlier_mask /* [n_match] or NULL */, double* H /* [9 n_query] or NULL */,
+                                  double* device_ms /* [2]: gate, LM; or NULL */);
+/* Host logic only (no device): the bound table a gate of max_pair_matches holds.  *table_len = its length, offsets
+ * [max_pair_matches + 1] (or NULL) = where size n's n + 1 entries begin (sizes below 5 have none), table (or NULL) = the
+ * entries: ptz_debug_homography_bounds size after size. */
+int32_t ptz_debug_match_gate_table(int32_t max_pair_matches, int32_t* table, int64_t* table_len, int64_t* offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_batch_sharded", "ptz_hbm_bandwidth", "ptz_ba_batch_set_disp", "ptz_ba_batch_get_disp", "ptz_ba_solve_disp",
            "ptz_ba_plan_tile_order", "ptz_rig_create", "ptz_rig_destroy", "ptz_ba_batch_create_views", "ptz_ba_batch_set_state_pix2ray",
            "ptz_debug_batch_structure_hash", "ptz_debug_batch_initial_rays", "ptz_krt_table_create", "ptz_krt_table_destroy",
-           "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds"]
+           "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds", "ptz_match_gate_create",
+           "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table"]
 
 
 class PtzError(RuntimeError):
@@ -416,6 +417,110 @@ def find_homographies(match_ptr, src_uv, dst_uv, ransac_thresh=4.0, device_id=0,
     _check(lib().ptz_homography_ransac_batch(n, _p(ptr), _p(src), _p(dst), C.c_double(ransac_thresh), device_id, _p(H), _p(found),
                                              _p(m), C.byref(ms)), "ptz_homography_ransac_batch")
     return H, found, m, ms.value
+
+
+def _dptr(x):
+    """A device buffer as a C pointer: an object with .data_ptr() (a torch tensor), an integer address, or None."""
+    if x is None:
+        return None
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+
+
+def match_gate_table(max_pair_matches):
+    """ptz_debug_match_gate_table (host logic only): (table int32, offsets int64 [max_pair_matches + 1])."""
+    n = C.c_int64()
+    off = np.zeros(max_pair_matches + 1, dtype=np.int64)
+    _check(lib().ptz_debug_match_gate_table(int(max_pair_matches), None, C.byref(n), _p(off)), "ptz_debug_match_gate_table")
+    tab = np.zeros(max(int(n.value), 1), dtype=np.int32)
+    _check(lib().ptz_debug_match_gate_table(int(max_pair_matches), _p(tab), C.byref(n), None), "ptz_debug_match_gate_table")
+    return tab[:int(n.value)], off
+
+
+class MatchGate:
+    """ptz_match_gate: RANSAC inlier gating of device-resident CSR match sets (up to max_pairs pairs, max_matches matches,
+    max_pair_matches matches in one pair)."""
+
+    def __init__(self, max_pairs, max_matches, max_pair_matches, device_id=0):
+        self.max_pairs, self.max_matches, self.max_pair_matches = int(max_pairs), int(max_matches), int(max_pair_matches)
+        self.handle = C.c_void_p()
+        lib().ptz_match_gate_destroy.restype = None
+        _check(lib().ptz_match_gate_create(self.max_pairs, C.c_int64(self.max_matches), self.max_pair_matches, int(device_id),
+                                           C.byref(self.handle)), "ptz_match_gate_create")
+
+    def run_device(self, n_pair, d_match_ptr, d_uv_a, d_uv_b, d_found, d_out_ptr, d_out_uv_a, d_out_uv_b, d_H=None, d_mask=None,
+                   d_out_index=None, ransac_thresh=4.0, min_inliers=0, stream=None):
+        """ptz_match_gate_run_device: every d_* is a device buffer (torch tensor or integer address).  Enqueues on `stream`
+        (integer hipStream_t handle, None = default stream) and returns without synchronising."""
+        _check(lib().ptz_match_gate_run_device(self.handle, int(n_pair), _dptr(d_match_ptr), _dptr(d_uv_a), _dptr(d_uv_b),
+                                               C.c_double(ransac_thresh), int(min_inliers), _dptr(d_H), _dptr(d_found), _dptr(d_mask),
+                                               _dptr(d_out_ptr), _dptr(d_out_uv_a), _dptr(d_out_uv_b), _dptr(d_out_index),
+                                               C.c_void_p(stream) if stream else None), "ptz_match_gate_run_device")
+
+    def close(self):
+        if self.handle:
+            lib().ptz_match_gate_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gate_matches(match_ptr, uv_a, uv_b, ransac_thresh=4.0, min_inliers=0, max_pair_matches=4096, device_id=0, gate=None):
+    """Gate a CSR match set on the device (ptz_match_gate_run; through `gate`, or a MatchGate of the set's size).
+    Returns a dict of numpy arrays: H [n_pair, 3, 3] (zeros where found != 1), found [n_pair] (-1: more than max_pair_matches
+    matches), mask [n_match] (zeros where found != 1), out_ptr [n_pair + 1], out_uv_a / out_uv_b [n_kept, 2], out_index [n_kept],
+    and device_ms."""
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    a = np.ascontiguousarray(uv_a, dtype=np.float32).reshape(-1, 2)
+    b = np.ascontiguousarray(uv_b, dtype=np.float32).reshape(-1, 2)
+    n, nm = len(ptr) - 1, len(a)
+    H = np.zeros((n, 3, 3))
+    found = np.zeros(n, dtype=np.int32)
+    mask = np.zeros(nm, dtype=np.uint8)
+    out_ptr = np.zeros(n + 1, dtype=np.int64)
+    oa, ob = np.zeros((nm, 2), dtype=np.float32), np.zeros((nm, 2), dtype=np.float32)
+    oi = np.zeros(nm, dtype=np.int32)
+    ms = C.c_double()
+    g = gate if gate is not None else MatchGate(max(n, 1), nm, max_pair_matches, device_id)
+    try:
+        _check(lib().ptz_match_gate_run(g.handle, n, _p(ptr), _p(a), _p(b), C.c_double(ransac_thresh), int(min_inliers), _p(H), _p(found),
+                                        _p(mask), _p(out_ptr), _p(oa), _p(ob), _p(oi), C.byref(ms)), "ptz_match_gate_run")
+    finally:
+        if gate is None:
+            g.close()
+    k = int(out_ptr[-1])
+    return dict(H=H, found=found, mask=mask, out_ptr=out_ptr, out_uv_a=oa[:k], out_uv_b=ob[:k], out_index=oi[:k], device_ms=ms.value)
+
+
+def krt_solve_batch_gated(batch, max_reproj_error=100.0, ransac_thresh=4.0, min_inliers=0, **opt):
+    """ptz_krt_solve_batch_gated: krt_solve_batch on the RANSAC inliers of every query's matches (uv_ref -> uv_cur homography).
+    Returns (cam_world [n, 15], summaries, accepted, n_inliers [n], inlier_mask [n_match], H [n, 3, 3], (gate ms, LM ms))."""
+    o = default_options(**opt)
+    n = batch.n_query
+    ptr = np.ascontiguousarray(batch.match_ptr, dtype=np.int64)
+    uvr = np.ascontiguousarray(batch.uv_ref, dtype=np.float32)
+    uvc = np.ascontiguousarray(batch.uv_cur, dtype=np.float32)
+    cref = np.ascontiguousarray(batch.cam_ref, dtype=np.float64)
+    ccur = np.array(batch.cam_init, dtype=np.float64, order="C").copy()
+    summ = (LmSummary * n)()
+    acc = np.zeros(n, dtype=np.int32)
+    ninl = np.zeros(n, dtype=np.int32)
+    mask = np.zeros(int(ptr[-1]), dtype=np.uint8)
+    H = np.zeros((n, 3, 3))
+    ms = np.zeros(2)
+    _check(lib().ptz_krt_solve_batch_gated(n, _p(ptr), _p(uvr), _p(uvc), _p(cref), _p(ccur), batch.factor_type, C.c_double(max_reproj_error),
+                                           C.c_double(ransac_thresh), int(min_inliers), C.byref(o), summ, _p(acc), _p(ninl), _p(mask),
+                                           _p(H), _p(ms)), "ptz_krt_solve_batch_gated")
+    return ccur, [s.as_dict() for s in summ], acc, ninl, mask, H, (float(ms[0]), float(ms[1]))
 
 
 def krt_solve_batch(batch, max_reproj_error=100.0, **opt):

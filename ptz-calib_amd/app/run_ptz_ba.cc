@@ -50,7 +50,14 @@ int main(int argc, char** argv)
   parser.Add("output", 'o', "Output directory", true);
   parser.AddFlag("dist", "Whether images have distortion");
   parser.AddFlag("gpu_homography", "Compute the pair homographies of the match table on the GPU (same results)");
+  parser.AddFlag("inlier_matches", "Keep only the RANSAC inliers of every pair's homography (4 px) as the pair's matches");
+  parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
   parser.ParseCheck(argc, argv);
+  const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
+  if (min_inliers < 0) {
+    fprintf(stderr, "--min_inliers must not be negative\n");
+    return 1;
+  }
 
   std::vector<std::string> fnames;
   std::vector<ImageFeatures> features;
@@ -61,7 +68,9 @@ int main(int argc, char** argv)
   }
   std::vector<MatchesInfo> matches_info;
   const std::string matches_path = parser.Get("features") + "/pairs_matches.txt";
-  const bool loaded = parser.Exist("gpu_homography") ? LoadMatchesInfo(matches_path, fnames, features, matches_info, 0)
+  const bool gpu_h = parser.Exist("gpu_homography");
+  const bool loaded = parser.Exist("inlier_matches") ? LoadInlierMatchesInfo(matches_path, fnames, features, matches_info, gpu_h ? 0 : -1, min_inliers)
+                      : gpu_h                        ? LoadMatchesInfo(matches_path, fnames, features, matches_info, 0)
                                                      : LoadMatchesInfo(matches_path, fnames, features, matches_info);
   if (!loaded) {
     fprintf(stderr, "Error loading matches from %s. Exiting ...\n", matches_path.c_str());

@@ -1,6 +1,7 @@
 // run_ptz_reloc -- relocalise test images against calibrated reference images; same options, inputs and output file as the
 // reference tool (src/app/run_ptz_reloc.cc:23-148).  Where the reference runs one KRTOptimizer per test image in a loop
 // (:68-118), this tool gathers every test image's problem and solves them all in ONE ptz_krt_solve_batch launch.
+// --inlier_matches (not in the reference) solves on the RANSAC inliers of each query's matches: ptz_krt_solve_batch_gated.
 #include <cstdio>
 #include <string>
 #include <unordered_set>
@@ -37,7 +38,15 @@ int main(int argc, char** argv)
   parser.Add("test_features", '\0', "Test images features and matches directory", true);
   parser.Add("output", '\0', "Output directory", true);
   parser.AddFlag("dist", "Whether images have distortion");
+  parser.AddFlag("inlier_matches", "Solve each test image on the RANSAC inliers (homography, 4 px) of its matches; the reference image "
+                                   "is still the one with the most raw matches");
+  parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
   parser.ParseCheck(argc, argv);
+  const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
+  if (min_inliers < 0) {
+    fprintf(stderr, "--min_inliers must not be negative\n");
+    return 1;
+  }
 
   std::vector<std::string> ref_fnames, test_fnames;
   std::vector<ImageFeatures> ref_features, test_features;
@@ -103,16 +112,23 @@ int main(int argc, char** argv)
     const int32_t nq = static_cast<int32_t>(query_image.size());
     std::vector<ptz_lm_summary> summaries(nq);
     std::vector<int32_t> accepted(nq, 0);
-    const int32_t rc = ptz_krt_solve_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(),
-                                           parser.Exist("dist") ? PTZ_KRT_FDist : PTZ_KRT_F, MAX_REPROJ_ERROR, &opt, summaries.data(),
-                                           accepted.data(), nullptr);
+    const int32_t type = parser.Exist("dist") ? PTZ_KRT_FDist : PTZ_KRT_F;
+    static const double RANSAC_THRESH = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
+    const bool gated = parser.Exist("inlier_matches");
+    std::vector<int32_t> n_inliers(nq, 0);
+    const int32_t rc = gated ? ptz_krt_solve_batch_gated(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
+                                                       MAX_REPROJ_ERROR, RANSAC_THRESH, min_inliers, &opt, summaries.data(), accepted.data(),
+                                                       n_inliers.data(), nullptr, nullptr, nullptr)
+                           : ptz_krt_solve_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
+                                                 MAX_REPROJ_ERROR, &opt, summaries.data(), accepted.data(), nullptr);
     if (rc != PTZ_OK) {
       fprintf(stderr, "ptz_krt_solve_batch failed with status %d (no usable HIP device?)\n", rc);
       return -1;
     }
     for (int32_t q = 0; q < nq; ++q) {
       const size_t test_idx = query_image[q];
-      if (accepted[q]) {
+      // (a query the gate left without matches is solved on nothing and comes back as it went in: not a relocalization)
+      if (accepted[q] && (!gated || n_inliers[q] > 0)) {
         test_cameras[test_idx].FromVector(std::vector<double>(cam_cur.begin() + 15 * q, cam_cur.begin() + 15 * (q + 1)));
         success_ids.insert(static_cast<long>(test_idx));
         fprintf(stderr, "Running ptz-reloc success: %s\n", test_fnames[test_idx].c_str());

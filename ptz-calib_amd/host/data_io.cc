@@ -287,8 +287,30 @@ bool LoadImgsAndFeatures(const std::string& img_dir, const std::string& feature_
   return fnames.size() >= 2;
 }
 
-bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
-                     std::vector<MatchesInfo>& matches_info)
+namespace {
+
+// The cell's match fields from the pair's matches: all of them (gated = false, the reference's table), or the inlier-gated
+// form -- the matches with mask byte 1 in their order if the pair has a model and at least max(min_inliers, 4) of them, else none.
+void FillCellMatches(MatchesInfo& mi, const std::vector<DMatch>& ms, bool gated, bool found, const unsigned char* keep, int min_inliers)
+{
+  if (!gated) mi.matches = ms;
+  else {
+    mi.matches.clear();
+    size_t ones = 0;
+    for (size_t k = 0; found && k < ms.size(); ++k) ones += keep[k] != 0;
+    if (found && ones >= static_cast<size_t>(std::max(min_inliers, 4)))
+      for (size_t k = 0; k < ms.size(); ++k)
+        if (keep[k]) mi.matches.push_back(ms[k]);
+  }
+  const size_t n = mi.matches.size();
+  mi.inliers_mask.assign(n, 1);
+  mi.num_inliers = static_cast<int>(n);
+  static const int kMaxNumMatches = 100;  // CalMatchingScore (:358-366): float ratio, stored in a double
+  mi.confidence = static_cast<int>(n) >= kMaxNumMatches ? 1.0f : static_cast<float>(n) / static_cast<float>(kMaxNumMatches);
+}
+
+bool LoadMatchesInfoHost(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                         std::vector<MatchesInfo>& matches_info, bool inliers, int min_inliers)
 {
   std::vector<std::vector<DMatch>> pairs_matches;
   std::vector<std::pair<std::string, std::string>> img_pairs_name;
@@ -311,13 +333,10 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
     }
     if (!in_range) continue;
     MatchesInfo mi;
-    mi.matches = ms;
     static const double kRansacThresh = 4.0;
-    mi.H_empty = !FindHomographyRansac(a, b, kRansacThresh, mi.H);  // H_j_i: pixel of image i -> pixel of image j
-    mi.inliers_mask.assign(ms.size(), 1);
-    mi.num_inliers = static_cast<int>(ms.size());
-    static const int kMaxNumMatches = 100;  // CalMatchingScore (:358-366): float ratio, stored in a double
-    mi.confidence = static_cast<int>(ms.size()) >= kMaxNumMatches ? 1.0f : static_cast<float>(ms.size()) / static_cast<float>(kMaxNumMatches);
+    std::vector<unsigned char> mask;
+    mi.H_empty = !FindHomographyRansac(a, b, kRansacThresh, mi.H, inliers ? &mask : nullptr);  // H_j_i: pixel of image i -> pixel of image j
+    FillCellMatches(mi, ms, inliers, !mi.H_empty, mask.data(), min_inliers);
     mi.src_img_idx = index_i;
     mi.dst_img_idx = index_j;
     matches_info[static_cast<size_t>(index_i) * num_images + static_cast<size_t>(index_j)] = mi;
@@ -325,8 +344,8 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
   return true;
 }
 
-bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
-                     std::vector<MatchesInfo>& matches_info, int device_id)
+bool LoadMatchesInfoDevice(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                           std::vector<MatchesInfo>& matches_info, int device_id, bool inliers, int min_inliers)
 {
   std::vector<std::vector<DMatch>> pairs_matches;
   std::vector<std::pair<std::string, std::string>> img_pairs_name;
@@ -366,8 +385,9 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
     std::copy(I.begin(), I.end(), H.begin() + 9 * q);
   }
   static const double kRansacThresh = 4.0;
+  std::vector<uint8_t> mask(inliers ? std::max<size_t>(static_cast<size_t>(match_ptr.back()), 1) : 0);
   const int32_t rc = ptz_homography_ransac_batch(n_pair, match_ptr.data(), src_uv.data(), dst_uv.data(), kRansacThresh, device_id,
-                                                 H.data(), found.data(), nullptr, nullptr);
+                                                 H.data(), found.data(), inliers ? mask.data() : nullptr, nullptr);
   if (rc != PTZ_OK) {
     fprintf(stderr, "[ptzcalib] LoadMatchesInfo: ptz_homography_ransac_batch failed (%d)\n", rc);
     return false;
@@ -375,18 +395,35 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
   for (int q = 0; q < n_pair; ++q) {
     const std::vector<DMatch>& ms = pairs_matches[kept[q]];
     MatchesInfo mi;
-    mi.matches = ms;
     std::copy(H.begin() + 9 * q, H.begin() + 9 * q + 9, mi.H.begin());
     mi.H_empty = !found[q];
-    mi.inliers_mask.assign(ms.size(), 1);
-    mi.num_inliers = static_cast<int>(ms.size());
-    static const int kMaxNumMatches = 100;
-    mi.confidence = static_cast<int>(ms.size()) >= kMaxNumMatches ? 1.0f : static_cast<float>(ms.size()) / static_cast<float>(kMaxNumMatches);
+    FillCellMatches(mi, ms, inliers, found[q] != 0, inliers ? mask.data() + match_ptr[q] : nullptr, min_inliers);
     mi.src_img_idx = idx_i[q];
     mi.dst_img_idx = idx_j[q];
     matches_info[static_cast<size_t>(idx_i[q]) * num_images + static_cast<size_t>(idx_j[q])] = mi;
   }
   return true;
+}
+
+}  // namespace
+
+bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                     std::vector<MatchesInfo>& matches_info)
+{
+  return LoadMatchesInfoHost(matches_path, fnames, features, matches_info, false, 0);
+}
+
+bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                     std::vector<MatchesInfo>& matches_info, int device_id)
+{
+  return LoadMatchesInfoDevice(matches_path, fnames, features, matches_info, device_id, false, 0);
+}
+
+bool LoadInlierMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                           std::vector<MatchesInfo>& matches_info, int device_id, int min_inliers)
+{
+  return device_id < 0 ? LoadMatchesInfoHost(matches_path, fnames, features, matches_info, true, min_inliers)
+                       : LoadMatchesInfoDevice(matches_path, fnames, features, matches_info, device_id, true, min_inliers);
 }
 
 bool LoadAnnotation(const std::string& annot_path, const std::vector<std::string>& fnames, std::vector<std::vector<Point2f>>& pixels,

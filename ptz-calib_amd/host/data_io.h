@@ -33,6 +33,17 @@ bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::str
 // pairs skipped, the same fields, the same bits.  Returns false (after a message on stderr) if the device call fails.
 bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                      std::vector<MatchesInfo>& matches_info, int device_id);
+// The inlier-gated table: the reference drops the mask cv::findHomography returns (data_io.cc:351-352) and hands every listed
+// match on; here a cell's `matches` are the matches with mask byte 1 of the pair's RANSAC homography, in their order, if the
+// pair has a model and at least max(min_inliers, 4) of them, and none otherwise.  (Four matches fit a homography exactly: a
+// model with four inliers is verified by nothing.  kDefaultMinInliers is what the tools ask for.)  inliers_mask (all ones), num_inliers and confidence follow
+// the kept matches; H, H_empty and the image indices are those of the ungated loader, computed on ALL matches.  Whatever
+// reads `matches` (the track builder, the resident tables, CalPixelDiff, the rankings) then sees inliers only.
+// device_id < 0: the host estimator; otherwise the pair estimator runs on that device.  Both give the same table.
+bool LoadInlierMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                           std::vector<MatchesInfo>& matches_info, int device_id = -1, int min_inliers = 0);
+// cv::detail::BestOf2NearestMatcher's num_matches_thresh2: the inliers OpenCV's stitching matcher wants before it trusts a pair
+static const int kDefaultMinInliers = 6;
 bool LoadAnnotation(const std::string& annot_path, const std::vector<std::string>& fnames, std::vector<std::vector<Point2f>>& pixels,
                     std::vector<std::vector<Point3d>>& pts3d);
 void SaveRegisteredCam(const std::vector<Camera>& cameras, const std::unordered_set<long>& reg_image_ids,

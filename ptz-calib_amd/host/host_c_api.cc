@@ -387,13 +387,25 @@ static char* DupText(const std::string& s)
 // cmd = "load": a = image dir, b = feature dir  -> {ok, fnames, sizes, n_keypoints, first_keypoint, pairs:[{src,dst,n,H,H_empty,confidence}]}
 // cmd = "load_device": a = image dir, b = feature dir -> {ok, loaded, table_cells, pairs, n_pairs_found, identical}: the match table of
 //       LoadMatchesInfo(..., device 0) (pairs as for "load"), identical = every cell equal to the host loader's, H bit for bit
+// cmd = "load_inliers": a = image dir, b = feature dir -> {ok, table_cells, cells}: LoadInlierMatchesInfo with the host estimator; every
+//       cell that is not value-initialised as {cell, src, dst, matches:[[query, train]..], mask_ones, mask_len, num_inliers, H, H_empty,
+//       confidence}
+// cmd = "load_inliers_device": the same table from LoadInlierMatchesInfo(..., device 0) plus loaded, identical (every cell equal to the
+//       host-gated loader's, H bit for bit) and same_H (every cell's H / H_empty equal to the ungated device loader's)
+//       both take min_inliers after a colon ("load_inliers:6"; none = 0)
 // cmd = "annotation": a = annotation json, b = image dir (for the file names) -> {ok, pixels, pts3d}
 // cmd = "rewrite": a = camera json in, b = camera json out (ReadFromJson -> SaveToJson)  -> {ok, names}
 // cmd = "image_size": a = file -> {ok, width, height}
 // cmd = "json": a = JSON text -> {ok, dump}
 char* ptzh_io_probe(const char* cmd_c, const char* a_c, const char* b_c)
 {
-  const std::string cmd = cmd_c ? cmd_c : "", a = a_c ? a_c : "", b = b_c ? b_c : "";
+  std::string cmd = cmd_c ? cmd_c : "";
+  const std::string a = a_c ? a_c : "", b = b_c ? b_c : "";
+  int min_inliers = 0;  // "load_inliers:N"
+  if (cmd.rfind("load_inliers", 0) == 0 && cmd.find(':') != std::string::npos) {
+    min_inliers = atoi(cmd.c_str() + cmd.find(':') + 1);
+    cmd = cmd.substr(0, cmd.find(':'));
+  }
   Json out = Json::Object();
   if (cmd == "image_size") {
     Size sz;
@@ -480,6 +492,59 @@ char* ptzh_io_probe(const char* cmd_c, const char* a_c, const char* b_c)
       out["n_pairs_found"] = Json::Int(n_found);
     }
     out["pairs"] = jp;
+  }
+  else if (cmd == "load_inliers" || cmd == "load_inliers_device") {
+    std::vector<std::string> fnames;
+    std::vector<ImageFeatures> features;
+    std::vector<Size> sizes;
+    const bool ok = LoadImgsAndFeatures(a, b, fnames, features, sizes);
+    out["ok"] = Json::Bool(ok);
+    Json jc = Json::Array();
+    if (ok) {
+      const std::string mpath = b + "/pairs_matches.txt";
+      std::vector<MatchesInfo> mis;
+      LoadInlierMatchesInfo(mpath, fnames, features, mis, -1, min_inliers);
+      if (cmd == "load_inliers_device") {
+        std::vector<MatchesInfo> dev, plain;
+        const bool loaded = LoadInlierMatchesInfo(mpath, fnames, features, dev, 0, min_inliers) && LoadMatchesInfo(mpath, fnames, features, plain, 0);
+        out["loaded"] = Json::Bool(loaded);
+        bool same = mis.size() == dev.size(), same_H = plain.size() == dev.size();
+        for (size_t c = 0; same && c < mis.size(); ++c) {
+          const MatchesInfo &x = mis[c], &y = dev[c];
+          same = x.src_img_idx == y.src_img_idx && x.dst_img_idx == y.dst_img_idx && x.matches.size() == y.matches.size() &&
+                 x.inliers_mask == y.inliers_mask && x.num_inliers == y.num_inliers && x.H_empty == y.H_empty &&
+                 memcmp(x.H.data(), y.H.data(), sizeof(double) * 9) == 0 && memcmp(&x.confidence, &y.confidence, sizeof(double)) == 0;
+          for (size_t k = 0; same && k < x.matches.size(); ++k)
+            same = x.matches[k].queryIdx == y.matches[k].queryIdx && x.matches[k].trainIdx == y.matches[k].trainIdx;
+        }
+        for (size_t c = 0; same_H && c < dev.size(); ++c)
+          same_H = plain[c].H_empty == dev[c].H_empty && memcmp(plain[c].H.data(), dev[c].H.data(), sizeof(double) * 9) == 0;
+        out["identical"] = Json::Bool(same);
+        out["same_H"] = Json::Bool(same_H);
+        mis.swap(dev);
+      }
+      out["table_cells"] = Json::Int(static_cast<long long>(mis.size()));
+      for (size_t c = 0; c < mis.size(); ++c) {
+        const MatchesInfo& mi = mis[c];
+        if (mi.matches.empty() && mi.H_empty && mi.src_img_idx == 0 && mi.dst_img_idx == 0) continue;
+        Json p = Json::Object();
+        p["cell"] = Json::Int(static_cast<long long>(c));
+        p["src"] = Json::Int(mi.src_img_idx); p["dst"] = Json::Int(mi.dst_img_idx);
+        Json jm = Json::Array();
+        for (const DMatch& m : mi.matches) jm.push_back(Json::FloatArray({static_cast<double>(m.queryIdx), static_cast<double>(m.trainIdx)}));
+        p["matches"] = jm;
+        long long ones = 0;
+        for (unsigned char v : mi.inliers_mask) ones += v == 1;
+        p["mask_ones"] = Json::Int(ones);
+        p["mask_len"] = Json::Int(static_cast<long long>(mi.inliers_mask.size()));
+        p["num_inliers"] = Json::Int(mi.num_inliers);
+        p["H"] = Json::FloatArray(std::vector<double>(mi.H.begin(), mi.H.end()));
+        p["H_empty"] = Json::Bool(mi.H_empty);
+        p["confidence"] = Json::Float(mi.confidence);
+        jc.push_back(p);
+      }
+    }
+    out["cells"] = jc;
   }
   else if (cmd == "annotation") {
     std::vector<std::string> fnames;

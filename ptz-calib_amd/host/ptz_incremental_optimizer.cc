@@ -152,7 +152,10 @@ bool PtzIncrementalOptimizer::Solve(std::vector<Camera>& cameras, std::unordered
   by_dst_.assign(features_.size(), {});
   for (size_t e = 0; e < matches_info_.size(); ++e) {
     const MatchesInfo& mi = matches_info_[e];
-    if (!mi.H_empty && mi.dst_img_idx >= 0 && static_cast<size_t>(mi.dst_img_idx) < by_dst_.size()) by_dst_[mi.dst_img_idx].push_back(e);
+    // (an inlier-gated table has cells with a homography and no matches left, LoadInlierMatchesInfo: an attempt on nothing
+    //  would be "accepted" with its initial camera, so such a cell is no attempt; without gating a homography means >= 4 matches)
+    if (!mi.H_empty && !mi.matches.empty() && mi.dst_img_idx >= 0 && static_cast<size_t>(mi.dst_img_idx) < by_dst_.size())
+      by_dst_[mi.dst_img_idx].push_back(e);
   }
 
   const int kInitNumTrials = 50;
