@@ -420,6 +420,56 @@ int32_t ptz_krt_solve_batch_gated(int32_t n_query, const int64_t* match_ptr, con
  * entries: ptz_debug_homography_bounds size after size. */
 int32_t ptz_debug_match_gate_table(int32_t max_pair_matches, int32_t* table, int64_t* table_len, int64_t* offsets);
 
+/* ------------------------------------------------------------------------------------------------
+ * Covariance of relocalized cameras (per query)
+ * ------------------------------------------------------------------------------------------------ */
+/* what calibration tools report beside a camera (cv::calibrateCamera's stdDeviations, ceres::Covariance) and the reference
+ * does not: its only quality signal is the mean reprojection error against max_reproj_error (CheckResults,
+ * krt_optimizer.cc:504-533), which a well and an ill constrained camera pass alike.
+ * For query q: the refined camera cam_cur (world frame, as ptz_krt_solve_batch returns it) is moved into the local frame of
+ * cam_ref as the solve does (krt_optimizer.cc:269-284).  Free parameters p = [fx, (fy), d1, d2, d3, (k1)], NF =
+ * ptz_krt_free_dim(factor_type) of them; d is a LEFT perturbation of the current rotation, R <- Exp(d) R, in radians about the
+ * current camera's own x (right), y (down), z (forward) axes -- it perturbs the world rotation R_local R_ref in the same way,
+ * so the result does not depend on the reference view.  F / FDist: fy := fx as in the solve.  Residual blocks that count:
+ * every match whose match_mask byte is non-zero (all, if match_mask = NULL) and that the border guard of the distortion
+ * variants does not skip (krt_optimizer.cc:97-101), and every 2D-3D point; B blocks, m = 2 B residuals.  N = J^T J and
+ * cost = 1/2 sum r^2 over them, sigma0^2 = 2 cost / (m - NF);  cov = sigma0^2 N^-1 if pixel_sigma = 0 (a-posteriori),
+ * pixel_sigma^2 N^-1 if pixel_sigma > 0 (a-priori); sigma0 is returned either way.  N is scaled to unit diagonal, factored by
+ * Cholesky and inverted in registers.  status[q]:
+ *   PTZ_COV_OK        covariance computed: cov [NF * NF] row-major and sigma0 written;
+ *   PTZ_COV_DOF       m <= NF (B = 0 included);
+ *   PTZ_COV_SINGULAR  a diagonal entry of N not positive and finite, a pivot of the scaled matrix <= 1e-10, or a non-finite cost
+ *                     or covariance;
+ *   PTZ_COV_SKIPPED   `accepted` given and accepted[q] = 0 (the solve never wrote that query's cam_cur);
+ * with every status but PTZ_COV_OK the query's cov and sigma0 are left untouched.  One reduction order whatever the launch: sixteen
+ * lanes per query, lane l sums matches l, l + 16, .. and then points l, l + 16, .., the lanes are added by the butterfly
+ * l ^ 8, l ^ 4, l ^ 2, l ^ 1 -- a query's bits depend on its own data only, not on its neighbours or their number.
+ * match_mask takes the inlier_mask of ptz_krt_solve_batch_gated as it is; point_ptr = pts2d = pts3d = NULL: no 2D-3D blocks.
+ * PTZ_EINVAL, before any device work: n_query < 0, match_ptr[0] != 0 or decreasing offsets, NULL required arrays with non-zero
+ * extents, pixel_sigma negative or not finite, point_ptr without pts2d / pts3d; PTZ_EUNSUPPORTED: factor_type;
+ * n_query = 0 is PTZ_OK; PTZ_ENODEVICE without a device (no CPU fallback). */
+#define PTZ_COV_OK 0
+#define PTZ_COV_DOF 1
+#define PTZ_COV_SINGULAR 2
+#define PTZ_COV_SKIPPED 3
+/* Host logic only: free parameters of a factor type -- 4, 5, 5, 6 for F, FDist, Fxfy, FxfyDist; PTZ_EUNSUPPORTED otherwise. */
+int32_t ptz_krt_free_dim(int32_t factor_type);
+int32_t ptz_krt_covariance_batch(int32_t n_query, const int64_t* match_ptr, const float* uv_ref, const float* uv_cur,
+                                 const int64_t* point_ptr, const float* pts2d, const double* pts3d, const double* cam_ref,
+                                 const double* cam_cur /* refined, world frame */, int32_t factor_type,
+                                 const uint8_t* match_mask /* [n_match] or NULL */, const int32_t* accepted /* [n_query] or NULL */,
+                                 double pixel_sigma, int32_t device_id, double* cov /* [NF * NF * n_query] row-major */,
+                                 double* sigma0 /* [n_query] */, int32_t* status /* [n_query] */, double* device_ms /* or NULL */);
+/* The same launch on DEVICE pointers: enqueued on `hip_stream` (NULL = the default stream) of the device that owns d_cam_cur,
+ * returns without synchronising.  Behind ptz_krt_solve_batch_device on the same stream it takes the d_cam_cur and d_accepted that
+ * call wrote, with no host round trip.  The CSR offsets are not validated (they live on the device); PTZ_EINVAL also for a
+ * stream of another device than the buffers. */
+int32_t ptz_krt_covariance_batch_device(int32_t n_query, const int64_t* d_match_ptr, const float* d_uv_ref, const float* d_uv_cur,
+                                        const int64_t* d_point_ptr, const float* d_pts2d, const double* d_pts3d,
+                                        const double* d_cam_ref, const double* d_cam_cur, int32_t factor_type,
+                                        const uint8_t* d_match_mask, const int32_t* d_accepted, double pixel_sigma, double* d_cov,
+                                        double* d_sigma0, int32_t* d_status, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

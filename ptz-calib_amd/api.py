@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PTZCALIB_LIB", os.path.join(_HERE, "libptzcalib_hip.s
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 BA_PTZRay, BA_PTZRayDist, BA_PTZRayFxfyDist, BA_PTZRayDistDisp = 0, 1, 2, 3
 KRT_F, KRT_FDist, KRT_Fxfy, KRT_FxfyDist = 0, 1, 2, 3
+COV_OK, COV_DOF, COV_SINGULAR, COV_SKIPPED = 0, 1, 2, 3
 PROF_SLOTS = 16
 _ERR = {-1: "PTZ_EINVAL", -2: "PTZ_ENODEVICE", -3: "PTZ_ENOMEM", -4: "PTZ_EUNSUPPORTED", -5: "PTZ_ELIMIT", -6: "PTZ_ENOOBS"}
 
@@ -28,7 +29,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_ba_plan_tile_order", "ptz_rig_create", "ptz_rig_destroy", "ptz_ba_batch_create_views", "ptz_ba_batch_set_state_pix2ray",
            "ptz_debug_batch_structure_hash", "ptz_debug_batch_initial_rays", "ptz_krt_table_create", "ptz_krt_table_destroy",
            "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds", "ptz_match_gate_create",
-           "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table"]
+           "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table",
+           "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device"]
 
 
 class PtzError(RuntimeError):
@@ -78,6 +80,7 @@ def lib():
         _lib.ptz_version.restype = C.c_char_p
         _lib.ptz_device_count.restype = C.c_int32
         _lib.ptz_ba_cam_block_dim.restype = C.c_int32
+        _lib.ptz_krt_free_dim.restype = C.c_int32
     return _lib
 
 
@@ -611,6 +614,61 @@ def krt_solve_batch_device(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_cam_ref, 
                                             ptr(d_pts3d), ptr(d_cam_ref), ptr(d_cam_cur), int(factor_type), C.c_double(max_reproj_error),
                                             C.byref(o), ptr(d_summaries), ptr(d_accepted), C.c_void_p(stream) if stream else None),
            "ptz_krt_solve_batch_device")
+
+
+def krt_free_dim(factor_type) -> int:
+    """ptz_krt_free_dim: free parameters [fx, (fy), d1, d2, d3, (k1)] of a factor type (4, 5, 5, 6)."""
+    nf = int(lib().ptz_krt_free_dim(int(factor_type)))
+    if nf < 0:
+        raise PtzError(nf, "ptz_krt_free_dim")
+    return nf
+
+
+def krt_covariance_batch(batch, cam_cur, match_mask=None, accepted=None, pixel_sigma=0.0, device_id=0, cov=None, sigma0=None):
+    """ptz_krt_covariance_batch: covariance of the refined cameras cam_cur [n, 15] (world frame, as krt_solve_batch returns them)
+    of the queries of `batch` (synth.RelocBatch-like: match_ptr, uv_ref, uv_cur, cam_ref, factor_type, optional point_ptr /
+    pts2d / pts3d).  match_mask [n_match] uint8 (the inlier mask of krt_solve_batch_gated) and accepted [n] int32 are optional.
+    Returns (cov [n, NF, NF], sigma0 [n], status [n], device_ms); parameters [fx, (fy), d1, d2, d3, (k1)], rotations in radians
+    about the camera's own axes.  Entries of queries whose status is not COV_OK keep what `cov` / `sigma0` held (NaN if not given)."""
+    n = batch.n_query
+    nf = krt_free_dim(batch.factor_type)
+    ptr = np.ascontiguousarray(batch.match_ptr, dtype=np.int64)
+    uvr = np.ascontiguousarray(batch.uv_ref, dtype=np.float32)
+    uvc = np.ascontiguousarray(batch.uv_cur, dtype=np.float32)
+    cref = np.ascontiguousarray(batch.cam_ref, dtype=np.float64)
+    ccur = np.ascontiguousarray(cam_cur, dtype=np.float64)
+    pp = p2 = p3 = None
+    if getattr(batch, "point_ptr", None) is not None:
+        pp = np.ascontiguousarray(batch.point_ptr, dtype=np.int64)
+        p2 = np.ascontiguousarray(batch.pts2d, dtype=np.float32)
+        p3 = np.ascontiguousarray(batch.pts3d, dtype=np.float64)
+    mk = None if match_mask is None else np.ascontiguousarray(match_mask, dtype=np.uint8)
+    ac = None if accepted is None else np.ascontiguousarray(accepted, dtype=np.int32)
+    if mk is not None and len(mk) != int(ptr[-1]):
+        raise ValueError("match_mask must have one byte per match")
+    if ac is not None and len(ac) != n:
+        raise ValueError("accepted must have one entry per query")
+    cov = np.full((n, nf, nf), np.nan) if cov is None else np.ascontiguousarray(cov, dtype=np.float64).reshape(n, nf, nf)
+    sigma0 = np.full(n, np.nan) if sigma0 is None else np.ascontiguousarray(sigma0, dtype=np.float64).reshape(n)
+    status = np.full(n, -1, dtype=np.int32)
+    ms = C.c_double()
+    _check(lib().ptz_krt_covariance_batch(n, _p(ptr), _p(uvr), _p(uvc), _p(pp), _p(p2), _p(p3), _p(cref), _p(ccur), int(batch.factor_type),
+                                          _p(mk), _p(ac), C.c_double(pixel_sigma), int(device_id), _p(cov), _p(sigma0), _p(status),
+                                          C.byref(ms)), "ptz_krt_covariance_batch")
+    return cov, sigma0, status, ms.value
+
+
+def krt_covariance_batch_device(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_cam_ref, d_cam_cur, d_cov, d_sigma0, d_status, factor_type=0,
+                                d_point_ptr=None, d_pts2d=None, d_pts3d=None, d_match_mask=None, d_accepted=None, pixel_sigma=0.0,
+                                stream=None):
+    """ptz_krt_covariance_batch_device: every d_* is a device buffer (torch tensor or integer address); enqueues on `stream`
+    (integer hipStream_t handle, None = default stream) and returns without synchronising -- behind krt_solve_batch_device on the
+    same stream it reads the d_cam_cur and d_accepted that call wrote."""
+    _check(lib().ptz_krt_covariance_batch_device(int(n_query), _dptr(d_match_ptr), _dptr(d_uv_ref), _dptr(d_uv_cur), _dptr(d_point_ptr),
+                                                 _dptr(d_pts2d), _dptr(d_pts3d), _dptr(d_cam_ref), _dptr(d_cam_cur), int(factor_type),
+                                                 _dptr(d_match_mask), _dptr(d_accepted), C.c_double(pixel_sigma), _dptr(d_cov),
+                                                 _dptr(d_sigma0), _dptr(d_status), C.c_void_p(stream) if stream else None),
+           "ptz_krt_covariance_batch_device")
 
 
 def mfma_f64_peak(device_id=0):

@@ -65,4 +65,10 @@ class Args {
   std::string prog_;
 };
 
+// --uncertainty of run_ptz_reloc (not in the reference): parameter standard deviations beside every registered camera
+static const char* const kUncertaintyFlag = "uncertainty";
+static const char* const kUncertaintyHelp =
+    "Write sigma_f (px), sigma_rot_deg (about the camera's x, y, z axes) and sigma0 (estimated pixel noise) into every registered "
+    "image's record: the covariance of its camera over the matches it was solved on";
+
 }  // namespace ptzapp

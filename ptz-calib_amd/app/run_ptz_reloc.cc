@@ -2,7 +2,12 @@
 // reference tool (src/app/run_ptz_reloc.cc:23-148).  Where the reference runs one KRTOptimizer per test image in a loop
 // (:68-118), this tool gathers every test image's problem and solves them all in ONE ptz_krt_solve_batch launch.
 // --inlier_matches (not in the reference) solves on the RANSAC inliers of each query's matches: ptz_krt_solve_batch_gated.
+// --uncertainty (not in the reference) adds the standard deviations of focal length and rotation to every registered image's
+// record, from ONE ptz_krt_covariance_batch call over all test images.
+#include <cmath>
 #include <cstdio>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <unordered_set>
 #include <utility>
@@ -10,6 +15,7 @@
 
 #include "../../include/ptz_calib_amd.h"
 #include "../host/data_io.h"
+#include "../host/json_mini.h"
 #include "args.h"
 
 using namespace ptzcalib;
@@ -41,6 +47,7 @@ int main(int argc, char** argv)
   parser.AddFlag("inlier_matches", "Solve each test image on the RANSAC inliers (homography, 4 px) of its matches; the reference image "
                                    "is still the one with the most raw matches");
   parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
+  parser.AddFlag(ptzapp::kUncertaintyFlag, ptzapp::kUncertaintyHelp);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -103,6 +110,9 @@ int main(int argc, char** argv)
 
   std::vector<Camera> test_cameras(test_fnames.size());
   std::unordered_set<long> success_ids;
+  const bool uncertainty = parser.Exist(ptzapp::kUncertaintyFlag);
+  struct Sigma { bool ok = false; double f = 0, rot_deg[3] = {0, 0, 0}, s0 = 0; };
+  std::vector<Sigma> sigmas(test_fnames.size());
   if (!query_image.empty()) {
     static const int MAX_ITER = 200;
     static const double MAX_REPROJ_ERROR = 100.0;
@@ -116,9 +126,10 @@ int main(int argc, char** argv)
     static const double RANSAC_THRESH = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
     const bool gated = parser.Exist("inlier_matches");
     std::vector<int32_t> n_inliers(nq, 0);
+    std::vector<uint8_t> inlier_mask(gated && uncertainty ? uv_ref.size() / 2 : 0);  // the covariance is over the matches a query kept
     const int32_t rc = gated ? ptz_krt_solve_batch_gated(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
                                                        MAX_REPROJ_ERROR, RANSAC_THRESH, min_inliers, &opt, summaries.data(), accepted.data(),
-                                                       n_inliers.data(), nullptr, nullptr, nullptr)
+                                                       n_inliers.data(), inlier_mask.empty() ? nullptr : inlier_mask.data(), nullptr, nullptr)
                            : ptz_krt_solve_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
                                                  MAX_REPROJ_ERROR, &opt, summaries.data(), accepted.data(), nullptr);
     if (rc != PTZ_OK) {
@@ -135,6 +146,27 @@ int main(int argc, char** argv)
       }
       else fprintf(stderr, "Running ptz-reloc failed: %s\n", test_fnames[test_idx].c_str());
     }
+    if (uncertainty) {
+      const int32_t nf = ptz_krt_free_dim(type);  // [fx, d1, d2, d3, (k1)]
+      std::vector<double> cov(static_cast<size_t>(nf) * nf * nq, 0.0), sigma0(nq, 0.0);
+      std::vector<int32_t> status(nq, -1);
+      const int32_t rc_cov = ptz_krt_covariance_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), nullptr, nullptr, nullptr, cam_ref.data(),
+                                                      cam_cur.data(), type, gated ? inlier_mask.data() : nullptr, accepted.data(), 0.0,
+                                                      opt.device_id, cov.data(), sigma0.data(), status.data(), nullptr);
+      if (rc_cov != PTZ_OK) {
+        fprintf(stderr, "ptz_krt_covariance_batch failed with status %d\n", rc_cov);
+        return -1;
+      }
+      for (int32_t q = 0; q < nq; ++q) {
+        if (status[q] != PTZ_COV_OK) continue;
+        Sigma& s = sigmas[query_image[q]];
+        const double* c = cov.data() + static_cast<size_t>(nf) * nf * q;
+        s.ok = true;
+        s.f = std::sqrt(c[0]);
+        for (int k = 0; k < 3; ++k) s.rot_deg[k] = std::sqrt(c[(1 + k) * nf + 1 + k]) * 180.0 / M_PI;
+        s.s0 = sigma0[q];
+      }
+    }
   }
 
   const std::string cam_id = BaseName(parser.Get("test_images"));
@@ -142,6 +174,35 @@ int main(int argc, char** argv)
   MkdirIfNotExist(out_dir);
   std::vector<std::vector<Point2f>> pixels(test_fnames.size());
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
-  SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_dir + "/" + cam_id + ".json");
+  const std::string out_path = out_dir + "/" + cam_id + ".json";
+  SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
+  if (uncertainty) {
+    // the three keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
+    // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
+    std::stringstream ss;
+    {
+      std::ifstream in(out_path);
+      ss << in.rdbuf();
+    }
+    Json all;
+    if (!Json::Parse(ss.str(), all) || !all.contains("cameras")) {
+      fprintf(stderr, "Error reading back %s\n", out_path.c_str());
+      return -1;
+    }
+    Json& cams = all["cameras"];
+    for (size_t i = 0; i < test_fnames.size(); ++i) {
+      if (!success_ids.count(static_cast<long>(i)) || !sigmas[i].ok) continue;
+      std::string rootname, ext;
+      SplitExt(test_fnames[i], &rootname, &ext);
+      if (!cams.contains(rootname)) continue;
+      Json& j = cams[rootname];
+      j["sigma_f"] = Json::Float(sigmas[i].f);
+      j["sigma_rot_deg"] = Json::FloatArray({sigmas[i].rot_deg[0], sigmas[i].rot_deg[1], sigmas[i].rot_deg[2]});
+      j["sigma0"] = Json::Float(sigmas[i].s0);
+    }
+    std::ofstream fout(out_path, std::ios_base::out);
+    if (!fout.good()) return -1;
+    fout << all.dump(4) << std::endl;
+  }
   return 0;
 }

@@ -1,0 +1,103 @@
+// ptz_krt_device.h -- device helpers shared by the single-view kernels: k_krt (ptz_krt.hip) and k_krt_cov (ptz_krt_cov.hip).
+#pragma once
+
+#include "ptz_common.h"
+#include "ptz_factor.h"
+
+namespace ptz {
+
+// 15-vector index of free parameter k: F {0,4,5,6}, FDist {0,4,5,6,10}, Fxfy {0,1,4,5,6}, FxfyDist {0,1,4,5,6,10}
+template <int KTYPE> struct KFree {
+  static __device__ __forceinline__ int at(int k)
+  {
+    constexpr int ROT0 = KrtDims<KTYPE>::ROT0;
+    return k < ROT0 ? k : (k < ROT0 + 3 ? 4 + (k - ROT0) : 10);
+  }
+};
+
+// in-register Cholesky solve of an NF x NF SPD system (row-major full storage); false if not SPD
+template <int NF>
+__device__ __forceinline__ bool spd_solve(double* A, double* b)
+{
+  double inv[NF];  // 1 / L_jj
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    double d = A[j * NF + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= A[j * NF + k] * A[j * NF + k];
+    if (!(d > 0.0)) return false;
+    // (round 6) ONE reciprocal per column -- 1 / sqrt(d) to working precision (rsq + two Newton steps) -- instead of a square root and
+    // 2 (NF - 1 - j) + 2 IEEE divisions by it: a division is ~18 instructions on this chip and the solve had twenty of them, every
+    // lane of the group its own copy.  The factor and the solution differ from the divided form in the last bits (the step is held
+    // to the oracle's QR step at 1e-6 either way).
+    double rs = __builtin_amdgcn_rsq(d);
+    rs = rs * (1.5 - 0.5 * d * rs * rs);
+    rs = rs * (1.5 - 0.5 * d * rs * rs);
+    inv[j] = rs;
+    A[j * NF + j] = d * rs;
+#pragma unroll
+    for (int i = j + 1; i < NF; ++i) {
+      double v = A[i * NF + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= A[i * NF + k] * A[j * NF + k];
+      A[i * NF + j] = v * rs;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NF; ++i) {
+    double v = b[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= A[i * NF + k] * b[k];
+    b[i] = v * inv[i];
+  }
+#pragma unroll
+  for (int i = NF - 1; i >= 0; --i) {
+    double v = b[i];
+#pragma unroll
+    for (int k = i + 1; k < NF; ++k) v -= A[k * NF + i] * b[k];
+    b[i] = v * inv[i];
+  }
+  return true;
+}
+
+template <int KTYPE>
+struct MatchEval {
+  // constant part of a match: unit ray of the reference pixel in the local frame (krt_optimizer.cc:31-33,
+  // 89-104) and the border guard of the distortion variant (:97-101)
+  static __device__ __forceinline__ void ray1(const double* kref, const double* dref, float u1, float v1, double r[3], bool& skip)
+  {
+    double u = u1, v = v1;
+    skip = false;
+    if (KTYPE & 1) {
+      float ou, ov;
+      undistort_point(kref[0], kref[1], kref[2], kref[3], dref, u1, v1, ou, ov);
+      skip = (ou < 0 || ou >= kref[2] * 2 || ov < 0 || ov >= kref[3] * 2);
+      u = ou; v = ov;
+    }
+    const double X0 = (u - kref[2]) / kref[0], X1 = (v - kref[3]) / kref[1];
+    const double n = sqrt(X0 * X0 + X1 * X1 + 1.0);
+    r[0] = X0 / n; r[1] = X1 / n; r[2] = 1.0 / n;
+  }
+};
+
+// Lanes per query.  G = 64 (a wave per query) is the latency form: a registration attempt of the incremental pipeline or a
+// handful of queries are as fast as they can be.  G = 16 (four queries per wave) is the throughput form for launches of
+// thousands of queries of a few hundred matches each: with 128 matches a wave of 64 has two matches per lane and then spends
+// as long on its 15 six-step reductions and on 64 redundant copies of one 4 x 4 solve as on the matches; 16 lanes take eight
+// matches each, reduce in four steps, and a wave's redundant solves serve four queries.  The two forms sum in different
+// orders: a query's bits depend on the form, never on its neighbours in the launch (ptz_krt_solve_batch picks the form from
+// the launch size alone, krt_group_size()).
+// (the butterfly v += v[lane ^ off], off = G / 2 .. 1, with the partners fetched by v_permlane32/16_swap and DPP instead of
+//  ds_bpermute -- 21 sums of four to six steps per linearisation: the same partners, the same sums, the same bits)
+template <int G> __device__ __forceinline__ double group_sum(double v)
+{
+  static_assert(G == 64 || G == 16, "a wave or a DPP row of lanes per query");
+  if (G == 64) return wave_sum(v);
+  v += lane_xor_dpp<8>(v);
+  v += lane_xor_dpp<4>(v);
+  v += lane_xor_dpp<2>(v);
+  v += lane_xor_dpp<1>(v);
+  return v;
+}
+
+}  // namespace ptz

@@ -670,4 +670,49 @@ int32_t ptzh_krt_solve_2d3d(const double* cam_ref15, double* cam_cur15, int32_t 
   return ok ? 1 : 0;
 }
 
+// KRTOptimizer::Solve followed by Covariance / StdDevs (n_pt = 0: no 2D-3D constraints).  cov needs room for 36 doubles; sig = {sigma_f,
+// sigma_rot x, y, z, sigma0}.  before_solve = the answer of Covariance() on the object before Solve() (must be 0).  Returns
+// Solve() | Covariance() << 1 | StdDevs() << 2.
+int32_t ptzh_krt_solve_cov(const double* cam_ref15, double* cam_cur15, int32_t n_match, const float* uv_ref, const float* uv_cur, int32_t n_pt,
+                           const float* pts2d, const double* pts3d, int32_t max_iter, double max_reproj_error, int32_t type, double* cov,
+                           double* sig, int32_t* before_solve)
+{
+  Camera ref, cur;
+  ref.FromVector(std::vector<double>(cam_ref15, cam_ref15 + 15));
+  cur.FromVector(std::vector<double>(cam_cur15, cam_cur15 + 15));
+  std::vector<KeyPoint> kr(n_match), kc(n_match);
+  std::vector<DMatch> ms(n_match);
+  for (int m = 0; m < n_match; ++m) {
+    kr[m].pt = Point2f(uv_ref[2 * m], uv_ref[2 * m + 1]);
+    kc[m].pt = Point2f(uv_cur[2 * m], uv_cur[2 * m + 1]);
+    ms[m].queryIdx = m; ms[m].trainIdx = m;
+  }
+  std::vector<Point2f> p2(n_pt);
+  std::vector<Point3d> p3(n_pt);
+  for (int i = 0; i < n_pt; ++i) {
+    p2[i] = Point2f(pts2d[2 * i], pts2d[2 * i + 1]);
+    p3[i] = Point3d(pts3d[3 * i], pts3d[3 * i + 1], pts3d[3 * i + 2]);
+  }
+  KRTOptimizer opt(max_iter, max_reproj_error, static_cast<KRTOptimizer::FACTOR_TYPE>(type));
+  opt.SetInitParams(cur.K(), cur.R(), cur.t(), cur.dist());
+  opt.Add2d2dConstraints(ref, kr, kc, ms);
+  if (n_pt > 0) opt.Add2d3dConstraints(p2, p3);
+  std::vector<double> c;
+  double s0 = 0;
+  if (before_solve) *before_solve = opt.Covariance(c, s0) ? 1 : 0;
+  Mat33 K, R; Vec3 t; Vec5 dist;
+  const bool ok = opt.Solve(K, R, t, dist);
+  if (ok) {
+    const std::vector<double> v = Camera(K, R, t, dist).ToVector();
+    memcpy(cam_cur15, v.data(), sizeof(double) * 15);
+  }
+  const bool okc = opt.Covariance(c, s0);
+  if (okc) {
+    memcpy(cov, c.data(), sizeof(double) * c.size());
+    sig[4] = s0;
+  }
+  const bool oks = opt.StdDevs(sig[0], sig + 1);
+  return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
+}
+
 }  // extern "C"

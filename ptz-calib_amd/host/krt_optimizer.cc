@@ -64,10 +64,45 @@ bool KRTOptimizer::Solve(Mat33& K, Mat33& R, Vec3& t, Vec5& dist)
   num_iter_ = summary_.num_successful_steps;  // krt_optimizer.cc:396
   if (!accepted) return false;                // CheckResults, :504-533
   cam_curr_world_.FromVector(cur);            // ObtainRefinedCameraParams, :535-567 (done on the device, world frame)
+  solved_ = true;
   K = cam_curr_world_.K();
   dist = cam_curr_world_.dist();
   R = cam_curr_world_.R();
   t = cam_curr_world_.t();
+  return true;
+}
+
+bool KRTOptimizer::Covariance(std::vector<double>& cov, double& sigma0) const
+{
+  if (!solved_ || uv_ref_.empty()) return false;
+  const int32_t nf = ptz_krt_free_dim(static_cast<int32_t>(factor_type_));
+  if (nf <= 0) return false;
+  const int64_t match_ptr[2] = {0, static_cast<int64_t>(uv_ref_.size() / 2)};
+  const int64_t point_ptr[2] = {0, static_cast<int64_t>(pts2d_.size() / 2)};
+  const bool p3 = !pts2d_.empty();
+  const std::vector<double> ref = cam_ref_.ToVector(), cur = cam_curr_world_.ToVector();
+  std::vector<double> c(static_cast<size_t>(nf) * nf, 0.0);
+  double s0 = 0;
+  int32_t status = -1;
+  if (ptz_krt_covariance_batch(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, p3 ? pts2d_.data() : nullptr,
+                               p3 ? pts3d_.data() : nullptr, ref.data(), cur.data(), static_cast<int32_t>(factor_type_), nullptr, nullptr,
+                               0.0, device_id_, c.data(), &s0, &status, nullptr) != PTZ_OK ||
+      status != PTZ_COV_OK)
+    return false;
+  cov.swap(c);
+  sigma0 = s0;
+  return true;
+}
+
+bool KRTOptimizer::StdDevs(double& sigma_f, double sigma_rot[3]) const
+{
+  std::vector<double> cov;
+  double s0;
+  if (!Covariance(cov, s0)) return false;
+  const int nf = ptz_krt_free_dim(static_cast<int32_t>(factor_type_));
+  const int rot0 = (factor_type_ == Fxfy || factor_type_ == FxfyDist) ? 2 : 1;  // [fx, (fy), d1, d2, d3, (k1)]
+  sigma_f = std::sqrt(cov[0]);
+  for (int k = 0; k < 3; ++k) sigma_rot[k] = std::sqrt(cov[(rot0 + k) * nf + rot0 + k]);
   return true;
 }
 

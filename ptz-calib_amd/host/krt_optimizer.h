@@ -22,6 +22,14 @@ class KRTOptimizer {
   double Cal2d2dReprojError(const Camera& cam_ref, const std::vector<KeyPoint>& kpts_ref, const std::vector<KeyPoint>& kpts_curr,
                             const std::vector<DMatch>& matches);
   double Cal2d3dReprojError(const std::vector<Point2f>& pts2d, const std::vector<Point3d>& pts3d);
+  // Covariance of the refined camera over the constraints this object holds (ptz_krt_covariance_batch with one query, a-posteriori
+  // scale): cov = [NF x NF] row-major in the parameters [fx, (fy), d1, d2, d3, (k1)], NF = ptz_krt_free_dim(factor type), d a left
+  // perturbation of the rotation in radians about the camera's own axes; sigma0 = the estimated pixel noise.  Valid after a Solve()
+  // that returned true; false otherwise, without a device, or when the query's status is not PTZ_COV_OK (too few constraints,
+  // a singular normal matrix).
+  bool Covariance(std::vector<double>& cov, double& sigma0) const;
+  // the square roots of its diagonal: focal length (fx) in pixels, rotation about x, y, z in radians
+  bool StdDevs(double& sigma_f, double sigma_rot[3]) const;
   void SetFixedFocal() { set_fixed_focal_ = true; }  // a flag nobody reads, as in the reference (krt_optimizer.cc:502)
   int num_iter_ = 0;
 
@@ -32,7 +40,7 @@ class KRTOptimizer {
   Camera cam_curr_world_, cam_ref_;
   std::vector<float> uv_ref_, uv_cur_, pts2d_;
   std::vector<double> pts3d_;
-  bool has_2d2d_ = false, set_fixed_focal_ = false;
+  bool has_2d2d_ = false, set_fixed_focal_ = false, solved_ = false;
   FACTOR_TYPE factor_type_;
   int max_iter_;
   double max_reproj_error_;
