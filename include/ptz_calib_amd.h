@@ -470,6 +470,52 @@ int32_t ptz_krt_covariance_batch_device(int32_t n_query, const int64_t* d_match_
                                         const uint8_t* d_match_mask, const int32_t* d_accepted, double pixel_sigma, double* d_cov,
                                         double* d_sigma0, int32_t* d_status, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Covariance of bundle-adjusted cameras (per view)
+ * ------------------------------------------------------------------------------------------------ */
+/* what cv::calibrateCamera and ceres::Covariance report and the reference does not: PTZRayOptimizer hands back N cameras and one
+ * scalar, the mean reprojection error of the whole rig (ptzray_optimizer.cc:960-968), with no sign of which views are weak.
+ * Scope: a batch of 2D-2D problems of type PTZRay, PTZRayDist or PTZRayFxfyDist (ptz_ba_batch_create or
+ * ptz_ba_batch_create_views), evaluated at exactly the state ptz_ba_batch_get_state would return at the moment of the call: after a
+ * solve the minimum-cost point, before any solve the state last set.
+ * Parameters: per camera p = [fx, (fy), d1, d2, d3, (k1)], NF = ptz_ba_cov_dim(factor_type) = 4 / 5 / 6 of them, order and meaning
+ * those of ptz_krt_covariance_batch: d is a LEFT perturbation R <- Exp(d) R in radians about the camera's own x, y, z axes (the
+ * kernels differentiate with respect to the additive Rodrigues vector and convert each camera's block with the left Jacobian of
+ * SO(3), C_d = A C_r A^T).
+ * Per ray r over its candidate observations o (closed-form Jacobians, no Jacobi scaling; A_o 2 x NF, B_o 2 x 3, w_r the track
+ * weight): V_r = w_r sum B_o^T B_o, E_o = w_r A_o^T B_o, P_r = (V_r + 1/2 tr(V_r) x^ x^T)^-1 -- every 2D-2D functor is invariant to
+ * the scale of the ray, so V_r has rank 2 with null vector x^ and, since E_o x^ = 0, E_o P_r E_o'^T = E_o V_r^+ E_o'^T exactly.
+ * Reduced matrices: S[c_o, c_o'] = sum_r ([o = o'] w_r A_o^T A_o - E_o P_r E_o'^T), T the same sum with every term multiplied once
+ * more by w_r; a ray with a single candidate observation contributes exactly zero.  The track weights are not inverse variances:
+ * under iid pixel noise the estimator's covariance is the sandwich s^2 H^-1 (J^T W^2 J) H^-1, whose camera part is s^2 S^-1 T S^-1
+ * (sigma0^2 (J^T W J)^-1 would understate the standard deviations about twofold for track lengths 2..6).
+ * Gauge: rotation-only bundle adjustment leaves the global rotation free.  gauge_cam[k] names the anchor of problem k (NULL: camera
+ * 0): its three rotation rows and columns are identity in S and zero in T, and zero in the result, which describes every view's
+ * rotation RELATIVE TO THE ANCHOR; the anchor's fx / fy / k1 entries are ordinary.
+ * Solve: S is scaled to unit diagonal and factored by the batch Cholesky (FP64 matrix cores), S^-1 is formed by 64 x 64 tiles;
+ * C = s^2 S^-1 T S^-1, of which the per-camera diagonal blocks are returned: cov [NF * NF per camera, concatenated over the
+ * problems in order], row-major, symmetric bit for bit.  s = pixel_sigma if pixel_sigma > 0, else s = sigma0 with
+ * sigma0^2 = sum_o |e_o|^2 / (m - p), the residuals UNWEIGHTED, m = 2 n_obs, p = NF n_cam - 3 + 2 n_ray; sigma0 [n problems] is
+ * returned either way.  It is an ESTIMATE of the pixel noise: exact in expectation for equal weights, within a per cent for track
+ * weights 2..6.
+ * status [n problems]: PTZ_COV_OK; PTZ_COV_DOF: m <= p; PTZ_COV_SINGULAR: the Cholesky's fail flag, a diagonal entry of S that is
+ * not positive and finite, a non-finite result, or an observation in the behind-the-camera penalty branch of PTZRayDist (no
+ * linearisation there).  With any status but PTZ_COV_OK the problem's cov and sigma0 are left untouched.
+ * PTZ_EUNSUPPORTED: PTZRayDistDisp, a batch with 2D-3D annotations, shared intrinsics.  PTZ_EINVAL, before any device work: NULL
+ * batch or outputs, no state, gauge_cam out of range, pixel_sigma negative or not finite.
+ * The call does not disturb the batch: a ptz_ba_batch_solve after it returns the bits it returns without it.  Large batches are
+ * processed in groups under a workspace budget (PTZ_BA_COV_MAX_MB, default 2048); a problem's bits depend neither on its position
+ * in the batch nor on the grouping nor on the run.  device_ms (may be NULL): device time of the covariance kernels. */
+/* Host logic only: 4, 5, 6 for PTZRay, PTZRayDist, PTZRayFxfyDist; PTZ_EUNSUPPORTED otherwise. */
+int32_t ptz_ba_cov_dim(int32_t factor_type);
+int32_t ptz_ba_batch_covariance(ptz_ba_batch* b, const int32_t* gauge_cam /* [n] or NULL */, double pixel_sigma,
+                                double* cov /* [NF * NF * sum n_cam] */, double* sigma0 /* [n] */, int32_t* status /* [n] */,
+                                double* device_ms /* or NULL */);
+/* One-shot: create + set_state + covariance + destroy for a single problem at the state (cam, ray) given, with no solve.
+ * cov [NF * NF * n_cam], sigma0 [1], status [1]. */
+int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const double* ray, int32_t gauge_cam, double pixel_sigma,
+                          const ptz_lm_options* opt, double* cov, double* sigma0, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

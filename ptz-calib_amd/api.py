@@ -30,7 +30,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_debug_batch_structure_hash", "ptz_debug_batch_initial_rays", "ptz_krt_table_create", "ptz_krt_table_destroy",
            "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds", "ptz_match_gate_create",
            "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table",
-           "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device"]
+           "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device", "ptz_ba_cov_dim",
+           "ptz_ba_batch_covariance", "ptz_ba_covariance"]
 
 
 class PtzError(RuntimeError):
@@ -81,6 +82,7 @@ def lib():
         _lib.ptz_device_count.restype = C.c_int32
         _lib.ptz_ba_cam_block_dim.restype = C.c_int32
         _lib.ptz_krt_free_dim.restype = C.c_int32
+        _lib.ptz_ba_cov_dim.restype = C.c_int32
     return _lib
 
 
@@ -229,6 +231,28 @@ class BaBatch:
                "ptz_ba_batch_linearize")
         return dict(cost=cost.value, g_c=g_c, U=U, g_r=g_r, V=V, W=W, nc=nc)
 
+    def covariance(self, gauge_cam=None, pixel_sigma=0.0, cov=None, sigma0=None):
+        """ptz_ba_batch_covariance at the batch's current state (after a solve: the minimum-cost point).  gauge_cam: the anchor
+        camera of every problem (None: camera 0).  Returns (cov: list of [n_cam, NF, NF], sigma0 [n], status [n], device_ms);
+        free parameters [fx, (fy), d1, d2, d3, (k1)] per camera.  Problems whose status is not COV_OK keep what `cov` / `sigma0`
+        held (zeros unless given: cov as one [sum n_cam, NF, NF] array)."""
+        n_cams = self.n_cams if hasattr(self, "n_cams") else [s.n_cam for s in self.scenes]
+        ft = self.scenes[0].factor_type if self.scenes else self.factor_type
+        nf = ba_cov_dim(ft)
+        off = np.concatenate([[0], np.cumsum(n_cams)]).astype(int)
+        cov = np.zeros((off[-1], nf, nf)) if cov is None else cov
+        sigma0 = np.zeros(self.n) if sigma0 is None else sigma0
+        assert cov.dtype == np.float64 and cov.flags.c_contiguous and cov.size == off[-1] * nf * nf
+        assert sigma0.dtype == np.float64 and sigma0.flags.c_contiguous and len(sigma0) == self.n
+        status = np.full(self.n, -1, dtype=np.int32)
+        g = None if gauge_cam is None else np.ascontiguousarray(gauge_cam, dtype=np.int32)
+        if g is not None and len(g) != self.n:
+            raise ValueError("gauge_cam must name one camera per problem")
+        ms = C.c_double()
+        _check(lib().ptz_ba_batch_covariance(self.handle, _p(g), C.c_double(pixel_sigma), _p(cov), _p(sigma0), _p(status), C.byref(ms)),
+               "ptz_ba_batch_covariance")
+        return [cov[off[i]:off[i + 1]] for i in range(self.n)], sigma0, status, ms.value
+
 
 class RigView(C.Structure):
     _fields_ = [("rig", C.c_void_p), ("n_cam", C.c_int32), ("cam_image", C.c_void_p)]
@@ -307,6 +331,7 @@ class ViewBatch(BaBatch):
         self.nw = int(lib().ptz_ba_cam_block_dim(int(factor_type)))
         self.nc = int(lib().ptz_ba_batch_cam_block_dim(self.handle))
         self.n_cams = [len(im) for im in self._keep]
+        self.factor_type = int(factor_type)
 
     def set_state_pix2ray(self, cams, rkinv):
         cam = np.ascontiguousarray(np.concatenate(cams), dtype=np.float64)
@@ -346,6 +371,30 @@ def ba_solve(scene, cam0=None, ray0=None, tlw0=None, return_tlw=False, **opt):
     s = LmSummary()
     _check(lib().ptz_ba_solve(C.byref(p), _p(cam), _p(ray), _p(tlw), C.byref(o), C.byref(s)), "ptz_ba_solve")
     return (cam, ray, s.as_dict(), tlw) if return_tlw else (cam, ray, s.as_dict())
+
+
+def ba_cov_dim(factor_type) -> int:
+    """free parameters per camera of ptz_ba_batch_covariance, [fx, (fy), d1, d2, d3, (k1)]: 4, 5, 6 for PTZRay, PTZRayDist, PTZRayFxfyDist"""
+    nf = int(lib().ptz_ba_cov_dim(int(factor_type)))
+    _check(min(nf, 0), "ptz_ba_cov_dim")
+    return nf
+
+
+def ba_covariance(scene, cam, ray, gauge_cam=0, pixel_sigma=0.0, cov=None, **opt):
+    """One-shot ptz_ba_covariance of one problem at the state (cam, ray), no solve.  Returns (cov [n_cam, NF, NF], sigma0, status);
+    cov / sigma0 are those given (zeros / 0.0) unless status is COV_OK."""
+    keep = []
+    p = _pack_problem(scene, keep)
+    nf = ba_cov_dim(scene.factor_type)
+    cam = np.ascontiguousarray(cam, dtype=np.float64)
+    ray = np.ascontiguousarray(ray, dtype=np.float64)
+    cov = np.zeros((scene.n_cam, nf, nf)) if cov is None else cov
+    s0 = C.c_double(0.0)
+    st = C.c_int32(-1)
+    o = default_options(**opt)
+    _check(lib().ptz_ba_covariance(C.byref(p), _p(cam), _p(ray), int(gauge_cam), C.c_double(pixel_sigma), C.byref(o), _p(cov), C.byref(s0),
+                                   C.byref(st)), "ptz_ba_covariance")
+    return cov, s0.value, int(st.value)
 
 
 def ba_solve_disp(scene, cam0=None, ray0=None, tlw0=None, disp0=None, **opt):

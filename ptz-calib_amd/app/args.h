@@ -71,4 +71,9 @@ static const char* const kUncertaintyHelp =
     "Write sigma_f (px), sigma_rot_deg (about the camera's x, y, z axes) and sigma0 (estimated pixel noise) into every registered "
     "image's record: the covariance of its camera over the matches it was solved on";
 
+// --uncertainty of run_ptz_ba (not in the reference): per-view standard deviations of the PTZ-IBA stage in a side file
+static const char* const kBaUncertaintyHelp =
+    "Write <output>/<images basename>_uncertainty.json: sigma0 (estimated pixel noise) and, per registered image, sigma_f (px) and "
+    "sigma_rot_deg (about the camera's x, y, z axes, relative to the first seed image) of the PTZ-IBA stage, before georeferencing";
+
 }  // namespace ptzapp

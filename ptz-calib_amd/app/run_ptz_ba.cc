@@ -2,6 +2,13 @@
 // file; writes <output>/<basename(images)>.json.  Same options, stages, messages and exit codes as the reference tool
 // (src/app/run_ptz_ba.cc:24-154): 0 on success, -1 when a stage fails, 1 on bad options.  Every solve runs on the MI355X
 // library through the C++ classes of ptz-calib_amd/host.
+// --uncertainty (not in the reference) writes a side file <output>/<basename(images)>_uncertainty.json with the standard
+// deviations of every registered view: the 2D-2D bundle adjustment over the registered views is solved once more from PTZ-IBA's
+// cameras and PTZRayOptimizer::StdDevs is taken at its solution, the first seed image anchoring the gauge.  This is the
+// uncertainty of the PTZ-IBA stage, rotations RELATIVE TO THE ANCHOR, before georeferencing; the main output file and the exit
+// codes do not depend on the flag.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <unordered_set>
@@ -16,13 +23,52 @@ using namespace ptzcalib;
 
 static bool RunPtzBA(const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                      const std::vector<MatchesInfo>& matches_info, int max_iter, std::vector<Camera>& cameras,
-                     std::unordered_set<long>& reg_image_ids)
+                     std::unordered_set<long>& reg_image_ids, long* first_seed = nullptr)
 {  // run_ptz_ba.cc:116-129
   cameras.clear();
   cameras.resize(fnames.size());
   PtzIncrementalOptimizer ptz_iba(features, matches_info, cameras, fnames, max_iter);
   reg_image_ids.clear();
-  return ptz_iba.Solve(cameras, reg_image_ids);
+  const bool ok = ptz_iba.Solve(cameras, reg_image_ids);
+  if (first_seed) {  // the first image of the seed pair the registered set grew from
+    *first_seed = -1;
+    for (const PtzIncrementalOptimizer::Event& e : ptz_iba.events())
+      if (e.kind == PtzIncrementalOptimizer::Event::kInitPair && e.success) *first_seed = e.a;
+  }
+  return ok;
+}
+
+// --uncertainty: standard deviations of the registered views at the solution of their 2D-2D bundle adjustment, into a side file.
+// Never changes `cameras`; a failure here is reported and is not a failure of the tool.
+static void WriteUncertainty(const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                             const std::vector<MatchesInfo>& matches_info, const std::vector<Camera>& cameras,
+                             const std::unordered_set<long>& reg_image_ids, long seed, int max_iter, const std::string& path)
+{
+  PTZRayOptimizer optimizer(features, matches_info, cameras, reg_image_ids, max_iter, PTZRay);  // the factor PTZ-IBA adjusts with
+  std::vector<Camera> refined = cameras;
+  std::vector<double> sd;
+  double sigma0 = 0;
+  if (seed < 0 || !reg_image_ids.count(seed)) seed = -1;
+  if (!optimizer.Solve(refined) || !optimizer.StdDevs(sd, sigma0, seed)) {
+    fprintf(stderr, "Uncertainty: not available (the bundle adjustment over the registered views or its covariance failed)\n");
+    return;
+  }
+  const std::vector<long>& images = optimizer.packed().cam_image;
+  const size_t nf = sd.size() / images.size();
+  const long anchor = seed >= 0 ? seed : images.front();
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) { fprintf(stderr, "Uncertainty: cannot write %s\n", path.c_str()); return; }
+  const double deg = 180.0 / 3.14159265358979323846;
+  fprintf(f, "{\n  \"sigma0\": %.17g,\n  \"anchor\": \"%s\",\n  \"images\": {\n", sigma0, fnames[anchor].c_str());
+  for (size_t c = 0; c < images.size(); ++c) {
+    const double* s = sd.data() + nf * c;
+    fprintf(f, "    \"%s\": {\"sigma_f\": %.17g, \"sigma_rot_deg\": [%.17g, %.17g, %.17g]", fnames[images[c]].c_str(), s[0], s[1] * deg,
+            s[2] * deg, s[3] * deg);
+    if (nf == 5) fprintf(f, ", \"sigma_k1\": %.17g", s[4]);
+    fprintf(f, "}%s\n", c + 1 < images.size() ? "," : "");
+  }
+  fprintf(f, "  }\n}\n");
+  fclose(f);
 }
 
 static bool RunGeoreferencing(const std::vector<ImageFeatures>& features, const std::vector<MatchesInfo>& matches_info,
@@ -52,6 +98,7 @@ int main(int argc, char** argv)
   parser.AddFlag("gpu_homography", "Compute the pair homographies of the match table on the GPU (same results)");
   parser.AddFlag("inlier_matches", "Keep only the RANSAC inliers of every pair's homography (4 px) as the pair's matches");
   parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
+  parser.AddFlag(ptzapp::kUncertaintyFlag, ptzapp::kBaUncertaintyHelp);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -80,11 +127,17 @@ int main(int argc, char** argv)
   std::vector<Camera> cameras;
   std::unordered_set<long> reg_image_ids;
   static const int MAX_ITER = 200;
-  if (!RunPtzBA(fnames, features, matches_info, MAX_ITER, cameras, reg_image_ids)) {
+  long first_seed = -1;
+  if (!RunPtzBA(fnames, features, matches_info, MAX_ITER, cameras, reg_image_ids, &first_seed)) {
     fprintf(stderr, "================== PTZ-IBA End: failed ==========================\n");
     return -1;
   }
   fprintf(stderr, "================== PTZ-IBA End: success ==========================\n");
+  if (parser.Exist(ptzapp::kUncertaintyFlag)) {
+    MkdirIfNotExist(parser.Get("output"));
+    WriteUncertainty(fnames, features, matches_info, cameras, reg_image_ids, first_seed, MAX_ITER,
+                     parser.Get("output") + "/" + BaseName(parser.Get("images")) + "_uncertainty.json");
+  }
 
   std::vector<std::vector<Point2f>> pixels;
   std::vector<std::vector<Point3d>> pts3d;

@@ -39,6 +39,7 @@
 
 #include "ptz_ba_kernels.h"
 #include "ptz_view_kernels.h"
+#include "ptz_ba_cov.h"
 #include <rocprim/rocprim.hpp>
 
 namespace ptz {
@@ -898,6 +899,24 @@ struct ptz_rig {
   std::vector<int> img_obs, img_ent;  // per image: its views, and its entries as the HIGHER camera of a pair
   std::vector<void*> allocs;
 };
+
+// ---- covariance (ptz_ba_cov.hip): what that file is given of a batch ------------------------------------------------------------
+// the scenes' real extents (a view batch finds them on the device) and the half of the double-buffered state that is current
+namespace ptz {
+namespace {
+__global__ void k_ba_cov_pack(Dev d, int initial_state, BaCovScene* out)
+{
+  const int sc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (sc >= d.n_scene) return;
+  const SceneDev s = d.scene[sc];
+  BaCovScene o;
+  o.n_cam = s.n_cam; o.n_ray = s.n_ray; o.n_obs = s.n_obs; o.n_pair = s.n_pair;
+  o.cam_off = s.cam_off; o.ray_off = s.ray_off; o.obs_off = s.obs_off; o.pair_off = s.pair_off;
+  o.idx = s.idx; o.cur = initial_state ? 0 : d.lm[sc].cur;
+  out[sc] = o;
+}
+}  // namespace
+}  // namespace ptz
 
 // =============================================================================================================
 // C-ABI
@@ -2347,6 +2366,65 @@ int32_t ptz_ba_batch_get_state(ptz_ba_batch* b, double* cam, double* ray, double
   ptzpool::dev_release(b->device, stage);
   if (e != hipSuccess) { (void)hipGetLastError(); return PTZ_ENODEVICE; }
   return PTZ_OK;
+}
+
+int32_t ptz_ba_cov_dim(int32_t factor_type)
+{
+  const int nf = ba_cov_dim(factor_type);
+  return nf < 0 ? PTZ_EUNSUPPORTED : nf;
+}
+
+int32_t ptz_ba_batch_covariance(ptz_ba_batch* b, const int32_t* gauge_cam, double pixel_sigma, double* cov, double* sigma0, int32_t* status,
+                                double* device_ms)
+{
+  if (!b || !b->has_state || !cov || !sigma0 || !status) return PTZ_EINVAL;
+  if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma)) return PTZ_EINVAL;
+  // PTZRayDistDisp, 2D-3D annotations and shared intrinsics couple the cameras through blocks this reduced system does not carry
+  if (ba_cov_dim(b->type) < 0 || b->has3d || b->d.shared) return PTZ_EUNSUPPORTED;
+  std::vector<int> gauge(b->n_scene, 0);
+  for (int i = 0; gauge_cam && i < b->n_scene; ++i) {
+    if (gauge_cam[i] < 0 || gauge_cam[i] >= b->scenes[i].n_cam) return PTZ_EINVAL;
+    gauge[i] = gauge_cam[i];
+  }
+  clear_stale_error(__func__);
+  PTZ_DEVICE_GUARD(b->device);
+  const Dev& d = b->d;
+  void* dsc = nullptr;
+  if (ptzpool::dev_acquire(b->device, sizeof(BaCovScene) * b->n_scene, &dsc) != hipSuccess) return PTZ_ENOMEM;
+  // before the first solve the state is the one last set (cam0 / ray0); afterwards the current half of every scene
+  const bool initial = b->n_solves == 0;
+  hipLaunchKernelGGL(k_ba_cov_pack, dim3((b->n_scene + 63) / 64), dim3(64), 0, b->stream, d, initial ? 1 : 0, static_cast<BaCovScene*>(dsc));
+  std::vector<BaCovScene> hs(b->n_scene);
+  int32_t rc = PTZ_OK;
+  if (copy_on(b->stream, hs.data(), dsc, sizeof(BaCovScene) * b->n_scene, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) rc = PTZ_ENODEVICE;
+  if (!rc) {
+    BaCovIn in;
+    in.n_scene = b->n_scene; in.type = b->type; in.device = b->device;
+    in.scene = static_cast<const BaCovScene*>(dsc);
+    in.obs_uv = d.obs_uv; in.obs_cam = d.obs_cam; in.ray_ptr = d.ray_ptr; in.cam_ptr = d.cam_ptr; in.cam_obs = d.cam_obs;
+    in.pair_cj = d.pair_cj; in.pair_ptr = d.pair_ptr; in.cam_pair = d.cam_pair; in.ent = d.ent; in.ray_w = d.ray_w;
+    in.cam_x = initial ? b->cam0 : d.cam_x; in.ray_x = initial ? b->ray0 : d.ray_x;
+    in.cam_stride = initial ? 0 : d.cam_stride; in.ray_stride = initial ? 0 : d.ray_stride;
+    rc = ba_cov_run(in, hs.data(), gauge.data(), pixel_sigma, b->stream, cov, sigma0, status, device_ms);
+  }
+  ptzpool::dev_release(b->device, dsc);
+  return rc;
+}
+
+int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const double* ray, int32_t gauge_cam, double pixel_sigma,
+                          const ptz_lm_options* opt, double* cov, double* sigma0, int32_t* status)
+{
+  if (!p || !cam || !ray || !cov || !sigma0 || !status) return PTZ_EINVAL;
+  if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma)) return PTZ_EINVAL;
+  if (ba_cov_dim(p->factor_type) < 0 || p->n_obs3d > 0 || p->ic_of_cam) return PTZ_EUNSUPPORTED;
+  if (gauge_cam < 0 || gauge_cam >= p->n_cam) return PTZ_EINVAL;
+  ptz_ba_batch* b = nullptr;
+  int rc = ptz_ba_batch_create(1, p, opt, &b);
+  if (rc) return rc;
+  rc = ptz_ba_batch_set_state(b, cam, ray, nullptr);
+  if (!rc) rc = ptz_ba_batch_covariance(b, &gauge_cam, pixel_sigma, cov, sigma0, status, nullptr);
+  ptz_ba_batch_destroy(b);
+  return rc;
 }
 
 int32_t ptz_ba_batch_set_disp(ptz_ba_batch* b, const double* disp)

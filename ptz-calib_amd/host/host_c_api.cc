@@ -715,4 +715,54 @@ int32_t ptzh_krt_solve_cov(const double* cam_ref15, double* cam_cur15, int32_t n
   return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
 }
 
+// PTZRayOptimizer::Solve followed by Covariance / StdDevs (ann_ptr = NULL: no annotations).  cov needs room for 36 doubles per
+// candidate, std_devs for 6; before_solve = the answer of Covariance() on the object before Solve() (must be 0).  The packed_*
+// outputs are the problem and the SOLVED state the class handed to ptz_ba_covariance.  Returns Solve() | Covariance() << 1 |
+// StdDevs() << 2.
+int32_t ptzh_ptzray_solve_cov(int32_t n_img, const int64_t* kp_ptr, const float* kp_xy, int32_t n_pairs, const int64_t* src,
+                              const int64_t* dst, const int64_t* match_ptr, const int32_t* q, const int32_t* t, double* cam15,
+                              const int64_t* ann_ptr, const float* ann_uv, const double* ann_xyz, const int64_t* cand_ids, int32_t n_cand,
+                              int32_t max_iter, int32_t type, int64_t gauge_image, double* cov, double* std_devs, double* sigma0,
+                              int32_t* before_solve, int32_t* n_obs_out, int32_t* n_ray_out, float** p_uv, int32_t** p_cam, int32_t** p_ray,
+                              double** p_w, double** p_cam15, double** p_ray3, int64_t** p_cam_image)
+{
+  std::vector<ImageFeatures> feats;
+  std::vector<MatchesInfo> mis;
+  std::vector<Camera> cams;
+  BuildInputs(n_img, kp_ptr, kp_xy, nullptr, n_pairs, src, dst, match_ptr, q, t, cam15, feats, mis, cams);
+  std::unordered_set<long> ids;
+  for (int i = 0; i < n_cand; ++i) ids.insert(static_cast<long>(cand_ids[i]));
+  std::vector<std::vector<Point2f>> pixels;
+  std::vector<std::vector<Point3d>> pts3d;
+  if (ann_ptr) {
+    pixels.resize(n_img);
+    pts3d.resize(n_img);
+    for (int i = 0; i < n_img; ++i)
+      for (int64_t k = ann_ptr[i]; k < ann_ptr[i + 1]; ++k) {
+        pixels[i].emplace_back(ann_uv[2 * k], ann_uv[2 * k + 1]);
+        pts3d[i].emplace_back(ann_xyz[3 * k], ann_xyz[3 * k + 1], ann_xyz[3 * k + 2]);
+      }
+  }
+  PTZRayOptimizer opt(feats, mis, cams, pixels, pts3d, ids, max_iter, static_cast<FACTOR_TYPE>(type));
+  std::vector<double> c, sd;
+  double s0 = 0;
+  if (before_solve) *before_solve = opt.Covariance(c, s0, static_cast<long>(gauge_image)) ? 1 : 0;
+  const bool ok = opt.Solve(cams);
+  ExportPacked(opt.packed(), PackedOut{n_obs_out, n_ray_out, p_uv, p_cam, p_ray, p_w, p_cam15, p_ray3, p_cam_image});
+  if (ok)
+    for (int i = 0; i < n_img; ++i) {
+      const std::vector<double> v = cams[i].ToVector();
+      memcpy(cam15 + 15 * i, v.data(), sizeof(double) * 15);
+    }
+  const bool okc = opt.Covariance(c, s0, static_cast<long>(gauge_image));
+  if (okc) {
+    memcpy(cov, c.data(), sizeof(double) * c.size());
+    *sigma0 = s0;
+  }
+  double s1 = 0;
+  const bool oks = opt.StdDevs(sd, s1, static_cast<long>(gauge_image));
+  if (oks) memcpy(std_devs, sd.data(), sizeof(double) * sd.size());
+  return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
+}
+
 }  // extern "C"

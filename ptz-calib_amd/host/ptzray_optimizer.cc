@@ -368,6 +368,7 @@ bool PTZRayOptimizer::SolveView(std::vector<Camera>& cameras)
 
 bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::vector<Ray>>* rays_out)
 {
+  solved_packed_ = false;
   if (!CheckValid()) return false;
   FindTracks();
   SetInitTransLocalToWorld();
@@ -481,6 +482,54 @@ bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::v
   p.cam = cam;
   p.ray = ray;
   for (int k = 0; k < 6; ++k) p.tlw[k] = tlw[k];
+  solved_packed_ = true;
+  return true;
+}
+
+bool PTZRayOptimizer::Covariance(std::vector<double>& cov, double& sigma0, long gauge_image) const
+{
+  const PackedBA& p = packed_;
+  if (!solved_packed_ || p.ray.empty() || !p.obs3d_cam.empty() || type_ == PTZRayDistDisp) return false;
+  for (size_t c = 0; c < p.cam_image.size() && c < p.ic_of_cam.size(); ++c)
+    if (p.ic_of_cam[c] != static_cast<int32_t>(p.cam_image[c])) return false;  // shared intrinsics
+  int32_t gauge = 0;
+  if (gauge_image >= 0) {
+    const auto it = std::lower_bound(p.cam_image.begin(), p.cam_image.end(), gauge_image);
+    if (it == p.cam_image.end() || *it != gauge_image) return false;
+    gauge = static_cast<int32_t>(it - p.cam_image.begin());
+  }
+  ptz_ba_problem prob{};
+  prob.n_cam = static_cast<int32_t>(p.cam_image.size());
+  prob.n_ray = static_cast<int32_t>(p.ray_track.size());
+  prob.n_obs = static_cast<int64_t>(p.obs_cam.size());
+  prob.obs_uv = p.obs_uv.data();
+  prob.obs_cam = p.obs_cam.data();
+  prob.obs_ray = p.obs_ray.data();
+  prob.ray_weight = p.ray_weight.data();
+  prob.factor_type = (type_ == PTZRay) ? PTZ_BA_PTZRay : (type_ == PTZRayDist ? PTZ_BA_PTZRayDist : PTZ_BA_PTZRayFxfyDist);
+  const int32_t nf = ptz_ba_cov_dim(prob.factor_type);
+  if (nf <= 0) return false;
+  ptz_lm_options opt;
+  ptz_lm_options_default(&opt);
+  opt.device_id = device_id_;
+  std::vector<double> c(static_cast<size_t>(nf) * nf * prob.n_cam, 0.0);
+  double s0 = 0;
+  int32_t status = -1;
+  const int32_t rc = ptz_ba_covariance(&prob, p.cam.data(), p.ray.data(), gauge, 0.0, &opt, c.data(), &s0, &status);
+  if (rc != PTZ_OK || status != PTZ_COV_OK) return false;
+  cov.swap(c);
+  sigma0 = s0;
+  return true;
+}
+
+bool PTZRayOptimizer::StdDevs(std::vector<double>& std_devs, double& sigma0, long gauge_image) const
+{
+  std::vector<double> cov;
+  if (!Covariance(cov, sigma0, gauge_image)) return false;
+  const size_t n_cam = packed_.cam_image.size(), nf = static_cast<size_t>(std::lround(std::sqrt(static_cast<double>(cov.size() / n_cam))));
+  std_devs.assign(nf * n_cam, 0.0);
+  for (size_t c = 0; c < n_cam; ++c)
+    for (size_t k = 0; k < nf; ++k) std_devs[nf * c + k] = std::sqrt(cov[nf * nf * c + nf * k + k]);
   return true;
 }
 

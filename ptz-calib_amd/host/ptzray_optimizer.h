@@ -64,6 +64,16 @@ class PTZRayOptimizer {
   const std::array<double, 3>& displacement() const { return disp_; }
   void SetDevice(int device_id) { device_id_ = device_id; }
   double device_ms() const { return device_ms_; }  // wall time of the ptz_ba_solve call of the last Solve
+  // Covariance of the candidate cameras at the solution (ptz_ba_covariance: the sandwich s^2 S^-1 T S^-1 of the reduced camera
+  // system, see include/ptz_calib_amd.h).  Valid after a successful Solve of a 2D-2D problem (PTZRay, PTZRayDist, PTZRayFxfyDist;
+  // no annotations, no shared intrinsics) that was packed on the host -- false otherwise, as KRTOptimizer::Covariance before
+  // Solve; a solve over a view of a device-resident rig (UseRig) keeps no rays and is "otherwise".  cov: per candidate camera, in
+  // the order of packed().cam_image, NF * NF row-major over [fx, (fy), d1, d2, d3, (k1)], d a left perturbation of the rotation
+  // in radians; gauge_image: the view whose rotation anchors the gauge (-1: the lowest candidate image), its rotation rows and
+  // columns are zero and every other view's rotation is relative to it.  sigma0: the estimated pixel noise, which scales cov.
+  bool Covariance(std::vector<double>& cov, double& sigma0, long gauge_image = -1) const;
+  // ... and the square roots of its diagonals: NF per candidate camera
+  bool StdDevs(std::vector<double>& std_devs, double& sigma0, long gauge_image = -1) const;
   // The tracks depend on the match table only, not on the candidate set: a caller that solves many candidate subsets of
   // one match table (PtzIncrementalOptimizer) builds them once and shares them instead of repeating FindTracks().
   void UseTracks(std::shared_ptr<const SharedTracks> tracks) { shared_tracks_ = std::move(tracks); }
@@ -110,6 +120,7 @@ class PTZRayOptimizer {
   std::array<double, 6> tlw_init_{{0, 0, 0, 0, 0, 0}};
   std::array<double, 3> disp_{{0, 0, 0}};  // disp_param_ (ptzray_optimizer.h: PTZRayDistDisp), refined by Solve
   ptz_lm_summary summary_{};
+  bool solved_packed_ = false;  // the last Solve succeeded on the host-packed path: packed_ holds the solution (Covariance)
   double init_reproj_error_all_ = 0, final_reproj_error_all_ = 0;
   void ComputeErrors() const;  // unweighted 2D-2D / 2D-3D RMS of the solved state, on first use
   mutable bool errors_ready_ = true;
