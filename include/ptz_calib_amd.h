@@ -516,6 +516,59 @@ int32_t ptz_ba_batch_covariance(ptz_ba_batch* b, const int32_t* gauge_cam /* [n]
 int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const double* ray, int32_t gauge_cam, double pixel_sigma,
                           const ptz_lm_options* opt, double* cov, double* sigma0, int32_t* status);
 
+/* ------------------------------------------------------------------------------------------------
+ * Covariance of georeferenced cameras and of the rig's projection centre
+ * ------------------------------------------------------------------------------------------------ */
+/* The uncertainty of what the georeferencing bundle adjustment outputs -- the world cameras R_i R_lw -- and of where the rig
+ * stands, which ptz_ba_batch_covariance (2D-2D problems only, rotations relative to an anchor view) stops one stage short of.
+ * Scope: a batch of type PTZRay or PTZRayDist (the two types the georeferencing stage uses), evaluated at exactly the state
+ * ptz_ba_batch_get_state would return, T_l_w included.  A problem takes part if it has n_obs3d > 0.
+ * Parameters of the linearisation (closed-form Jacobians, no Jacobi scaling): per camera the NC = ptz_ba_batch_cam_block_dim
+ * columns [fx, fy, (k1), r1, r2, r3], per problem the T_l_w block L = [rho1..3, t1..3], per ray its rank-2 block, eliminated as
+ * in ptz_ba_batch_covariance (rays do not enter 2D-3D residuals).  fy is read only by the 2D-3D functor: the fy column of a camera
+ * WITHOUT annotations is identically zero and is treated like a gauge row (identity in S, zero in M).
+ * Reduced system, order NC n_cam + 6: S = the 2D-2D part of ptz_ba_batch_covariance plus, per annotation a of camera c (weight 1;
+ * A_a 2 x NC, G_a 2 x 6): A_a^T A_a into block (c, c), A_a^T G_a into the border (c, L), G_a^T G_a into (L, L).
+ * Noise: clicked annotations and matched key points do not share one level.  M = s_f^2 T_f + s_a^2 T_a with T_f the T of
+ * ptz_ba_batch_covariance and T_a the annotation terms of S; the full covariance is C = S^-1 M S^-1.  s_f = pixel_sigma and
+ * s_a = annotation_sigma where positive; a zero is estimated from the UNWEIGHTED residuals:
+ * s_f^2 = SSE_2d2d / (2 n_obs - p_f), p_f = NF2 n_cam - 3 + 2 n_ray with NF2 = 4 / 5 (the rule of ptz_ba_batch_covariance), and
+ * s_a^2 = SSE_2d3d / (2 n_obs3d - p_a), p_a = 6 + (number of annotated cameras); p_f + p_a is the parameter count.  Both estimates
+ * are returned either way, sigma0[2k] and sigma0[2k + 1].  They are ESTIMATES, not exact: the split of the degrees of freedom
+ * between the two kinds of residual is a heuristic, and s_a comes out a few per cent low (about 0.96 of the truth on a 6-view rig
+ * with 24 annotations).
+ * Gauge: gauge_cam[k] (NULL: camera 0) names the camera whose three rotation columns are anchored, as in
+ * ptz_ba_batch_covariance.  The outputs are WORLD-frame quantities: they do not depend on the anchor beyond round-off, and the
+ * anchor's rows are NOT zero.
+ * Outputs per problem: cov [NF * NF per camera, concatenated over the problems in order], NF = ptz_ba_geo_cov_dim = 4 / 5, order
+ * [fx, d1, d2, d3, (k1)] -- the slots of ptz_ba_batch_covariance, but d is now a LEFT perturbation of the WORLD rotation
+ * R_w = R_i R_lw about the camera's own axes: to first order d_w = d_i + R_i d_lw, so the block is
+ * C_ii + R_i C_ll R_i^T + C_il R_i^T + R_i C_li over the left-perturbation forms of both rotations (the additive Rodrigues columns
+ * convert with the left Jacobian of SO(3), for the cameras and likewise for rho); fy is marginalised.  cov_centre [9 per problem]:
+ * covariance of the projection centre C_w = -R_lw^T t_lw in world units, dC_w = -R_lw^T ([t_lw]_x d_lw + tau); the extrinsic
+ * translation t_i is not part of the 2D-3D model and not part of this.  Both row-major, symmetric bit for bit.
+ * status [n problems]: PTZ_COV_OK; PTZ_COV_DOF: 2 n_obs <= p_f or 2 n_obs3d <= p_a (a problem without annotations lands here);
+ * PTZ_COV_SINGULAR: the Cholesky's fail flag, a diagonal entry of S that is not positive and finite, a non-finite result, a 2D-2D
+ * observation in the penalty branch of PTZRayDist, or a 2D-3D point with camera-frame z <= 0.  With any status but PTZ_COV_OK the
+ * problem's cov, cov_centre and sigma0 are left untouched.
+ * PTZ_EUNSUPPORTED: PTZRayFxfyDist, PTZRayDistDisp, shared intrinsics.  PTZ_EINVAL, before any device work: NULL batch or
+ * outputs, no state, gauge_cam out of range, a sigma negative or not finite.
+ * No floating-point atomics: a camera's annotation terms are summed over its annotations in stored order, (L, L) in stored
+ * order; a problem's bits depend neither on its position in the batch nor on the grouping under PTZ_BA_COV_MAX_MB nor on the
+ * run.  The call does not disturb the batch: a ptz_ba_batch_solve after it returns the bits it returns without it.
+ * device_ms (may be NULL): device time of the covariance kernels. */
+/* Host logic only: 4, 5 for PTZRay, PTZRayDist; PTZ_EUNSUPPORTED otherwise. */
+int32_t ptz_ba_geo_cov_dim(int32_t factor_type);
+int32_t ptz_ba_batch_covariance_georef(ptz_ba_batch* b, const int32_t* gauge_cam /* [n] or NULL */, double pixel_sigma,
+                                       double annotation_sigma, double* cov /* [NF * NF * sum n_cam] */,
+                                       double* cov_centre /* [9 n] */, double* sigma0 /* [2 n] */, int32_t* status /* [n] */,
+                                       double* device_ms /* or NULL */);
+/* One-shot: create + set_state + covariance_georef + destroy for a single problem at the state (cam, ray, tlw) given, with no
+ * solve.  cov [NF * NF * n_cam], cov_centre [9], sigma0 [2], status [1]. */
+int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, const double* ray, const double* tlw, int32_t gauge_cam,
+                                 double pixel_sigma, double annotation_sigma, const ptz_lm_options* opt, double* cov,
+                                 double* cov_centre, double* sigma0, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

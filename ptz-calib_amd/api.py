@@ -31,7 +31,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_attempts", "ptz_homography_ransac_batch", "ptz_debug_homography_bounds", "ptz_match_gate_create",
            "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table",
            "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device", "ptz_ba_cov_dim",
-           "ptz_ba_batch_covariance", "ptz_ba_covariance"]
+           "ptz_ba_batch_covariance", "ptz_ba_covariance", "ptz_ba_geo_cov_dim", "ptz_ba_batch_covariance_georef",
+           "ptz_ba_covariance_georef"]
 
 
 class PtzError(RuntimeError):
@@ -83,6 +84,7 @@ def lib():
         _lib.ptz_ba_cam_block_dim.restype = C.c_int32
         _lib.ptz_krt_free_dim.restype = C.c_int32
         _lib.ptz_ba_cov_dim.restype = C.c_int32
+        _lib.ptz_ba_geo_cov_dim.restype = C.c_int32
     return _lib
 
 
@@ -253,6 +255,29 @@ class BaBatch:
                "ptz_ba_batch_covariance")
         return [cov[off[i]:off[i + 1]] for i in range(self.n)], sigma0, status, ms.value
 
+    def covariance_georef(self, gauge_cam=None, pixel_sigma=0.0, annotation_sigma=0.0, cov=None, cov_centre=None, sigma0=None):
+        """ptz_ba_batch_covariance_georef at the batch's current state, T_l_w included: the covariance of the WORLD cameras
+        R_i R_lw and of the rig's projection centre.  Returns (cov: list of [n_cam, NF, NF] over [fx, d1, d2, d3, (k1)],
+        cov_centre [n, 3, 3], sigma0 [n, 2] = (key points, annotations), status [n], device_ms).  Problems whose status is not
+        COV_OK keep what `cov` / `cov_centre` / `sigma0` held (zeros unless given: cov as one [sum n_cam, NF, NF] array)."""
+        n_cams = self.n_cams if hasattr(self, "n_cams") else [s.n_cam for s in self.scenes]
+        ft = self.scenes[0].factor_type if self.scenes else self.factor_type
+        nf = ba_geo_cov_dim(ft)
+        off = np.concatenate([[0], np.cumsum(n_cams)]).astype(int)
+        cov = np.zeros((off[-1], nf, nf)) if cov is None else cov
+        cov_centre = np.zeros((self.n, 3, 3)) if cov_centre is None else cov_centre
+        sigma0 = np.zeros((self.n, 2)) if sigma0 is None else sigma0
+        for a, size in ((cov, off[-1] * nf * nf), (cov_centre, 9 * self.n), (sigma0, 2 * self.n)):
+            assert a.dtype == np.float64 and a.flags.c_contiguous and a.size == size
+        status = np.full(self.n, -1, dtype=np.int32)
+        g = None if gauge_cam is None else np.ascontiguousarray(gauge_cam, dtype=np.int32)
+        if g is not None and len(g) != self.n:
+            raise ValueError("gauge_cam must name one camera per problem")
+        ms = C.c_double()
+        _check(lib().ptz_ba_batch_covariance_georef(self.handle, _p(g), C.c_double(pixel_sigma), C.c_double(annotation_sigma), _p(cov),
+                                                    _p(cov_centre), _p(sigma0), _p(status), C.byref(ms)), "ptz_ba_batch_covariance_georef")
+        return [cov[off[i]:off[i + 1]] for i in range(self.n)], cov_centre, sigma0, status, ms.value
+
 
 class RigView(C.Structure):
     _fields_ = [("rig", C.c_void_p), ("n_cam", C.c_int32), ("cam_image", C.c_void_p)]
@@ -395,6 +420,33 @@ def ba_covariance(scene, cam, ray, gauge_cam=0, pixel_sigma=0.0, cov=None, **opt
     _check(lib().ptz_ba_covariance(C.byref(p), _p(cam), _p(ray), int(gauge_cam), C.c_double(pixel_sigma), C.byref(o), _p(cov), C.byref(s0),
                                    C.byref(st)), "ptz_ba_covariance")
     return cov, s0.value, int(st.value)
+
+
+def ba_geo_cov_dim(factor_type) -> int:
+    """entries per camera of ptz_ba_batch_covariance_georef, [fx, d1, d2, d3, (k1)]: 4, 5 for PTZRay, PTZRayDist"""
+    nf = int(lib().ptz_ba_geo_cov_dim(int(factor_type)))
+    _check(min(nf, 0), "ptz_ba_geo_cov_dim")
+    return nf
+
+
+def ba_covariance_georef(scene, cam, ray, tlw, gauge_cam=0, pixel_sigma=0.0, annotation_sigma=0.0, cov=None, cov_centre=None, **opt):
+    """One-shot ptz_ba_covariance_georef of one annotated problem at the state (cam, ray, tlw), no solve.  Returns
+    (cov [n_cam, NF, NF], cov_centre [3, 3], sigma0 [2], status); the outputs are those given (zeros) unless status is COV_OK."""
+    keep = []
+    p = _pack_problem(scene, keep)
+    nf = ba_geo_cov_dim(scene.factor_type)
+    cam = np.ascontiguousarray(cam, dtype=np.float64)
+    ray = np.ascontiguousarray(ray, dtype=np.float64)
+    tlw = np.ascontiguousarray(tlw, dtype=np.float64)
+    cov = np.zeros((scene.n_cam, nf, nf)) if cov is None else cov
+    cov_centre = np.zeros((3, 3)) if cov_centre is None else cov_centre
+    s0 = np.zeros(2)
+    st = C.c_int32(-1)
+    o = default_options(**opt)
+    _check(lib().ptz_ba_covariance_georef(C.byref(p), _p(cam), _p(ray), _p(tlw), int(gauge_cam), C.c_double(pixel_sigma),
+                                          C.c_double(annotation_sigma), C.byref(o), _p(cov), _p(cov_centre), _p(s0), C.byref(st)),
+           "ptz_ba_covariance_georef")
+    return cov, cov_centre, s0, int(st.value)
 
 
 def ba_solve_disp(scene, cam0=None, ray0=None, tlw0=None, disp0=None, **opt):

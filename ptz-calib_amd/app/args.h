@@ -74,6 +74,7 @@ static const char* const kUncertaintyHelp =
 // --uncertainty of run_ptz_ba (not in the reference): per-view standard deviations of the PTZ-IBA stage in a side file
 static const char* const kBaUncertaintyHelp =
     "Write <output>/<images basename>_uncertainty.json: sigma0 (estimated pixel noise) and, per registered image, sigma_f (px) and "
-    "sigma_rot_deg (about the camera's x, y, z axes, relative to the first seed image) of the PTZ-IBA stage, before georeferencing";
+    "sigma_rot_deg (about the camera's x, y, z axes, relative to the first seed image) of the PTZ-IBA stage, before georeferencing; "
+    "with -a also \"georeferenced\": the same of the cameras written, in the world frame, with the rig's centre and sigma_centre";
 
 }  // namespace ptzapp

@@ -6,9 +6,12 @@
 // deviations of every registered view: the 2D-2D bundle adjustment over the registered views is solved once more from PTZ-IBA's
 // cameras and PTZRayOptimizer::StdDevs is taken at its solution, the first seed image anchoring the gauge.  This is the
 // uncertainty of the PTZ-IBA stage, rotations RELATIVE TO THE ANCHOR, before georeferencing; the main output file and the exit
-// codes do not depend on the flag.
+// codes do not depend on the flag.  With -a the side file gains one key, "georeferenced": after the georeferencing bundle
+// adjustment succeeds, PTZRayOptimizer::WorldStdDevs of THAT optimizer (no extra solve) -- the standard deviations of the cameras
+// the tool writes, in the world frame, and of the rig's projection centre.
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <unordered_set>
@@ -40,9 +43,22 @@ static bool RunPtzBA(const std::vector<std::string>& fnames, const std::vector<I
 
 // --uncertainty: standard deviations of the registered views at the solution of their 2D-2D bundle adjustment, into a side file.
 // Never changes `cameras`; a failure here is reported and is not a failure of the tool.
+static void Appendf(std::string& s, const char* fmt, ...)
+{
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  s += buf;
+}
+
+// `body` (if given) receives the file's text up to, not including, the "\n}\n" that closes it: the georeferencing stage appends
+// its key there.
 static void WriteUncertainty(const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                              const std::vector<MatchesInfo>& matches_info, const std::vector<Camera>& cameras,
-                             const std::unordered_set<long>& reg_image_ids, long seed, int max_iter, const std::string& path)
+                             const std::unordered_set<long>& reg_image_ids, long seed, int max_iter, const std::string& path,
+                             std::string* body = nullptr)
 {
   PTZRayOptimizer optimizer(features, matches_info, cameras, reg_image_ids, max_iter, PTZRay);  // the factor PTZ-IBA adjusts with
   std::vector<Camera> refined = cameras;
@@ -56,26 +72,30 @@ static void WriteUncertainty(const std::vector<std::string>& fnames, const std::
   const std::vector<long>& images = optimizer.packed().cam_image;
   const size_t nf = sd.size() / images.size();
   const long anchor = seed >= 0 ? seed : images.front();
-  FILE* f = fopen(path.c_str(), "w");
-  if (!f) { fprintf(stderr, "Uncertainty: cannot write %s\n", path.c_str()); return; }
   const double deg = 180.0 / 3.14159265358979323846;
-  fprintf(f, "{\n  \"sigma0\": %.17g,\n  \"anchor\": \"%s\",\n  \"images\": {\n", sigma0, fnames[anchor].c_str());
+  std::string text;
+  Appendf(text, "{\n  \"sigma0\": %.17g,\n  \"anchor\": \"%s\",\n  \"images\": {\n", sigma0, fnames[anchor].c_str());
   for (size_t c = 0; c < images.size(); ++c) {
     const double* s = sd.data() + nf * c;
-    fprintf(f, "    \"%s\": {\"sigma_f\": %.17g, \"sigma_rot_deg\": [%.17g, %.17g, %.17g]", fnames[images[c]].c_str(), s[0], s[1] * deg,
+    Appendf(text, "    \"%s\": {\"sigma_f\": %.17g, \"sigma_rot_deg\": [%.17g, %.17g, %.17g]", fnames[images[c]].c_str(), s[0], s[1] * deg,
             s[2] * deg, s[3] * deg);
-    if (nf == 5) fprintf(f, ", \"sigma_k1\": %.17g", s[4]);
-    fprintf(f, "}%s\n", c + 1 < images.size() ? "," : "");
+    if (nf == 5) Appendf(text, ", \"sigma_k1\": %.17g", s[4]);
+    Appendf(text, "}%s\n", c + 1 < images.size() ? "," : "");
   }
-  fprintf(f, "  }\n}\n");
+  text += "  }";
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) { fprintf(stderr, "Uncertainty: cannot write %s\n", path.c_str()); return; }
+  fprintf(f, "%s\n}\n", text.c_str());
   fclose(f);
+  if (body) *body = text;
 }
 
 static bool RunGeoreferencing(const std::vector<ImageFeatures>& features, const std::vector<MatchesInfo>& matches_info,
                               const std::vector<std::vector<Point2f>>& pixels, const std::vector<std::vector<Point3d>>& pts3d,
                               const std::unordered_set<long>& cam_ids, int max_iter, bool has_dist, std::vector<Camera>& cameras,
-                              double& error_2d2d, double& error_2d3d)
-{  // run_ptz_ba.cc:131-154
+                              double& error_2d2d, double& error_2d3d, const std::vector<std::string>* fnames = nullptr,
+                              std::string* georef = nullptr)
+{  // run_ptz_ba.cc:131-154; fnames / georef (--uncertainty): the "georeferenced" record of the side file, empty if not available
   PTZRayOptimizer optimizer(features, matches_info, cameras, pixels, pts3d, cam_ids, max_iter, has_dist ? PTZRayDist : PTZRay);
   std::vector<std::vector<Ray>> rays;
   if (!optimizer.Solve(cameras, rays)) {
@@ -84,6 +104,30 @@ static bool RunGeoreferencing(const std::vector<ImageFeatures>& features, const 
   }
   error_2d2d = optimizer.final_reproj_error_2d2d();
   error_2d3d = optimizer.final_reproj_error_2d3d();
+  if (fnames && georef) {
+    std::vector<double> sd;
+    std::array<double, 3> sc, centre;
+    std::array<double, 2> s0;
+    if (!optimizer.WorldStdDevs(sd, sc, s0) || !optimizer.WorldCentre(centre)) {
+      fprintf(stderr, "Uncertainty: the covariance of the georeferenced cameras is not available\n");
+      return true;
+    }
+    const std::vector<long>& images = optimizer.packed().cam_image;
+    const size_t nf = sd.size() / images.size();
+    const double deg = 180.0 / 3.14159265358979323846;
+    std::string& t = *georef;
+    Appendf(t, "{\n    \"sigma0_features\": %.17g,\n    \"sigma0_annotations\": %.17g,\n", s0[0], s0[1]);
+    Appendf(t, "    \"centre\": [%.17g, %.17g, %.17g],\n    \"sigma_centre\": [%.17g, %.17g, %.17g],\n    \"images\": {\n", centre[0], centre[1],
+            centre[2], sc[0], sc[1], sc[2]);
+    for (size_t c = 0; c < images.size(); ++c) {
+      const double* s = sd.data() + nf * c;
+      Appendf(t, "      \"%s\": {\"sigma_f\": %.17g, \"sigma_rot_deg\": [%.17g, %.17g, %.17g]", (*fnames)[images[c]].c_str(), s[0], s[1] * deg,
+              s[2] * deg, s[3] * deg);
+      if (nf == 5) Appendf(t, ", \"sigma_k1\": %.17g", s[4]);
+      Appendf(t, "}%s\n", c + 1 < images.size() ? "," : "");
+    }
+    t += "    }\n  }";
+  }
   return true;
 }
 
@@ -133,10 +177,12 @@ int main(int argc, char** argv)
     return -1;
   }
   fprintf(stderr, "================== PTZ-IBA End: success ==========================\n");
-  if (parser.Exist(ptzapp::kUncertaintyFlag)) {
+  const bool uncertainty = parser.Exist(ptzapp::kUncertaintyFlag);
+  const std::string side_path = parser.Get("output") + "/" + BaseName(parser.Get("images")) + "_uncertainty.json";
+  std::string side_body;
+  if (uncertainty) {
     MkdirIfNotExist(parser.Get("output"));
-    WriteUncertainty(fnames, features, matches_info, cameras, reg_image_ids, first_seed, MAX_ITER,
-                     parser.Get("output") + "/" + BaseName(parser.Get("images")) + "_uncertainty.json");
+    WriteUncertainty(fnames, features, matches_info, cameras, reg_image_ids, first_seed, MAX_ITER, side_path, &side_body);
   }
 
   std::vector<std::vector<Point2f>> pixels;
@@ -147,11 +193,21 @@ int main(int argc, char** argv)
   }
   fprintf(stderr, "================== Georeferencing Begin ==========================\n");
   double error_2d2d, error_2d3d;
-  if (!RunGeoreferencing(features, matches_info, pixels, pts3d, reg_image_ids, MAX_ITER, parser.Exist("dist"), cameras, error_2d2d, error_2d3d)) {
+  std::string georef;
+  if (!RunGeoreferencing(features, matches_info, pixels, pts3d, reg_image_ids, MAX_ITER, parser.Exist("dist"), cameras, error_2d2d, error_2d3d,
+                         uncertainty ? &fnames : nullptr, uncertainty ? &georef : nullptr)) {
     fprintf(stderr, "================== Georeferencing End: failed ==========================\n");
     return -1;
   }
   fprintf(stderr, "================== Georeferencing End: success ==========================\n");
+  if (uncertainty && !georef.empty()) {  // the side file again, its earlier keys as they were, plus "georeferenced"
+    FILE* f = fopen(side_path.c_str(), "w");
+    if (!f) fprintf(stderr, "Uncertainty: cannot write %s\n", side_path.c_str());
+    else {
+      fprintf(f, "%s\n  \"georeferenced\": %s\n}\n", side_body.empty() ? "{" : (side_body + ",").c_str(), georef.c_str());
+      fclose(f);
+    }
+  }
 
   const std::string cam_id = BaseName(parser.Get("images"));
   const std::string out_dir = parser.Get("output");

@@ -40,6 +40,7 @@
 #include "ptz_ba_kernels.h"
 #include "ptz_view_kernels.h"
 #include "ptz_ba_cov.h"
+#include "ptz_ba_cov_georef.h"
 #include <rocprim/rocprim.hpp>
 
 namespace ptz {
@@ -913,6 +914,7 @@ __global__ void k_ba_cov_pack(Dev d, int initial_state, BaCovScene* out)
   o.n_cam = s.n_cam; o.n_ray = s.n_ray; o.n_obs = s.n_obs; o.n_pair = s.n_pair;
   o.cam_off = s.cam_off; o.ray_off = s.ray_off; o.obs_off = s.obs_off; o.pair_off = s.pair_off;
   o.idx = s.idx; o.cur = initial_state ? 0 : d.lm[sc].cur;
+  o.o3_off = s.o3_off; o.n_o3 = s.n_o3;
   out[sc] = o;
 }
 }  // namespace
@@ -2423,6 +2425,73 @@ int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const doub
   if (rc) return rc;
   rc = ptz_ba_batch_set_state(b, cam, ray, nullptr);
   if (!rc) rc = ptz_ba_batch_covariance(b, &gauge_cam, pixel_sigma, cov, sigma0, status, nullptr);
+  ptz_ba_batch_destroy(b);
+  return rc;
+}
+
+int32_t ptz_ba_geo_cov_dim(int32_t factor_type)
+{
+  const int nf = ba_geo_cov_dim(factor_type);
+  return nf < 0 ? PTZ_EUNSUPPORTED : nf;
+}
+
+int32_t ptz_ba_batch_covariance_georef(ptz_ba_batch* b, const int32_t* gauge_cam, double pixel_sigma, double annotation_sigma, double* cov,
+                                       double* cov_centre, double* sigma0, int32_t* status, double* device_ms)
+{
+  if (!b || !b->has_state || !cov || !cov_centre || !sigma0 || !status) return PTZ_EINVAL;
+  if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma) || !(annotation_sigma >= 0.0) || !std::isfinite(annotation_sigma)) return PTZ_EINVAL;
+  // PTZRayFxfyDist, PTZRayDistDisp and shared intrinsics are not what the georeferencing stage solves
+  if (ba_geo_cov_dim(b->type) < 0 || b->d.shared) return PTZ_EUNSUPPORTED;
+  std::vector<int> gauge(b->n_scene, 0);
+  for (int i = 0; gauge_cam && i < b->n_scene; ++i) {
+    if (gauge_cam[i] < 0 || gauge_cam[i] >= b->scenes[i].n_cam) return PTZ_EINVAL;
+    gauge[i] = gauge_cam[i];
+  }
+  if (!b->has3d) {  // no problem of the batch carries an annotation: every one is short of constraints, nothing to compute
+    for (int i = 0; i < b->n_scene; ++i) status[i] = kBaCovDof;
+    if (device_ms) *device_ms = 0.0;
+    return PTZ_OK;
+  }
+  clear_stale_error(__func__);
+  PTZ_DEVICE_GUARD(b->device);
+  const Dev& d = b->d;
+  void* dsc = nullptr;
+  if (ptzpool::dev_acquire(b->device, sizeof(BaCovScene) * b->n_scene, &dsc) != hipSuccess) return PTZ_ENOMEM;
+  const bool initial = b->n_solves == 0;
+  hipLaunchKernelGGL(k_ba_cov_pack, dim3((b->n_scene + 63) / 64), dim3(64), 0, b->stream, d, initial ? 1 : 0, static_cast<BaCovScene*>(dsc));
+  std::vector<BaCovScene> hs(b->n_scene);
+  int32_t rc = PTZ_OK;
+  if (copy_on(b->stream, hs.data(), dsc, sizeof(BaCovScene) * b->n_scene, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) rc = PTZ_ENODEVICE;
+  if (!rc) {
+    BaCovIn in;
+    in.n_scene = b->n_scene; in.type = b->type; in.device = b->device;
+    in.scene = static_cast<const BaCovScene*>(dsc);
+    in.obs_uv = d.obs_uv; in.obs_cam = d.obs_cam; in.ray_ptr = d.ray_ptr; in.cam_ptr = d.cam_ptr; in.cam_obs = d.cam_obs;
+    in.pair_cj = d.pair_cj; in.pair_ptr = d.pair_ptr; in.cam_pair = d.cam_pair; in.ent = d.ent; in.ray_w = d.ray_w;
+    in.cam_x = initial ? b->cam0 : d.cam_x; in.ray_x = initial ? b->ray0 : d.ray_x;
+    in.cam_stride = initial ? 0 : d.cam_stride; in.ray_stride = initial ? 0 : d.ray_stride;
+    BaGeoIn geo;
+    geo.o3_uv = d.o3_uv; geo.o3_xyz = d.o3_xyz; geo.o3_cam = d.o3_cam;
+    geo.tlw_x = initial ? b->tlw0 : d.tlw_x; geo.tlw_stride = initial ? 0 : d.tlw_stride;
+    rc = ba_geo_cov_run(in, geo, hs.data(), gauge.data(), pixel_sigma, annotation_sigma, b->stream, cov, cov_centre, sigma0, status, device_ms);
+  }
+  ptzpool::dev_release(b->device, dsc);
+  return rc;
+}
+
+int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, const double* ray, const double* tlw, int32_t gauge_cam,
+                                 double pixel_sigma, double annotation_sigma, const ptz_lm_options* opt, double* cov, double* cov_centre,
+                                 double* sigma0, int32_t* status)
+{
+  if (!p || !cam || !ray || !tlw || !cov || !cov_centre || !sigma0 || !status) return PTZ_EINVAL;
+  if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma) || !(annotation_sigma >= 0.0) || !std::isfinite(annotation_sigma)) return PTZ_EINVAL;
+  if (ba_geo_cov_dim(p->factor_type) < 0 || p->ic_of_cam) return PTZ_EUNSUPPORTED;
+  if (gauge_cam < 0 || gauge_cam >= p->n_cam) return PTZ_EINVAL;
+  ptz_ba_batch* b = nullptr;
+  int rc = ptz_ba_batch_create(1, p, opt, &b);
+  if (rc) return rc;
+  rc = ptz_ba_batch_set_state(b, cam, ray, tlw);
+  if (!rc) rc = ptz_ba_batch_covariance_georef(b, &gauge_cam, pixel_sigma, annotation_sigma, cov, cov_centre, sigma0, status, nullptr);
   ptz_ba_batch_destroy(b);
   return rc;
 }

@@ -170,6 +170,7 @@ struct BaCovScene {  // per problem, on the device: the real extents (a view bat
   int n_cam, n_ray, n_obs, n_pair;
   int cam_off, ray_off, obs_off, pair_off;
   int idx, cur;
+  int o3_off, n_o3;  // 2D-3D annotations (read by the georeferenced covariance only, ptz_ba_cov_georef.h)
 };
 struct BaCovIn {
   int n_scene, type, device;

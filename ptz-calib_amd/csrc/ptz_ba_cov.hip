@@ -14,6 +14,8 @@
 //   finish     diagonal blocks of G S^-1 (O(n^2 NF)), unscaling, left-perturbation form, s^2               [wave / camera]
 // Every sum has one order that depends on the problem alone (a tile's k loop runs over the problem's own tiles, not the
 // group's padded order), so a problem's bits do not depend on its position in the batch, on the grouping or on the run.
+// The second half of the file is the covariance of GEOREFERENCED cameras (definition: ptz_ba_cov_georef.h): the same matrix stage
+// behind kernels of its own for the 2D-3D annotations, the bordered assembly and the world-frame finish.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -22,6 +24,7 @@
 #include "ptz_common.h"
 #include "ptz_pool.h"
 #include "ptz_ba_cov.h"
+#include "ptz_ba_cov_georef.h"
 
 namespace ptz {
 
@@ -49,6 +52,16 @@ struct BaCovWork {  // one group of problems
   double* cov;             // [cameras of the group][NF NF]
   double* sig;             // [count] sigma0
   double pixel_sigma;
+  // the georeferenced covariance only (ptz_ba_cov_georef.h; the second half of this file)
+  int o3_lo;               // first annotation of the group (global index)
+  double* tlwblk;          // [count][TLWBLK]
+  double* arec;            // [annotations of the group][ba_geo_rec(NC)]: A_a, G_a, |e_a|^2
+  double* asum;            // [cameras of the group][NC NC + 6 NC]: the camera's annotation sums A^T A, A^T G
+  int* live;               // [cameras of the group] 1: the camera has annotations, its fy column is live
+  double* var;             // [count][4]: s_f^2 and s_a^2 of M, then the two estimates
+  int* n_ann;              // [count] annotated cameras
+  double* cen;             // [count][9]
+  double annotation_sigma;
 };
 
 __global__ void k_ba_cov_cam(BaCovIn in, BaCovWork w, int nf)
@@ -396,6 +409,307 @@ template <int TYPE> void enqueue_group(const BaCovIn& in, const BaCovWork& w, co
   hipLaunchKernelGGL(k_ba_cov_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
 }
 
+// ==== the georeferenced covariance (definition: ptz_ba_cov_georef.h) ===============================================================
+// The same pipeline in the block dimension NC = NF + 1 with the six T_l_w columns bordering the system; k_ba_cov_ray, k_ba_cov_sse,
+// the Cholesky, k_ba_cov_tri_inv and k_ba_cov_gemm run unchanged.  Per group:
+//   geo_cam      camera blocks, the T_l_w block, n = NC n_cam + 6                                          [thread / camera]
+//   ray, sse     as above (the 2D-2D records in their NF columns)
+//   geo_annot    a camera's annotations: records (A_a, G_a, |e_a|^2), then A^T A and A^T G summed over the
+//                camera's annotations in stored order, one lane per element                                 [wave / camera]
+//   geo_reduce   (L, L) = sum G^T G and SSE_2d3d in stored order, the annotated cameras, the two variances   [wave / problem]
+//   geo_assemble block row ci of S and of M = s_f^2 T_f + s_a^2 T_a, the border (ci, L) and its mirror        [workgroup / camera]
+//   geo_scale    identity rows (gauge, dead fy), unit diagonal                                              [workgroup / row]
+//   cholesky, tri_inv, gemm x 2
+//   geo_finish   blocks (c, c), (c, L), (L, L) of G S^-1, unscaling, the world block; camera 0: the centre    [wave / camera]
+// M is ONE matrix in absolute units: both variances are known before the assembly (the residuals are summed by the kernels that
+// linearise), so there is one product S^-1 M, no second n x n matrix, and no ratio s_a^2 / s_f^2 that an exact fit would make 0 / 0.
+__global__ void k_geo_cam(BaCovIn in, BaGeoIn geo, BaCovWork w, int nc)
+{
+  const int g = blockIdx.y;
+  const BaCovScene s = in.scene[w.first + g];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0) {
+    w.n[g] = nc * s.n_cam + 6;
+    ba_geo_tlwblk(geo.tlw_x + (size_t)s.cur * geo.tlw_stride + (size_t)s.idx * 6, w.tlwblk + (size_t)g * TLWBLK);
+  }
+  if (c >= s.n_cam) return;
+  const double* c15 = in.cam_x + (size_t)s.cur * in.cam_stride + (size_t)(s.cam_off + c) * 15;
+  ba_cov_camblk(c15, w.camblk + (size_t)(s.cam_off + c - w.cam_lo) * CAMBLK);
+}
+
+template <int TYPE>
+__global__ __launch_bounds__(64) void k_geo_annot(BaCovIn in, BaGeoIn geo, BaCovWork w)
+{
+  constexpr int NC = BaDims<TYPE>::NC + 1, REC = ba_geo_rec(NC), NA = NC * NC + 6 * NC;
+  const int g = blockIdx.y, c = blockIdx.x;
+  const BaCovScene s = in.scene[w.first + g];
+  if (c >= s.n_cam) return;
+  const size_t gc = (size_t)(s.cam_off + c - w.cam_lo);
+  const double* cb = w.camblk + gc * CAMBLK;
+  const double* tb = w.tlwblk + (size_t)g * TLWBLK;
+  const int* oc = geo.o3_cam + s.o3_off;
+  double* rec0 = w.arec + (size_t)(s.o3_off - w.o3_lo) * REC;
+  int mine = 0, behind = 0;
+  for (int a = threadIdx.x; a < s.n_o3; a += 64) {
+    if (oc[a] != c) continue;
+    mine = 1;
+    const size_t ga = (size_t)s.o3_off + a;
+    const float2 uv = geo.o3_uv[ga];
+    const double xyz[3] = {geo.o3_xyz[3 * ga], geo.o3_xyz[3 * ga + 1], geo.o3_xyz[3 * ga + 2]};
+    if (!ba_geo_annot<TYPE>(cb, tb, xyz, uv.x, uv.y, rec0 + (size_t)a * REC)) behind = 1;
+  }
+  if (behind) atomicOr(&w.flags[g], kBaCovBehind);
+  __threadfence_block();
+  __syncthreads();  // (the records this wave wrote are read back by it below)
+  for (int e = threadIdx.x; e < NA; e += 64) {
+    double sum = 0;
+    for (int a = 0; a < s.n_o3; ++a) {
+      if (oc[a] != c) continue;
+      const double* rec = rec0 + (size_t)a * REC;
+      sum += e < NC * NC ? ba_geo_cc(rec, NC, e / NC, e % NC) : ba_geo_cl(rec, NC, (e - NC * NC) / 6, (e - NC * NC) % 6);
+    }
+    w.asum[gc * NA + e] = sum;
+  }
+  mine = __any(mine);
+  if (threadIdx.x == 0) w.live[gc] = mine ? 1 : 0;
+}
+
+template <int TYPE>
+__global__ __launch_bounds__(64) void k_geo_reduce(BaCovIn in, BaCovWork w)
+{
+  constexpr int NF = BaDims<TYPE>::NC, NC = NF + 1, REC = ba_geo_rec(NC);
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const BaCovScene s = in.scene[w.first + g];
+  const double* rec0 = w.arec + (size_t)(s.o3_off - w.o3_lo) * REC;
+  __shared__ double va;
+  if (lane == 63) {
+    double t = 0;
+    for (int a = 0; a < s.n_o3; ++a) t += rec0[(size_t)a * REC + 2 * NC + 12];
+    int na = 0;
+    for (int c = 0; c < s.n_cam; ++c) na += w.live[s.cam_off + c - w.cam_lo];
+    double est2[2], var[2];
+    ba_geo_noise(NF, s.n_cam, s.n_ray, s.n_obs, s.n_o3, na, w.sse[g], t, w.pixel_sigma, w.annotation_sigma, est2, var);
+    double* o = w.var + 4 * (size_t)g;
+    o[0] = var[0]; o[1] = var[1]; o[2] = est2[0]; o[3] = est2[1];
+    w.n_ann[g] = na;
+    va = var[1];
+  }
+  const int m = lane / 6, q = lane % 6;
+  double sum = 0;
+  if (lane < 36)
+    for (int a = 0; a < s.n_o3; ++a) sum += ba_geo_ll(rec0 + (size_t)a * REC, NC, m >= q ? m : q, m >= q ? q : m);
+  __syncthreads();
+  if (lane >= 36) return;
+  const int np = w.np, nL = NC * s.n_cam;
+  const size_t e = (size_t)g * np * np + (size_t)(nL + m) * np + nL + q;
+  w.A[e] = sum;
+  w.T[e] = va * sum;
+  if (m == q) {
+    const bool ok = sum > 0.0 && isfinite(sum);
+    if (!ok) atomicOr(&w.flags[g], kBaCovBadDiag);
+    w.dsc[(size_t)g * np + nL + m] = ok ? 1.0 / sqrt(sum) : 1.0;
+  }
+}
+
+template <int TYPE>
+__global__ __launch_bounds__(256) void k_geo_assemble(BaCovIn in, BaCovWork w)
+{
+  constexpr int NF = BaDims<TYPE>::NC, NE = NF * NF, NC = NF + 1, NA = NC * NC + 6 * NC;
+  const int g = blockIdx.y, ci = blockIdx.x;
+  const BaCovScene s = in.scene[w.first + g];
+  if (ci >= s.n_cam) return;
+  const int np = w.np, nL = NC * s.n_cam;
+  double* A = w.A + (size_t)g * np * np;
+  double* T = w.T + (size_t)g * np * np;
+  const double vf = w.var[4 * (size_t)g], va = w.var[4 * (size_t)g + 1];
+  const size_t gc = (size_t)(s.cam_off + ci - w.cam_lo);
+  const double* as = w.asum + gc * NA;
+  const int* cp = in.cam_ptr + s.cam_off + s.idx;
+  const int o0 = cp[ci], no = cp[ci + 1] - o0;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (wv == 0 && lane < NC * NC) {  // the diagonal block: the 2D-2D terms over the camera's observation list, then its annotations' sum
+    const int k = lane / NC, l = lane % NC;
+    const int kk = k >= l ? k : l, ll = k >= l ? l : k;  // (the lower triangle's element for both halves: symmetric bit for bit)
+    double sS = 0, sT = 0;
+    if (k != 1 && l != 1) {
+      const int el = (kk ? kk - 1 : 0) * NF + (ll ? ll - 1 : 0);  // (ba_geo_pos inverted)
+      for (int q = 0; q < no; ++q) {
+        const double* dg = w.Dg + (size_t)(in.cam_obs[o0 + q] - w.obs_lo) * (NE + 1);
+        const double v = dg[el];
+        sS += v;
+        sT += dg[NE] * v;
+      }
+    }
+    const double a = as[kk * NC + ll], d = sS + a;
+    A[(size_t)(ci * NC + k) * np + ci * NC + l] = d;
+    T[(size_t)(ci * NC + k) * np + ci * NC + l] = vf * sT + va * a;
+    if (k == l) {
+      const bool ident = (ci == w.gauge[g] && k >= NC - 3) || (k == 1 && !w.live[gc]);
+      const bool ok = ident || (d > 0.0 && isfinite(d));
+      if (!ok) atomicOr(&w.flags[g], kBaCovBadDiag);
+      w.dsc[(size_t)g * np + ci * NC + k] = (ok && !ident) ? 1.0 / sqrt(d) : 1.0;
+    }
+  }
+  if (wv == 1 && lane < 6 * NC) {  // the border (ci, L) and its mirror
+    const double a = as[NC * NC + lane];
+    const size_t r = (size_t)(ci * NC + lane / 6), c = (size_t)(nL + lane % 6);
+    A[r * np + c] = a; A[c * np + r] = a;
+    T[r * np + c] = va * a; T[c * np + r] = va * a;
+  }
+  // block (ci, cj), cj < ci, as k_ba_cov_assemble, the 2D-2D columns at ba_geo_pos
+  const int* cpair = in.cam_pair + s.cam_off + s.idx;
+  const int pr0 = cpair[ci], npr = cpair[ci + 1] - pr0;
+  const int* pps = in.pair_ptr + s.pair_off + s.idx + pr0;
+  const int* pcj = in.pair_cj + s.pair_off + pr0;
+  if (lane >= NE) return;
+  const int k = lane / NF, l = lane % NF;
+  for (int pl = wv; pl < npr; pl += 4) {
+    const int cj = pcj[pl], e0 = pps[pl], e1 = pps[pl + 1];
+    if (cj < 0 || cj >= ci) continue;
+    const int oj = cp[cj];
+    double sS = 0, sT = 0;
+    for (int e = e0; e < e1; ++e) {
+      const unsigned ab = in.ent[e];
+      const size_t a = (size_t)(in.cam_obs[o0 + (int)(ab & 0xffffu)] - w.obs_lo), b = (size_t)(in.cam_obs[oj + (int)(ab >> 16)] - w.obs_lo);
+      const double v = ba_cov_pair_term(w.EY + a * (6 * NF) + 3 * NF, w.EY + b * (6 * NF), k, l);
+      sS += v;
+      sT += w.Dg[a * (NE + 1) + NE] * v;
+    }
+    const size_t r = (size_t)(ci * NC + ba_geo_pos(k)), c = (size_t)(cj * NC + ba_geo_pos(l));
+    A[r * np + c] = sS; A[c * np + r] = sS;
+    T[r * np + c] = vf * sT; T[c * np + r] = vf * sT;
+  }
+}
+
+// identity rows / columns (the gauge, the dead fy columns: identity in S, zero in M), then both matrices to the unit diagonal of S
+__global__ __launch_bounds__(256) void k_geo_scale(BaCovIn in, BaCovWork w, int nc)
+{
+  const int g = blockIdx.y, i = blockIdx.x;
+  const int n = w.n[g], np = w.np;
+  if (i >= n) return;
+  const BaCovScene s = in.scene[w.first + g];
+  const int nL = nc * s.n_cam, r0 = w.gauge[g] * nc + nc - 3;
+  const int* live = w.live + (s.cam_off - w.cam_lo);
+  auto ident = [&](int j) { return (j >= r0 && j < r0 + 3) || (j < nL && j % nc == 1 && !live[j / nc]); };
+  double* A = w.A + (size_t)g * np * np + (size_t)i * np;
+  double* T = w.T + (size_t)g * np * np + (size_t)i * np;
+  const double* sc = w.dsc + (size_t)g * np;
+  const double si = sc[i];
+  const bool gi = ident(i);
+  for (int j = threadIdx.x; j < n; j += 256) {
+    if (gi || ident(j)) { A[j] = i == j ? 1.0 : 0.0; T[j] = 0.0; }
+    else { const double f = si * sc[j]; A[j] *= f; T[j] *= f; }
+  }
+}
+
+// Z = the blocks (c, c), (c, L), (L, L) of G S^-1 (row p of G against row q of the symmetric S^-1), unscaled; the world block
+// W Z W^T, one lane per element; camera 0 also writes the centre's covariance
+template <int TYPE>
+__global__ __launch_bounds__(64) void k_geo_finish(BaCovIn in, BaCovWork w)
+{
+  constexpr int NF = BaDims<TYPE>::NC, NE = NF * NF, NC = NF + 1, NZ = NC + 6, NH = NZ * (NZ + 1) / 2;
+  const int g = blockIdx.y, c = blockIdx.x;
+  const BaCovScene s = in.scene[w.first + g];
+  if (c >= s.n_cam) return;
+  const int np = w.np, n = w.n[g], nL = NC * s.n_cam;
+  const double* G = w.A + (size_t)g * np * np;
+  const double* Si = w.Si + (size_t)g * np * np;
+  double acc[NH];
+#pragma unroll
+  for (int e = 0; e < NH; ++e) acc[e] = 0;
+  for (int j = threadIdx.x; j < n; j += 64) {
+    double gk[NZ], sk[NZ];
+#pragma unroll
+    for (int p = 0; p < NZ; ++p) {
+      const size_t row = (size_t)(p < NC ? c * NC + p : nL + p - NC) * np;
+      gk[p] = G[row + j]; sk[p] = Si[row + j];
+    }
+    int e = 0;
+#pragma unroll
+    for (int p = 0; p < NZ; ++p)
+#pragma unroll
+      for (int q = 0; q <= p; ++q) acc[e++] += gk[p] * sk[q];
+  }
+#pragma unroll
+  for (int e = 0; e < NH; ++e) acc[e] = wave_sum(acc[e]);
+  __shared__ double Z[NZ * NZ], W[NF * NZ], J[18], cen[3];
+  const double* sc = w.dsc + (size_t)g * np;
+  const size_t gc = (size_t)(s.cam_off + c - w.cam_lo);
+  const double* tb = w.tlwblk + (size_t)g * TLWBLK;
+  if (threadIdx.x == 0) {
+    int e = 0;
+#pragma unroll
+    for (int p = 0; p < NZ; ++p)
+#pragma unroll
+      for (int q = 0; q <= p; ++q) {
+        const double v = acc[e++] * sc[p < NC ? c * NC + p : nL + p - NC] * sc[q < NC ? c * NC + q : nL + q - NC];
+        Z[p * NZ + q] = v; Z[q * NZ + p] = v;
+      }
+    const double* cb = w.camblk + gc * CAMBLK;
+    ba_geo_world_W<TYPE>(cb + CB_JL, cb + CB_R, tb, W);
+    ba_geo_centre_J(tb, cen, J);
+  }
+  __syncthreads();
+  bool fin = true;
+  if (threadIdx.x < NE) {
+    const int k = threadIdx.x / NF, l = threadIdx.x % NF;
+    const double v = ba_geo_quad(W + (k >= l ? k : l) * NZ, W + (k >= l ? l : k) * NZ, Z, NZ, NZ);
+    fin = isfinite(v);
+    w.cov[gc * NE + threadIdx.x] = v;
+  }
+  else if (c == 0 && threadIdx.x < NE + 9) {
+    const int i = (threadIdx.x - NE) / 3, j = (threadIdx.x - NE) % 3;
+    const double v = ba_geo_quad(J + 6 * (i >= j ? i : j), J + 6 * (i >= j ? j : i), Z + NC * NZ + NC, 6, NZ);
+    fin = isfinite(v);
+    w.cen[9 * (size_t)g + threadIdx.x - NE] = v;
+  }
+  else if (c == 0 && threadIdx.x == 63) {
+    const double* v4 = w.var + 4 * (size_t)g;
+    fin = isfinite(v4[2]) && isfinite(v4[3]);
+    w.sig[2 * (size_t)g] = sqrt(v4[2]); w.sig[2 * (size_t)g + 1] = sqrt(v4[3]);
+  }
+  if (!fin) atomicOr(&w.flags[g], kBaCovNonFinite);
+}
+
+template <int TYPE>
+void enqueue_geo_group(const BaCovIn& in, const BaGeoIn& geo, const BaCovWork& w, const CholBatch& cb, double* x, int max_cam, int max_ray,
+                       int max_n, hipStream_t st)
+{
+  constexpr int NC = BaDims<TYPE>::NC + 1;
+  const int nt = w.np / NB;
+  hipLaunchKernelGGL(k_geo_cam, dim3((max_cam + 63) / 64, w.count), dim3(64), 0, st, in, geo, w, NC);
+  chol_clear(cb, st);  // zero, padding rows, fail flags (reads n)
+  hipLaunchKernelGGL(k_ba_cov_ray<TYPE>, dim3((max_ray + 255) / 256, w.count), dim3(256), 0, st, in, w);
+  hipLaunchKernelGGL(k_ba_cov_sse, dim3((w.count + 63) / 64), dim3(64), 0, st, in, w);
+  hipLaunchKernelGGL(k_geo_annot<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, geo, w);
+  hipLaunchKernelGGL(k_geo_reduce<TYPE>, dim3(w.count), dim3(64), 0, st, in, w);
+  hipLaunchKernelGGL(k_geo_assemble<TYPE>, dim3(max_cam, w.count), dim3(256), 0, st, in, w);
+  hipLaunchKernelGGL(k_geo_scale, dim3(max_n, w.count), dim3(256), 0, st, in, w, NC);
+  chol_factor_solve(cb, x, st);
+  hipLaunchKernelGGL(k_ba_cov_tri_inv, dim3(nt, w.count), dim3(256), 0, st, w);
+  hipLaunchKernelGGL(k_ba_cov_gemm<0>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
+  hipLaunchKernelGGL(k_ba_cov_gemm<1>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
+  hipLaunchKernelGGL(k_geo_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
+}
+
+// what a run holds until it returns: the group's workspace and the two timing events, released once the stream is idle
+struct CovHeld {
+  int dev; void* base = nullptr; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~CovHeld()
+  {
+    (void)stream_wait(st);
+    if (base) ptzpool::dev_release(dev, base);
+    if (e0) ptzpool::event_release(dev, true, e0);
+    if (e1) ptzpool::event_release(dev, true, e1);
+  }
+};
+// bytes of workspace per group of problems (PTZ_BA_COV_MAX_MB, default 2048)
+size_t cov_budget()
+{
+  if (const char* e = getenv("PTZ_BA_COV_MAX_MB")) return (size_t)std::max(1ll, atoll(e)) << 20;
+  return (size_t)2048 << 20;
+}
+
 }  // namespace
 
 int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double pixel_sigma, hipStream_t st, double* cov, double* sigma0,
@@ -403,19 +717,9 @@ int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double
 {
   const int nf = ba_cov_dim(in.type), NE = nf * nf;
   if (nf < 0) return PTZ_EUNSUPPORTED;
-  size_t budget = (size_t)2048 << 20;  // of workspace per group of problems
-  if (const char* e = getenv("PTZ_BA_COV_MAX_MB")) budget = (size_t)std::max(1ll, atoll(e)) << 20;
+  const size_t budget = cov_budget();
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  struct Held {
-    int dev; void* base = nullptr; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      (void)stream_wait(st);
-      if (base) ptzpool::dev_release(dev, base);
-      if (e0) ptzpool::event_release(dev, true, e0);
-      if (e1) ptzpool::event_release(dev, true, e1);
-    }
-  } h;
+  CovHeld h;
   h.dev = in.device; h.st = st;
   PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
   PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
@@ -499,6 +803,114 @@ int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double
       if (stt != kBaCovOk) continue;
       memcpy(cov + (size_t)s.cam_off * NE, hc.data() + (size_t)(s.cam_off - w.cam_lo) * NE, sizeof(double) * NE * s.n_cam);
       sigma0[first + k] = hsig[k];
+    }
+    ptzpool::dev_release(h.dev, h.base);
+    h.base = nullptr;
+    first += count;
+  }
+  if (device_ms) *device_ms = total_ms;
+  return PTZ_OK;
+}
+
+int ba_geo_cov_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, const int* gauge, double pixel_sigma, double annotation_sigma,
+                   hipStream_t st, double* cov, double* cov_centre, double* sigma0, int* status, double* device_ms)
+{
+  const int nf = ba_geo_cov_dim(in.type), NE = nf * nf, nc = nf + 1;
+  if (nf < 0) return PTZ_EUNSUPPORTED;
+  const size_t budget = cov_budget();
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  CovHeld h;
+  h.dev = in.device; h.st = st;
+  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
+  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  double total_ms = 0;
+  constexpr int NOFF = 24;
+  // bytes of a group of `count` problems of padded order np over `cams` cameras, `obs` observation and `o3` annotation slots
+  auto group_bytes = [&](size_t count, size_t np, size_t cams, size_t obs, size_t o3, size_t waves, size_t* offs) {
+    const size_t nt = np / NB;
+    size_t o = 0;
+    auto take = [&](int k, size_t bytes) { if (offs) offs[k] = o; o += up(bytes); };
+    for (int k = 0; k < 4; ++k) take(k, sizeof(double) * count * np * np);  // A, T, X, Si
+    take(4, sizeof(double) * count * nt * NB * NB);                         // Ldiag
+    take(5, sizeof(double) * count * nt * NB * NB);                         // Linv
+    take(6, sizeof(double) * count * nt * 4 * 16 * 16);                     // Dinv
+    take(7, sizeof(double) * count * np);                                   // x
+    take(8, sizeof(double) * count * np);                                   // dsc
+    take(9, sizeof(double) * cams * CAMBLK);
+    take(10, sizeof(double) * obs * 6 * nf);
+    take(11, sizeof(double) * obs * (NE + 1));
+    take(12, sizeof(double) * count * waves);
+    take(13, sizeof(double) * count);                                       // sse
+    take(14, sizeof(double) * cams * NE);                                   // cov
+    take(15, sizeof(double) * count * 2);                                   // sig
+    take(16, sizeof(int) * count * 5);                                      // n, flags, gauge, fail, n_ann
+    take(17, sizeof(double) * count * TLWBLK);
+    take(18, sizeof(double) * (o3 + 1) * ba_geo_rec(nc));                   // arec
+    take(19, sizeof(double) * cams * (nc * nc + 6 * nc));                   // asum
+    take(20, sizeof(int) * cams);                                           // live
+    take(21, sizeof(double) * count * 4);                                   // var
+    take(22, sizeof(double) * count * 9);                                   // cen
+    return o;
+  };
+  for (int first = 0; first < in.n_scene;) {
+    // the group: problems first .. first + count - 1, as many as the budget holds (one at least)
+    int count = 0, max_cam = 0, max_ray = 0, max_n = 0;
+    size_t cams = 0, obs = 0, o3 = 0, bytes = 0;
+    for (int i = first; i < in.n_scene; ++i) {
+      const int mc = std::max(max_cam, hs[i].n_cam), mr = std::max(max_ray, hs[i].n_ray);
+      const size_t c2 = (size_t)(hs[i].cam_off + hs[i].n_cam - hs[first].cam_off), o2 = (size_t)(hs[i].obs_off + hs[i].n_obs - hs[first].obs_off);
+      const size_t a2 = (size_t)(hs[i].o3_off + hs[i].n_o3 - hs[first].o3_off);
+      const size_t b2 = group_bytes((size_t)(i - first + 1), (size_t)chol_padded_order(nc * mc + 6), c2, o2, a2, (size_t)(mr + 63) / 64 + 1, nullptr);
+      if (count > 0 && b2 > budget) break;
+      count = i - first + 1; max_cam = mc; max_ray = mr; max_n = nc * mc + 6; cams = c2; obs = o2; o3 = a2; bytes = b2;
+    }
+    BaCovWork w;
+    w.first = first; w.count = count; w.np = chol_padded_order(max_n);
+    w.cam_lo = hs[first].cam_off; w.obs_lo = hs[first].obs_off; w.o3_lo = hs[first].o3_off;
+    w.max_waves = (max_ray + 63) / 64 + 1;
+    w.pixel_sigma = pixel_sigma; w.annotation_sigma = annotation_sigma;
+    size_t offs[NOFF];
+    (void)group_bytes((size_t)count, (size_t)w.np, cams, obs, o3, (size_t)w.max_waves, offs);
+    if (ptzpool::dev_acquire(h.dev, bytes, &h.base) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+    char* base = static_cast<char*>(h.base);
+    auto at = [&](int k) { return reinterpret_cast<double*>(base + offs[k]); };
+    w.A = at(0); w.T = at(1); w.X = at(2); w.Si = at(3);
+    w.Linv = at(5); w.dsc = at(8); w.camblk = at(9); w.EY = at(10); w.Dg = at(11); w.sse_part = at(12); w.sse = at(13); w.cov = at(14); w.sig = at(15);
+    w.tlwblk = at(17); w.arec = at(18); w.asum = at(19); w.live = reinterpret_cast<int*>(base + offs[20]); w.var = at(21); w.cen = at(22);
+    int* ints = reinterpret_cast<int*>(base + offs[16]);
+    w.n = ints; w.flags = ints + count; w.gauge = ints + 2 * count; w.n_ann = ints + 4 * count;
+    CholBatch cb;
+    cb.count = count; cb.np = w.np; cb.A = w.A; cb.Ldiag = at(4); cb.Linv = w.Linv; cb.Dinv = at(6); cb.n = w.n; cb.fail = ints + 3 * count;
+    std::vector<int> hg(gauge + first, gauge + first + count);
+    PTZ_HIP_TRY(hipMemsetAsync(ints, 0, sizeof(int) * 5 * count, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(ints + 2 * count, hg.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
+    PTZ_HIP_TRY(hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)count * w.np * w.np, st));
+    PTZ_HIP_TRY(hipEventRecord(h.e0, st));
+    if (in.type == 0) enqueue_geo_group<0>(in, geo, w, cb, at(7), max_cam, max_ray, max_n, st);
+    else enqueue_geo_group<1>(in, geo, w, cb, at(7), max_cam, max_ray, max_n, st);
+    PTZ_HIP_TRY(hipEventRecord(h.e1, st));
+    // the group's results come back into buffers of their own: only problems whose status is OK reach the caller's arrays
+    std::vector<double> hc(cams * NE), hsig(2 * (size_t)count), hcen(9 * (size_t)count);
+    std::vector<int> hi(5 * (size_t)count);
+    PTZ_HIP_TRY(hipMemcpyAsync(hc.data(), w.cov, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(hsig.data(), w.sig, sizeof(double) * hsig.size(), hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(hcen.data(), w.cen, sizeof(double) * hcen.size(), hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(hi.data(), ints, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(stream_wait(st));
+    PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, h.e0, h.e1);
+    total_ms += ms;
+    for (int k = 0; k < count; ++k) {
+      const BaCovScene& s = hs[first + k];
+      const int fail = hi[3 * (size_t)count + k], flags = hi[(size_t)count + k], n_ann = hi[4 * (size_t)count + k];
+      if (fail & 2) return PTZ_ENODEVICE;  // (a hand-over of the one-launch factorisation: not a path this call takes)
+      const int stt = ba_geo_status(nf, s.n_cam, s.n_ray, s.n_obs, s.n_o3, n_ann, fail & 1, flags);
+      status[first + k] = stt;
+      if (stt != kBaCovOk) continue;
+      memcpy(cov + (size_t)s.cam_off * NE, hc.data() + (size_t)(s.cam_off - w.cam_lo) * NE, sizeof(double) * NE * s.n_cam);
+      memcpy(cov_centre + 9 * (size_t)(first + k), hcen.data() + 9 * (size_t)k, sizeof(double) * 9);
+      sigma0[2 * (size_t)(first + k)] = hsig[2 * (size_t)k]; sigma0[2 * (size_t)(first + k) + 1] = hsig[2 * (size_t)k + 1];
     }
     ptzpool::dev_release(h.dev, h.base);
     h.base = nullptr;

@@ -765,4 +765,77 @@ int32_t ptzh_ptzray_solve_cov(int32_t n_img, const int64_t* kp_ptr, const float*
   return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
 }
 
+// PTZRayOptimizer::Solve with annotations followed by WorldCovariance / WorldStdDevs / Covariance.  cov needs room for 25
+// doubles per candidate, std_devs for 5; before_solve = the answer of WorldCovariance() on the object before Solve() (must be 0);
+// plain_cov = the answer of Covariance() after Solve() (0 on an annotated problem).  The packed_* outputs are the 2D-2D part of
+// the problem and the SOLVED state (tlw6 included) the class handed to ptz_ba_covariance_georef; the annotations it packed come
+// back in o3_* (n_o3 entries).  Returns Solve() | WorldCovariance() << 1 | WorldStdDevs() << 2.
+int32_t ptzh_ptzray_solve_world_cov(int32_t n_img, const int64_t* kp_ptr, const float* kp_xy, int32_t n_pairs, const int64_t* src,
+                                    const int64_t* dst, const int64_t* match_ptr, const int32_t* q, const int32_t* t, double* cam15,
+                                    const int64_t* ann_ptr, const float* ann_uv, const double* ann_xyz, const int64_t* cand_ids, int32_t n_cand,
+                                    int32_t max_iter, int32_t type, double* cov, double* cov_centre, double* std_devs, double* sigma_centre,
+                                    double* sigma0, double* centre, double* tlw6, int32_t* before_solve, int32_t* plain_cov, int32_t* n_obs_out,
+                                    int32_t* n_ray_out, float** p_uv, int32_t** p_cam, int32_t** p_ray, double** p_w, double** p_cam15,
+                                    double** p_ray3, int64_t** p_cam_image, int32_t* n_o3, float** o3_uv, double** o3_xyz, int32_t** o3_cam)
+{
+  std::vector<ImageFeatures> feats;
+  std::vector<MatchesInfo> mis;
+  std::vector<Camera> cams;
+  BuildInputs(n_img, kp_ptr, kp_xy, nullptr, n_pairs, src, dst, match_ptr, q, t, cam15, feats, mis, cams);
+  std::unordered_set<long> ids;
+  for (int i = 0; i < n_cand; ++i) ids.insert(static_cast<long>(cand_ids[i]));
+  std::vector<std::vector<Point2f>> pixels;
+  std::vector<std::vector<Point3d>> pts3d;
+  if (ann_ptr) {
+    pixels.resize(n_img);
+    pts3d.resize(n_img);
+    for (int i = 0; i < n_img; ++i)
+      for (int64_t k = ann_ptr[i]; k < ann_ptr[i + 1]; ++k) {
+        pixels[i].emplace_back(ann_uv[2 * k], ann_uv[2 * k + 1]);
+        pts3d[i].emplace_back(ann_xyz[3 * k], ann_xyz[3 * k + 1], ann_xyz[3 * k + 2]);
+      }
+  }
+  PTZRayOptimizer opt(feats, mis, cams, pixels, pts3d, ids, max_iter, static_cast<FACTOR_TYPE>(type));
+  std::vector<double> c, sd;
+  std::array<double, 9> cc{};
+  std::array<double, 3> sc{}, cen{};
+  std::array<double, 2> s0{};
+  if (before_solve) *before_solve = opt.WorldCovariance(c, cc, s0) ? 1 : 0;
+  const bool ok = opt.Solve(cams);
+  const PackedBA& p = opt.packed();
+  ExportPacked(p, PackedOut{n_obs_out, n_ray_out, p_uv, p_cam, p_ray, p_w, p_cam15, p_ray3, p_cam_image});
+  *n_o3 = static_cast<int32_t>(p.obs3d_cam.size());
+  *o3_uv = static_cast<float*>(malloc(sizeof(float) * (p.obs3d_uv.size() + 1)));
+  *o3_xyz = static_cast<double*>(malloc(sizeof(double) * (p.obs3d_xyz.size() + 1)));
+  *o3_cam = static_cast<int32_t*>(malloc(sizeof(int32_t) * (p.obs3d_cam.size() + 1)));
+  std::copy(p.obs3d_uv.begin(), p.obs3d_uv.end(), *o3_uv);
+  std::copy(p.obs3d_xyz.begin(), p.obs3d_xyz.end(), *o3_xyz);
+  std::copy(p.obs3d_cam.begin(), p.obs3d_cam.end(), *o3_cam);
+  for (int k = 0; k < 6; ++k) tlw6[k] = p.tlw[k];
+  if (ok)
+    for (int i = 0; i < n_img; ++i) {
+      const std::vector<double> v = cams[i].ToVector();
+      memcpy(cam15 + 15 * i, v.data(), sizeof(double) * 15);
+    }
+  const bool okc = opt.WorldCovariance(c, cc, s0);
+  if (okc) {
+    memcpy(cov, c.data(), sizeof(double) * c.size());
+    memcpy(cov_centre, cc.data(), sizeof(double) * 9);
+    sigma0[0] = s0[0]; sigma0[1] = s0[1];
+  }
+  std::array<double, 2> s1{};
+  const bool oks = opt.WorldStdDevs(sd, sc, s1) && opt.WorldCentre(cen);
+  if (oks) {
+    memcpy(std_devs, sd.data(), sizeof(double) * sd.size());
+    memcpy(sigma_centre, sc.data(), sizeof(double) * 3);
+    memcpy(centre, cen.data(), sizeof(double) * 3);
+  }
+  if (plain_cov) {
+    double sp = 0;
+    std::vector<double> cp;
+    *plain_cov = opt.Covariance(cp, sp) ? 1 : 0;
+  }
+  return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
+}
+
 }  // extern "C"

@@ -533,4 +533,69 @@ bool PTZRayOptimizer::StdDevs(std::vector<double>& std_devs, double& sigma0, lon
   return true;
 }
 
+bool PTZRayOptimizer::WorldCovariance(std::vector<double>& cov, std::array<double, 9>& cov_centre, std::array<double, 2>& sigma0,
+                                      double pixel_sigma, double annotation_sigma) const
+{
+  const PackedBA& p = packed_;
+  if (!solved_packed_ || p.ray.empty() || p.obs3d_cam.empty() || (type_ != PTZRay && type_ != PTZRayDist)) return false;
+  for (size_t c = 0; c < p.cam_image.size() && c < p.ic_of_cam.size(); ++c)
+    if (p.ic_of_cam[c] != static_cast<int32_t>(p.cam_image[c])) return false;  // shared intrinsics
+  ptz_ba_problem prob{};
+  prob.n_cam = static_cast<int32_t>(p.cam_image.size());
+  prob.n_ray = static_cast<int32_t>(p.ray_track.size());
+  prob.n_obs = static_cast<int64_t>(p.obs_cam.size());
+  prob.obs_uv = p.obs_uv.data();
+  prob.obs_cam = p.obs_cam.data();
+  prob.obs_ray = p.obs_ray.data();
+  prob.ray_weight = p.ray_weight.data();
+  prob.factor_type = type_ == PTZRay ? PTZ_BA_PTZRay : PTZ_BA_PTZRayDist;
+  prob.n_obs3d = static_cast<int32_t>(p.obs3d_cam.size());
+  prob.obs3d_uv = p.obs3d_uv.data();
+  prob.obs3d_xyz = p.obs3d_xyz.data();
+  prob.obs3d_cam = p.obs3d_cam.data();
+  const int32_t nf = ptz_ba_geo_cov_dim(prob.factor_type);
+  if (nf <= 0) return false;
+  ptz_lm_options opt;
+  ptz_lm_options_default(&opt);
+  opt.device_id = device_id_;
+  std::vector<double> c(static_cast<size_t>(nf) * nf * prob.n_cam, 0.0);
+  double cc[9] = {0}, s0[2] = {0, 0};
+  int32_t status = -1;
+  // (world-frame quantities do not depend on the anchor: camera 0)
+  const int32_t rc = ptz_ba_covariance_georef(&prob, p.cam.data(), p.ray.data(), p.tlw.data(), 0, pixel_sigma, annotation_sigma, &opt, c.data(), cc,
+                                              s0, &status);
+  if (rc != PTZ_OK || status != PTZ_COV_OK) return false;
+  cov.swap(c);
+  for (int k = 0; k < 9; ++k) cov_centre[k] = cc[k];
+  sigma0 = {{s0[0], s0[1]}};
+  return true;
+}
+
+bool PTZRayOptimizer::WorldStdDevs(std::vector<double>& std_devs, std::array<double, 3>& sigma_centre, std::array<double, 2>& sigma0,
+                                   double pixel_sigma, double annotation_sigma) const
+{
+  std::vector<double> cov;
+  std::array<double, 9> cc;
+  if (!WorldCovariance(cov, cc, sigma0, pixel_sigma, annotation_sigma)) return false;
+  const size_t n_cam = packed_.cam_image.size(), nf = static_cast<size_t>(std::lround(std::sqrt(static_cast<double>(cov.size() / n_cam))));
+  std_devs.assign(nf * n_cam, 0.0);
+  for (size_t c = 0; c < n_cam; ++c)
+    for (size_t k = 0; k < nf; ++k) std_devs[nf * c + k] = std::sqrt(cov[nf * nf * c + nf * k + k]);
+  for (int k = 0; k < 3; ++k) sigma_centre[k] = std::sqrt(cc[4 * k]);
+  return true;
+}
+
+bool PTZRayOptimizer::WorldCentre(std::array<double, 3>& centre) const
+{
+  if (!solved_packed_ || packed_.obs3d_cam.empty()) return false;
+  Mat33 R_l_w;
+  Vec3 t_l_w;
+  double tlw[6];
+  for (int k = 0; k < 6; ++k) tlw[k] = packed_.tlw[k];
+  T_l_w(tlw, R_l_w, t_l_w);
+  const Vec3 c = Mul(Transpose(R_l_w), t_l_w);
+  centre = {{-c[0], -c[1], -c[2]}};
+  return true;
+}
+
 }  // namespace ptzcalib

@@ -74,6 +74,20 @@ class PTZRayOptimizer {
   bool Covariance(std::vector<double>& cov, double& sigma0, long gauge_image = -1) const;
   // ... and the square roots of its diagonals: NF per candidate camera
   bool StdDevs(std::vector<double>& std_devs, double& sigma0, long gauge_image = -1) const;
+  // Covariance of the GEOREFERENCED cameras Solve hands back -- R_i R_lw -- and of the rig's projection centre
+  // (ptz_ba_covariance_georef, see include/ptz_calib_amd.h).  Valid at the state of the last successful Solve WITH annotations
+  // (PTZRay, PTZRayDist; no shared intrinsics) that was packed on the host -- false otherwise; Covariance() above keeps refusing
+  // such a problem.  cov: per candidate camera, in the order of packed().cam_image, NF * NF row-major over [fx, d1, d2, d3, (k1)],
+  // d a left perturbation of the WORLD rotation in radians; world-frame quantities need no anchor.  cov_centre: 3 x 3 of
+  // C_w = -R_lw^T t_lw in world units.  sigma0: the estimated noise of the key points and of the annotations; a positive
+  // pixel_sigma / annotation_sigma replaces the respective estimate in the covariance.
+  bool WorldCovariance(std::vector<double>& cov, std::array<double, 9>& cov_centre, std::array<double, 2>& sigma0, double pixel_sigma = 0.0,
+                       double annotation_sigma = 0.0) const;
+  // ... and the square roots of the diagonals: NF per candidate camera, three of the centre
+  bool WorldStdDevs(std::vector<double>& std_devs, std::array<double, 3>& sigma_centre, std::array<double, 2>& sigma0, double pixel_sigma = 0.0,
+                    double annotation_sigma = 0.0) const;
+  // the rig's projection centre C_w = -R_lw^T t_lw at the same state; false where WorldCovariance has no state
+  bool WorldCentre(std::array<double, 3>& centre) const;
   // The tracks depend on the match table only, not on the candidate set: a caller that solves many candidate subsets of
   // one match table (PtzIncrementalOptimizer) builds them once and shares them instead of repeating FindTracks().
   void UseTracks(std::shared_ptr<const SharedTracks> tracks) { shared_tracks_ = std::move(tracks); }
