@@ -36,6 +36,7 @@
 #include "ptz_common.h"
 #include "ptz_pool.h"
 #include "ptz_factor.h"
+#include "ptz_pass_shape.h"
 
 #include "ptz_ba_kernels.h"
 #include "ptz_view_kernels.h"
@@ -60,15 +61,19 @@ using namespace ptz;
 
 // chol_factor_solve split so that the three kernel families can be timed separately
 namespace ptz {
-void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stream, void* prof, bool fused);
+void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stream, void* prof, bool fused, int path_count);
 }
 
-// The launch shape of one LM pass.  A batch's passes start at full size; once few of its scenes are still active the host
-// switches to compacted shapes whose grids cover `slots` scenes (blockIdx.y -> scene through the device's compacted list), with
-// the workgroup size, the kernel variants and the factorisation path a batch of that size would get -- the stragglers of a
-// 1000-scene batch then cost what a handful of scenes cost, not a thousand empty workgroups per kernel.
+// The launch shape of one LM pass.  A batch keeps a ladder of them (ptz_ba_batch::shapes): full size, then compacted shapes of
+// 2, 8, 32 ... slots, each with the workgroup size, the kernel variants and the factorisation path a batch of that size would get
+// -- the stragglers of a 1000-scene batch then cost what a handful of scenes cost.  The ladder shape that covers the scenes last
+// reported active gives a pass its VARIANT fields (everything below `path_slots`).  Its grid EXTENT is a separate matter
+// (pass_extent, ptz_pass_shape.h): a pass replayed from a captured graph has the ladder shape's own extent; a pass enqueued launch
+// by launch covers exactly the reported count, through the device's compacted list (blockIdx.y -> slot -> scene) as soon as one
+// scene of the group has retired, so no workgroup is launched for a scene known to be finished.
 struct PassShape {
   int slots = 0;          // grid extent over scenes
+  int path_slots = 0;     // slot count of the ladder shape the variants come from: decides the factorisation path (chol_chain_fits)
   bool compact = false;   // blockIdx.y is a slot of the compacted list
   int ray_block = 1024;   // rays per workgroup of the ray-centric kernels
   bool small_blocks = false, fused = false;  // SMALL kernel variants; one-launch-per-column factorisation
@@ -126,6 +131,7 @@ struct ptz_ba_batch {
   std::vector<std::vector<hipGraphExec_t>> pass_graph;  // [group][shape]
   int* d_act = nullptr;                                 // compacted scene lists, n_scene ints (each group its own range)
   bool compaction = true;
+  bool exact_fit = true;                                // eagerly enqueued passes cover exactly the reported count (PTZ_BA_EXACT_FIT=0: the ladder's extents)
   double *cam0 = nullptr, *ray0 = nullptr, *tlw0 = nullptr;  // device copies of the initial state
   std::vector<int> sched_kmin;  // CholBatch::sched_kmin
   double* dsp0 = nullptr;  // PTZRayDistDisp: initial displacement block, one copy per camera (zeros unless ptz_ba_batch_set_disp)
@@ -505,6 +511,7 @@ template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const Pa
   d.chol.count = sh.slots;
   d.chol.act = sh.compact ? d.act : nullptr;
   d.chol.act_n = d.grp_ctl + 2;
+  const int path_slots = sh.path_slots > 0 ? sh.path_slots : sh.slots;
   if (!sh.fused) d.chol.L = nullptr;  // (the second matrix marks the one-launch-per-column path)
   // Scenes without annotation residuals and shared blocks: the camera-side linearisation of the CANDIDATE is evaluated before the
   // step is judged (k_lin_cam, Dev::spec_lin), and one control point per pass judges the step and opens the next iteration
@@ -551,7 +558,7 @@ template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const Pa
   if (Dims<TYPE>::HAS3D) LAUNCH(k_schur_3d<TYPE>, dim3(B), dim3(64), 0, d);
   if (d.shared) LAUNCH(k_fold_system<TYPE>, dim3(B), dim3(1024), sizeof(double) * (size_t)(b->max_n + 4) + (size_t)(d.chol.np / CHOL_NB) * (d.chol.np / CHOL_NB), d);
   b->prof_end();
-  chol_factor_solve_profiled(d.chol, d.yc, st, b, sh.fused);
+  chol_factor_solve_profiled(d.chol, d.yc, st, b, sh.fused, path_slots);
   if (d.shared) LAUNCH(k_group_expand<TYPE>, dim3(B), dim3(256), 0, d);
   if (!fuse) {
     b->prof_begin(P_BACKSUB);
@@ -651,6 +658,7 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
       g_recorder = &rec;
       PassShape shg = b->shapes[si];
       if (si == 0) shg.slots = b->group_count[g];
+      shg.path_slots = shg.slots;
       enqueue_pass<TYPE>(b, b->dg[g], shg);
       g_recorder = nullptr;
       ok = rec.ok && hipGraphInstantiate(&b->pass_graph[g][si], rec.graph, nullptr, nullptr, 0) == hipSuccess;
@@ -660,7 +668,10 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
     return b->pass_graph[g][si];
   };
   std::vector<char> galive(G, 1);
-  std::vector<int> enq(G, 0), shape_used;
+  std::vector<int> enq(G, 0), shape_used, ladder;
+  for (const PassShape& s : b->shapes) ladder.push_back(s.slots);
+  struct PassLog { int g, si, slots, cnt; };
+  std::vector<PassLog> pass_log;  // PTZ_BA_DEBUG_TIMING: what the host chose for every enqueued pass
   // Watchdog.  The loop below only ever waits on words the DEVICE writes; if a launch was refused, a kernel faulted or the
   // progress word stops moving for any other reason, nothing would ever clear the wait.  So whenever no group has made
   // progress for `watchdog_ms`, every waiting group's stream is asked for its state: an error ends the solve with
@@ -682,21 +693,26 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
       if (enq[g] - std::max(__atomic_load_n(&b->h_ctl[4 * g], __ATOMIC_ACQUIRE), credit[g]) >= b->ahead) continue;
       const double te0 = now();
       b->stream = b->streams[g];
-      // launch shape: the smallest one that covers the scenes last reported active (the count only ever decreases, so a stale
-      // value is an upper bound); full size while more than the largest compacted shape are
-      int si = 0;
-      if (b->compaction) {
-        const int cnt = __atomic_load_n(&b->h_ctl[4 * g + 2], __ATOMIC_ACQUIRE);
-        for (int k = 1; k < (int)b->shapes.size(); ++k)
-          if (b->shapes[k].slots >= cnt && b->shapes[k].slots < b->group_count[g]) { si = k; break; }
-      }
+      // launch shape: the variants of the smallest ladder shape that covers the scenes last reported active (the count only ever
+      // decreases, so a stale value is an upper bound); the extent is the ladder shape's for a replayed graph and the count itself
+      // for a pass enqueued here (pass_extent)
+      const int cnt = __atomic_load_n(&b->h_ctl[4 * g + 2], __ATOMIC_ACQUIRE);
+      const bool replay = graph && b->use_graph;
+      const PassExtent ext = pass_extent(cnt, b->group_count[g], ladder.data(), b->compaction ? (int)ladder.size() : 1, replay, b->exact_fit);
+      const int si = ext.shape;
       PassShape sh = b->shapes[si];
-      if (si == 0) { sh.slots = b->group_count[g]; }
-      if (dbg) { if (shape_used.size() < b->shapes.size()) shape_used.resize(b->shapes.size(), 0); ++shape_used[si]; }
+      sh.path_slots = si == 0 ? b->group_count[g] : sh.slots;
+      sh.slots = ext.slots;
+      sh.compact = ext.compact;
+      if (dbg) {
+        if (shape_used.size() < b->shapes.size()) shape_used.resize(b->shapes.size(), 0);
+        ++shape_used[si];
+        pass_log.push_back({g, si, sh.slots, cnt});
+      }
       // (one or two rigs: the passes are enqueued as they are -- a pass is ~200 us of device time against ~25 us of host time for its
       //  six launches, and between two REPLAYED graphs the device idles 8.4 us: 5.20 -> 5.09 ms per 25-iteration solve of the C2 rig,
       //  A/B on one box)
-      hipGraphExec_t ge = (graph && b->use_graph && sh.slots > 2) ? graph_of(g, si) : nullptr;
+      hipGraphExec_t ge = (replay && sh.slots > 2) ? graph_of(g, si) : nullptr;
       if (ge) PTZ_HIP_TRY(hipGraphLaunch(ge, b->streams[g]));
       else { b->stream = b->streams[g]; enqueue_pass<TYPE>(b, b->dg[g], sh); }
       ++enq[g];
@@ -773,6 +789,24 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
     else PTZ_HIP_TRY(copy_on(b->stream, h.data(), d.lm, sizeof(LmState) * B, hipMemcpyDeviceToHost));
     int timeouts = 0;
     for (int i = 0; i < B; ++i) timeouts += h[i].chain_timeouts;
+    if (dbg && !pass_log.empty()) {
+      // Launch extents against the scenes that were really active: pass p of a group works on the scenes that took more than p
+      // LM steps.  Per ladder shape: slots launched, live scenes, empty slots (slots without a live scene), summed over its passes.
+      // PTZ_BA_DEBUG_TIMING=2 lists every pass: group, pass, shape, slots, the host's (stale) count, live scenes.
+      const bool each = atoi(getenv("PTZ_BA_DEBUG_TIMING")) >= 2;
+      std::vector<int> pass_of(G, 0);
+      std::vector<long long> slots_sum(b->shapes.size(), 0), live_sum(b->shapes.size(), 0), stale_sum(b->shapes.size(), 0);
+      for (const PassLog& pl : pass_log) {
+        const int p = pass_of[pl.g]++;
+        int live = 0;
+        for (int i = b->group_first[pl.g]; i < b->group_first[pl.g] + b->group_count[pl.g]; ++i) live += h[i].num_lm_steps > p;
+        slots_sum[pl.si] += pl.slots; live_sum[pl.si] += live; stale_sum[pl.si] += pl.cnt;
+        if (each) fprintf(stderr, "[ptz_ba] pass g%d p%d: shape %d, %d slots, host count %d, live %d\n", pl.g, p, pl.si, pl.slots, pl.cnt, live);
+      }
+      for (size_t k = 0; k < b->shapes.size(); ++k)
+        if (slots_sum[k]) fprintf(stderr, "[ptz_ba] launch shape %zu: slots x passes %lld, host count x passes %lld, live scenes x passes %lld, empty slots x passes %lld\n",
+                                  k, slots_sum[k], stale_sum[k], live_sum[k], slots_sum[k] - live_sum[k]);
+    }
     if (timeouts) {  // never a silently different trajectory: a hand-over that did not arrive is a device problem, not a rejected step
       fprintf(stderr, "[ptz_ba] %d linear solve(s) of this batch lost a tile hand-over of the one-launch factorisation (bounded wait ran out); "
                       "the solve is reported as failed\n", timeouts);
@@ -801,7 +835,7 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
 
 namespace ptz {
 // defined here (needs ptz_ba_batch) but uses the kernels of ptz_chol.hip through chol_factor_solve pieces
-void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stream, void* prof, bool fused)
+void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stream, void* prof, bool fused, int path_count)
 {
   // One-step look-ahead: after the triangular solve of block column k, the small update of block column k+1 stays on
   // the main stream, so the (latency-bound) diagonal factorisation and triangular solve of step k+1 start at once,
@@ -814,7 +848,8 @@ void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stre
   if (la) b->lookahead_events(stream, &evT, &evR);
   bool rest_pending = false;
   if (fused) {  // a few scenes: the whole factorisation in one launch (chol_chain_kernel), or one launch per step of the schedule (chol_col_step_kernel)
-    if (chol_chain_enabled(cb)) {
+    // (the path is that of the ladder shape, `path_count` systems, whatever the launch's own extent cb.count)
+    if (cb.L && cb.Linv && cb.chain_ctl && chol_chain_fits(path_count, cb.np)) {
       b->prof_begin(P_CHOL_SYRK);
       chol_chain_launch(cb, stream);
       b->prof_end();
@@ -2138,6 +2173,8 @@ static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_
   if (const char* e = getenv("PTZ_BA_GLOBAL_TABLES")) b->gtab = atoi(e) != 0;
   b->compaction = true;
   if (const char* e = getenv("PTZ_BA_COMPACT")) b->compaction = atoi(e) != 0;
+  b->exact_fit = true;
+  if (const char* e = getenv("PTZ_BA_EXACT_FIT")) b->exact_fit = atoi(e) != 0;
   auto make_shape = [&](int slots, bool compact) {
     PassShape sh;
     sh.slots = slots; sh.compact = compact;
