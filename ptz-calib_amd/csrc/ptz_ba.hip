@@ -2407,6 +2407,53 @@ int32_t ptz_ba_batch_get_state(ptz_ba_batch* b, double* cam, double* ray, double
   return PTZ_OK;
 }
 
+namespace {
+// the anchors of a batch covariance: gauge_cam checked against each problem's cameras (NULL: camera 0 everywhere)
+bool ba_cov_gauges(const ptz_ba_batch* b, const int32_t* gauge_cam, std::vector<int>& gauge)
+{
+  gauge.assign(b->n_scene, 0);
+  for (int i = 0; gauge_cam && i < b->n_scene; ++i) {
+    if (gauge_cam[i] < 0 || gauge_cam[i] >= b->scenes[i].n_cam) return false;
+    gauge[i] = gauge_cam[i];
+  }
+  return true;
+}
+
+// What ptz_ba_cov.hip is given of a batch, for both covariances: the scenes' real extents and state halves (k_ba_cov_pack) on the
+// device and on the host, BaCovIn (with_geo: BaGeoIn too) from the batch's resident structure.  Owns the device scene array.
+struct BaCovPrep {
+  int32_t rc = PTZ_OK;  // PTZ_OK, or why there is nothing to run
+  std::vector<BaCovScene> hs;
+  BaCovIn in;
+  BaGeoIn geo{};
+  BaCovPrep(ptz_ba_batch* b, bool with_geo) : device(b->device)
+  {
+    const Dev& d = b->d;
+    if (ptzpool::dev_acquire(device, sizeof(BaCovScene) * b->n_scene, &dsc) != hipSuccess) { rc = PTZ_ENOMEM; return; }
+    // before the first solve the state is the one last set (cam0 / ray0 / tlw0); afterwards the current half of every scene
+    const bool initial = b->n_solves == 0;
+    hipLaunchKernelGGL(k_ba_cov_pack, dim3((b->n_scene + 63) / 64), dim3(64), 0, b->stream, d, initial ? 1 : 0, static_cast<BaCovScene*>(dsc));
+    hs.resize(b->n_scene);
+    if (copy_on(b->stream, hs.data(), dsc, sizeof(BaCovScene) * b->n_scene, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) { rc = PTZ_ENODEVICE; return; }
+    in.n_scene = b->n_scene; in.type = b->type; in.device = device;
+    in.scene = static_cast<const BaCovScene*>(dsc);
+    in.obs_uv = d.obs_uv; in.obs_cam = d.obs_cam; in.ray_ptr = d.ray_ptr; in.cam_ptr = d.cam_ptr; in.cam_obs = d.cam_obs;
+    in.pair_cj = d.pair_cj; in.pair_ptr = d.pair_ptr; in.cam_pair = d.cam_pair; in.ent = d.ent; in.ray_w = d.ray_w;
+    in.cam_x = initial ? b->cam0 : d.cam_x; in.ray_x = initial ? b->ray0 : d.ray_x;
+    in.cam_stride = initial ? 0 : d.cam_stride; in.ray_stride = initial ? 0 : d.ray_stride;
+    if (!with_geo) return;
+    geo.o3_uv = d.o3_uv; geo.o3_xyz = d.o3_xyz; geo.o3_cam = d.o3_cam;
+    geo.tlw_x = initial ? b->tlw0 : d.tlw_x; geo.tlw_stride = initial ? 0 : d.tlw_stride;
+  }
+  ~BaCovPrep() { ptzpool::dev_release(device, dsc); }
+  BaCovPrep(const BaCovPrep&) = delete;
+
+ private:
+  int device;
+  void* dsc = nullptr;
+};
+}  // namespace
+
 int32_t ptz_ba_cov_dim(int32_t factor_type)
 {
   const int nf = ba_cov_dim(factor_type);
@@ -2420,34 +2467,13 @@ int32_t ptz_ba_batch_covariance(ptz_ba_batch* b, const int32_t* gauge_cam, doubl
   if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma)) return PTZ_EINVAL;
   // PTZRayDistDisp, 2D-3D annotations and shared intrinsics couple the cameras through blocks this reduced system does not carry
   if (ba_cov_dim(b->type) < 0 || b->has3d || b->d.shared) return PTZ_EUNSUPPORTED;
-  std::vector<int> gauge(b->n_scene, 0);
-  for (int i = 0; gauge_cam && i < b->n_scene; ++i) {
-    if (gauge_cam[i] < 0 || gauge_cam[i] >= b->scenes[i].n_cam) return PTZ_EINVAL;
-    gauge[i] = gauge_cam[i];
-  }
+  std::vector<int> gauge;
+  if (!ba_cov_gauges(b, gauge_cam, gauge)) return PTZ_EINVAL;
   clear_stale_error(__func__);
   PTZ_DEVICE_GUARD(b->device);
-  const Dev& d = b->d;
-  void* dsc = nullptr;
-  if (ptzpool::dev_acquire(b->device, sizeof(BaCovScene) * b->n_scene, &dsc) != hipSuccess) return PTZ_ENOMEM;
-  // before the first solve the state is the one last set (cam0 / ray0); afterwards the current half of every scene
-  const bool initial = b->n_solves == 0;
-  hipLaunchKernelGGL(k_ba_cov_pack, dim3((b->n_scene + 63) / 64), dim3(64), 0, b->stream, d, initial ? 1 : 0, static_cast<BaCovScene*>(dsc));
-  std::vector<BaCovScene> hs(b->n_scene);
-  int32_t rc = PTZ_OK;
-  if (copy_on(b->stream, hs.data(), dsc, sizeof(BaCovScene) * b->n_scene, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) rc = PTZ_ENODEVICE;
-  if (!rc) {
-    BaCovIn in;
-    in.n_scene = b->n_scene; in.type = b->type; in.device = b->device;
-    in.scene = static_cast<const BaCovScene*>(dsc);
-    in.obs_uv = d.obs_uv; in.obs_cam = d.obs_cam; in.ray_ptr = d.ray_ptr; in.cam_ptr = d.cam_ptr; in.cam_obs = d.cam_obs;
-    in.pair_cj = d.pair_cj; in.pair_ptr = d.pair_ptr; in.cam_pair = d.cam_pair; in.ent = d.ent; in.ray_w = d.ray_w;
-    in.cam_x = initial ? b->cam0 : d.cam_x; in.ray_x = initial ? b->ray0 : d.ray_x;
-    in.cam_stride = initial ? 0 : d.cam_stride; in.ray_stride = initial ? 0 : d.ray_stride;
-    rc = ba_cov_run(in, hs.data(), gauge.data(), pixel_sigma, b->stream, cov, sigma0, status, device_ms);
-  }
-  ptzpool::dev_release(b->device, dsc);
-  return rc;
+  BaCovPrep prep(b, false);
+  if (prep.rc) return prep.rc;
+  return ba_cov_run(prep.in, prep.hs.data(), gauge.data(), pixel_sigma, b->stream, cov, sigma0, status, device_ms);
 }
 
 int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const double* ray, int32_t gauge_cam, double pixel_sigma,
@@ -2479,11 +2505,8 @@ int32_t ptz_ba_batch_covariance_georef(ptz_ba_batch* b, const int32_t* gauge_cam
   if (!(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma) || !(annotation_sigma >= 0.0) || !std::isfinite(annotation_sigma)) return PTZ_EINVAL;
   // PTZRayFxfyDist, PTZRayDistDisp and shared intrinsics are not what the georeferencing stage solves
   if (ba_geo_cov_dim(b->type) < 0 || b->d.shared) return PTZ_EUNSUPPORTED;
-  std::vector<int> gauge(b->n_scene, 0);
-  for (int i = 0; gauge_cam && i < b->n_scene; ++i) {
-    if (gauge_cam[i] < 0 || gauge_cam[i] >= b->scenes[i].n_cam) return PTZ_EINVAL;
-    gauge[i] = gauge_cam[i];
-  }
+  std::vector<int> gauge;
+  if (!ba_cov_gauges(b, gauge_cam, gauge)) return PTZ_EINVAL;
   if (!b->has3d) {  // no problem of the batch carries an annotation: every one is short of constraints, nothing to compute
     for (int i = 0; i < b->n_scene; ++i) status[i] = kBaCovDof;
     if (device_ms) *device_ms = 0.0;
@@ -2491,29 +2514,10 @@ int32_t ptz_ba_batch_covariance_georef(ptz_ba_batch* b, const int32_t* gauge_cam
   }
   clear_stale_error(__func__);
   PTZ_DEVICE_GUARD(b->device);
-  const Dev& d = b->d;
-  void* dsc = nullptr;
-  if (ptzpool::dev_acquire(b->device, sizeof(BaCovScene) * b->n_scene, &dsc) != hipSuccess) return PTZ_ENOMEM;
-  const bool initial = b->n_solves == 0;
-  hipLaunchKernelGGL(k_ba_cov_pack, dim3((b->n_scene + 63) / 64), dim3(64), 0, b->stream, d, initial ? 1 : 0, static_cast<BaCovScene*>(dsc));
-  std::vector<BaCovScene> hs(b->n_scene);
-  int32_t rc = PTZ_OK;
-  if (copy_on(b->stream, hs.data(), dsc, sizeof(BaCovScene) * b->n_scene, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) rc = PTZ_ENODEVICE;
-  if (!rc) {
-    BaCovIn in;
-    in.n_scene = b->n_scene; in.type = b->type; in.device = b->device;
-    in.scene = static_cast<const BaCovScene*>(dsc);
-    in.obs_uv = d.obs_uv; in.obs_cam = d.obs_cam; in.ray_ptr = d.ray_ptr; in.cam_ptr = d.cam_ptr; in.cam_obs = d.cam_obs;
-    in.pair_cj = d.pair_cj; in.pair_ptr = d.pair_ptr; in.cam_pair = d.cam_pair; in.ent = d.ent; in.ray_w = d.ray_w;
-    in.cam_x = initial ? b->cam0 : d.cam_x; in.ray_x = initial ? b->ray0 : d.ray_x;
-    in.cam_stride = initial ? 0 : d.cam_stride; in.ray_stride = initial ? 0 : d.ray_stride;
-    BaGeoIn geo;
-    geo.o3_uv = d.o3_uv; geo.o3_xyz = d.o3_xyz; geo.o3_cam = d.o3_cam;
-    geo.tlw_x = initial ? b->tlw0 : d.tlw_x; geo.tlw_stride = initial ? 0 : d.tlw_stride;
-    rc = ba_geo_cov_run(in, geo, hs.data(), gauge.data(), pixel_sigma, annotation_sigma, b->stream, cov, cov_centre, sigma0, status, device_ms);
-  }
-  ptzpool::dev_release(b->device, dsc);
-  return rc;
+  BaCovPrep prep(b, true);
+  if (prep.rc) return prep.rc;
+  return ba_geo_cov_run(prep.in, prep.geo, prep.hs.data(), gauge.data(), pixel_sigma, annotation_sigma, b->stream, cov, cov_centre, sigma0, status,
+                        device_ms);
 }
 
 int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, const double* ray, const double* tlw, int32_t gauge_cam,

@@ -1,7 +1,8 @@
 // ptz_ba_cov.h -- per-view covariance of bundle-adjusted cameras: the definition and the per-ray / per-camera algebra (FP64).
 //
 // PTZ_HD like ptz_factor.h and ptz_krt_cov.h: the kernels of ptz_ba_cov.hip instantiate these functions on the device,
-// tests/cpu_harness/ba_cov_harness.cc instantiates them on the host and finishes the computation in plain loops.
+// tests/cpu_harness/ba_cov_harness.cc (with ba_cov_common.h, which it shares with ba_cov_georef_harness.cc) instantiates them on the
+// host and finishes the computation in plain loops.
 //
 // Definition (ptz_ba_batch_covariance).
 //  Scope: a ptz_ba_batch of 2D-2D problems of type PTZRay, PTZRayDist or PTZRayFxfyDist (ptz_ba_batch_create or

@@ -1,21 +1,27 @@
-// ptz_ba_cov.hip -- per-view covariance of bundle-adjusted cameras on MI355X (gfx950).  Definition: ptz_ba_cov.h.
+// ptz_ba_cov.hip -- covariance of bundle-adjusted cameras on MI355X (gfx950): ONE pipeline in two variants.  2D-2D: the per-view
+// covariance of ptz_ba_cov.h, block dimension NF.  GEO: the georeferenced cameras and the rig centre of ptz_ba_cov_georef.h, block
+// dimension NC = NF + 1 with the six T_l_w columns bordering the system.  One driver (cov_run) groups the problems, lays out a
+// group's workspace (CovLayout), enqueues the group (enqueue_group) and reads back; a CovVariant says what differs.
 //
 // Per group of problems (as many as fit the workspace budget, PTZ_BA_COV_MAX_MB), on the batch's stream:
-//   cam        camera blocks (R, intrinsics, Jl) at the state                                           [thread / camera]
+//   cam        camera blocks (R, intrinsics, Jl) at the state, n; GEO: the T_l_w block                       [thread / camera]
 //   ray        P_r per ray; E_o, Y_o, the diagonal term and |e_o|^2 per observation; the squared residuals
 //              are summed per wave of 64 rays by the butterfly, the waves of a problem in wave order      [thread / ray]
-//   assemble   block row ci of S and T: the diagonal block over the camera's observation list, block (ci, cj)
-//              over the pair's entry list, both in stored order, one lane per element -- no atomics        [workgroup / camera]
-//   scale      gauge rows / columns, unit diagonal                                                        [workgroup / row]
+//   annot      GEO: a camera's annotations: records (A_a, G_a, |e_a|^2), then A^T A and A^T G summed over the
+//              camera's annotations in stored order, one lane per element                                  [wave / camera]
+//   reduce     GEO: (L, L) = sum G^T G and SSE_2d3d in stored order, the annotated cameras, the two variances [wave / problem]
+//   assemble   block row ci of S and T: the diagonal block over the camera's observation list (cov_diag_sum), block (ci, cj)
+//              over the pair's entry list (cov_pair_blocks), both in stored order, one lane per element -- no atomics.  GEO: T is
+//              M = s_f^2 T_f + s_a^2 T_a, the 2D-2D columns sit at ba_geo_pos, plus the border (ci, L) and its mirror [workgroup / camera]
+//   scale      identity rows / columns (the gauge; GEO: the dead fy columns), unit diagonal                [workgroup / row]
 //   cholesky   chol_factor_solve (dense path, right-hand side zero): L in the strictly-lower tiles, the
 //              inverses of the factored diagonal tiles in Linv
 //   tri_inv    X = L^-1 by 64 x 64 tiles: X_jj = Linv_jj, X_ij = -Linv_ii sum_{k = j}^{i-1} L_ik X_kj     [workgroup / block column]
 //   gemm       S^-1 = X^T X, then G = S^-1 T, on v_mfma_f64_16x16x4_f64                                    [workgroup / tile]
-//   finish     diagonal blocks of G S^-1 (O(n^2 NF)), unscaling, left-perturbation form, s^2               [wave / camera]
+//   finish     2D-2D: diagonal blocks of G S^-1 (O(n^2 NF)), unscaling, left-perturbation form, s^2.  GEO: blocks (c, c), (c, L),
+//              (L, L), unscaling, the world block; camera 0: the centre                                    [wave / camera]
 // Every sum has one order that depends on the problem alone (a tile's k loop runs over the problem's own tiles, not the
 // group's padded order), so a problem's bits do not depend on its position in the batch, on the grouping or on the run.
-// The second half of the file is the covariance of GEOREFERENCED cameras (definition: ptz_ba_cov_georef.h): the same matrix stage
-// behind kernels of its own for the 2D-3D annotations, the bordered assembly and the world-frame finish.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -52,7 +58,7 @@ struct BaCovWork {  // one group of problems
   double* cov;             // [cameras of the group][NF NF]
   double* sig;             // [count] sigma0
   double pixel_sigma;
-  // the georeferenced covariance only (ptz_ba_cov_georef.h; the second half of this file)
+  // the georeferenced variant only (ptz_ba_cov_georef.h)
   int o3_lo;               // first annotation of the group (global index)
   double* tlwblk;          // [count][TLWBLK]
   double* arec;            // [annotations of the group][ba_geo_rec(NC)]: A_a, G_a, |e_a|^2
@@ -64,12 +70,17 @@ struct BaCovWork {  // one group of problems
   double annotation_sigma;
 };
 
-__global__ void k_ba_cov_cam(BaCovIn in, BaCovWork w, int nf)
+// nc: the block dimension (NF; GEO: NF + 1, and the six T_l_w columns border the system)
+template <bool GEO>
+__global__ void k_ba_cov_cam(BaCovIn in, BaGeoIn geo, BaCovWork w, int nc)
 {
   const int g = blockIdx.y;
   const BaCovScene s = in.scene[w.first + g];
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0) w.n[g] = nf * s.n_cam;
+  if (c == 0) {
+    w.n[g] = nc * s.n_cam + (GEO ? 6 : 0);
+    if (GEO) ba_geo_tlwblk(geo.tlw_x + (size_t)s.cur * geo.tlw_stride + (size_t)s.idx * 6, w.tlwblk + (size_t)g * TLWBLK);
+  }
   if (c >= s.n_cam) return;
   const double* c15 = in.cam_x + (size_t)s.cur * in.cam_stride + (size_t)(s.cam_off + c) * 15;
   ba_cov_camblk(c15, w.camblk + (size_t)(s.cam_off + c - w.cam_lo) * CAMBLK);
@@ -147,6 +158,53 @@ __global__ void k_ba_cov_sse(BaCovIn in, BaCovWork w)
   w.sse[g] = t;
 }
 
+// element el of the diagonal term summed over a camera's observation list (o0, no) in stored order: into S, times w_r into T
+template <int NF>
+__device__ __forceinline__ void cov_diag_sum(const BaCovIn& in, const BaCovWork& w, int o0, int no, int el, double& sS, double& sT)
+{
+  constexpr int NE = NF * NF;
+  for (int q = 0; q < no; ++q) {
+    const double* dg = w.Dg + (size_t)(in.cam_obs[o0 + q] - w.obs_lo) * (NE + 1);
+    const double v = dg[el];
+    sS += v;
+    sT += dg[NE] * v;
+  }
+}
+
+// blocks (ci, cj), cj < ci, of S and T and their mirrors, each over the pair's entries in stored order, one lane per element; the
+// waves take the camera's pairs in turn.  Row stride NC = NF (GEO: NF + 1, the NF columns at ba_geo_pos, T's terms times vf).
+template <int NF, bool GEO>
+__device__ __forceinline__ void cov_pair_blocks(const BaCovIn& in, const BaCovWork& w, const BaCovScene& s, const int* cp, int ci, int o0, double* A,
+                                                double* T, double vf)
+{
+  constexpr int NE = NF * NF, NC = NF + (GEO ? 1 : 0);
+  const int np = w.np;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int* cpair = in.cam_pair + s.cam_off + s.idx;
+  const int pr0 = cpair[ci], npr = cpair[ci + 1] - pr0;
+  const int* pps = in.pair_ptr + s.pair_off + s.idx + pr0;
+  const int* pcj = in.pair_cj + s.pair_off + pr0;
+  if (lane >= NE) return;
+  const int k = lane / NF, l = lane % NF;
+  for (int pl = wv; pl < npr; pl += 4) {
+    const int cj = pcj[pl], e0 = pps[pl], e1 = pps[pl + 1];
+    if (cj < 0 || cj >= ci) continue;
+    const int oj = cp[cj];
+    double sS = 0, sT = 0;
+    for (int e = e0; e < e1; ++e) {
+      const unsigned ab = in.ent[e];
+      const size_t a = (size_t)(in.cam_obs[o0 + (int)(ab & 0xffffu)] - w.obs_lo), b = (size_t)(in.cam_obs[oj + (int)(ab >> 16)] - w.obs_lo);
+      const double v = ba_cov_pair_term(w.EY + a * (6 * NF) + 3 * NF, w.EY + b * (6 * NF), k, l);
+      sS += v;
+      sT += w.Dg[a * (NE + 1) + NE] * v;
+    }
+    const size_t r = (size_t)(ci * NC + (GEO ? ba_geo_pos(k) : k)), c = (size_t)(cj * NC + (GEO ? ba_geo_pos(l) : l));
+    const double t = GEO ? vf * sT : sT;
+    A[r * np + c] = sS; A[c * np + r] = sS;
+    T[r * np + c] = t; T[c * np + r] = t;
+  }
+}
+
 template <int NF>
 __global__ __launch_bounds__(256) void k_ba_cov_assemble(BaCovIn in, BaCovWork w)
 {
@@ -162,14 +220,8 @@ __global__ __launch_bounds__(256) void k_ba_cov_assemble(BaCovIn in, BaCovWork w
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int k = lane / NF, l = lane % NF;
   if (wv == 0 && lane < NE) {  // the diagonal block over the camera's observation list
-    const int el = k >= l ? k * NF + l : l * NF + k;  // (the lower triangle's element for both halves: symmetric bit for bit)
     double sS = 0, sT = 0;
-    for (int q = 0; q < no; ++q) {
-      const double* dg = w.Dg + (size_t)(in.cam_obs[o0 + q] - w.obs_lo) * (NE + 1);
-      const double v = dg[el];
-      sS += v;
-      sT += dg[NE] * v;
-    }
+    cov_diag_sum<NF>(in, w, o0, no, k >= l ? k * NF + l : l * NF + k, sS, sT);  // (the lower triangle's element for both halves: symmetric bit for bit)
     A[(size_t)(ci * NF + k) * np + ci * NF + l] = sS;
     T[(size_t)(ci * NF + k) * np + ci * NF + l] = sT;
     if (k == l) {
@@ -179,44 +231,33 @@ __global__ __launch_bounds__(256) void k_ba_cov_assemble(BaCovIn in, BaCovWork w
       w.dsc[(size_t)g * np + ci * NF + k] = (ok && !anchor_rot) ? 1.0 / sqrt(sS) : 1.0;
     }
   }
-  // block (ci, cj), cj < ci, over the pair's entries in stored order; the waves take the camera's pairs in turn
-  const int* cpair = in.cam_pair + s.cam_off + s.idx;
-  const int pr0 = cpair[ci], npr = cpair[ci + 1] - pr0;
-  const int* pps = in.pair_ptr + s.pair_off + s.idx + pr0;
-  const int* pcj = in.pair_cj + s.pair_off + pr0;
-  if (lane >= NE) return;
-  for (int pl = wv; pl < npr; pl += 4) {
-    const int cj = pcj[pl], e0 = pps[pl], e1 = pps[pl + 1];
-    if (cj < 0 || cj >= ci) continue;
-    const int oj = cp[cj];
-    double sS = 0, sT = 0;
-    for (int e = e0; e < e1; ++e) {
-      const unsigned ab = in.ent[e];
-      const size_t a = (size_t)(in.cam_obs[o0 + (int)(ab & 0xffffu)] - w.obs_lo), b = (size_t)(in.cam_obs[oj + (int)(ab >> 16)] - w.obs_lo);
-      const double v = ba_cov_pair_term(w.EY + a * (6 * NF) + 3 * NF, w.EY + b * (6 * NF), k, l);
-      sS += v;
-      sT += w.Dg[a * (NE + 1) + NE] * v;
-    }
-    const size_t r = (size_t)(ci * NF + k), c = (size_t)(cj * NF + l);
-    A[r * np + c] = sS; A[c * np + r] = sS;
-    T[r * np + c] = sT; T[c * np + r] = sT;
-  }
+  cov_pair_blocks<NF, false>(in, w, s, cp, ci, o0, A, T, 1.0);
 }
 
-// gauge rows / columns (identity in S, zero in T), then both matrices to the unit diagonal of S
-__global__ __launch_bounds__(256) void k_ba_cov_scale(BaCovWork w, int nf)
+// identity rows / columns (the gauge; GEO: the dead fy columns too -- identity in S, zero in T), then both matrices to the unit
+// diagonal of S
+template <bool GEO>
+__global__ __launch_bounds__(256) void k_ba_cov_scale(BaCovIn in, BaCovWork w, int nc)
 {
   const int g = blockIdx.y, i = blockIdx.x;
   const int n = w.n[g], np = w.np;
   if (i >= n) return;
-  const int r0 = w.gauge[g] * nf + nf - 3;
+  const int r0 = w.gauge[g] * nc + nc - 3;
+  int nL = 0;
+  const int* live = nullptr;
+  if (GEO) {
+    const BaCovScene s = in.scene[w.first + g];
+    nL = nc * s.n_cam;
+    live = w.live + (s.cam_off - w.cam_lo);
+  }
+  auto ident = [&](int j) { return (j >= r0 && j < r0 + 3) || (GEO && j < nL && j % nc == 1 && !live[j / nc]); };
   double* A = w.A + (size_t)g * np * np + (size_t)i * np;
   double* T = w.T + (size_t)g * np * np + (size_t)i * np;
   const double* sc = w.dsc + (size_t)g * np;
   const double si = sc[i];
-  const bool gi = i >= r0 && i < r0 + 3;
+  const bool gi = ident(i);
   for (int j = threadIdx.x; j < n; j += 256) {
-    if (gi || (j >= r0 && j < r0 + 3)) { A[j] = i == j ? 1.0 : 0.0; T[j] = 0.0; }
+    if (gi || ident(j)) { A[j] = i == j ? 1.0 : 0.0; T[j] = 0.0; }
     else { const double f = si * sc[j]; A[j] *= f; T[j] *= f; }
   }
 }
@@ -392,51 +433,9 @@ __global__ __launch_bounds__(64) void k_ba_cov_finish(BaCovIn in, BaCovWork w)
   if (c == 0) w.sig[g] = sqrt(s2);
 }
 
-template <int TYPE> void enqueue_group(const BaCovIn& in, const BaCovWork& w, const CholBatch& cb, double* x, int max_cam, int max_ray, int max_n, hipStream_t st)
-{
-  constexpr int NF = BaDims<TYPE>::NC;
-  const int nt = w.np / NB;
-  hipLaunchKernelGGL(k_ba_cov_cam, dim3((max_cam + 63) / 64, w.count), dim3(64), 0, st, in, w, NF);
-  chol_clear(cb, st);  // zero, padding rows, fail flags (reads n)
-  hipLaunchKernelGGL(k_ba_cov_ray<TYPE>, dim3((max_ray + 255) / 256, w.count), dim3(256), 0, st, in, w);
-  hipLaunchKernelGGL(k_ba_cov_sse, dim3((w.count + 63) / 64), dim3(64), 0, st, in, w);
-  hipLaunchKernelGGL(k_ba_cov_assemble<NF>, dim3(max_cam, w.count), dim3(256), 0, st, in, w);
-  hipLaunchKernelGGL(k_ba_cov_scale, dim3(max_n, w.count), dim3(256), 0, st, w, NF);
-  chol_factor_solve(cb, x, st);
-  hipLaunchKernelGGL(k_ba_cov_tri_inv, dim3(nt, w.count), dim3(256), 0, st, w);
-  hipLaunchKernelGGL(k_ba_cov_gemm<0>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
-  hipLaunchKernelGGL(k_ba_cov_gemm<1>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
-  hipLaunchKernelGGL(k_ba_cov_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
-}
-
-// ==== the georeferenced covariance (definition: ptz_ba_cov_georef.h) ===============================================================
-// The same pipeline in the block dimension NC = NF + 1 with the six T_l_w columns bordering the system; k_ba_cov_ray, k_ba_cov_sse,
-// the Cholesky, k_ba_cov_tri_inv and k_ba_cov_gemm run unchanged.  Per group:
-//   geo_cam      camera blocks, the T_l_w block, n = NC n_cam + 6                                          [thread / camera]
-//   ray, sse     as above (the 2D-2D records in their NF columns)
-//   geo_annot    a camera's annotations: records (A_a, G_a, |e_a|^2), then A^T A and A^T G summed over the
-//                camera's annotations in stored order, one lane per element                                 [wave / camera]
-//   geo_reduce   (L, L) = sum G^T G and SSE_2d3d in stored order, the annotated cameras, the two variances   [wave / problem]
-//   geo_assemble block row ci of S and of M = s_f^2 T_f + s_a^2 T_a, the border (ci, L) and its mirror        [workgroup / camera]
-//   geo_scale    identity rows (gauge, dead fy), unit diagonal                                              [workgroup / row]
-//   cholesky, tri_inv, gemm x 2
-//   geo_finish   blocks (c, c), (c, L), (L, L) of G S^-1, unscaling, the world block; camera 0: the centre    [wave / camera]
+// ==== the kernels of the georeferenced variant alone (definition: ptz_ba_cov_georef.h) ============================================
 // M is ONE matrix in absolute units: both variances are known before the assembly (the residuals are summed by the kernels that
 // linearise), so there is one product S^-1 M, no second n x n matrix, and no ratio s_a^2 / s_f^2 that an exact fit would make 0 / 0.
-__global__ void k_geo_cam(BaCovIn in, BaGeoIn geo, BaCovWork w, int nc)
-{
-  const int g = blockIdx.y;
-  const BaCovScene s = in.scene[w.first + g];
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0) {
-    w.n[g] = nc * s.n_cam + 6;
-    ba_geo_tlwblk(geo.tlw_x + (size_t)s.cur * geo.tlw_stride + (size_t)s.idx * 6, w.tlwblk + (size_t)g * TLWBLK);
-  }
-  if (c >= s.n_cam) return;
-  const double* c15 = in.cam_x + (size_t)s.cur * in.cam_stride + (size_t)(s.cam_off + c) * 15;
-  ba_cov_camblk(c15, w.camblk + (size_t)(s.cam_off + c - w.cam_lo) * CAMBLK);
-}
-
 template <int TYPE>
 __global__ __launch_bounds__(64) void k_geo_annot(BaCovIn in, BaGeoIn geo, BaCovWork w)
 {
@@ -514,7 +513,7 @@ __global__ __launch_bounds__(64) void k_geo_reduce(BaCovIn in, BaCovWork w)
 template <int TYPE>
 __global__ __launch_bounds__(256) void k_geo_assemble(BaCovIn in, BaCovWork w)
 {
-  constexpr int NF = BaDims<TYPE>::NC, NE = NF * NF, NC = NF + 1, NA = NC * NC + 6 * NC;
+  constexpr int NF = BaDims<TYPE>::NC, NC = NF + 1, NA = NC * NC + 6 * NC;
   const int g = blockIdx.y, ci = blockIdx.x;
   const BaCovScene s = in.scene[w.first + g];
   if (ci >= s.n_cam) return;
@@ -531,15 +530,7 @@ __global__ __launch_bounds__(256) void k_geo_assemble(BaCovIn in, BaCovWork w)
     const int k = lane / NC, l = lane % NC;
     const int kk = k >= l ? k : l, ll = k >= l ? l : k;  // (the lower triangle's element for both halves: symmetric bit for bit)
     double sS = 0, sT = 0;
-    if (k != 1 && l != 1) {
-      const int el = (kk ? kk - 1 : 0) * NF + (ll ? ll - 1 : 0);  // (ba_geo_pos inverted)
-      for (int q = 0; q < no; ++q) {
-        const double* dg = w.Dg + (size_t)(in.cam_obs[o0 + q] - w.obs_lo) * (NE + 1);
-        const double v = dg[el];
-        sS += v;
-        sT += dg[NE] * v;
-      }
-    }
+    if (k != 1 && l != 1) cov_diag_sum<NF>(in, w, o0, no, (kk ? kk - 1 : 0) * NF + (ll ? ll - 1 : 0), sS, sT);  // (ba_geo_pos inverted)
     const double a = as[kk * NC + ll], d = sS + a;
     A[(size_t)(ci * NC + k) * np + ci * NC + l] = d;
     T[(size_t)(ci * NC + k) * np + ci * NC + l] = vf * sT + va * a;
@@ -556,50 +547,7 @@ __global__ __launch_bounds__(256) void k_geo_assemble(BaCovIn in, BaCovWork w)
     A[r * np + c] = a; A[c * np + r] = a;
     T[r * np + c] = va * a; T[c * np + r] = va * a;
   }
-  // block (ci, cj), cj < ci, as k_ba_cov_assemble, the 2D-2D columns at ba_geo_pos
-  const int* cpair = in.cam_pair + s.cam_off + s.idx;
-  const int pr0 = cpair[ci], npr = cpair[ci + 1] - pr0;
-  const int* pps = in.pair_ptr + s.pair_off + s.idx + pr0;
-  const int* pcj = in.pair_cj + s.pair_off + pr0;
-  if (lane >= NE) return;
-  const int k = lane / NF, l = lane % NF;
-  for (int pl = wv; pl < npr; pl += 4) {
-    const int cj = pcj[pl], e0 = pps[pl], e1 = pps[pl + 1];
-    if (cj < 0 || cj >= ci) continue;
-    const int oj = cp[cj];
-    double sS = 0, sT = 0;
-    for (int e = e0; e < e1; ++e) {
-      const unsigned ab = in.ent[e];
-      const size_t a = (size_t)(in.cam_obs[o0 + (int)(ab & 0xffffu)] - w.obs_lo), b = (size_t)(in.cam_obs[oj + (int)(ab >> 16)] - w.obs_lo);
-      const double v = ba_cov_pair_term(w.EY + a * (6 * NF) + 3 * NF, w.EY + b * (6 * NF), k, l);
-      sS += v;
-      sT += w.Dg[a * (NE + 1) + NE] * v;
-    }
-    const size_t r = (size_t)(ci * NC + ba_geo_pos(k)), c = (size_t)(cj * NC + ba_geo_pos(l));
-    A[r * np + c] = sS; A[c * np + r] = sS;
-    T[r * np + c] = vf * sT; T[c * np + r] = vf * sT;
-  }
-}
-
-// identity rows / columns (the gauge, the dead fy columns: identity in S, zero in M), then both matrices to the unit diagonal of S
-__global__ __launch_bounds__(256) void k_geo_scale(BaCovIn in, BaCovWork w, int nc)
-{
-  const int g = blockIdx.y, i = blockIdx.x;
-  const int n = w.n[g], np = w.np;
-  if (i >= n) return;
-  const BaCovScene s = in.scene[w.first + g];
-  const int nL = nc * s.n_cam, r0 = w.gauge[g] * nc + nc - 3;
-  const int* live = w.live + (s.cam_off - w.cam_lo);
-  auto ident = [&](int j) { return (j >= r0 && j < r0 + 3) || (j < nL && j % nc == 1 && !live[j / nc]); };
-  double* A = w.A + (size_t)g * np * np + (size_t)i * np;
-  double* T = w.T + (size_t)g * np * np + (size_t)i * np;
-  const double* sc = w.dsc + (size_t)g * np;
-  const double si = sc[i];
-  const bool gi = ident(i);
-  for (int j = threadIdx.x; j < n; j += 256) {
-    if (gi || ident(j)) { A[j] = i == j ? 1.0 : 0.0; T[j] = 0.0; }
-    else { const double f = si * sc[j]; A[j] *= f; T[j] *= f; }
-  }
+  cov_pair_blocks<NF, true>(in, w, s, cp, ci, o0, A, T, vf);
 }
 
 // Z = the blocks (c, c), (c, L), (L, L) of G S^-1 (row p of G against row q of the symmetric S^-1), unscaled; the world block
@@ -671,25 +619,87 @@ __global__ __launch_bounds__(64) void k_geo_finish(BaCovIn in, BaCovWork w)
   if (!fin) atomicOr(&w.flags[g], kBaCovNonFinite);
 }
 
-template <int TYPE>
-void enqueue_geo_group(const BaCovIn& in, const BaGeoIn& geo, const BaCovWork& w, const CholBatch& cb, double* x, int max_cam, int max_ray,
-                       int max_n, hipStream_t st)
+// one group's launches; GEO selects the variant's kernels at compile time
+template <int TYPE, bool GEO>
+void enqueue_group(const BaCovIn& in, const BaGeoIn& geo, const BaCovWork& w, const CholBatch& cb, double* x, int max_cam, int max_ray, int max_n,
+                   hipStream_t st)
 {
-  constexpr int NC = BaDims<TYPE>::NC + 1;
+  constexpr int NF = BaDims<TYPE>::NC, NC = NF + (GEO ? 1 : 0);
   const int nt = w.np / NB;
-  hipLaunchKernelGGL(k_geo_cam, dim3((max_cam + 63) / 64, w.count), dim3(64), 0, st, in, geo, w, NC);
+  hipLaunchKernelGGL(k_ba_cov_cam<GEO>, dim3((max_cam + 63) / 64, w.count), dim3(64), 0, st, in, geo, w, NC);
   chol_clear(cb, st);  // zero, padding rows, fail flags (reads n)
   hipLaunchKernelGGL(k_ba_cov_ray<TYPE>, dim3((max_ray + 255) / 256, w.count), dim3(256), 0, st, in, w);
   hipLaunchKernelGGL(k_ba_cov_sse, dim3((w.count + 63) / 64), dim3(64), 0, st, in, w);
-  hipLaunchKernelGGL(k_geo_annot<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, geo, w);
-  hipLaunchKernelGGL(k_geo_reduce<TYPE>, dim3(w.count), dim3(64), 0, st, in, w);
-  hipLaunchKernelGGL(k_geo_assemble<TYPE>, dim3(max_cam, w.count), dim3(256), 0, st, in, w);
-  hipLaunchKernelGGL(k_geo_scale, dim3(max_n, w.count), dim3(256), 0, st, in, w, NC);
+  if constexpr (GEO) {
+    hipLaunchKernelGGL(k_geo_annot<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, geo, w);
+    hipLaunchKernelGGL(k_geo_reduce<TYPE>, dim3(w.count), dim3(64), 0, st, in, w);
+    hipLaunchKernelGGL(k_geo_assemble<TYPE>, dim3(max_cam, w.count), dim3(256), 0, st, in, w);
+  }
+  else hipLaunchKernelGGL(k_ba_cov_assemble<NF>, dim3(max_cam, w.count), dim3(256), 0, st, in, w);
+  hipLaunchKernelGGL(k_ba_cov_scale<GEO>, dim3(max_n, w.count), dim3(256), 0, st, in, w, NC);
   chol_factor_solve(cb, x, st);
   hipLaunchKernelGGL(k_ba_cov_tri_inv, dim3(nt, w.count), dim3(256), 0, st, w);
   hipLaunchKernelGGL(k_ba_cov_gemm<0>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
   hipLaunchKernelGGL(k_ba_cov_gemm<1>, dim3(nt * nt, w.count), dim3(256), 0, st, w);
-  hipLaunchKernelGGL(k_geo_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
+  if constexpr (GEO) hipLaunchKernelGGL(k_geo_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
+  else hipLaunchKernelGGL(k_ba_cov_finish<TYPE>, dim3(max_cam, w.count), dim3(64), 0, st, in, w);
+}
+
+// ==== the driver ==================================================================================================================
+// what differs between the two variants
+struct CovVariant {
+  int nf;        // entries per camera of the result
+  int nc;        // block dimension of the reduced system: nf, georef nf + 1
+  int border;    // columns bordering the system: 0, georef 6 (T_l_w)
+  int n_sig;     // sigmas per problem: 1, georef 2
+  bool centre;   // georef: annotations, the T_l_w block and the centre's covariance
+  int (*status)(int nf, const BaCovScene& s, int n_ann, int chol_fail, int flags);
+  void (*enqueue)(const BaCovIn&, const BaGeoIn&, const BaCovWork&, const CholBatch&, double* x, int max_cam, int max_ray, int max_n, hipStream_t);
+};
+int status_2d2d(int nf, const BaCovScene& s, int, int fail, int flags) { return ba_cov_status(nf, s.n_cam, s.n_ray, s.n_obs, fail, flags); }
+int status_geo(int nf, const BaCovScene& s, int n_ann, int fail, int flags) { return ba_geo_status(nf, s.n_cam, s.n_ray, s.n_obs, s.n_o3, n_ann, fail, flags); }
+template <int TYPE, bool GEO>
+constexpr CovVariant kVariant = {BaDims<TYPE>::NC, BaDims<TYPE>::NC + (GEO ? 1 : 0), GEO ? 6 : 0, GEO ? 2 : 1, GEO, GEO ? status_geo : status_2d2d,
+                                 enqueue_group<TYPE, GEO>};
+
+// byte offsets of a group's buffers in its workspace, each aligned to 256 bytes (an empty buffer takes none)
+struct CovLayout {
+  size_t A, T, X, Si;                    // [count][np][np]
+  size_t Ldiag, Linv, Dinv, x;           // the Cholesky's: diagonal tiles, their inverses, the 16 x 16 inverses, the (zero) solution
+  size_t dsc, camblk, EY, Dg, sse_part, sse, cov, sig;
+  size_t ints;                           // the int block, [count] each: at i_n, i_flags, i_gauge, i_fail (georef: i_n_ann) ints from `ints`
+  size_t tlwblk, arec, asum, live, var, cen;  // georef only
+  size_t i_n, i_flags, i_gauge, i_fail, i_n_ann, n_ints;
+};
+// lays out a group of `count` problems of padded order np over `cams` cameras, `obs` observation slots, `o3` annotations and `waves`
+// partial sums per problem; returns the bytes.  Sizes a candidate group and places the chosen one.
+size_t cov_layout(const CovVariant& v, size_t count, size_t np, size_t cams, size_t obs, size_t o3, size_t waves, CovLayout& l)
+{
+  const size_t nt = np / NB, ne = (size_t)v.nf * v.nf, geo = v.centre ? 1 : 0, D = sizeof(double);
+  size_t o = 0;
+  auto take = [&o](size_t& slot, size_t bytes) { slot = o; o += (bytes + 255) & ~(size_t)255; };
+  take(l.A, D * count * np * np); take(l.T, D * count * np * np); take(l.X, D * count * np * np); take(l.Si, D * count * np * np);
+  take(l.Ldiag, D * count * nt * NB * NB);
+  take(l.Linv, D * count * nt * NB * NB);
+  take(l.Dinv, D * count * nt * 4 * 16 * 16);
+  take(l.x, D * count * np);
+  take(l.dsc, D * count * np);
+  take(l.camblk, D * cams * CAMBLK);
+  take(l.EY, D * obs * 6 * v.nf);
+  take(l.Dg, D * obs * (ne + 1));
+  take(l.sse_part, D * count * waves);
+  take(l.sse, D * count);
+  take(l.cov, D * cams * ne);
+  take(l.sig, D * count * v.n_sig);
+  l.i_n = 0; l.i_flags = count; l.i_gauge = 2 * count; l.i_fail = 3 * count; l.i_n_ann = 4 * count; l.n_ints = (4 + geo) * count;
+  take(l.ints, sizeof(int) * l.n_ints);
+  take(l.tlwblk, geo * D * count * TLWBLK);
+  take(l.arec, geo * D * (o3 + 1) * ba_geo_rec(v.nc));
+  take(l.asum, geo * D * cams * (v.nc * v.nc + 6 * v.nc));
+  take(l.live, geo * sizeof(int) * cams);
+  take(l.var, geo * D * count * 4);
+  take(l.cen, geo * D * count * 9);
+  return o;
 }
 
 // what a run holds until it returns: the group's workspace and the two timing events, released once the stream is idle
@@ -710,84 +720,61 @@ size_t cov_budget()
   return (size_t)2048 << 20;
 }
 
-}  // namespace
-
-int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double pixel_sigma, hipStream_t st, double* cov, double* sigma0,
-               int* status, double* device_ms)
+// Both variants: group by group under the budget -- lay out, enqueue, read back, hand the OK problems' results to the caller.
+int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, const int* gauge, double pixel_sigma,
+            double annotation_sigma, hipStream_t st, double* cov, double* cov_centre, double* sigma0, int* status, double* device_ms)
 {
-  const int nf = ba_cov_dim(in.type), NE = nf * nf;
-  if (nf < 0) return PTZ_EUNSUPPORTED;
+  const int NE = v.nf * v.nf;
   const size_t budget = cov_budget();
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   CovHeld h;
   h.dev = in.device; h.st = st;
   PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
   PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
   double total_ms = 0;
-  // bytes of a group of `count` problems of padded order np over `cams` cameras and `obs` observation slots
-  auto group_bytes = [&](size_t count, size_t np, size_t cams, size_t obs, size_t waves, size_t* offs) {
-    const size_t nt = np / NB;
-    size_t o = 0;
-    auto take = [&](int k, size_t bytes) { if (offs) offs[k] = o; o += up(bytes); };
-    for (int k = 0; k < 4; ++k) take(k, sizeof(double) * count * np * np);  // A, T, X, Si
-    take(4, sizeof(double) * count * nt * NB * NB);                         // Ldiag
-    take(5, sizeof(double) * count * nt * NB * NB);                         // Linv
-    take(6, sizeof(double) * count * nt * 4 * 16 * 16);                     // Dinv
-    take(7, sizeof(double) * count * np);                                   // x
-    take(8, sizeof(double) * count * np);                                   // dsc
-    take(9, sizeof(double) * cams * CAMBLK);
-    take(10, sizeof(double) * obs * 6 * nf);
-    take(11, sizeof(double) * obs * (NE + 1));
-    take(12, sizeof(double) * count * waves);
-    take(13, sizeof(double) * count);                                       // sse
-    take(14, sizeof(double) * cams * NE);                                   // cov
-    take(15, sizeof(double) * count);                                       // sig
-    take(16, sizeof(int) * count * 4);                                      // n, flags, gauge, fail
-    return o;
-  };
   for (int first = 0; first < in.n_scene;) {
     // the group: problems first .. first + count - 1, as many as the budget holds (one at least)
-    int count = 0, max_cam = 0, max_ray = 0, max_n = 0;
-    size_t cams = 0, obs = 0, bytes = 0;
+    int count = 0, max_cam = 0, max_ray = 0;
+    size_t cams = 0, obs = 0, o3 = 0, bytes = 0;
+    CovLayout l;
     for (int i = first; i < in.n_scene; ++i) {
       const int mc = std::max(max_cam, hs[i].n_cam), mr = std::max(max_ray, hs[i].n_ray);
       const size_t c2 = (size_t)(hs[i].cam_off + hs[i].n_cam - hs[first].cam_off), o2 = (size_t)(hs[i].obs_off + hs[i].n_obs - hs[first].obs_off);
-      const size_t b2 = group_bytes((size_t)(i - first + 1), (size_t)chol_padded_order(nf * mc), c2, o2, (size_t)(mr + 63) / 64 + 1, nullptr);
+      const size_t a2 = v.centre ? (size_t)(hs[i].o3_off + hs[i].n_o3 - hs[first].o3_off) : 0;
+      const size_t b2 = cov_layout(v, (size_t)(i - first + 1), (size_t)chol_padded_order(v.nc * mc + v.border), c2, o2, a2, (size_t)(mr + 63) / 64 + 1, l);
       if (count > 0 && b2 > budget) break;
-      count = i - first + 1; max_cam = mc; max_ray = mr; max_n = nf * mc; cams = c2; obs = o2; bytes = b2;
+      count = i - first + 1; max_cam = mc; max_ray = mr; cams = c2; obs = o2; o3 = a2; bytes = b2;
     }
+    const int max_n = v.nc * max_cam + v.border;  // the order of the group's largest problem
     BaCovWork w;
     w.first = first; w.count = count; w.np = chol_padded_order(max_n);
-    w.cam_lo = hs[first].cam_off; w.obs_lo = hs[first].obs_off;
+    w.cam_lo = hs[first].cam_off; w.obs_lo = hs[first].obs_off; w.o3_lo = hs[first].o3_off;
     w.max_waves = (max_ray + 63) / 64 + 1;
-    w.pixel_sigma = pixel_sigma;
-    size_t offs[17];
-    (void)group_bytes((size_t)count, (size_t)w.np, cams, obs, (size_t)w.max_waves, offs);
+    w.pixel_sigma = pixel_sigma; w.annotation_sigma = annotation_sigma;
+    (void)cov_layout(v, (size_t)count, (size_t)w.np, cams, obs, o3, (size_t)w.max_waves, l);
     if (ptzpool::dev_acquire(h.dev, bytes, &h.base) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
     char* base = static_cast<char*>(h.base);
-    auto at = [&](int k) { return reinterpret_cast<double*>(base + offs[k]); };
-    w.A = at(0); w.T = at(1); w.X = at(2); w.Si = at(3);
-    w.Linv = at(5); w.dsc = at(8); w.camblk = at(9); w.EY = at(10); w.Dg = at(11); w.sse_part = at(12); w.sse = at(13); w.cov = at(14); w.sig = at(15);
-    int* ints = reinterpret_cast<int*>(base + offs[16]);
-    w.n = ints; w.flags = ints + count; w.gauge = ints + 2 * count;
+    auto at = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
+    w.A = at(l.A); w.T = at(l.T); w.X = at(l.X); w.Si = at(l.Si);
+    w.Linv = at(l.Linv); w.dsc = at(l.dsc); w.camblk = at(l.camblk); w.EY = at(l.EY); w.Dg = at(l.Dg);
+    w.sse_part = at(l.sse_part); w.sse = at(l.sse); w.cov = at(l.cov); w.sig = at(l.sig);
+    w.tlwblk = at(l.tlwblk); w.arec = at(l.arec); w.asum = at(l.asum); w.live = reinterpret_cast<int*>(base + l.live); w.var = at(l.var); w.cen = at(l.cen);
+    int* ints = reinterpret_cast<int*>(base + l.ints);
+    w.n = ints + l.i_n; w.flags = ints + l.i_flags; w.gauge = ints + l.i_gauge; w.n_ann = ints + l.i_n_ann;
     CholBatch cb;
-    cb.count = count; cb.np = w.np; cb.A = w.A; cb.Ldiag = at(4); cb.Linv = w.Linv; cb.Dinv = at(6); cb.n = w.n; cb.fail = ints + 3 * count;
+    cb.count = count; cb.np = w.np; cb.A = w.A; cb.Ldiag = at(l.Ldiag); cb.Linv = w.Linv; cb.Dinv = at(l.Dinv); cb.n = w.n; cb.fail = ints + l.i_fail;
     std::vector<int> hg(gauge + first, gauge + first + count);
-    PTZ_HIP_TRY(hipMemsetAsync(ints, 0, sizeof(int) * 4 * count, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(ints + 2 * count, hg.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
+    PTZ_HIP_TRY(hipMemsetAsync(ints, 0, sizeof(int) * l.n_ints, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(ints + l.i_gauge, hg.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
     PTZ_HIP_TRY(hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)count * w.np * w.np, st));
     PTZ_HIP_TRY(hipEventRecord(h.e0, st));
-    switch (in.type) {
-      case 0: enqueue_group<0>(in, w, cb, at(7), max_cam, max_ray, max_n, st); break;
-      case 1: enqueue_group<1>(in, w, cb, at(7), max_cam, max_ray, max_n, st); break;
-      default: enqueue_group<2>(in, w, cb, at(7), max_cam, max_ray, max_n, st); break;
-    }
+    v.enqueue(in, geo, w, cb, at(l.x), max_cam, max_ray, max_n, st);
     PTZ_HIP_TRY(hipEventRecord(h.e1, st));
     // the group's results come back into buffers of their own: only problems whose status is OK reach the caller's arrays
-    std::vector<double> hc(cams * NE), hsig(count);
-    std::vector<int> hi(4 * (size_t)count);
+    std::vector<double> hc(cams * NE), hsig((size_t)v.n_sig * count), hcen(v.centre ? 9 * (size_t)count : 0);
+    std::vector<int> hi(l.n_ints);
     PTZ_HIP_TRY(hipMemcpyAsync(hc.data(), w.cov, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(hsig.data(), w.sig, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(hsig.data(), w.sig, sizeof(double) * hsig.size(), hipMemcpyDeviceToHost, st));
+    if (v.centre) PTZ_HIP_TRY(hipMemcpyAsync(hcen.data(), w.cen, sizeof(double) * hcen.size(), hipMemcpyDeviceToHost, st));
     PTZ_HIP_TRY(hipMemcpyAsync(hi.data(), ints, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, st));
     PTZ_HIP_TRY(stream_wait(st));
     PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
@@ -796,13 +783,14 @@ int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double
     total_ms += ms;
     for (int k = 0; k < count; ++k) {
       const BaCovScene& s = hs[first + k];
-      const int fail = hi[3 * (size_t)count + k], flags = hi[(size_t)count + k];
+      const int fail = hi[l.i_fail + k], flags = hi[l.i_flags + k], n_ann = v.centre ? hi[l.i_n_ann + k] : 0;
       if (fail & 2) return PTZ_ENODEVICE;  // (a hand-over of the one-launch factorisation: not a path this call takes)
-      const int stt = ba_cov_status(nf, s.n_cam, s.n_ray, s.n_obs, fail & 1, flags);
+      const int stt = v.status(v.nf, s, n_ann, fail & 1, flags);
       status[first + k] = stt;
       if (stt != kBaCovOk) continue;
       memcpy(cov + (size_t)s.cam_off * NE, hc.data() + (size_t)(s.cam_off - w.cam_lo) * NE, sizeof(double) * NE * s.n_cam);
-      sigma0[first + k] = hsig[k];
+      if (v.centre) memcpy(cov_centre + 9 * (size_t)(first + k), hcen.data() + 9 * (size_t)k, sizeof(double) * 9);
+      memcpy(sigma0 + (size_t)v.n_sig * (first + k), hsig.data() + (size_t)v.n_sig * k, sizeof(double) * v.n_sig);
     }
     ptzpool::dev_release(h.dev, h.base);
     h.base = nullptr;
@@ -812,112 +800,22 @@ int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double
   return PTZ_OK;
 }
 
+}  // namespace
+
+int ba_cov_run(const BaCovIn& in, const BaCovScene* hs, const int* gauge, double pixel_sigma, hipStream_t st, double* cov, double* sigma0,
+               int* status, double* device_ms)
+{
+  if (ba_cov_dim(in.type) < 0) return PTZ_EUNSUPPORTED;
+  const CovVariant& v = in.type == 0 ? kVariant<0, false> : in.type == 1 ? kVariant<1, false> : kVariant<2, false>;
+  return cov_run(v, in, BaGeoIn{}, hs, gauge, pixel_sigma, 0.0, st, cov, nullptr, sigma0, status, device_ms);
+}
+
 int ba_geo_cov_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, const int* gauge, double pixel_sigma, double annotation_sigma,
                    hipStream_t st, double* cov, double* cov_centre, double* sigma0, int* status, double* device_ms)
 {
-  const int nf = ba_geo_cov_dim(in.type), NE = nf * nf, nc = nf + 1;
-  if (nf < 0) return PTZ_EUNSUPPORTED;
-  const size_t budget = cov_budget();
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  CovHeld h;
-  h.dev = in.device; h.st = st;
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
-  double total_ms = 0;
-  constexpr int NOFF = 24;
-  // bytes of a group of `count` problems of padded order np over `cams` cameras, `obs` observation and `o3` annotation slots
-  auto group_bytes = [&](size_t count, size_t np, size_t cams, size_t obs, size_t o3, size_t waves, size_t* offs) {
-    const size_t nt = np / NB;
-    size_t o = 0;
-    auto take = [&](int k, size_t bytes) { if (offs) offs[k] = o; o += up(bytes); };
-    for (int k = 0; k < 4; ++k) take(k, sizeof(double) * count * np * np);  // A, T, X, Si
-    take(4, sizeof(double) * count * nt * NB * NB);                         // Ldiag
-    take(5, sizeof(double) * count * nt * NB * NB);                         // Linv
-    take(6, sizeof(double) * count * nt * 4 * 16 * 16);                     // Dinv
-    take(7, sizeof(double) * count * np);                                   // x
-    take(8, sizeof(double) * count * np);                                   // dsc
-    take(9, sizeof(double) * cams * CAMBLK);
-    take(10, sizeof(double) * obs * 6 * nf);
-    take(11, sizeof(double) * obs * (NE + 1));
-    take(12, sizeof(double) * count * waves);
-    take(13, sizeof(double) * count);                                       // sse
-    take(14, sizeof(double) * cams * NE);                                   // cov
-    take(15, sizeof(double) * count * 2);                                   // sig
-    take(16, sizeof(int) * count * 5);                                      // n, flags, gauge, fail, n_ann
-    take(17, sizeof(double) * count * TLWBLK);
-    take(18, sizeof(double) * (o3 + 1) * ba_geo_rec(nc));                   // arec
-    take(19, sizeof(double) * cams * (nc * nc + 6 * nc));                   // asum
-    take(20, sizeof(int) * cams);                                           // live
-    take(21, sizeof(double) * count * 4);                                   // var
-    take(22, sizeof(double) * count * 9);                                   // cen
-    return o;
-  };
-  for (int first = 0; first < in.n_scene;) {
-    // the group: problems first .. first + count - 1, as many as the budget holds (one at least)
-    int count = 0, max_cam = 0, max_ray = 0, max_n = 0;
-    size_t cams = 0, obs = 0, o3 = 0, bytes = 0;
-    for (int i = first; i < in.n_scene; ++i) {
-      const int mc = std::max(max_cam, hs[i].n_cam), mr = std::max(max_ray, hs[i].n_ray);
-      const size_t c2 = (size_t)(hs[i].cam_off + hs[i].n_cam - hs[first].cam_off), o2 = (size_t)(hs[i].obs_off + hs[i].n_obs - hs[first].obs_off);
-      const size_t a2 = (size_t)(hs[i].o3_off + hs[i].n_o3 - hs[first].o3_off);
-      const size_t b2 = group_bytes((size_t)(i - first + 1), (size_t)chol_padded_order(nc * mc + 6), c2, o2, a2, (size_t)(mr + 63) / 64 + 1, nullptr);
-      if (count > 0 && b2 > budget) break;
-      count = i - first + 1; max_cam = mc; max_ray = mr; max_n = nc * mc + 6; cams = c2; obs = o2; o3 = a2; bytes = b2;
-    }
-    BaCovWork w;
-    w.first = first; w.count = count; w.np = chol_padded_order(max_n);
-    w.cam_lo = hs[first].cam_off; w.obs_lo = hs[first].obs_off; w.o3_lo = hs[first].o3_off;
-    w.max_waves = (max_ray + 63) / 64 + 1;
-    w.pixel_sigma = pixel_sigma; w.annotation_sigma = annotation_sigma;
-    size_t offs[NOFF];
-    (void)group_bytes((size_t)count, (size_t)w.np, cams, obs, o3, (size_t)w.max_waves, offs);
-    if (ptzpool::dev_acquire(h.dev, bytes, &h.base) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-    char* base = static_cast<char*>(h.base);
-    auto at = [&](int k) { return reinterpret_cast<double*>(base + offs[k]); };
-    w.A = at(0); w.T = at(1); w.X = at(2); w.Si = at(3);
-    w.Linv = at(5); w.dsc = at(8); w.camblk = at(9); w.EY = at(10); w.Dg = at(11); w.sse_part = at(12); w.sse = at(13); w.cov = at(14); w.sig = at(15);
-    w.tlwblk = at(17); w.arec = at(18); w.asum = at(19); w.live = reinterpret_cast<int*>(base + offs[20]); w.var = at(21); w.cen = at(22);
-    int* ints = reinterpret_cast<int*>(base + offs[16]);
-    w.n = ints; w.flags = ints + count; w.gauge = ints + 2 * count; w.n_ann = ints + 4 * count;
-    CholBatch cb;
-    cb.count = count; cb.np = w.np; cb.A = w.A; cb.Ldiag = at(4); cb.Linv = w.Linv; cb.Dinv = at(6); cb.n = w.n; cb.fail = ints + 3 * count;
-    std::vector<int> hg(gauge + first, gauge + first + count);
-    PTZ_HIP_TRY(hipMemsetAsync(ints, 0, sizeof(int) * 5 * count, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(ints + 2 * count, hg.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
-    PTZ_HIP_TRY(hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)count * w.np * w.np, st));
-    PTZ_HIP_TRY(hipEventRecord(h.e0, st));
-    if (in.type == 0) enqueue_geo_group<0>(in, geo, w, cb, at(7), max_cam, max_ray, max_n, st);
-    else enqueue_geo_group<1>(in, geo, w, cb, at(7), max_cam, max_ray, max_n, st);
-    PTZ_HIP_TRY(hipEventRecord(h.e1, st));
-    // the group's results come back into buffers of their own: only problems whose status is OK reach the caller's arrays
-    std::vector<double> hc(cams * NE), hsig(2 * (size_t)count), hcen(9 * (size_t)count);
-    std::vector<int> hi(5 * (size_t)count);
-    PTZ_HIP_TRY(hipMemcpyAsync(hc.data(), w.cov, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(hsig.data(), w.sig, sizeof(double) * hsig.size(), hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(hcen.data(), w.cen, sizeof(double) * hcen.size(), hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(hi.data(), ints, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(stream_wait(st));
-    PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-    total_ms += ms;
-    for (int k = 0; k < count; ++k) {
-      const BaCovScene& s = hs[first + k];
-      const int fail = hi[3 * (size_t)count + k], flags = hi[(size_t)count + k], n_ann = hi[4 * (size_t)count + k];
-      if (fail & 2) return PTZ_ENODEVICE;  // (a hand-over of the one-launch factorisation: not a path this call takes)
-      const int stt = ba_geo_status(nf, s.n_cam, s.n_ray, s.n_obs, s.n_o3, n_ann, fail & 1, flags);
-      status[first + k] = stt;
-      if (stt != kBaCovOk) continue;
-      memcpy(cov + (size_t)s.cam_off * NE, hc.data() + (size_t)(s.cam_off - w.cam_lo) * NE, sizeof(double) * NE * s.n_cam);
-      memcpy(cov_centre + 9 * (size_t)(first + k), hcen.data() + 9 * (size_t)k, sizeof(double) * 9);
-      sigma0[2 * (size_t)(first + k)] = hsig[2 * (size_t)k]; sigma0[2 * (size_t)(first + k) + 1] = hsig[2 * (size_t)k + 1];
-    }
-    ptzpool::dev_release(h.dev, h.base);
-    h.base = nullptr;
-    first += count;
-  }
-  if (device_ms) *device_ms = total_ms;
-  return PTZ_OK;
+  if (ba_geo_cov_dim(in.type) < 0) return PTZ_EUNSUPPORTED;
+  return cov_run(in.type == 0 ? kVariant<0, true> : kVariant<1, true>, in, geo, hs, gauge, pixel_sigma, annotation_sigma, st, cov, cov_centre, sigma0,
+                 status, device_ms);
 }
 
 }  // namespace ptz

@@ -486,19 +486,14 @@ bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::v
   return true;
 }
 
-bool PTZRayOptimizer::Covariance(std::vector<double>& cov, double& sigma0, long gauge_image) const
+namespace {
+// the 2D-2D part of the packed problem as the covariance calls take it (factor_type is the caller's); false with shared intrinsics,
+// which couple the cameras through blocks the reduced system does not carry
+bool CovProblem(const PackedBA& p, ptz_ba_problem& prob)
 {
-  const PackedBA& p = packed_;
-  if (!solved_packed_ || p.ray.empty() || !p.obs3d_cam.empty() || type_ == PTZRayDistDisp) return false;
   for (size_t c = 0; c < p.cam_image.size() && c < p.ic_of_cam.size(); ++c)
-    if (p.ic_of_cam[c] != static_cast<int32_t>(p.cam_image[c])) return false;  // shared intrinsics
-  int32_t gauge = 0;
-  if (gauge_image >= 0) {
-    const auto it = std::lower_bound(p.cam_image.begin(), p.cam_image.end(), gauge_image);
-    if (it == p.cam_image.end() || *it != gauge_image) return false;
-    gauge = static_cast<int32_t>(it - p.cam_image.begin());
-  }
-  ptz_ba_problem prob{};
+    if (p.ic_of_cam[c] != static_cast<int32_t>(p.cam_image[c])) return false;
+  prob = ptz_ba_problem{};
   prob.n_cam = static_cast<int32_t>(p.cam_image.size());
   prob.n_ray = static_cast<int32_t>(p.ray_track.size());
   prob.n_obs = static_cast<int64_t>(p.obs_cam.size());
@@ -506,6 +501,29 @@ bool PTZRayOptimizer::Covariance(std::vector<double>& cov, double& sigma0, long 
   prob.obs_cam = p.obs_cam.data();
   prob.obs_ray = p.obs_ray.data();
   prob.ray_weight = p.ray_weight.data();
+  return true;
+}
+// square roots of the diagonals of n_cam square blocks
+void BlockStdDevs(const std::vector<double>& cov, size_t n_cam, std::vector<double>& std_devs)
+{
+  const size_t nf = static_cast<size_t>(std::lround(std::sqrt(static_cast<double>(cov.size() / n_cam))));
+  std_devs.assign(nf * n_cam, 0.0);
+  for (size_t c = 0; c < n_cam; ++c)
+    for (size_t k = 0; k < nf; ++k) std_devs[nf * c + k] = std::sqrt(cov[nf * nf * c + nf * k + k]);
+}
+}  // namespace
+
+bool PTZRayOptimizer::Covariance(std::vector<double>& cov, double& sigma0, long gauge_image) const
+{
+  const PackedBA& p = packed_;
+  ptz_ba_problem prob;
+  if (!solved_packed_ || p.ray.empty() || !p.obs3d_cam.empty() || type_ == PTZRayDistDisp || !CovProblem(p, prob)) return false;
+  int32_t gauge = 0;
+  if (gauge_image >= 0) {
+    const auto it = std::lower_bound(p.cam_image.begin(), p.cam_image.end(), gauge_image);
+    if (it == p.cam_image.end() || *it != gauge_image) return false;
+    gauge = static_cast<int32_t>(it - p.cam_image.begin());
+  }
   prob.factor_type = (type_ == PTZRay) ? PTZ_BA_PTZRay : (type_ == PTZRayDist ? PTZ_BA_PTZRayDist : PTZ_BA_PTZRayFxfyDist);
   const int32_t nf = ptz_ba_cov_dim(prob.factor_type);
   if (nf <= 0) return false;
@@ -526,10 +544,7 @@ bool PTZRayOptimizer::StdDevs(std::vector<double>& std_devs, double& sigma0, lon
 {
   std::vector<double> cov;
   if (!Covariance(cov, sigma0, gauge_image)) return false;
-  const size_t n_cam = packed_.cam_image.size(), nf = static_cast<size_t>(std::lround(std::sqrt(static_cast<double>(cov.size() / n_cam))));
-  std_devs.assign(nf * n_cam, 0.0);
-  for (size_t c = 0; c < n_cam; ++c)
-    for (size_t k = 0; k < nf; ++k) std_devs[nf * c + k] = std::sqrt(cov[nf * nf * c + nf * k + k]);
+  BlockStdDevs(cov, packed_.cam_image.size(), std_devs);
   return true;
 }
 
@@ -537,17 +552,8 @@ bool PTZRayOptimizer::WorldCovariance(std::vector<double>& cov, std::array<doubl
                                       double pixel_sigma, double annotation_sigma) const
 {
   const PackedBA& p = packed_;
-  if (!solved_packed_ || p.ray.empty() || p.obs3d_cam.empty() || (type_ != PTZRay && type_ != PTZRayDist)) return false;
-  for (size_t c = 0; c < p.cam_image.size() && c < p.ic_of_cam.size(); ++c)
-    if (p.ic_of_cam[c] != static_cast<int32_t>(p.cam_image[c])) return false;  // shared intrinsics
-  ptz_ba_problem prob{};
-  prob.n_cam = static_cast<int32_t>(p.cam_image.size());
-  prob.n_ray = static_cast<int32_t>(p.ray_track.size());
-  prob.n_obs = static_cast<int64_t>(p.obs_cam.size());
-  prob.obs_uv = p.obs_uv.data();
-  prob.obs_cam = p.obs_cam.data();
-  prob.obs_ray = p.obs_ray.data();
-  prob.ray_weight = p.ray_weight.data();
+  ptz_ba_problem prob;
+  if (!solved_packed_ || p.ray.empty() || p.obs3d_cam.empty() || (type_ != PTZRay && type_ != PTZRayDist) || !CovProblem(p, prob)) return false;
   prob.factor_type = type_ == PTZRay ? PTZ_BA_PTZRay : PTZ_BA_PTZRayDist;
   prob.n_obs3d = static_cast<int32_t>(p.obs3d_cam.size());
   prob.obs3d_uv = p.obs3d_uv.data();
@@ -577,10 +583,7 @@ bool PTZRayOptimizer::WorldStdDevs(std::vector<double>& std_devs, std::array<dou
   std::vector<double> cov;
   std::array<double, 9> cc;
   if (!WorldCovariance(cov, cc, sigma0, pixel_sigma, annotation_sigma)) return false;
-  const size_t n_cam = packed_.cam_image.size(), nf = static_cast<size_t>(std::lround(std::sqrt(static_cast<double>(cov.size() / n_cam))));
-  std_devs.assign(nf * n_cam, 0.0);
-  for (size_t c = 0; c < n_cam; ++c)
-    for (size_t k = 0; k < nf; ++k) std_devs[nf * c + k] = std::sqrt(cov[nf * nf * c + nf * k + k]);
+  BlockStdDevs(cov, packed_.cam_image.size(), std_devs);
   for (int k = 0; k < 3; ++k) sigma_centre[k] = std::sqrt(cc[4 * k]);
   return true;
 }

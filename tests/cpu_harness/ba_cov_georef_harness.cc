@@ -3,47 +3,12 @@
 // ptz_ba_cov.hip run on the device: the per-ray, per-annotation and per-camera functions come from the headers; the dense
 // assembly, the inverse and the sandwich are plain serial loops here, every sum in the kernels' order (a camera's annotations and
 // the (L, L) block in stored order).  Never part of the product library.
-#include <math.h>
-#include <stdint.h>
-
-#include <vector>
-
 #include "../../ptz-calib_amd/csrc/ptz_ba_cov_georef.h"
+#include "ba_cov_common.h"
 
-using namespace ptz;
+using namespace cov_harness;
 
 namespace {
-
-// in-place inverse of a symmetric positive definite n x n matrix (row-major) through its Cholesky factor; false: a pivot <= 0
-bool spd_inverse(std::vector<double>& A, int n)
-{
-  std::vector<double> L((size_t)n * n, 0.0), W((size_t)n * n, 0.0);
-  for (int j = 0; j < n; ++j) {
-    double d = A[(size_t)j * n + j];
-    for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-    if (!(d > 0.0)) return false;
-    const double l = sqrt(d);
-    L[(size_t)j * n + j] = l;
-    for (int i = j + 1; i < n; ++i) {
-      double v = A[(size_t)i * n + j];
-      for (int k = 0; k < j; ++k) v -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
-      L[(size_t)i * n + j] = v / l;
-    }
-  }
-  for (int c = 0; c < n; ++c)  // W = L^-1
-    for (int i = c; i < n; ++i) {
-      double v = i == c ? 1.0 : 0.0;
-      for (int k = c; k < i; ++k) v -= L[(size_t)i * n + k] * W[(size_t)k * n + c];
-      W[(size_t)i * n + c] = v / L[(size_t)i * n + i];
-    }
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double v = 0;
-      for (int k = i; k < n; ++k) v += W[(size_t)k * n + i] * W[(size_t)k * n + j];
-      A[(size_t)i * n + j] = v; A[(size_t)j * n + i] = v;
-    }
-  return true;
-}
 
 struct Problem {
   int n_cam, n_ray;
@@ -66,56 +31,7 @@ int run(const Problem& p, int gauge, double pixel_sigma, double annotation_sigma
   int flags = 0;
   double sse_f = 0, sse_a = 0;
   // ---- the 2D-2D part, as ba_cov_harness.cc, its columns at ba_geo_pos
-  std::vector<double> E, Y;
-  for (int64_t a0 = 0; a0 < p.n_obs;) {
-    int64_t a1 = a0;
-    while (a1 < p.n_obs && p.oray[a1] == p.oray[a0]) ++a1;
-    const int r = p.oray[a0];
-    const double* X = p.ray + 3 * (size_t)r;
-    const double w = p.rw[r];
-    const int len = (int)(a1 - a0);
-    double V[6] = {0, 0, 0, 0, 0, 0};
-    E.assign((size_t)len * 3 * NF, 0.0); Y.assign((size_t)len * 3 * NF, 0.0);
-    std::vector<double> JcAll((size_t)len * 2 * NF);
-    for (int o = 0; o < len; ++o) {
-      const double* c = &cb[(size_t)p.ocam[a0 + o] * CAMBLK];
-      double res[2], Jc[2][NF], Jr[2][3];
-      ba_linearize<TYPE>(c, X, p.uv[2 * (a0 + o)], p.uv[2 * (a0 + o) + 1], res, Jc, Jr);
-      if (TYPE == 1 && c[CB_R + 6] * X[0] + c[CB_R + 7] * X[1] + c[CB_R + 8] * X[2] < 0) flags |= kBaCovPenalty;
-      ba_cov_add_V(Jr, V);
-      sse_f += res[0] * res[0] + res[1] * res[1];
-      ba_cov_E<NF>(Jc, Jr, w, &E[(size_t)o * 3 * NF]);
-      for (int k = 0; k < NF; ++k) { JcAll[(size_t)o * 2 * NF + k] = Jc[0][k]; JcAll[(size_t)o * 2 * NF + NF + k] = Jc[1][k]; }
-    }
-    a0 = a1;
-    if (len < 2) continue;  // contributes exactly zero
-    double P[6];
-    if (!ba_cov_ray_P(V, w, X, P)) { flags |= kBaCovBadRay; continue; }
-    for (int o = 0; o < len; ++o) ba_cov_Y<NF>(&E[(size_t)o * 3 * NF], P, &Y[(size_t)o * 3 * NF]);
-    for (int o = 0; o < len; ++o) {
-      const int co = p.ocam[a1 - len + o];
-      double Jc[2][NF];
-      for (int k = 0; k < NF; ++k) { Jc[0][k] = JcAll[(size_t)o * 2 * NF + k]; Jc[1][k] = JcAll[(size_t)o * 2 * NF + NF + k]; }
-      for (int k = 0; k < NF; ++k)
-        for (int l = 0; l <= k; ++l) {
-          const double v = ba_cov_diag_term<NF>(Jc, w, &Y[(size_t)o * 3 * NF], &E[(size_t)o * 3 * NF], k, l);
-          const size_t i = (size_t)co * NC + ba_geo_pos(k), j = (size_t)co * NC + ba_geo_pos(l);
-          S[i * n + j] += v; Tf[i * n + j] += w * v;
-          if (l < k) { S[j * n + i] += v; Tf[j * n + i] += w * v; }
-        }
-      for (int q = 0; q < len; ++q) {
-        const int cq = p.ocam[a1 - len + q];
-        if (cq >= co) continue;  // block (co, cq), co > cq, and its mirror
-        for (int k = 0; k < NF; ++k)
-          for (int l = 0; l < NF; ++l) {
-            const double v = ba_cov_pair_term(&Y[(size_t)o * 3 * NF], &E[(size_t)q * 3 * NF], k, l);
-            const size_t i = (size_t)co * NC + ba_geo_pos(k), j = (size_t)cq * NC + ba_geo_pos(l);
-            S[i * n + j] += v; S[j * n + i] += v;
-            Tf[i * n + j] += w * v; Tf[j * n + i] += w * v;
-          }
-      }
-    }
-  }
+  ray_loop<TYPE>(p.n_obs, p.uv, p.ocam, p.oray, p.rw, cb.data(), p.ray, n, [](int c, int k) { return c * NC + ba_geo_pos(k); }, S, Tf, sse_f, flags);
   // ---- the annotations, in stored order
   std::vector<char> live(n_cam, 0);
   for (int a = 0; a < p.n_o3; ++a) {

@@ -2,47 +2,11 @@
 // ptz-calib_amd/csrc/ptz_ba_cov.h (what the kernels of ptz_ba_cov.hip run on the device): the per-ray and per-camera functions
 // come from the header, the dense assembly, the inverse and the sandwich are plain serial loops here.  Never part of the
 // product library.
-#include <math.h>
-#include <stdint.h>
+#include "ba_cov_common.h"
 
-#include <vector>
-
-#include "../../ptz-calib_amd/csrc/ptz_ba_cov.h"
-
-using namespace ptz;
+using namespace cov_harness;
 
 namespace {
-
-// in-place inverse of a symmetric positive definite n x n matrix (row-major) through its Cholesky factor; false: a pivot <= 0
-bool spd_inverse(std::vector<double>& A, int n)
-{
-  std::vector<double> L((size_t)n * n, 0.0), W((size_t)n * n, 0.0);
-  for (int j = 0; j < n; ++j) {
-    double d = A[(size_t)j * n + j];
-    for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-    if (!(d > 0.0)) return false;
-    const double l = sqrt(d);
-    L[(size_t)j * n + j] = l;
-    for (int i = j + 1; i < n; ++i) {
-      double v = A[(size_t)i * n + j];
-      for (int k = 0; k < j; ++k) v -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
-      L[(size_t)i * n + j] = v / l;
-    }
-  }
-  for (int c = 0; c < n; ++c)  // W = L^-1
-    for (int i = c; i < n; ++i) {
-      double v = i == c ? 1.0 : 0.0;
-      for (int k = c; k < i; ++k) v -= L[(size_t)i * n + k] * W[(size_t)k * n + c];
-      W[(size_t)i * n + c] = v / L[(size_t)i * n + i];
-    }
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double v = 0;
-      for (int k = i; k < n; ++k) v += W[(size_t)k * n + i] * W[(size_t)k * n + j];
-      A[(size_t)i * n + j] = v; A[(size_t)j * n + i] = v;
-    }
-  return true;
-}
 
 template <int TYPE>
 int run(int n_cam, int n_ray, int64_t n_obs, const float* uv, const int* ocam, const int* oray, const double* rw, const double* cam,
@@ -54,54 +18,7 @@ int run(int n_cam, int n_ray, int64_t n_obs, const float* uv, const int* ocam, c
   for (int c = 0; c < n_cam; ++c) ba_cov_camblk(cam + 15 * (size_t)c, &cb[(size_t)c * CAMBLK]);
   int flags = 0;
   double sse = 0;
-  std::vector<double> E, Y;
-  for (int64_t a0 = 0; a0 < n_obs;) {
-    int64_t a1 = a0;
-    while (a1 < n_obs && oray[a1] == oray[a0]) ++a1;
-    const int r = oray[a0];
-    const double* X = ray + 3 * (size_t)r;
-    const double w = rw[r];
-    const int len = (int)(a1 - a0);
-    double V[6] = {0, 0, 0, 0, 0, 0};
-    E.assign((size_t)len * 3 * NF, 0.0); Y.assign((size_t)len * 3 * NF, 0.0);
-    std::vector<double> JcAll((size_t)len * 2 * NF);
-    for (int o = 0; o < len; ++o) {
-      const double* c = &cb[(size_t)ocam[a0 + o] * CAMBLK];
-      double res[2], Jc[2][NF], Jr[2][3];
-      ba_linearize<TYPE>(c, X, uv[2 * (a0 + o)], uv[2 * (a0 + o) + 1], res, Jc, Jr);
-      if (TYPE == 1 && c[CB_R + 6] * X[0] + c[CB_R + 7] * X[1] + c[CB_R + 8] * X[2] < 0) flags |= kBaCovPenalty;
-      ba_cov_add_V(Jr, V);
-      sse += res[0] * res[0] + res[1] * res[1];
-      ba_cov_E<NF>(Jc, Jr, w, &E[(size_t)o * 3 * NF]);
-      for (int k = 0; k < NF; ++k) { JcAll[(size_t)o * 2 * NF + k] = Jc[0][k]; JcAll[(size_t)o * 2 * NF + NF + k] = Jc[1][k]; }
-    }
-    a0 = a1;
-    if (len < 2) continue;  // contributes exactly zero
-    double P[6];
-    if (!ba_cov_ray_P(V, w, X, P)) { flags |= kBaCovBadRay; continue; }
-    for (int o = 0; o < len; ++o) ba_cov_Y<NF>(&E[(size_t)o * 3 * NF], P, &Y[(size_t)o * 3 * NF]);
-    for (int o = 0; o < len; ++o) {
-      const int co = ocam[a1 - len + o];
-      double Jc[2][NF];
-      for (int k = 0; k < NF; ++k) { Jc[0][k] = JcAll[(size_t)o * 2 * NF + k]; Jc[1][k] = JcAll[(size_t)o * 2 * NF + NF + k]; }
-      for (int k = 0; k < NF; ++k)
-        for (int l = 0; l <= k; ++l) {
-          const double v = ba_cov_diag_term<NF>(Jc, w, &Y[(size_t)o * 3 * NF], &E[(size_t)o * 3 * NF], k, l);
-          S[(size_t)(co * NF + k) * n + co * NF + l] += v; T[(size_t)(co * NF + k) * n + co * NF + l] += w * v;
-          if (l < k) { S[(size_t)(co * NF + l) * n + co * NF + k] += v; T[(size_t)(co * NF + l) * n + co * NF + k] += w * v; }
-        }
-      for (int p = 0; p < len; ++p) {
-        const int cp = ocam[a1 - len + p];
-        if (cp >= co) continue;  // block (co, cp), co > cp, and its mirror
-        for (int k = 0; k < NF; ++k)
-          for (int l = 0; l < NF; ++l) {
-            const double v = ba_cov_pair_term(&Y[(size_t)o * 3 * NF], &E[(size_t)p * 3 * NF], k, l);
-            S[(size_t)(co * NF + k) * n + cp * NF + l] += v; S[(size_t)(cp * NF + l) * n + co * NF + k] += v;
-            T[(size_t)(co * NF + k) * n + cp * NF + l] += w * v; T[(size_t)(cp * NF + l) * n + co * NF + k] += w * v;
-          }
-      }
-    }
-  }
+  ray_loop<TYPE>(n_obs, uv, ocam, oray, rw, cb.data(), ray, n, [](int c, int k) { return c * NF + k; }, S, T, sse, flags);
   // gauge, unit diagonal
   const int r0 = gauge * NF + NF - 3;
   std::vector<double> sc(n, 1.0);
