@@ -2149,6 +2149,10 @@ static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_
   //  enqueued beyond the last real one is a dozen empty launches; large batches, whose passes last milliseconds, keep three)
   b->ahead = n <= 32 ? 2 : 3;
   if (const char* e = getenv("PTZ_BA_AHEAD")) b->ahead = std::max(1, atoi(e));
+  // compacted (item, slot) launches deal their workgroups over the XCDs by the device's live count (ptz_xcd_map.h); 0: by the grid
+  b->d.xcd_live = 1;
+  if (const char* e = getenv("PTZ_BA_XCD_LIVE")) b->d.xcd_live = atoi(e) != 0;
+  b->d.chol.xcd_live = b->d.xcd_live;
   if (const char* e = getenv("PTZ_BA_DEBUG_STALL")) b->d.debug_stall = std::max(0, atoi(e));
   if (const char* e = getenv("PTZ_BA_DEBUG_CHAIN_SPIN")) b->d.chol.chain_spin_limit = std::max(0, atoi(e));  // tests: hand-overs that time out
   if (const char* e = getenv("PTZ_BA_GRAPH")) b->use_graph = atoi(e) != 0;

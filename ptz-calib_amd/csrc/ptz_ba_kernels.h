@@ -175,6 +175,9 @@ struct Dev {
   // host sizes those grids from a stale -- hence larger or equal -- count.  use_act = 0: slot == scene (full-size launches).
   int* act;
   int use_act;
+  // 1: the (camera, slot) launches of a compacted pass deal their workgroups over the XCDs by grp_ctl[2], the slots in use, not by
+  // their grid (live_slots); 0 (PTZ_BA_XCD_LIVE=0, A/B measurements): by the grid.  Placement only, never bits.
+  int xcd_live;
   Opt opt;
   // reduced camera system
   CholBatch chol;
@@ -223,6 +226,13 @@ __device__ __forceinline__ int scene_of_slot(const Dev& d, int slot)
 {
   if (!d.use_act) return slot;
   return slot < d.grp_ctl[2] ? d.act[slot] : -1;
+}
+
+// Rows of a (camera, slot) launch that have work, for xcd_remap: one uniform scalar load ahead of the early returns.  grp_ctl[2] is
+// written by k_compact only, the last launch of a pass (retire_scene touches grp_ctl[0]): every launch of a pass reads one value.
+__device__ __forceinline__ unsigned live_slots(const Dev& d)
+{
+  return (d.use_act && d.xcd_live) ? (unsigned)max(d.grp_ctl[2], 0) : gridDim.y;
 }
 
 // A scene leaves the pass pipeline (one thread of the scene's LM block calls this, once per scene and solve).
@@ -1228,7 +1238,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, Dims<TYPE>::DISP ? 2 : PTZ_SCHUR_WAV
   constexpr int NT = NW * 3;
   constexpr int TS = NT;  // row stride of the T table in LDS (an odd stride was measured: 25 % slower, it breaks the 16-byte reads of phase 2)
   int ci, slot;
-  xcd_remap(ci, slot);
+  if (!xcd_remap(ci, slot, live_slots(d))) return;
   const int sc = scene_of_slot(d, slot);
   if (sc < 0 || !d.active[sc]) return;
   const SceneDev s = d.scene[sc];
@@ -1465,7 +1475,7 @@ __global__ __launch_bounds__(schur_threads<TYPE>(), schur_threads<TYPE>() == 512
   constexpr int TS = (NT + 3) | 1;
   constexpr int ROT0 = BaDims<F>::ROT0;
   int ci, slot;
-  xcd_remap(ci, slot);
+  if (!xcd_remap(ci, slot, live_slots(d))) return;
   const int sc = scene_of_slot(d, slot);
   if (sc < 0 || !d.active[sc]) return;
   const SceneDev s = d.scene[sc];
@@ -1878,7 +1888,7 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
   constexpr int NU = NW * (NW + 1) / 2;
   constexpr int TS = SCHUR_F_ROW;   // 8 doubles at an odd pitch
   int ci, slot;
-  xcd_remap(ci, slot);
+  if (!xcd_remap(ci, slot, live_slots(d))) return;
   const int sc = scene_of_slot(d, slot);
   if (sc < 0 || !d.active[sc]) return;
   const SceneDev s = d.scene[sc];

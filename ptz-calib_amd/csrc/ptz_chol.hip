@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256) void chol_diag_kernel(CholBatch cb, int kk)
 __global__ __launch_bounds__(256, 3) void chol_trsm_kernel(CholBatch cb, const double* __restrict__ Dinv, int k)
 {
   int bx, slot;
-  xcd_remap(bx, slot);
+  if (!xcd_remap(bx, slot, chol_live_rows(cb))) return;
   const int sys = chol_system_of(cb, slot);
   if (sys < 0 || (cb.active && !cb.active[sys])) return;
   const int np = cb.np, nt = np / NB;
@@ -746,7 +746,7 @@ __global__ __launch_bounds__(256, 3) void chol_trsm_kernel(CholBatch cb, const d
 __global__ __launch_bounds__(256) void chol_syrk_kernel(CholBatch cb, int k, int mode, int fuse_diag)
 {
   int bx, slot;
-  xcd_remap(bx, slot);
+  if (!xcd_remap(bx, slot, chol_live_rows(cb))) return;
   const int sys = chol_system_of(cb, slot);
   if (sys < 0 || (cb.active && !cb.active[sys])) return;
   const int np = cb.np, nt = np / NB;
@@ -1001,7 +1001,7 @@ __device__ __forceinline__ void trsm_block_solve2(const d4 (&acc1)[4], const d4 
 __global__ __launch_bounds__(256) void chol_col_step_kernel(CholBatch cb, int step, int kmin)
 {
   int bx, slot;
-  xcd_remap(bx, slot);
+  if (!xcd_remap(bx, slot, chol_live_rows(cb))) return;
   const int sys = chol_system_of(cb, slot);
   if (sys < 0 || (cb.active && !cb.active[sys])) return;
   const int np = cb.np, nt = np / NB;
@@ -1565,7 +1565,7 @@ __device__ __forceinline__ d8 half_fetch(const double* __restrict__ g, int ld)
 __global__ __launch_bounds__(256, 3) void chol_update_col_h_kernel(CholBatch cb, int j, int fuse_diag)
 {
   int bx, slot;
-  xcd_remap(bx, slot);
+  if (!xcd_remap(bx, slot, chol_live_rows(cb))) return;
   const int sys = chol_system_of(cb, slot);
   if (sys < 0 || (cb.active && !cb.active[sys])) return;
   const int np = cb.np, nt = np / NB;

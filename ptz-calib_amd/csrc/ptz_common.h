@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "../../include/ptz_calib_amd.h"
+#include "ptz_xcd_map.h"
 
 namespace ptz {
 
@@ -114,14 +115,16 @@ inline void launch(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t smem, h
 // Workgroups are dealt round-robin over the 8 XCDs by linear block id.  For 2-D grids (x = item, y = scene) this
 // bijective remap gives each XCD a contiguous range of the logical (scene, item) space, so the workgroups that
 // share a scene's data share one XCD's L2.  Placement is a speed matter only; results never depend on it.
-__device__ __forceinline__ void xcd_remap(int& bx, int& by)
+// live: the rows (scenes) of the launch that have work, rows 0 .. live-1 -- the device's own count in a compacted launch, whose
+// grid the host sized from an older count, gridDim.y otherwise.  The eight ranges are cut from the gx x live space, so every XCD
+// gets an eighth of the WORK (ptz_xcd_map.h); false: this workgroup is surplus and returns.  live == gridDim.y accepts every id.
+__device__ __forceinline__ bool xcd_remap(int& bx, int& by, unsigned live)
 {
-  const unsigned gx = gridDim.x, total = gridDim.x * gridDim.y;
-  const unsigned L = blockIdx.x + gx * blockIdx.y;
-  const unsigned q = total / 8, r = total % 8, xcd = L % 8, idx = L / 8;
-  const unsigned Lp = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  bx = (int)(Lp % gx);
-  by = (int)(Lp / gx);
+  const unsigned gx = gridDim.x;
+  const XcdItem it = xcd_live_item(blockIdx.x + gx * blockIdx.y, gx, min(live, gridDim.y));
+  bx = (int)it.bx;
+  by = (int)it.by;
+  return it.work;
 }
 
 // ---- deterministic reductions ----------------------------------------------------------------------
@@ -267,6 +270,9 @@ struct CholBatch {
   // number of slots in use.  nullptr: slot == system.  The second matrix L of the one-launch-per-column path is indexed by slot.
   const int* act = nullptr;
   const int* act_n = nullptr;
+  // 1: a compacted launch deals its workgroups over the XCDs by *act_n, the slots in use, not by its grid (chol_live_rows);
+  // 0 (PTZ_BA_XCD_LIVE=0, A/B measurements): by the grid.  Placement only: the same tiles get the same arithmetic either way.
+  int xcd_live = 1;
   double* Ldiag = nullptr;  // device [count][np/NB][NB*NB]
   double* Dinv = nullptr;   // device [count][np/NB][4][16*16]: inverses of the 16x16 diagonal blocks of L_kk
   const int* n = nullptr;   // device [count]
@@ -413,6 +419,13 @@ __device__ __forceinline__ int chol_system_of(const CholBatch& cb, int slot)
 {
   if (!cb.act) return slot;
   return slot < *cb.act_n ? cb.act[slot] : -1;
+}
+// rows of a (tile, slot) launch that have work, for xcd_remap: read once per workgroup, ahead of its early returns.  *act_n is
+// written by the bundle adjustment's k_compact only, the last launch of an LM pass, after every launch of the factorisation --
+// those on the look-ahead stream included, which the pass joins before its back-substitution -- so it is one value per pass.
+__device__ __forceinline__ unsigned chol_live_rows(const CholBatch& cb)
+{
+  return (cb.act && cb.xcd_live) ? (unsigned)max(*cb.act_n, 0) : gridDim.y;
 }
 inline int chol_padded_order(int n_max) { return ((n_max + 1 + CHOL_NB - 1) / CHOL_NB) * CHOL_NB; }
 // enqueue factorisation + solve on `stream`; x: device [count][np]

@@ -2,7 +2,9 @@
 with the most expensive empty workgroups (k_schur_f, k_eval) cost per launch and per live scene.
 
   run:   python tools/probes/probe_pass_extents.py run [scenes]        (under rocprofv3 --kernel-trace --stats --output-format csv;
-         one scene group, one warm solve, then one solve with PTZ_BA_DEBUG_TIMING=2, whose per-pass lines go to stderr)
+         one scene group, one warm solve, then one solve with PTZ_BA_DEBUG_TIMING=2, whose per-pass lines go to stderr.
+         Fill the scene cache in a plain process first: under the tracer the generator's forked pool workers do not exit,
+         profiles/NOTES_r08.md section 4)
   join:  python tools/probes/probe_pass_extents.py join <stderr-file> <dir-with-kernel_trace.csv>
          -> one line per pass (shape, slots, host count, live scenes, k_schur_f us, k_eval us) and the sums per ladder shape"""
 import csv, glob, os, re, sys
