@@ -569,6 +569,82 @@ int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, con
                                  double pixel_sigma, double annotation_sigma, const ptz_lm_options* opt, double* cov,
                                  double* cov_centre, double* sigma0, int32_t* status);
 
+/* ------------------------------------------------------------------------------------------------
+ * Residual report and outlier trimming of the bundle adjustment
+ * ------------------------------------------------------------------------------------------------ */
+/* what incremental SfM tools do between solves and the reference does not: every observation of every track goes into its
+ * squared-loss LM (ptzray_optimizer.cc:799-850) and the only figure that comes back is the rig's mean reprojection error (:960-968).
+ *
+ * ptz_ba_batch_residuals -- the report, on the device, at exactly the state ptz_ba_batch_get_state would return.  Scope: a batch
+ * of ptz_ba_batch_create or ptz_ba_batch_create_views, type PTZRay, PTZRayDist or PTZRayFxfyDist, annotations allowed;
+ * PTZ_EUNSUPPORTED: PTZRayDistDisp, shared intrinsics.  Host outputs, concatenated over the problems at their real extents, any
+ * may be NULL (all NULL: PTZ_EINVAL, like a NULL batch or a batch without state -- checked before any device work):
+ *   err_px [sum n_obs]      |e_o|, the norm of the UNWEIGHTED 2-vector residual (the functors of the LM, the 1e6 penalty branch of
+ *                           PTZRayDist as it stands), in the caller's observation order; for a view batch that is the order of
+ *                           the packed problem of the same view
+ *   ray_max, ray_worst [sum n_ray]   the largest err_px of the track and the problem-local index of that observation (the lowest
+ *                           index on a tie), in the caller's ray numbering
+ *   view_rms, view_max, view_count [sum n_cam]   over the camera's observations: sqrt(mean |e_o|^2), max |e_o|, their number
+ *   rms, median [n]         sqrt(mean |e_o|^2) of the problem (PTZRayOptimizer's final_reproj_error_2d2d); the exact LOWER median,
+ *                           element (n_obs - 1) / 2 of the sorted err_px (not computed when NULL)
+ *   err3d_px [sum n_obs3d], rms3d [n]   the same for the 2D-3D annotations; rms3d is NaN for a problem without annotations
+ * No floating-point atomics, one reduction shape per figure: a problem's bits depend neither on its position in the batch nor on
+ * the run.  The call does not disturb the batch: a ptz_ba_batch_solve after it returns the bits it returns without it.
+ * device_ms (may be NULL): device time of the report's kernels. */
+int32_t ptz_ba_batch_residuals(ptz_ba_batch* b, double* err_px, double* ray_max, int32_t* ray_worst, double* view_rms, double* view_max,
+                               int32_t* view_count, double* rms, double* median, double* err3d_px, double* rms3d, double* device_ms);
+/* The selection rule on that report: threshold[k] = max(trim_px, k_sigma * median / 1.1774) (1.1774: the median of a Rayleigh
+ * variable with unit per-axis sigma; k_sigma = 0: trim_px, no median taken); every ray rejects AT MOST ONE observation, its
+ * ray_worst, if ray_max > threshold -- one wrong observation drags its whole ray, so the others are judged after the next solve.
+ * reject [sum n_obs] (1 = rejected, caller's order), threshold [n], n_reject [n]; any may be NULL, not all.  PTZ_EINVAL also for
+ * trim_px not positive and finite, k_sigma negative or not finite. */
+int32_t ptz_ba_batch_trim_select(ptz_ba_batch* b, double trim_px, double k_sigma, uint8_t* reject, double* threshold, int32_t* n_reject,
+                                 double* device_ms);
+/* Host logic only (no device): the problem `in` without the observations whose reject byte is non-zero and without every ray
+ * left with fewer than 2 observations (with what it still had: a single-observation ray adds exactly zero to the reduced system).
+ * Surviving rays are renumbered ascending, the order inside a ray is kept; ray_weight_out = ray_weight_in - (observations of
+ * that ray removed); ray_map [n_ray_in] = new index or -1.  The out arrays need room for the input's extents; annotations and
+ * ic_of_cam are not touched (the caller copies `in` and swaps the five fields).  PTZ_ENOOBS: a camera would be left without any
+ * observation -- nothing is written, trimming never drops a view.  PTZ_EINVAL: NULL arguments, empty extents, indices out of
+ * range, obs_ray decreasing. */
+int32_t ptz_ba_problem_trim(const ptz_ba_problem* in, const uint8_t* reject, float* obs_uv_out, int32_t* obs_cam_out, int32_t* obs_ray_out,
+                            double* ray_weight_out, int32_t* ray_map, int32_t* n_ray_out, int64_t* n_obs_out);
+
+typedef struct ptz_trim_options {
+  double trim_px;      /* 4.0 */
+  double k_sigma;      /* 3.0 */
+  int32_t max_rounds;  /* 8: solves per problem at most */
+  int32_t reserved_;   /* 0 */
+} ptz_trim_options;
+void ptz_trim_options_default(ptz_trim_options* o);
+#define PTZ_TRIM_ENOOBS 1     /* re-packing would have emptied a view: finished at the result it had */
+#define PTZ_TRIM_MAX_ROUNDS 2 /* observations above the threshold remain after max_rounds solves */
+typedef struct ptz_trim_report {
+  int32_t rounds;         /* solves of this problem */
+  int32_t flags;          /* PTZ_TRIM_* */
+  int64_t n_obs_removed;  /* rejected observations and those that left with their ray */
+  int32_t n_ray_removed;
+  int32_t reserved_;
+  double threshold;       /* of the last selection */
+  double rms_first;       /* 2D-2D rms after the first solve, all observations */
+  double rms_last;        /* ... after the last solve, over the observations kept */
+} ptz_trim_report;
+/* The trimmed solve.  Round 0: the n problems as given, one batch, from (cam, ray, tlw).  After every round: the report and the
+ * selection on the round's batch; a problem with n_reject = 0, or one that has run max_rounds solves, is finished; the others
+ * are re-packed (ptz_ba_problem_trim; PTZ_ENOOBS finishes the problem at the result it has, flagged) and solved together in one
+ * new batch, cameras from the previous round's solution, rays through ray_map, nothing re-initialised.  The existing batch API is
+ * used as it is: a problem's result is the bits of the manual loop over ptz_ba_solve, ptz_ba_batch_trim_select and
+ * ptz_ba_problem_trim, whatever the other problems of the call do.
+ * Out: cam / tlw and summaries [n] (or NULL) of each problem's last solve; ray in the INPUT numbering, removed rays left as given;
+ * kept [sum n_obs] (or NULL): 1 for every observation of the last solve; report [n] (or NULL).  trim = NULL: the defaults.
+ * PTZ_EUNSUPPORTED: PTZRayDistDisp, shared intrinsics.  PTZ_EINVAL: malformed problems or options.  Annotations pass through
+ * untrimmed. */
+int32_t ptz_ba_solve_trimmed_batch(int32_t n, const ptz_ba_problem* problems, double* cam, double* ray, double* tlw,
+                                   const ptz_trim_options* trim, const ptz_lm_options* opt, ptz_lm_summary* summaries,
+                                   uint8_t* kept /* [sum n_obs] */, ptz_trim_report* report /* [n] */);
+int32_t ptz_ba_solve_trimmed(const ptz_ba_problem* p, double* cam, double* ray, double* tlw, const ptz_trim_options* trim,
+                             const ptz_lm_options* opt, ptz_lm_summary* summary, uint8_t* kept, ptz_trim_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_match_gate_destroy", "ptz_match_gate_run_device", "ptz_match_gate_run", "ptz_krt_solve_batch_gated", "ptz_debug_match_gate_table",
            "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device", "ptz_ba_cov_dim",
            "ptz_ba_batch_covariance", "ptz_ba_covariance", "ptz_ba_geo_cov_dim", "ptz_ba_batch_covariance_georef",
-           "ptz_ba_covariance_georef"]
+           "ptz_ba_covariance_georef", "ptz_ba_batch_residuals", "ptz_ba_batch_trim_select", "ptz_ba_problem_trim",
+           "ptz_trim_options_default", "ptz_ba_solve_trimmed_batch", "ptz_ba_solve_trimmed"]
 
 
 class PtzError(RuntimeError):
@@ -68,6 +69,20 @@ class BaProblem(C.Structure):
                 ("n_obs3d", C.c_int32), ("obs3d_uv", C.c_void_p), ("obs3d_xyz", C.c_void_p),
                 ("obs3d_cam", C.c_void_p), ("factor_type", C.c_int32), ("ic_of_cam", C.c_void_p)]
 
+
+class TrimOptions(C.Structure):
+    _fields_ = [("trim_px", C.c_double), ("k_sigma", C.c_double), ("max_rounds", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class TrimReport(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("flags", C.c_int32), ("n_obs_removed", C.c_int64), ("n_ray_removed", C.c_int32),
+                ("reserved_", C.c_int32), ("threshold", C.c_double), ("rms_first", C.c_double), ("rms_last", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
+TRIM_ENOOBS, TRIM_MAX_ROUNDS = 1, 2
 
 _lib = None
 
@@ -279,6 +294,60 @@ class BaBatch:
         return [cov[off[i]:off[i + 1]] for i in range(self.n)], cov_centre, sigma0, status, ms.value
 
 
+    def _extents(self, n_obs, n_ray):
+        """per-problem (n_cam, n_ray, n_obs, n_obs3d); a ViewBatch has no host-side scenes and is told the packed problems' counts"""
+        if self.scenes:
+            return ([s.n_cam for s in self.scenes], [s.n_ray for s in self.scenes], [s.n_obs for s in self.scenes],
+                    [0 if getattr(s, "obs3d", None) is None else len(s.obs3d["cam"]) for s in self.scenes])
+        if n_obs is None or n_ray is None:
+            raise ValueError("a ViewBatch needs n_obs and n_ray of the packed problem of every view (api.view_problem)")
+        return list(self.n_cams), [int(x) for x in n_ray], [int(x) for x in n_obs], [0] * self.n
+
+    def residuals(self, median=True, n_obs=None, n_ray=None, only=None):
+        """ptz_ba_batch_residuals at the batch's current state.  Returns a list of dicts, one per problem: err_px [n_obs] in the
+        caller's observation order, ray_max / ray_worst [n_ray], view_rms / view_max / view_count [n_cam], rms, median (the exact
+        lower median; None when median=False), err3d_px [n_obs3d], rms3d (NaN without annotations); plus device_ms on the first.
+        only: names of the outputs wanted (the others are passed as NULL and come back as None)."""
+        ncam, nray, nobs, no3 = self._extents(n_obs, n_ray)
+        names = ["err_px", "ray_max", "ray_worst", "view_rms", "view_max", "view_count", "rms", "median", "err3d_px", "rms3d"]
+        want = set(names if only is None else only)
+        if not median:
+            want.discard("median")
+        size = dict(err_px=sum(nobs), ray_max=sum(nray), ray_worst=sum(nray), view_rms=sum(ncam), view_max=sum(ncam), view_count=sum(ncam),
+                    rms=self.n, median=self.n, err3d_px=sum(no3), rms3d=self.n)
+        arr = {k: (np.zeros(max(size[k], 1), dtype=np.int32 if k in ("ray_worst", "view_count") else np.float64) if k in want else None)
+               for k in names}
+        ms = C.c_double()
+        _check(lib().ptz_ba_batch_residuals(self.handle, *[_p(arr[k]) for k in names], C.byref(ms)), "ptz_ba_batch_residuals")
+        out = []
+        off = dict(o=0, r=0, c=0, a=0)
+        for i in range(self.n):
+            d = {}
+            for k, (key, cnt) in dict(err_px=("o", nobs[i]), ray_max=("r", nray[i]), ray_worst=("r", nray[i]), view_rms=("c", ncam[i]),
+                                      view_max=("c", ncam[i]), view_count=("c", ncam[i]), err3d_px=("a", no3[i])).items():
+                d[k] = None if arr[k] is None else arr[k][off[key]:off[key] + cnt].copy()
+            for k in ("rms", "median", "rms3d"):
+                d[k] = None if arr[k] is None else float(arr[k][i])
+            off["o"] += nobs[i]; off["r"] += nray[i]; off["c"] += ncam[i]; off["a"] += no3[i]
+            out.append(d)
+        if out:
+            out[0]["device_ms"] = ms.value
+        return out
+
+    def trim_select(self, trim_px=4.0, k_sigma=3.0, n_obs=None, n_ray=None):
+        """ptz_ba_batch_trim_select at the batch's current state.  Returns (reject: list of uint8 [n_obs] in the caller's order,
+        threshold [n], n_reject [n], device_ms)."""
+        _, _, nobs, _ = self._extents(n_obs, n_ray)
+        rej = np.zeros(max(sum(nobs), 1), dtype=np.uint8)
+        thr = np.zeros(self.n)
+        nrej = np.zeros(self.n, dtype=np.int32)
+        ms = C.c_double()
+        _check(lib().ptz_ba_batch_trim_select(self.handle, C.c_double(trim_px), C.c_double(k_sigma), _p(rej), _p(thr), _p(nrej), C.byref(ms)),
+               "ptz_ba_batch_trim_select")
+        oo = np.concatenate([[0], np.cumsum(nobs)]).astype(int)
+        return [rej[oo[i]:oo[i + 1]].copy() for i in range(self.n)], thr, nrej, ms.value
+
+
 class RigView(C.Structure):
     _fields_ = [("rig", C.c_void_p), ("n_cam", C.c_int32), ("cam_image", C.c_void_p)]
 
@@ -396,6 +465,81 @@ def ba_solve(scene, cam0=None, ray0=None, tlw0=None, return_tlw=False, **opt):
     s = LmSummary()
     _check(lib().ptz_ba_solve(C.byref(p), _p(cam), _p(ray), _p(tlw), C.byref(o), C.byref(s)), "ptz_ba_solve")
     return (cam, ray, s.as_dict(), tlw) if return_tlw else (cam, ray, s.as_dict())
+
+
+def ba_trim_problem(scene, reject):
+    """ptz_ba_problem_trim (host logic, no device): `scene` without the observations with a non-zero reject byte and without the
+    rays left with fewer than two observations.  Returns (trimmed scene-like copy, ray_map [n_ray] with -1 for removed rays);
+    ray_init / ray_gt of the copy follow the map.  Raises PtzError(PTZ_ENOOBS) if a camera would lose every observation."""
+    import copy
+    keep = []
+    p = _pack_problem(scene, keep)
+    rej = np.ascontiguousarray(reject, dtype=np.uint8)
+    if len(rej) != p.n_obs:
+        raise ValueError("one reject byte per observation")
+    uv = np.zeros((p.n_obs, 2), dtype=np.float32)
+    oc = np.zeros(p.n_obs, dtype=np.int32)
+    orr = np.zeros(p.n_obs, dtype=np.int32)
+    w = np.zeros(p.n_ray)
+    rmap = np.zeros(p.n_ray, dtype=np.int32)
+    nr, no = C.c_int32(), C.c_int64()
+    _check(lib().ptz_ba_problem_trim(C.byref(p), _p(rej), _p(uv), _p(oc), _p(orr), _p(w), _p(rmap), C.byref(nr), C.byref(no)),
+           "ptz_ba_problem_trim")
+    t = copy.copy(scene)
+    t.n_ray, n_obs = int(nr.value), int(no.value)
+    t.obs_uv, t.obs_cam, t.obs_ray, t.ray_weight = uv[:n_obs].copy(), oc[:n_obs].copy(), orr[:n_obs].copy(), w[:t.n_ray].copy()
+    for k in ("ray_init", "ray_gt"):
+        if getattr(scene, k, None) is not None:
+            setattr(t, k, np.asarray(getattr(scene, k))[rmap >= 0].copy())
+    return t, rmap
+
+
+def ba_solve_trimmed_batch(scenes, cams=None, rays=None, trim_px=4.0, k_sigma=3.0, max_rounds=8, **opt):
+    """ptz_ba_solve_trimmed_batch.  Returns (cams, rays, summaries, kept, reports): per problem the cameras and summary of its
+    last solve, the rays in the input numbering (removed rays as given), kept uint8 [n_obs], and the report dict (rounds, flags,
+    n_obs_removed, n_ray_removed, threshold, rms_first, rms_last)."""
+    keep = []
+    n = len(scenes)
+    probs = (BaProblem * n)(*[_pack_problem(s, keep) for s in scenes])
+    o = default_options(**opt)
+    cam = np.ascontiguousarray(np.concatenate([s.cam_init for s in scenes] if cams is None else cams), dtype=np.float64).copy()
+    ray = np.ascontiguousarray(np.concatenate([s.ray_init for s in scenes] if rays is None else rays), dtype=np.float64).copy()
+    tlw = np.ascontiguousarray(np.stack([getattr(s, "tlw_init", None) if getattr(s, "tlw_init", None) is not None else np.zeros(6)
+                                         for s in scenes]), dtype=np.float64).copy()
+    to = TrimOptions()
+    lib().ptz_trim_options_default(C.byref(to))
+    to.trim_px, to.k_sigma, to.max_rounds = float(trim_px), float(k_sigma), int(max_rounds)
+    summ = (LmSummary * n)()
+    rep = (TrimReport * n)()
+    oo = np.concatenate([[0], np.cumsum([len(k["cam"]) for k in keep])]).astype(int)
+    kept = np.zeros(max(int(oo[-1]), 1), dtype=np.uint8)
+    _check(lib().ptz_ba_solve_trimmed_batch(n, probs, _p(cam), _p(ray), _p(tlw), C.byref(to), C.byref(o), summ, _p(kept), rep),
+           "ptz_ba_solve_trimmed_batch")
+    co = np.concatenate([[0], np.cumsum([s.n_cam for s in scenes])]).astype(int)
+    ro = np.concatenate([[0], np.cumsum([s.n_ray for s in scenes])]).astype(int)
+    ba_solve_trimmed_batch.last_tlw = tlw
+    return ([cam[co[i]:co[i + 1]] for i in range(n)], [ray[ro[i]:ro[i + 1]] for i in range(n)], [s.as_dict() for s in summ],
+            [kept[oo[i]:oo[i + 1]].copy() for i in range(n)], [r.as_dict() for r in rep])
+
+
+def ba_solve_trimmed(scene, cam0=None, ray0=None, trim_px=4.0, k_sigma=3.0, max_rounds=8, **opt):
+    """One problem through ptz_ba_solve_trimmed.  Returns (cam, ray, summary, kept, report)."""
+    keep = []
+    p = _pack_problem(scene, keep)
+    cam = np.array(scene.cam_init if cam0 is None else cam0, dtype=np.float64, order="C").copy()
+    ray = np.array(scene.ray_init if ray0 is None else ray0, dtype=np.float64, order="C").copy()
+    tlw0 = getattr(scene, "tlw_init", None)
+    tlw = np.zeros(6) if tlw0 is None else np.array(tlw0, dtype=np.float64).copy()
+    o = default_options(**opt)
+    to = TrimOptions()
+    lib().ptz_trim_options_default(C.byref(to))
+    to.trim_px, to.k_sigma, to.max_rounds = float(trim_px), float(k_sigma), int(max_rounds)
+    s = LmSummary()
+    rep = TrimReport()
+    kept = np.zeros(max(int(p.n_obs), 1), dtype=np.uint8)
+    _check(lib().ptz_ba_solve_trimmed(C.byref(p), _p(cam), _p(ray), _p(tlw), C.byref(to), C.byref(o), C.byref(s), _p(kept), C.byref(rep)),
+           "ptz_ba_solve_trimmed")
+    return cam, ray, s.as_dict(), kept[:int(p.n_obs)].copy(), rep.as_dict()
 
 
 def ba_cov_dim(factor_type) -> int:

@@ -9,6 +9,11 @@
 // codes do not depend on the flag.  With -a the side file gains one key, "georeferenced": after the georeferencing bundle
 // adjustment succeeds, PTZRayOptimizer::WorldStdDevs of THAT optimizer (no extra solve) -- the standard deviations of the cameras
 // the tool writes, in the world frame, and of the rig's projection centre.
+// --trim_px <px> (with --trim_sigma, default 3, and --trim_rounds, default 8; not in the reference) trims outlying observations in
+// the solves whose cameras and sigmas the tool writes: the georeferencing bundle adjustment and the re-solve of --uncertainty run
+// PTZRayOptimizer::SetTrimming (solve, residual report, one rejected observation per offending track, re-pack, solve again).  A side
+// file <output>/<basename(images)>_residuals.json then holds the rounds, the last threshold, the observations removed and, per
+// registered image, rms_px / max_px / n_obs / n_removed of the georeferencing fit.  Without the flag nothing changes.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -23,6 +28,12 @@
 #include "args.h"
 
 using namespace ptzcalib;
+
+struct TrimArgs {
+  bool on = false;
+  double px = 0, sigma = 3.0;
+  int rounds = 8;
+};
 
 static bool RunPtzBA(const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                      const std::vector<MatchesInfo>& matches_info, int max_iter, std::vector<Camera>& cameras,
@@ -58,9 +69,10 @@ static void Appendf(std::string& s, const char* fmt, ...)
 static void WriteUncertainty(const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                              const std::vector<MatchesInfo>& matches_info, const std::vector<Camera>& cameras,
                              const std::unordered_set<long>& reg_image_ids, long seed, int max_iter, const std::string& path,
-                             std::string* body = nullptr)
+                             std::string* body = nullptr, const TrimArgs& trim = TrimArgs())
 {
   PTZRayOptimizer optimizer(features, matches_info, cameras, reg_image_ids, max_iter, PTZRay);  // the factor PTZ-IBA adjusts with
+  if (trim.on) optimizer.SetTrimming(trim.px, trim.sigma, trim.rounds);
   std::vector<Camera> refined = cameras;
   std::vector<double> sd;
   double sigma0 = 0;
@@ -94,9 +106,11 @@ static bool RunGeoreferencing(const std::vector<ImageFeatures>& features, const 
                               const std::vector<std::vector<Point2f>>& pixels, const std::vector<std::vector<Point3d>>& pts3d,
                               const std::unordered_set<long>& cam_ids, int max_iter, bool has_dist, std::vector<Camera>& cameras,
                               double& error_2d2d, double& error_2d3d, const std::vector<std::string>* fnames = nullptr,
-                              std::string* georef = nullptr)
+                              std::string* georef = nullptr, const TrimArgs& trim = TrimArgs(), const std::vector<std::string>* all_fnames = nullptr,
+                              const std::string& residuals_path = std::string())
 {  // run_ptz_ba.cc:131-154; fnames / georef (--uncertainty): the "georeferenced" record of the side file, empty if not available
   PTZRayOptimizer optimizer(features, matches_info, cameras, pixels, pts3d, cam_ids, max_iter, has_dist ? PTZRayDist : PTZRay);
+  if (trim.on) optimizer.SetTrimming(trim.px, trim.sigma, trim.rounds);
   std::vector<std::vector<Ray>> rays;
   if (!optimizer.Solve(cameras, rays)) {
     error_2d2d = error_2d3d = -1;
@@ -104,6 +118,31 @@ static bool RunGeoreferencing(const std::vector<ImageFeatures>& features, const 
   }
   error_2d2d = optimizer.final_reproj_error_2d2d();
   error_2d3d = optimizer.final_reproj_error_2d3d();
+  if (trim.on && all_fnames) {  // --trim_px: what was removed and how every registered image fits, into the side file
+    std::vector<double> rms, mx;
+    std::vector<int32_t> cnt;
+    const std::vector<long>& images = optimizer.packed().cam_image;
+    if (!optimizer.ViewResiduals(rms, mx, cnt)) fprintf(stderr, "Residuals: the residual report is not available\n");
+    else {
+      std::vector<long> removed(images.size(), 0);
+      const std::vector<uint8_t>& kept = optimizer.kept();
+      const std::vector<int32_t>& oc = optimizer.packed_obs_cam_before_trim();
+      for (size_t a = 0; a < kept.size() && a < oc.size(); ++a)
+        if (!kept[a]) ++removed[oc[a]];
+      const ptz_trim_report& r = optimizer.trim_report();
+      std::string t;
+      Appendf(t, "{\n  \"rounds\": %d,\n  \"threshold\": %.17g,\n  \"observations_removed\": %lld,\n  \"rays_removed\": %d,\n", (int)r.rounds, r.threshold,
+              (long long)r.n_obs_removed, (int)r.n_ray_removed);
+      Appendf(t, "  \"rms_px_first\": %.17g,\n  \"rms_px_last\": %.17g,\n  \"flags\": %d,\n  \"images\": {\n", r.rms_first, r.rms_last, (int)r.flags);
+      for (size_t c = 0; c < images.size(); ++c)
+        Appendf(t, "    \"%s\": {\"rms_px\": %.17g, \"max_px\": %.17g, \"n_obs\": %d, \"n_removed\": %ld}%s\n", (*all_fnames)[images[c]].c_str(), rms[c], mx[c],
+                (int)cnt[c], removed[c], c + 1 < images.size() ? "," : "");
+      t += "  }\n}\n";
+      FILE* f = fopen(residuals_path.c_str(), "w");
+      if (!f) fprintf(stderr, "Residuals: cannot write %s\n", residuals_path.c_str());
+      else { fputs(t.c_str(), f); fclose(f); }
+    }
+  }
   if (fnames && georef) {
     std::vector<double> sd;
     std::array<double, 3> sc, centre;
@@ -143,7 +182,21 @@ int main(int argc, char** argv)
   parser.AddFlag("inlier_matches", "Keep only the RANSAC inliers of every pair's homography (4 px) as the pair's matches");
   parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
   parser.AddFlag(ptzapp::kUncertaintyFlag, ptzapp::kBaUncertaintyHelp);
+  parser.Add("trim_px", '\0', "Trim outlying observations in the georeferencing / uncertainty solves: threshold floor in pixels (off unless given)", false);
+  parser.Add("trim_sigma", '\0', "With --trim_px: threshold = max(trim_px, trim_sigma * robust sigma) (default 3; 0: trim_px alone)", false);
+  parser.Add("trim_rounds", '\0', "With --trim_px: solves at most (default 8)", false);
   parser.ParseCheck(argc, argv);
+  TrimArgs trim;
+  if (parser.Exist("trim_px")) {
+    trim.on = true;
+    trim.px = atof(parser.Get("trim_px").c_str());
+    if (parser.Exist("trim_sigma")) trim.sigma = atof(parser.Get("trim_sigma").c_str());
+    if (parser.Exist("trim_rounds")) trim.rounds = atoi(parser.Get("trim_rounds").c_str());
+    if (!(trim.px > 0.0) || !(trim.sigma >= 0.0) || trim.rounds < 1) {
+      fprintf(stderr, "--trim_px must be positive, --trim_sigma not negative, --trim_rounds at least 1\n");
+      return 1;
+    }
+  }
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
     fprintf(stderr, "--min_inliers must not be negative\n");
@@ -180,9 +233,10 @@ int main(int argc, char** argv)
   const bool uncertainty = parser.Exist(ptzapp::kUncertaintyFlag);
   const std::string side_path = parser.Get("output") + "/" + BaseName(parser.Get("images")) + "_uncertainty.json";
   std::string side_body;
+  if (uncertainty || trim.on) MkdirIfNotExist(parser.Get("output"));
   if (uncertainty) {
     MkdirIfNotExist(parser.Get("output"));
-    WriteUncertainty(fnames, features, matches_info, cameras, reg_image_ids, first_seed, MAX_ITER, side_path, &side_body);
+    WriteUncertainty(fnames, features, matches_info, cameras, reg_image_ids, first_seed, MAX_ITER, side_path, &side_body, trim);
   }
 
   std::vector<std::vector<Point2f>> pixels;
@@ -195,7 +249,8 @@ int main(int argc, char** argv)
   double error_2d2d, error_2d3d;
   std::string georef;
   if (!RunGeoreferencing(features, matches_info, pixels, pts3d, reg_image_ids, MAX_ITER, parser.Exist("dist"), cameras, error_2d2d, error_2d3d,
-                         uncertainty ? &fnames : nullptr, uncertainty ? &georef : nullptr)) {
+                         uncertainty ? &fnames : nullptr, uncertainty ? &georef : nullptr, trim, &fnames,
+                         parser.Get("output") + "/" + BaseName(parser.Get("images")) + "_residuals.json")) {
     fprintf(stderr, "================== Georeferencing End: failed ==========================\n");
     return -1;
   }

@@ -42,6 +42,7 @@
 #include "ptz_view_kernels.h"
 #include "ptz_ba_cov.h"
 #include "ptz_ba_cov_georef.h"
+#include "ptz_ba_resid.h"
 #include <rocprim/rocprim.hpp>
 
 namespace ptz {
@@ -2539,6 +2540,44 @@ int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, con
   if (!rc) rc = ptz_ba_batch_covariance_georef(b, &gauge_cam, pixel_sigma, annotation_sigma, cov, cov_centre, sigma0, status, nullptr);
   ptz_ba_batch_destroy(b);
   return rc;
+}
+
+namespace {
+// the residual report / the selection on it at the batch's current state: the checks the two entry points share, then ptz_ba_resid.hip
+int32_t ba_resid_call(ptz_ba_batch* b, const BaResidOut& out, double* device_ms)
+{
+  // PTZRayDistDisp carries a displacement block, shared intrinsics one state per group: not what these kernels read
+  if (ba_cov_dim(b->type) < 0 || b->d.shared) return PTZ_EUNSUPPORTED;
+  clear_stale_error(__func__);
+  PTZ_DEVICE_GUARD(b->device);
+  BaCovPrep prep(b, b->has3d != 0);
+  if (prep.rc) return prep.rc;
+  return ba_resid_run(prep.in, prep.geo, prep.hs.data(), b->d_ray_perm, b->stream, out, device_ms);
+}
+}  // namespace
+
+int32_t ptz_ba_batch_residuals(ptz_ba_batch* b, double* err_px, double* ray_max, int32_t* ray_worst, double* view_rms, double* view_max,
+                               int32_t* view_count, double* rms, double* median, double* err3d_px, double* rms3d, double* device_ms)
+{
+  if (!b || !b->has_state) return PTZ_EINVAL;
+  if (!err_px && !ray_max && !ray_worst && !view_rms && !view_max && !view_count && !rms && !median && !err3d_px && !rms3d) return PTZ_EINVAL;
+  BaResidOut out;
+  out.err_px = err_px; out.ray_max = ray_max; out.ray_worst = ray_worst; out.view_rms = view_rms; out.view_max = view_max;
+  out.view_count = view_count; out.rms = rms; out.median = median; out.err3d_px = err3d_px; out.rms3d = rms3d;
+  return ba_resid_call(b, out, device_ms);
+}
+
+int32_t ptz_ba_batch_trim_select(ptz_ba_batch* b, double trim_px, double k_sigma, uint8_t* reject, double* threshold, int32_t* n_reject,
+                                 double* device_ms)
+{
+  if (!b || !b->has_state) return PTZ_EINVAL;
+  if (!reject && !threshold && !n_reject) return PTZ_EINVAL;
+  BaResidOut out;
+  out.select = true;
+  out.rule = TrimRule{trim_px, k_sigma, 2};
+  if (!trim_rule_valid(out.rule)) return PTZ_EINVAL;
+  out.reject = reject; out.threshold = threshold; out.n_reject = n_reject;
+  return ba_resid_call(b, out, device_ms);
 }
 
 int32_t ptz_ba_batch_set_disp(ptz_ba_batch* b, const double* disp)

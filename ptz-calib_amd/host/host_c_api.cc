@@ -838,4 +838,59 @@ int32_t ptzh_ptzray_solve_world_cov(int32_t n_img, const int64_t* kp_ptr, const 
   return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
 }
 
+// PTZRayOptimizer::Solve with SetTrimming(trim_px, k_sigma, max_rounds) (trim_px <= 0: not called) followed by ViewResiduals.
+// use_rig != 0: the tracks go to the device (UseTracks / UseRig) and the solve is a view of them, which ignores trimming.
+// kept (malloc'ed, n_kept entries: the observations of the problem as it was packed; n_kept = 0 without trimming), report, and
+// per candidate view_rms / view_max / view_count (room for n_cand, or n_img without candidates).  The packed_* outputs are the
+// problem packed() holds after the Solve: the trimmed one.  Returns Solve() | ViewResiduals() << 1.
+int32_t ptzh_ptzray_solve_trim(int32_t n_img, const int64_t* kp_ptr, const float* kp_xy, int32_t n_pairs, const int64_t* src, const int64_t* dst,
+                               const int64_t* match_ptr, const int32_t* q, const int32_t* t, double* cam15, const int64_t* cand_ids, int32_t n_cand,
+                               int32_t max_iter, int32_t type, double trim_px, double k_sigma, int32_t max_rounds, int32_t use_rig,
+                               ptz_lm_summary* summary, ptz_trim_report* report, uint8_t** kept, int32_t* n_kept, double* view_rms, double* view_max,
+                               int32_t* view_count, int32_t* n_obs_out, int32_t* n_ray_out, float** p_uv, int32_t** p_cam, int32_t** p_ray, double** p_w,
+                               double** p_cam15, double** p_ray3, int64_t** p_cam_image)
+{
+  std::vector<ImageFeatures> feats;
+  std::vector<MatchesInfo> mis;
+  std::vector<Camera> cams;
+  BuildInputs(n_img, kp_ptr, kp_xy, nullptr, n_pairs, src, dst, match_ptr, q, t, cam15, feats, mis, cams);
+  std::unordered_set<long> ids;
+  for (int i = 0; i < n_cand; ++i) ids.insert(static_cast<long>(cand_ids[i]));
+  PTZRayOptimizer opt(feats, mis, cams, ids, max_iter, static_cast<FACTOR_TYPE>(type));
+  ptz_rig* rig = nullptr;
+  if (use_rig) {
+    std::shared_ptr<const SharedTracks> st = PTZRayOptimizer::BuildTracks(mis);
+    std::vector<float> uv(2 * st->img.size());
+    for (size_t e = 0; e < st->img.size(); ++e) {
+      const Point2f pt = feats[st->img[e]].keypoints[st->feat[e]].pt;
+      uv[2 * e] = pt.x; uv[2 * e + 1] = pt.y;
+    }
+    if (ptz_rig_create(n_img, static_cast<int32_t>(st->id.size()), st->ptr.data(), st->img.data(), uv.data(), 0, &rig) != PTZ_OK) return -1;
+    opt.UseTracks(st);
+    opt.UseRig(rig);
+  }
+  if (trim_px > 0.0) opt.SetTrimming(trim_px, k_sigma, max_rounds);
+  const bool ok = opt.Solve(cams);
+  if (summary) *summary = opt.summary();
+  if (report) *report = opt.trim_report();
+  if (kept) *kept = Dup(opt.kept());
+  if (n_kept) *n_kept = static_cast<int32_t>(opt.kept().size());
+  ExportPacked(opt.packed(), PackedOut{n_obs_out, n_ray_out, p_uv, p_cam, p_ray, p_w, p_cam15, p_ray3, p_cam_image});
+  if (ok)
+    for (int i = 0; i < n_img; ++i) {
+      const std::vector<double> v = cams[i].ToVector();
+      memcpy(cam15 + 15 * i, v.data(), sizeof(double) * 15);
+    }
+  std::vector<double> r, m;
+  std::vector<int32_t> c;
+  const bool okv = opt.ViewResiduals(r, m, c);
+  if (okv) {
+    memcpy(view_rms, r.data(), sizeof(double) * r.size());
+    memcpy(view_max, m.data(), sizeof(double) * m.size());
+    memcpy(view_count, c.data(), sizeof(int32_t) * c.size());
+  }
+  if (rig) ptz_rig_destroy(rig);
+  return (ok ? 1 : 0) | (okv ? 2 : 0);
+}
+
 }  // extern "C"

@@ -313,6 +313,11 @@ bool PTZRayOptimizer::SolveView(std::vector<Camera>& cameras)
 {
   PackedBA& p = packed_;
   p = PackedBA();
+  if (trim_on_) {
+    static bool said = false;
+    if (!said) fprintf(stderr, "[ptzcalib] PTZRayOptimizer::Solve: trimming is not applied to a solve over a view of a device-resident rig (UseRig)\n");
+    said = true;
+  }
   std::vector<int32_t> cam_image;
   for (size_t i = 0; i < num_cams_; ++i) {
     if (!isCandidate(static_cast<long>(i))) continue;
@@ -346,6 +351,9 @@ bool PTZRayOptimizer::SolveView(std::vector<Camera>& cameras)
   }
   init_reproj_error_all_ = std::sqrt(2.0) * std::sqrt((2 * summary_.initial_cost) / summary_.num_residuals);
   final_reproj_error_all_ = std::sqrt(2.0) * std::sqrt((2 * summary_.final_cost) / summary_.num_residuals);
+  view_cam0_ = p.cam;
+  view_rkinv_ = rkinv;
+  resid_state_ = 2;
   p.cam = cam;
   errors_ready_ = true;  // (the unweighted statistics need the packed residuals; callers of this path -- the incremental pipeline -- never read them)
   final_reproj_error_2d2d_ = final_reproj_error_2d3d_ = std::numeric_limits<double>::quiet_NaN();
@@ -366,9 +374,96 @@ bool PTZRayOptimizer::SolveView(std::vector<Camera>& cameras)
   return true;
 }
 
+namespace {
+bool CovProblem(const PackedBA& p, ptz_ba_problem& prob);  // (below, with the covariance calls)
+}
+
+void PTZRayOptimizer::SetTrimming(double trim_px, double k_sigma, int max_rounds)
+{
+  trim_on_ = trim_px > 0.0;
+  trim_opt_ = ptz_trim_options{trim_px, k_sigma, max_rounds, 0};
+}
+
+// packed_ after a trimmed solve: the observations kept_ marks, the rays that still have any (the re-packing leaves a ray two at
+// least or none), weights less the observations removed -- the arrays ptz_ba_problem_trim handed the last solve.  ray: in = the
+// rays in the numbering packed_ had, out = in the new one.
+void PTZRayOptimizer::ApplyTrim(std::vector<double>& ray)
+{
+  PackedBA& p = packed_;
+  obs_cam_before_trim_ = p.obs_cam;
+  const size_t n_obs = p.obs_cam.size(), n_ray = p.ray_track.size();
+  std::vector<int32_t> left(n_ray, 0), total(n_ray, 0), map(n_ray, -1);
+  for (size_t a = 0; a < n_obs; ++a) {
+    ++total[p.obs_ray[a]];
+    if (kept_[a]) ++left[p.obs_ray[a]];
+  }
+  size_t nr = 0;
+  for (size_t j = 0; j < n_ray; ++j) {
+    if (left[j] == 0) continue;
+    map[j] = static_cast<int32_t>(nr);
+    p.ray_track[nr] = p.ray_track[j];
+    p.ray_weight[nr] = p.ray_weight[j] - static_cast<double>(total[j] - left[j]);
+    for (int e = 0; e < 3; ++e) ray[3 * nr + e] = ray[3 * j + e];
+    ++nr;
+  }
+  p.ray_track.resize(nr); p.ray_weight.resize(nr); ray.resize(3 * nr);
+  size_t no = 0;
+  for (size_t a = 0; a < n_obs; ++a) {
+    if (!kept_[a]) continue;
+    p.obs_uv[2 * no] = p.obs_uv[2 * a]; p.obs_uv[2 * no + 1] = p.obs_uv[2 * a + 1];
+    p.obs_cam[no] = p.obs_cam[a];
+    p.obs_ray[no] = map[p.obs_ray[a]];
+    ++no;
+  }
+  p.obs_uv.resize(2 * no); p.obs_cam.resize(no); p.obs_ray.resize(no);
+}
+
+bool PTZRayOptimizer::ViewResiduals(std::vector<double>& rms, std::vector<double>& max, std::vector<int32_t>& count) const
+{
+  const PackedBA& p = packed_;
+  if (resid_state_ == 0 || p.cam_image.empty()) return false;
+  const size_t n_cam = p.cam_image.size();
+  ptz_lm_options opt;
+  ptz_lm_options_default(&opt);
+  opt.max_num_iterations = max_iter_;
+  opt.device_id = device_id_;
+  const int32_t ftype = (type_ == PTZRay) ? PTZ_BA_PTZRay : (type_ == PTZRayDist ? PTZ_BA_PTZRayDist : PTZ_BA_PTZRayFxfyDist);
+  ptz_ba_batch* b = nullptr;
+  int32_t rc;
+  if (resid_state_ == 1) {
+    ptz_ba_problem prob;
+    if (!CovProblem(p, prob)) return false;
+    prob.factor_type = ftype;
+    prob.n_obs3d = static_cast<int32_t>(p.obs3d_cam.size());
+    if (prob.n_obs3d > 0) { prob.obs3d_uv = p.obs3d_uv.data(); prob.obs3d_xyz = p.obs3d_xyz.data(); prob.obs3d_cam = p.obs3d_cam.data(); }
+    rc = ptz_ba_batch_create(1, &prob, &opt, &b);
+    if (rc == PTZ_OK) rc = ptz_ba_batch_set_state(b, p.cam.data(), p.ray.data(), p.tlw.data());
+  }
+  else {
+    // the view's batch once more, solved from the same initial state: the bits of the solve Solve ran
+    std::vector<int32_t> cam_image(p.cam_image.begin(), p.cam_image.end());
+    ptz_rig_view view{rig_, static_cast<int32_t>(cam_image.size()), cam_image.data()};
+    std::vector<ptz_lm_summary> summ(1);
+    rc = ptz_ba_batch_create_views(1, &view, ftype, &opt, &b);
+    if (rc == PTZ_OK) rc = ptz_ba_batch_set_state_pix2ray(b, view_cam0_.data(), view_rkinv_.data());
+    if (rc == PTZ_OK) rc = ptz_ba_batch_solve(b, summ.data());
+  }
+  std::vector<double> r(n_cam), m(n_cam);
+  std::vector<int32_t> c(n_cam);
+  if (rc == PTZ_OK) rc = ptz_ba_batch_residuals(b, nullptr, nullptr, nullptr, r.data(), m.data(), c.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (b) ptz_ba_batch_destroy(b);
+  if (rc != PTZ_OK) return false;
+  rms.swap(r); max.swap(m); count.swap(c);
+  return true;
+}
+
 bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::vector<Ray>>* rays_out)
 {
   solved_packed_ = false;
+  resid_state_ = 0;
+  kept_.clear();
+  obs_cam_before_trim_.clear();
+  trim_report_ = ptz_trim_report{};
   if (!CheckValid()) return false;
   FindTracks();
   SetInitTransLocalToWorld();
@@ -415,8 +510,16 @@ bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::v
   for (int k = 0; k < 6; ++k) tlw[k] = p.tlw[k];
   const auto t_dev = std::chrono::steady_clock::now();
   disp_ = {{0.0, 0.0, 0.0}};  // disp_param_ starts at zero (:655)
-  const int32_t rc = type_ == PTZRayDistDisp ? ptz_ba_solve_disp(&prob, cam.data(), ray.data(), tlw, disp_.data(), &opt, &summary_)
-                                             : DeviceBaSolve(&prob, cam.data(), ray.data(), tlw, &opt, &summary_);  // (through the thread's DeviceBatcher, if any)
+  int32_t rc;
+  if (trim_on_) {
+    // solve / report / select / re-pack rounds (PTZRayDistDisp and shared intrinsics: PTZ_EUNSUPPORTED, reported below)
+    kept_.assign(p.obs_cam.size(), 1);
+    rc = ptz_ba_solve_trimmed(&prob, cam.data(), ray.data(), tlw, &trim_opt_, &opt, &summary_, kept_.data(), &trim_report_);
+    if (rc == PTZ_OK) ApplyTrim(ray);
+  }
+  else
+    rc = type_ == PTZRayDistDisp ? ptz_ba_solve_disp(&prob, cam.data(), ray.data(), tlw, disp_.data(), &opt, &summary_)
+                                 : DeviceBaSolve(&prob, cam.data(), ray.data(), tlw, &opt, &summary_);  // (through the thread's DeviceBatcher, if any)
   device_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dev).count();
   if (rc != PTZ_OK) {
     // not a convergence failure: the device path refused or could not run the problem.  Say so -- the reference's callers
@@ -436,6 +539,7 @@ bool PTZRayOptimizer::SolveImpl(std::vector<Camera>& cameras, std::vector<std::v
   p.ray = ray;
   for (int k = 0; k < 6; ++k) p.tlw[k] = tlw[k];
   errors_ready_ = false;
+  if (type_ != PTZRayDistDisp && !shared) resid_state_ = 1;
 
   if (summary_.termination_type != PTZ_CONVERGENCE) return false;  // :482-488
 

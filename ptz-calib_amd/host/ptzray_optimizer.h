@@ -88,6 +88,22 @@ class PTZRayOptimizer {
                     double annotation_sigma = 0.0) const;
   // the rig's projection centre C_w = -R_lw^T t_lw at the same state; false where WorldCovariance has no state
   bool WorldCentre(std::array<double, 3>& centre) const;
+  // Outlier trimming (ptz_ba_solve_trimmed, see include/ptz_calib_amd.h): Solve runs solve / report / select / re-pack rounds instead
+  // of one solve.  Off by default -- Solve is then what it is without this call.  It applies where the problem is packed on the
+  // host (2D-2D residuals with or without annotations, no shared intrinsics, not PTZRayDistDisp: Solve returns false for those); a
+  // solve over a view of a device-resident rig (UseRig) ignores it and says so once on stderr.  After a trimmed Solve packed()
+  // holds the TRIMMED problem, so Covariance / WorldCovariance describe the fit that was kept; kept() marks, per observation of the
+  // problem as it was packed, the ones still in it.  trim_px <= 0 switches trimming off again.
+  void SetTrimming(double trim_px, double k_sigma = 3.0, int max_rounds = 8);
+  const ptz_trim_report& trim_report() const { return trim_report_; }
+  const std::vector<uint8_t>& kept() const { return kept_; }
+  const std::vector<int32_t>& packed_obs_cam_before_trim() const { return obs_cam_before_trim_; }
+  // Per candidate image, in the order of packed().cam_image: rms and maximum of the unweighted 2D-2D errors |e_o| of its
+  // observations and their number, from the device's residual report (ptz_ba_batch_residuals) at the state of the last Solve (any
+  // termination type).  Works on both paths; after a solve over a view of a device-resident rig, which keeps no rays, the view's
+  // batch is built and solved once more (the same batch, the same bits) to take the report.  false: no solve yet, PTZRayDistDisp,
+  // shared intrinsics, or a device error.
+  bool ViewResiduals(std::vector<double>& rms, std::vector<double>& max, std::vector<int32_t>& count) const;
   // The tracks depend on the match table only, not on the candidate set: a caller that solves many candidate subsets of
   // one match table (PtzIncrementalOptimizer) builds them once and shares them instead of repeating FindTracks().
   void UseTracks(std::shared_ptr<const SharedTracks> tracks) { shared_tracks_ = std::move(tracks); }
@@ -106,6 +122,7 @@ class PTZRayOptimizer {
   bool CheckValid() const;
   bool SolveImpl(std::vector<Camera>& cameras, std::vector<std::vector<Ray>>* rays);
   bool SolveView(std::vector<Camera>& cameras);
+  void ApplyTrim(std::vector<double>& ray);
   void FindTracks();
   bool isCandidate(long image_id) const { return cam_ids_.count(image_id) != 0; }
   void Pack();
@@ -135,6 +152,15 @@ class PTZRayOptimizer {
   std::array<double, 3> disp_{{0, 0, 0}};  // disp_param_ (ptzray_optimizer.h: PTZRayDistDisp), refined by Solve
   ptz_lm_summary summary_{};
   bool solved_packed_ = false;  // the last Solve succeeded on the host-packed path: packed_ holds the solution (Covariance)
+  bool trim_on_ = false;
+  ptz_trim_options trim_opt_{4.0, 3.0, 8, 0};
+  ptz_trim_report trim_report_{};
+  std::vector<uint8_t> kept_;
+  std::vector<int32_t> obs_cam_before_trim_;
+  // what ViewResiduals needs of the last Solve: 0 none, 1 the packed problem and its state in packed_, 2 a rig view (its initial
+  // cameras and R^-1 K^-1)
+  int resid_state_ = 0;
+  std::vector<double> view_cam0_, view_rkinv_;
   double init_reproj_error_all_ = 0, final_reproj_error_all_ = 0;
   void ComputeErrors() const;  // unweighted 2D-2D / 2D-3D RMS of the solved state, on first use
   mutable bool errors_ready_ = true;
