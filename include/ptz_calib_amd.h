@@ -645,6 +645,106 @@ int32_t ptz_ba_solve_trimmed_batch(int32_t n, const ptz_ba_problem* problems, do
 int32_t ptz_ba_solve_trimmed(const ptz_ba_problem* p, double* cam, double* ray, double* tlw, const ptz_trim_options* trim,
                              const ptz_lm_options* opt, ptz_lm_summary* summary, uint8_t* kept, ptz_trim_report* report);
 
+/* ------------------------------------------------------------------------------------------------
+ * Residual report and outlier trimming of relocalized cameras (per query)
+ * ------------------------------------------------------------------------------------------------ */
+/* the online counterpart of the section above.  A relocalized camera comes back with one scalar, the mean reprojection error that
+ * CheckResults compares with max_reproj_error (krt_optimizer.cc:504-533); nobody sees which matches the fit rests on, and a match
+ * inside the homography gate's threshold is never judged again by the functors the LM fits.
+ *
+ * ptz_krt_residuals_batch -- the report.  Arguments as ptz_krt_covariance_batch: CSR matches, optional 2D-3D points, cam_ref, the
+ * refined cam_cur (world frame), match_mask, accepted.  The LM's own functors, evaluated once at the refined camera in the form the
+ * solve takes its final cost with (IEEE quotients), the camera moved into the local frame of cam_ref as the solve does.  Outputs,
+ * any may be NULL (all NULL: PTZ_EINVAL):
+ *   err_px [n_match]     |e_m|, the norm of the UNWEIGHTED 2-vector residual, in the caller's order, for EVERY match of the query,
+ *                        masked or not; -1.0 for a match the border guard of the distortion variants skips (krt_optimizer.cc:97-101)
+ *   err3d_px [n_point]   the same for the 2D-3D points
+ *   rms, max, median, count [n_query]   over the COUNTED matches: mask byte non-zero (all, if match_mask = NULL) and not skipped;
+ *                        sqrt(mean |e_m|^2), max |e_m|, the exact LOWER median -- element (count - 1) / 2 of the sorted errors --,
+ *                        their number.  rms, max and median are NaN with count = 0
+ *   rms3d [n_query]      over the query's points; NaN without points
+ * For a query with accepted[q] = 0 every output is left untouched and its cam_cur is not read.
+ * lanes_per_query: 16 or 64 lanes of a wave per query, anything else: by the launch size as ptz_krt_solve_batch
+ * (ptz_lm_options::krt_lanes_per_query).  A speed matter only: one reduction order per figure whatever the group (64 partial sums,
+ * partial v takes matches v, v + 64, ..; added by the butterfly v ^ 32, v ^ 16, .. v ^ 1), the median a selection by counting over
+ * the bit patterns, no floating-point atomics -- a query's bits depend on its own data only, not on its neighbours, their number,
+ * the group size or the run.
+ * PTZ_EINVAL, before any device work: n_query < 0, match_ptr[0] != 0 or decreasing offsets, NULL required arrays with non-zero
+ * extents, point_ptr without pts2d / pts3d; PTZ_EUNSUPPORTED: factor_type; n_query = 0 is PTZ_OK; PTZ_ENODEVICE without a device. */
+int32_t ptz_krt_residuals_batch(int32_t n_query, const int64_t* match_ptr, const float* uv_ref, const float* uv_cur,
+                                const int64_t* point_ptr, const float* pts2d, const double* pts3d, const double* cam_ref,
+                                const double* cam_cur /* refined, world frame */, int32_t factor_type,
+                                const uint8_t* match_mask /* [n_match] or NULL */, const int32_t* accepted /* [n_query] or NULL */,
+                                int32_t lanes_per_query, int32_t device_id, double* err_px, double* err3d_px, double* rms, double* max,
+                                double* median, int32_t* count, double* rms3d, double* device_ms /* or NULL */);
+/* The same launch on DEVICE pointers: enqueued on `hip_stream` (NULL = the default stream) of the device that owns d_cam_cur,
+ * returns without synchronising; behind ptz_krt_solve_batch_device on the same stream it takes the d_cam_cur and d_accepted that call
+ * wrote.  The CSR offsets are not validated (they live on the device).  The call keeps no scratch of its own: d_median needs
+ * d_err_px (the selection reads the errors of a query of more than 8 x lanes matches back from it), PTZ_EINVAL otherwise, as for a
+ * stream of another device than the buffers. */
+int32_t ptz_krt_residuals_batch_device(int32_t n_query, const int64_t* d_match_ptr, const float* d_uv_ref, const float* d_uv_cur,
+                                       const int64_t* d_point_ptr, const float* d_pts2d, const double* d_pts3d, const double* d_cam_ref,
+                                       const double* d_cam_cur, int32_t factor_type, const uint8_t* d_match_mask,
+                                       const int32_t* d_accepted, int32_t lanes_per_query, double* d_err_px, double* d_err3d_px,
+                                       double* d_rms, double* d_max, double* d_median, int32_t* d_count, double* d_rms3d, void* hip_stream);
+
+typedef struct ptz_krt_trim_options {
+  double trim_px;      /* 4.0 */
+  double k_sigma;      /* 3.0 */
+  int32_t max_rounds;  /* 8: solves per query at most (1 .. 64) */
+  int32_t min_keep;    /* 8: counted matches a kept set needs */
+} ptz_krt_trim_options;
+void ptz_krt_trim_options_default(ptz_krt_trim_options* o);
+/* flags of ptz_krt_trim_report, beside PTZ_TRIM_MAX_ROUNDS: matches changed sides in the round of the last solve allowed */
+#define PTZ_KRT_TRIM_MIN_KEEP 4 /* the next kept set would have counted fewer than min_keep matches: finished on the set it had */
+#define PTZ_KRT_TRIM_REJECTED 8 /* a solve of the query was not accepted under the open bound: cam_cur is left untouched */
+typedef struct ptz_krt_trim_report {
+  int32_t rounds;      /* solves of this query */
+  int32_t flags;       /* PTZ_TRIM_MAX_ROUNDS, PTZ_KRT_TRIM_* */
+  int32_t n_removed;   /* matches of the universe that the last solve's set lacks */
+  int32_t n_kept;      /* matches of the last solve's set (skipped ones included) */
+  double threshold;    /* of the last round judged; NaN if none was */
+  double rms_first;    /* rms of the report after the first solve, over the universe */
+  double rms_last;     /* ... after the last solve, over its set */
+  double median_last;
+} ptz_krt_trim_report;
+/* The trimmed solve: sigma clipping with the LM's own functors, all rounds on the device, on one stream, no host round trip.
+ * The rule (csrc/ptz_krt_trim.h).  Universe U: the query's matches whose match_mask byte is non-zero (all, if NULL; the inlier_mask
+ * of ptz_krt_solve_batch_gated as it is).  Round 0 solves on K = U from cam_cur like ptz_krt_solve_batch, with an OPEN error bound
+ * (max_reproj_error = 1e300: CheckResults' convergence and field-of-view tests apply).  After every round, for the queries still
+ * active: the report above at the round's camera, over the counted matches of K (a match the border guard skips stays in K, counts
+ * for nothing and is never rejected); t = max(trim_px, k_sigma * median / 1.1774) (k_sigma = 0: trim_px); the new set
+ * K' = { m in U : skipped, or |e_m| <= t } -- EVERY match of U is judged again, a good match that a dragged early fit pushed out
+ * comes back.  The query is finished if K' == K; if K' would count fewer than min_keep matches (PTZ_KRT_TRIM_MIN_KEEP, keeps K); if it
+ * has run max_rounds solves (PTZ_TRIM_MAX_ROUNDS, keeps K); if its solve was not accepted (PTZ_KRT_TRIM_REJECTED).  Otherwise K'
+ * is packed from the ORIGINAL arrays, order kept, and solved from the camera the previous round ended at.  A finished query is not
+ * solved again: camera and summary are those of its last solve.  2D-3D points are in every round's solve and are not trimmed.
+ * Every round runs with the lanes per query ptz_krt_solve_batch takes for the call's n_query (krt_lanes_per_query honoured).
+ * At the end accepted[q] = (last solve accepted under the open bound) && sqrt(2) * sqrt(2 * final_cost / num_residuals) <
+ * max_reproj_error; cam_cur is written only for accepted queries.  summaries [n]: of each query's last solve; kept [n_match] (or
+ * NULL): 1 for every match of the last solve's set; report [n] (or NULL); trim = NULL: the defaults.
+ * Contract: a query's result is the bits of the manual loop over ptz_krt_solve_batch[_2d3d] with the open bound,
+ * ptz_krt_residuals_batch, the rule and a compaction of the caller's arrays -- whatever the other queries of the call do.
+ * PTZ_EINVAL, before any device work: as ptz_krt_residuals_batch, NULL summaries / accepted, trim_px not positive and finite, k_sigma
+ * negative or not finite, max_rounds outside 1 .. 64, min_keep negative. */
+int32_t ptz_krt_solve_batch_trimmed(int32_t n_query, const int64_t* match_ptr, const float* uv_ref, const float* uv_cur,
+                                    const int64_t* point_ptr, const float* pts2d, const double* pts3d, const double* cam_ref,
+                                    double* cam_cur, int32_t factor_type, double max_reproj_error,
+                                    const uint8_t* match_mask /* [n_match] or NULL */, const ptz_krt_trim_options* trim,
+                                    const ptz_lm_options* opt, ptz_lm_summary* summaries, int32_t* accepted, uint8_t* kept,
+                                    ptz_krt_trim_report* report, double* device_ms /* or NULL */);
+/* The same on DEVICE pointers: max_rounds rounds are enqueued on `hip_stream` and the call returns without synchronising; a round
+ * in which no query is active costs its launches' early returns.  n_match: the extent of the match arrays (the offsets live on the
+ * device and are not validated).  d_workspace: 256-byte aligned device memory of at least
+ * ptz_krt_trim_workspace_bytes(n_query, n_match) bytes, the caller's until the stream has run the call. */
+int64_t ptz_krt_trim_workspace_bytes(int32_t n_query, int64_t n_match);
+int32_t ptz_krt_solve_batch_trimmed_device(int32_t n_query, int64_t n_match, const int64_t* d_match_ptr, const float* d_uv_ref,
+                                           const float* d_uv_cur, const int64_t* d_point_ptr, const float* d_pts2d, const double* d_pts3d,
+                                           const double* d_cam_ref, double* d_cam_cur, int32_t factor_type, double max_reproj_error,
+                                           const uint8_t* d_match_mask, const ptz_krt_trim_options* trim, const ptz_lm_options* opt,
+                                           ptz_lm_summary* d_summaries, int32_t* d_accepted, uint8_t* d_kept,
+                                           ptz_krt_trim_report* d_report, void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,9 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_free_dim", "ptz_krt_covariance_batch", "ptz_krt_covariance_batch_device", "ptz_ba_cov_dim",
            "ptz_ba_batch_covariance", "ptz_ba_covariance", "ptz_ba_geo_cov_dim", "ptz_ba_batch_covariance_georef",
            "ptz_ba_covariance_georef", "ptz_ba_batch_residuals", "ptz_ba_batch_trim_select", "ptz_ba_problem_trim",
-           "ptz_trim_options_default", "ptz_ba_solve_trimmed_batch", "ptz_ba_solve_trimmed"]
+           "ptz_trim_options_default", "ptz_ba_solve_trimmed_batch", "ptz_ba_solve_trimmed", "ptz_krt_residuals_batch",
+           "ptz_krt_residuals_batch_device", "ptz_krt_trim_options_default", "ptz_krt_trim_workspace_bytes", "ptz_krt_solve_batch_trimmed",
+           "ptz_krt_solve_batch_trimmed_device"]
 
 
 class PtzError(RuntimeError):
@@ -84,6 +86,22 @@ class TrimReport(C.Structure):
 
 TRIM_ENOOBS, TRIM_MAX_ROUNDS = 1, 2
 
+
+class KrtTrimOptions(C.Structure):
+    _fields_ = [("trim_px", C.c_double), ("k_sigma", C.c_double), ("max_rounds", C.c_int32), ("min_keep", C.c_int32)]
+
+
+class KrtTrimReport(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("flags", C.c_int32), ("n_removed", C.c_int32), ("n_kept", C.c_int32),
+                ("threshold", C.c_double), ("rms_first", C.c_double), ("rms_last", C.c_double), ("median_last", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+KRT_TRIM_MIN_KEEP, KRT_TRIM_REJECTED = 4, 8
+KRT_OPEN_BOUND = 1e300  # the error bound of the trimmed solve's rounds
+
 _lib = None
 
 
@@ -100,6 +118,8 @@ def lib():
         _lib.ptz_krt_free_dim.restype = C.c_int32
         _lib.ptz_ba_cov_dim.restype = C.c_int32
         _lib.ptz_ba_geo_cov_dim.restype = C.c_int32
+        _lib.ptz_krt_trim_workspace_bytes.restype = C.c_int64
+        _lib.ptz_krt_trim_workspace_bytes.argtypes = [C.c_int32, C.c_int64]
     return _lib
 
 
@@ -914,6 +934,116 @@ def krt_covariance_batch_device(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_cam_
                                                  _dptr(d_match_mask), _dptr(d_accepted), C.c_double(pixel_sigma), _dptr(d_cov),
                                                  _dptr(d_sigma0), _dptr(d_status), C.c_void_p(stream) if stream else None),
            "ptz_krt_covariance_batch_device")
+
+
+def _krt_batch_arrays(batch):
+    """the CSR arrays of a RelocBatch-like object: (ptr, uv_ref, uv_cur, cam_ref, point_ptr, pts2d, pts3d), the last three None
+    without 2D-3D constraints"""
+    ptr = np.ascontiguousarray(batch.match_ptr, dtype=np.int64)
+    uvr = np.ascontiguousarray(batch.uv_ref, dtype=np.float32)
+    uvc = np.ascontiguousarray(batch.uv_cur, dtype=np.float32)
+    cref = np.ascontiguousarray(batch.cam_ref, dtype=np.float64)
+    pp = p2 = p3 = None
+    if getattr(batch, "point_ptr", None) is not None:
+        pp = np.ascontiguousarray(batch.point_ptr, dtype=np.int64)
+        p2 = np.ascontiguousarray(batch.pts2d, dtype=np.float32)
+        p3 = np.ascontiguousarray(batch.pts3d, dtype=np.float64)
+    return ptr, uvr, uvc, cref, pp, p2, p3
+
+
+def krt_residuals_batch(batch, cam_cur, match_mask=None, accepted=None, lanes_per_query=0, device_id=0, out=None):
+    """ptz_krt_residuals_batch: the residual report of the refined cameras cam_cur [n, 15] (world frame) of the queries of `batch`.
+    Returns a dict: err_px [n_match] (-1 where the border guard skips), err3d_px [n_point] or None, rms / max / median / rms3d [n],
+    count [n], device_ms.  Over the matches of match_mask [n_match] uint8 (all if None); entries of queries with accepted[q] = 0
+    keep what `out` (a dict of arrays by the same names) held, NaN / -1 (count) if not given."""
+    n = batch.n_query
+    ptr, uvr, uvc, cref, pp, p2, p3 = _krt_batch_arrays(batch)
+    ccur = np.ascontiguousarray(cam_cur, dtype=np.float64)
+    mk = None if match_mask is None else np.ascontiguousarray(match_mask, dtype=np.uint8)
+    ac = None if accepted is None else np.ascontiguousarray(accepted, dtype=np.int32)
+    if mk is not None and len(mk) != int(ptr[-1]):
+        raise ValueError("match_mask must have one byte per match")
+    if ac is not None and len(ac) != n:
+        raise ValueError("accepted must have one entry per query")
+    out = dict(out or {})
+    res = {}
+    for key, size in (("err_px", int(ptr[-1])), ("rms", n), ("max", n), ("median", n), ("rms3d", n)):
+        res[key] = np.full(size, np.nan) if key not in out else np.ascontiguousarray(out[key], dtype=np.float64)
+    res["err3d_px"] = None
+    if pp is not None:
+        res["err3d_px"] = np.full(int(pp[-1]), np.nan) if "err3d_px" not in out else np.ascontiguousarray(out["err3d_px"], dtype=np.float64)
+    res["count"] = np.full(n, -1, dtype=np.int32) if "count" not in out else np.ascontiguousarray(out["count"], dtype=np.int32)
+    ms = C.c_double()
+    _check(lib().ptz_krt_residuals_batch(n, _p(ptr), _p(uvr), _p(uvc), _p(pp), _p(p2), _p(p3), _p(cref), _p(ccur), int(batch.factor_type),
+                                         _p(mk), _p(ac), int(lanes_per_query), int(device_id), _p(res["err_px"]), _p(res["err3d_px"]),
+                                         _p(res["rms"]), _p(res["max"]), _p(res["median"]), _p(res["count"]), _p(res["rms3d"]),
+                                         C.byref(ms)), "ptz_krt_residuals_batch")
+    res["device_ms"] = ms.value
+    return res
+
+
+def krt_residuals_batch_device(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_cam_ref, d_cam_cur, factor_type=0, d_point_ptr=None, d_pts2d=None,
+                               d_pts3d=None, d_match_mask=None, d_accepted=None, lanes_per_query=0, d_err_px=None, d_err3d_px=None,
+                               d_rms=None, d_max=None, d_median=None, d_count=None, d_rms3d=None, stream=None):
+    """ptz_krt_residuals_batch_device: every d_* is a device buffer (torch tensor or integer address); enqueues on `stream` (integer
+    hipStream_t handle, None = default stream) and returns without synchronising.  d_median needs d_err_px."""
+    _check(lib().ptz_krt_residuals_batch_device(int(n_query), _dptr(d_match_ptr), _dptr(d_uv_ref), _dptr(d_uv_cur), _dptr(d_point_ptr),
+                                                _dptr(d_pts2d), _dptr(d_pts3d), _dptr(d_cam_ref), _dptr(d_cam_cur), int(factor_type),
+                                                _dptr(d_match_mask), _dptr(d_accepted), int(lanes_per_query), _dptr(d_err_px),
+                                                _dptr(d_err3d_px), _dptr(d_rms), _dptr(d_max), _dptr(d_median), _dptr(d_count),
+                                                _dptr(d_rms3d), C.c_void_p(stream) if stream else None),
+           "ptz_krt_residuals_batch_device")
+
+
+def krt_trim_options(**kw) -> KrtTrimOptions:
+    t = KrtTrimOptions()
+    lib().ptz_krt_trim_options_default(C.byref(t))
+    for k, v in kw.items():
+        setattr(t, k, v)
+    return t
+
+
+def krt_solve_batch_trimmed(batch, max_reproj_error=100.0, match_mask=None, trim_px=4.0, k_sigma=3.0, max_rounds=8, min_keep=8, **opt):
+    """ptz_krt_solve_batch_trimmed: krt_solve_batch with the sigma-clipping loop on the device (solve, report, rule, compaction, solve
+    again; include/ptz_calib_amd.h).  match_mask [n_match] uint8: the universe (all matches if None).
+    Returns (cam_world [n, 15], summaries, accepted [n], kept [n_match] uint8, reports (list of dicts), device_ms)."""
+    o = default_options(**opt)
+    t = krt_trim_options(trim_px=trim_px, k_sigma=k_sigma, max_rounds=max_rounds, min_keep=min_keep)
+    n = batch.n_query
+    ptr, uvr, uvc, cref, pp, p2, p3 = _krt_batch_arrays(batch)
+    ccur = np.array(batch.cam_init, dtype=np.float64, order="C").copy()
+    mk = None if match_mask is None else np.ascontiguousarray(match_mask, dtype=np.uint8)
+    if mk is not None and len(mk) != int(ptr[-1]):
+        raise ValueError("match_mask must have one byte per match")
+    summ = (LmSummary * n)()
+    rep = (KrtTrimReport * n)()
+    acc = np.zeros(n, dtype=np.int32)
+    kept = np.zeros(int(ptr[-1]), dtype=np.uint8)
+    ms = C.c_double()
+    _check(lib().ptz_krt_solve_batch_trimmed(n, _p(ptr), _p(uvr), _p(uvc), _p(pp), _p(p2), _p(p3), _p(cref), _p(ccur), int(batch.factor_type),
+                                             C.c_double(max_reproj_error), _p(mk), C.byref(t), C.byref(o), summ, _p(acc), _p(kept), rep,
+                                             C.byref(ms)), "ptz_krt_solve_batch_trimmed")
+    return ccur, [s.as_dict() for s in summ], acc, kept, [r.as_dict() for r in rep], ms.value
+
+
+def krt_trim_workspace_bytes(n_query, n_match) -> int:
+    return int(lib().ptz_krt_trim_workspace_bytes(int(n_query), int(n_match)))
+
+
+def krt_solve_batch_trimmed_device(n_query, n_match, d_match_ptr, d_uv_ref, d_uv_cur, d_cam_ref, d_cam_cur, d_summaries, d_accepted,
+                                   d_workspace, workspace_bytes, factor_type=0, max_reproj_error=100.0, d_point_ptr=None, d_pts2d=None,
+                                   d_pts3d=None, d_match_mask=None, d_kept=None, d_report=None, trim=None, stream=None, **opt):
+    """ptz_krt_solve_batch_trimmed_device: every d_* is a device buffer (torch tensor or integer address); d_workspace needs
+    krt_trim_workspace_bytes(n_query, n_match) bytes, d_report n_query * sizeof(KrtTrimReport).  Enqueues every round on `stream`
+    and returns without synchronising."""
+    o = default_options(**opt)
+    t = trim if trim is not None else krt_trim_options()
+    _check(lib().ptz_krt_solve_batch_trimmed_device(int(n_query), C.c_int64(int(n_match)), _dptr(d_match_ptr), _dptr(d_uv_ref), _dptr(d_uv_cur),
+                                                    _dptr(d_point_ptr), _dptr(d_pts2d), _dptr(d_pts3d), _dptr(d_cam_ref), _dptr(d_cam_cur),
+                                                    int(factor_type), C.c_double(max_reproj_error), _dptr(d_match_mask), C.byref(t),
+                                                    C.byref(o), _dptr(d_summaries), _dptr(d_accepted), _dptr(d_kept), _dptr(d_report),
+                                                    _dptr(d_workspace), C.c_int64(int(workspace_bytes)),
+                                                    C.c_void_p(stream) if stream else None), "ptz_krt_solve_batch_trimmed_device")
 
 
 def mfma_f64_peak(device_id=0):

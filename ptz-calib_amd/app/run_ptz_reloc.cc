@@ -4,6 +4,9 @@
 // --inlier_matches (not in the reference) solves on the RANSAC inliers of each query's matches: ptz_krt_solve_batch_gated.
 // --uncertainty (not in the reference) adds the standard deviations of focal length and rotation to every registered image's
 // record, from ONE ptz_krt_covariance_batch call over all test images.
+// --trim_px <px> (not in the reference; with --trim_sigma, --trim_rounds) solves every test image with the outlier-trimming loop of
+// ptz_krt_solve_batch_trimmed: with --inlier_matches the gate's inliers are the loop's universe, with --uncertainty the covariance is
+// taken over the matches the last solve kept, and every record gains rms_px, n_matches, n_removed, trim_rounds.
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -48,11 +51,28 @@ int main(int argc, char** argv)
                                    "is still the one with the most raw matches");
   parser.Add("min_inliers", '\0', "With --inlier_matches: inliers a pair needs to keep any match (default 6, at least 4)", false);
   parser.AddFlag(ptzapp::kUncertaintyFlag, ptzapp::kUncertaintyHelp);
+  parser.Add("trim_px", '\0', "Trim outlier matches: solve, measure every match with the fitted camera, drop those above "
+                              "max(trim_px, trim_sigma * median / 1.1774) pixels, solve again, until nothing changes", false);
+  parser.Add("trim_sigma", '\0', "With --trim_px: the threshold's multiple of the robust pixel noise (default 3, 0: trim_px alone)", false);
+  parser.Add("trim_rounds", '\0', "With --trim_px: solves per test image at most (default 8)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
     fprintf(stderr, "--min_inliers must not be negative\n");
     return 1;
+  }
+
+  const bool trimming = parser.Exist("trim_px");
+  ptz_krt_trim_options trim;
+  ptz_krt_trim_options_default(&trim);
+  if (trimming) {
+    trim.trim_px = atof(parser.Get("trim_px").c_str());
+    if (parser.Exist("trim_sigma")) trim.k_sigma = atof(parser.Get("trim_sigma").c_str());
+    if (parser.Exist("trim_rounds")) trim.max_rounds = atoi(parser.Get("trim_rounds").c_str());
+    if (!(trim.trim_px > 0) || !(trim.k_sigma >= 0) || trim.max_rounds < 1 || trim.max_rounds > 64) {
+      fprintf(stderr, "--trim_px must be positive, --trim_sigma not negative, --trim_rounds in 1 .. 64\n");
+      return 1;
+    }
   }
 
   std::vector<std::string> ref_fnames, test_fnames;
@@ -113,6 +133,8 @@ int main(int argc, char** argv)
   const bool uncertainty = parser.Exist(ptzapp::kUncertaintyFlag);
   struct Sigma { bool ok = false; double f = 0, rot_deg[3] = {0, 0, 0}, s0 = 0; };
   std::vector<Sigma> sigmas(test_fnames.size());
+  struct Trimmed { double rms = 0; int n_matches = 0, n_removed = 0, rounds = 0; };
+  std::vector<Trimmed> trimmed(test_fnames.size());
   if (!query_image.empty()) {
     static const int MAX_ITER = 200;
     static const double MAX_REPROJ_ERROR = 100.0;
@@ -126,12 +148,44 @@ int main(int argc, char** argv)
     static const double RANSAC_THRESH = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
     const bool gated = parser.Exist("inlier_matches");
     std::vector<int32_t> n_inliers(nq, 0);
-    std::vector<uint8_t> inlier_mask(gated && uncertainty ? uv_ref.size() / 2 : 0);  // the covariance is over the matches a query kept
-    const int32_t rc = gated ? ptz_krt_solve_batch_gated(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
-                                                       MAX_REPROJ_ERROR, RANSAC_THRESH, min_inliers, &opt, summaries.data(), accepted.data(),
-                                                       n_inliers.data(), inlier_mask.empty() ? nullptr : inlier_mask.data(), nullptr, nullptr)
-                           : ptz_krt_solve_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
-                                                 MAX_REPROJ_ERROR, &opt, summaries.data(), accepted.data(), nullptr);
+    std::vector<uint8_t> inlier_mask((gated && uncertainty) || trimming ? uv_ref.size() / 2 : 0);  // the covariance is over the matches a query kept
+    std::vector<ptz_krt_trim_report> reports(trimming ? nq : 0);
+    int32_t rc = PTZ_OK;
+    if (trimming) {
+      // the gate first: its kept set is the universe of the loop (a query that does not pass has an empty one)
+      std::vector<uint8_t> universe;
+      if (gated) {
+        std::vector<double> H(9 * static_cast<size_t>(nq));
+        std::vector<int32_t> found(nq, 0);
+        universe.assign(uv_ref.size() / 2, 0);
+        rc = ptz_homography_ransac_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), RANSAC_THRESH, opt.device_id, H.data(), found.data(),
+                                         universe.data(), nullptr);
+        for (int32_t q = 0; q < nq && rc == PTZ_OK; ++q) {
+          int32_t ones = 0;
+          for (int64_t m = match_ptr[q]; m < match_ptr[q + 1]; ++m) ones += found[q] == 1 && universe[m] != 0;
+          n_inliers[q] = (found[q] == 1 && ones >= (min_inliers > 4 ? min_inliers : 4)) ? ones : 0;
+          if (n_inliers[q] == 0)
+            for (int64_t m = match_ptr[q]; m < match_ptr[q + 1]; ++m) universe[m] = 0;
+        }
+      }
+      if (rc == PTZ_OK)
+        rc = ptz_krt_solve_batch_trimmed(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), nullptr, nullptr, nullptr, cam_ref.data(), cam_cur.data(),
+                                         type, MAX_REPROJ_ERROR, gated ? universe.data() : nullptr, &trim, &opt, summaries.data(), accepted.data(),
+                                         inlier_mask.data(), reports.data(), nullptr);
+      for (int32_t q = 0; q < nq && rc == PTZ_OK; ++q) {
+        Trimmed& t = trimmed[query_image[q]];
+        t.rms = reports[q].rms_last;
+        t.n_matches = static_cast<int>(match_ptr[q + 1] - match_ptr[q]);
+        t.n_removed = t.n_matches - reports[q].n_kept;
+        t.rounds = reports[q].rounds;
+      }
+    }
+    else
+      rc = gated ? ptz_krt_solve_batch_gated(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
+                                             MAX_REPROJ_ERROR, RANSAC_THRESH, min_inliers, &opt, summaries.data(), accepted.data(),
+                                             n_inliers.data(), inlier_mask.empty() ? nullptr : inlier_mask.data(), nullptr, nullptr)
+               : ptz_krt_solve_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), cam_ref.data(), cam_cur.data(), type,
+                                     MAX_REPROJ_ERROR, &opt, summaries.data(), accepted.data(), nullptr);
     if (rc != PTZ_OK) {
       fprintf(stderr, "ptz_krt_solve_batch failed with status %d (no usable HIP device?)\n", rc);
       return -1;
@@ -151,7 +205,7 @@ int main(int argc, char** argv)
       std::vector<double> cov(static_cast<size_t>(nf) * nf * nq, 0.0), sigma0(nq, 0.0);
       std::vector<int32_t> status(nq, -1);
       const int32_t rc_cov = ptz_krt_covariance_batch(nq, match_ptr.data(), uv_ref.data(), uv_cur.data(), nullptr, nullptr, nullptr, cam_ref.data(),
-                                                      cam_cur.data(), type, gated ? inlier_mask.data() : nullptr, accepted.data(), 0.0,
+                                                      cam_cur.data(), type, (gated || trimming) ? inlier_mask.data() : nullptr, accepted.data(), 0.0,
                                                       opt.device_id, cov.data(), sigma0.data(), status.data(), nullptr);
       if (rc_cov != PTZ_OK) {
         fprintf(stderr, "ptz_krt_covariance_batch failed with status %d\n", rc_cov);
@@ -176,8 +230,8 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty) {
-    // the three keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
+  if (uncertainty || trimming) {
+    // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
     {
@@ -191,11 +245,18 @@ int main(int argc, char** argv)
     }
     Json& cams = all["cameras"];
     for (size_t i = 0; i < test_fnames.size(); ++i) {
-      if (!success_ids.count(static_cast<long>(i)) || !sigmas[i].ok) continue;
+      if (!success_ids.count(static_cast<long>(i))) continue;
       std::string rootname, ext;
       SplitExt(test_fnames[i], &rootname, &ext);
       if (!cams.contains(rootname)) continue;
       Json& j = cams[rootname];
+      if (trimming) {
+        j["rms_px"] = Json::Float(trimmed[i].rms);
+        j["n_matches"] = Json::Int(trimmed[i].n_matches);
+        j["n_removed"] = Json::Int(trimmed[i].n_removed);
+        j["trim_rounds"] = Json::Int(trimmed[i].rounds);
+      }
+      if (!uncertainty || !sigmas[i].ok) continue;
       j["sigma_f"] = Json::Float(sigmas[i].f);
       j["sigma_rot_deg"] = Json::FloatArray({sigmas[i].rot_deg[0], sigmas[i].rot_deg[1], sigmas[i].rot_deg[2]});
       j["sigma0"] = Json::Float(sigmas[i].s0);

@@ -23,6 +23,7 @@
 
 #include "ptz_common.h"
 #include "ptz_homography.h"
+#include "ptz_gate_compact.h"
 #include "ptz_pool.h"
 
 namespace ptz {
@@ -215,11 +216,13 @@ __global__ void k_gate_prepare(int n_pair, const int64_t* __restrict__ ptr, int3
 // kept matches per pair: the ones of its mask if the pair has a model and at least `need` of them, else none.  found decides
 // first: the mask bytes of a pair without a model are whatever an earlier run left there.
 __global__ __launch_bounds__(GATE_WG) void k_gate_count(int n_pair, const int64_t* __restrict__ ptr, const int32_t* __restrict__ found,
-                                                        const uint8_t* __restrict__ mask, int32_t need, int32_t* __restrict__ cnt)
+                                                        const uint8_t* __restrict__ mask, int32_t need, int32_t* __restrict__ cnt,
+                                                        const int32_t* __restrict__ live)
 {
   const int p = blockIdx.x * (GATE_WG / WAVE) + threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
   if (p >= n_pair) return;
+  if (live && *live == 0) return;  // (ptz_gate_compact.h: no pair has work, nothing is read afterwards)
   int c = 0;
   if (found[p] == 1) {
     const int64_t base = ptr[p];
@@ -234,10 +237,12 @@ __global__ __launch_bounds__(GATE_WG) void k_gate_count(int n_pair, const int64_
 
 // out_ptr = exclusive scan of cnt, out_ptr[n_pair] = the total.  One workgroup walks the counts 1024 at a time with a running
 // carry: a shuffle scan inside each wave, the sixteen wave totals through LDS.
-__global__ __launch_bounds__(SCAN_WG) void k_gate_scan(int n_pair, const int32_t* __restrict__ cnt, int64_t* __restrict__ out_ptr)
+__global__ __launch_bounds__(SCAN_WG) void k_gate_scan(int n_pair, const int32_t* __restrict__ cnt, int64_t* __restrict__ out_ptr,
+                                                       const int32_t* __restrict__ live)
 {
   __shared__ long long s_wave[SCAN_WG / WAVE];
   __shared__ long long s_carry;
+  if (live && *live == 0) return;  // (the whole workgroup: one value)
   const int t = threadIdx.x, lane = t % WAVE, w = t / WAVE;
   if (t == 0) s_carry = 0;
   __syncthreads();
@@ -267,11 +272,11 @@ __global__ __launch_bounds__(GATE_WG) void k_gate_scatter(int n_pair, const int6
                                                           const float2* __restrict__ uv_b, const uint8_t* __restrict__ mask,
                                                           const int32_t* __restrict__ cnt, const int64_t* __restrict__ out_ptr,
                                                           float2* __restrict__ out_a, float2* __restrict__ out_b,
-                                                          int32_t* __restrict__ out_index)
+                                                          int32_t* __restrict__ out_index, const int32_t* __restrict__ live)
 {
   const int p = blockIdx.x * (GATE_WG / WAVE) + threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
-  if (p >= n_pair || cnt[p] == 0) return;
+  if (p >= n_pair || (live && *live == 0) || cnt[p] == 0) return;
   const int64_t base = ptr[p];
   const int n = static_cast<int>(ptr[p + 1] - base);
   int64_t o = out_ptr[p];
@@ -289,6 +294,24 @@ __global__ __launch_bounds__(GATE_WG) void k_gate_scatter(int n_pair, const int6
   }
 }
 
+}  // namespace
+
+// ptz_gate_compact.h: kept counts, scan, scatter of a byte mask over a CSR, on one stream
+void enqueue_compact(int n_pair, const int64_t* d_ptr, const int32_t* d_found, const uint8_t* d_mask, int32_t need, int32_t* d_cnt,
+                     int64_t* d_out_ptr, const float2* d_a, const float2* d_b, float2* d_out_a, float2* d_out_b, int32_t* d_out_index,
+                     hipStream_t st, const int32_t* d_live)
+{
+  const int per = GATE_WG / WAVE;
+  if (n_pair > 0)
+    hipLaunchKernelGGL(k_gate_count, dim3((n_pair + per - 1) / per), dim3(GATE_WG), 0, st, n_pair, d_ptr, d_found, d_mask, need, d_cnt, d_live);
+  hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(SCAN_WG), 0, st, n_pair, (const int32_t*)d_cnt, d_out_ptr, d_live);
+  if (n_pair > 0)
+    hipLaunchKernelGGL(k_gate_scatter, dim3((n_pair + per - 1) / per), dim3(GATE_WG), 0, st, n_pair, d_ptr, d_a, d_b, d_mask, (const int32_t*)d_cnt,
+                       (const int64_t*)d_out_ptr, d_out_a, d_out_b, d_out_index, d_live);
+}
+
+namespace {
+
 // The three stages on one stream, device pointers throughout: estimator (d_order = nullptr: pair order), kept counts, scan,
 // scatter.  d_found of the pairs the estimator skips (k_gate_prepare's -1) is already written.
 void enqueue_gate(int n_pair, const int64_t* d_ptr, const int32_t* d_order, const int64_t* d_boff, const int32_t* d_tab, const float* d_a,
@@ -296,20 +319,11 @@ void enqueue_gate(int n_pair, const int64_t* d_ptr, const int32_t* d_order, cons
                   uint8_t* d_mask, int32_t* d_inl, int32_t* d_cnt, int64_t* d_out_ptr, float* d_out_a, float* d_out_b,
                   int32_t* d_out_index, hipStream_t st)
 {
-  if (n_pair > 0) {
-    const int per = GATE_WG / WAVE;
+  if (n_pair > 0)
     hipLaunchKernelGGL(k_homography_ransac, dim3(n_pair), dim3(HB), 0, st, d_ptr, d_order, d_a, d_b, thr * thr, d_boff, d_tab, d_H,
                        d_found, d_mask, d_inl, max_n, max_matches);
-    hipLaunchKernelGGL(k_gate_count, dim3((n_pair + per - 1) / per), dim3(GATE_WG), 0, st, n_pair, d_ptr, (const int32_t*)d_found,
-                       (const uint8_t*)d_mask, std::max(min_inliers, 4), d_cnt);
-  }
-  hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(SCAN_WG), 0, st, n_pair, (const int32_t*)d_cnt, d_out_ptr);
-  if (n_pair > 0) {
-    const int per = GATE_WG / WAVE;
-    hipLaunchKernelGGL(k_gate_scatter, dim3((n_pair + per - 1) / per), dim3(GATE_WG), 0, st, n_pair, d_ptr, (const float2*)d_a,
-                       (const float2*)d_b, (const uint8_t*)d_mask, (const int32_t*)d_cnt, (const int64_t*)d_out_ptr, (float2*)d_out_a,
-                       (float2*)d_out_b, d_out_index);
-  }
+  enqueue_compact(n_pair, d_ptr, (const int32_t*)d_found, (const uint8_t*)d_mask, std::max(min_inliers, 4), d_cnt, d_out_ptr,
+                  (const float2*)d_a, (const float2*)d_b, (float2*)d_out_a, (float2*)d_out_b, d_out_index, st);
 }
 
 // host side of the entries that read the offsets: the adaptive bound per distinct pair size (>= 5) and the launch order

@@ -48,13 +48,14 @@ __global__ __launch_bounds__(256, (KTYPE & 1) ? PTZ_KRT_OCC_DIST : PTZ_KRT_OCC_P
                                              const float2* __restrict__ pt_uv, const double* __restrict__ pt_xyz,
                                              const double* __restrict__ cam_ref, double* __restrict__ cam_cur, KrtOpt o,
                                              ptz_lm_summary* __restrict__ summ, int* __restrict__ accepted,
-                                             const long long* __restrict__ cur_delta)
+                                             const long long* __restrict__ cur_delta, const int* __restrict__ active)
 {
   constexpr int NF = KrtDims<KTYPE>::NF;
   constexpr int NH = NF * (NF + 1) / 2;
   constexpr int QPB = 256 / G, KRT_CACHE = KrtCache<G>::N;  // queries per workgroup
   const int q = blockIdx.x * QPB + (int)threadIdx.x / G;
   if (q >= n_query) return;
+  if (active && active[q] == 0) return;  // a finished query of the trimmed solve: nothing of it is read or written (whole groups leave)
   const int lane = threadIdx.x % G;
   // cur_delta = nullptr: the queries' matches one after the other (CSR offsets).  Otherwise (ptz_krt_solve_attempts: matches of
   // resident tables) match_ptr holds a [begin, end) PAIR per query, relative to uv_ref, and the query's current-image pixels
@@ -381,7 +382,7 @@ KrtOpt make_krt_opt(const ptz_lm_options& o, double max_reproj_error)
 // lanes per query of a launch of n_query queries (see k_krt): ptz_lm_options::krt_lanes_per_query, else PTZ_KRT_GROUP, else by launch size
 // (the throughput form only once the launch fills the chip -- 256 compute units x 8 waves x 4 queries: below that a launch
 // lasts as long as its slowest query, which sixteen lanes make four times slower)
-inline int krt_group_size(int n_query, int requested)
+inline int group_size(int n_query, int requested)
 {
   if (requested == 16 || requested == 64) return requested;
   if (const char* e = getenv("PTZ_KRT_GROUP")) { const int g = atoi(e); if (g == 16 || g == 64) return g; }
@@ -391,18 +392,18 @@ inline int krt_group_size(int n_query, int requested)
 // one launch over device-resident queries (all pointers are device pointers; d_pptr = nullptr: no 2D-3D constraints)
 void launch_krt(int n_query, const long long* d_ptr, const float2* d_ref, const float2* d_cur, const long long* d_pptr,
                 const float2* d_puv, const double* d_pxyz, const double* d_cref, double* d_ccur, int factor_type, const KrtOpt& ko,
-                ptz_lm_summary* d_sum, int* d_acc, hipStream_t st, const long long* d_delta = nullptr)
+                ptz_lm_summary* d_sum, int* d_acc, hipStream_t st, const long long* d_delta = nullptr, const int* d_active = nullptr)
 {
-  const int G = krt_group_size(n_query, ko.lanes_per_query);
+  const int G = group_size(n_query, ko.lanes_per_query);
   const int qpb = 256 / G;
   const dim3 grid((n_query + qpb - 1) / qpb), block(256);
   const bool p3 = d_pptr != nullptr;
 #define PTZ_KRT_LAUNCH(T, P)                                                                                                   \
   do {                                                                                                                         \
     if (G == 16) hipLaunchKernelGGL((k_krt<T, P, 16>), grid, block, 0, st, n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, \
-                                    d_cref, d_ccur, ko, d_sum, d_acc, d_delta);                                                \
+                                    d_cref, d_ccur, ko, d_sum, d_acc, d_delta, d_active);                                      \
     else hipLaunchKernelGGL((k_krt<T, P, 64>), grid, block, 0, st, n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, d_cref, \
-                            d_ccur, ko, d_sum, d_acc, d_delta);                                                                \
+                            d_ccur, ko, d_sum, d_acc, d_delta, d_active);                                                      \
   } while (0)
   switch (factor_type * 2 + (p3 ? 1 : 0)) {
     case 0: PTZ_KRT_LAUNCH(0, false); break;
@@ -418,6 +419,20 @@ void launch_krt(int n_query, const long long* d_ptr, const float2* d_ref, const 
 }
 
 }  // namespace
+
+int krt_group_size(int n_query, int requested) { return group_size(n_query, requested); }
+
+void krt_enqueue(int n_query, const long long* d_match_ptr, const float2* d_uv_ref, const float2* d_uv_cur, const long long* d_point_ptr,
+                 const float2* d_pts2d, const double* d_pts3d, const double* d_cam_ref, double* d_cam_cur, int factor_type,
+                 const ptz_lm_options& o, double max_reproj_error, int lanes, ptz_lm_summary* d_summaries, int* d_accepted,
+                 const int* d_active, hipStream_t st)
+{
+  KrtOpt ko = make_krt_opt(o, max_reproj_error);
+  ko.lanes_per_query = lanes;
+  launch_krt(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur, factor_type, ko, d_summaries,
+             d_accepted, st, nullptr, d_active);
+}
+
 }  // namespace ptz
 
 using namespace ptz;

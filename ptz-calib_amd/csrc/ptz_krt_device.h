@@ -1,4 +1,5 @@
-// ptz_krt_device.h -- device helpers shared by the single-view kernels: k_krt (ptz_krt.hip) and k_krt_cov (ptz_krt_cov.hip).
+// ptz_krt_device.h -- device helpers shared by the single-view kernels: k_krt (ptz_krt.hip), k_krt_cov (ptz_krt_cov.hip) and the
+// residual report / trimming step (ptz_krt_resid.hip); and the host-side launch of k_krt those files share.
 #pragma once
 
 #include "ptz_common.h"
@@ -99,5 +100,26 @@ template <int G> __device__ __forceinline__ double group_sum(double v)
   v += lane_xor_dpp<1>(v);
   return v;
 }
+template <int G> __device__ __forceinline__ double group_max(double v)  // (the same butterfly)
+{
+  static_assert(G == 64 || G == 16, "a wave or a DPP row of lanes per query");
+  if (G == 64) return wave_max(v);
+  v = fmax(v, lane_xor_dpp<8>(v));
+  v = fmax(v, lane_xor_dpp<4>(v));
+  v = fmax(v, lane_xor_dpp<2>(v));
+  v = fmax(v, lane_xor_dpp<1>(v));
+  return v;
+}
+
+// ---- host side: the one launch path of k_krt (ptz_krt.hip) ---------------------------------------------------------------------
+// lanes per query of a launch of n_query queries: `requested` (ptz_lm_options::krt_lanes_per_query) if 16 or 64, else PTZ_KRT_GROUP,
+// else by launch size
+int krt_group_size(int n_query, int requested);
+// k_krt over device-resident queries on `st` (d_point_ptr = nullptr: no 2D-3D constraints).  lanes: the group size, 16 or 64.
+// d_active (nullable): queries whose entry is 0 are left alone -- camera, summary and accepted as they were.
+void krt_enqueue(int n_query, const long long* d_match_ptr, const float2* d_uv_ref, const float2* d_uv_cur, const long long* d_point_ptr,
+                 const float2* d_pts2d, const double* d_pts3d, const double* d_cam_ref, double* d_cam_cur, int factor_type,
+                 const ptz_lm_options& o, double max_reproj_error, int lanes, ptz_lm_summary* d_summaries, int* d_accepted,
+                 const int* d_active, hipStream_t st);
 
 }  // namespace ptz

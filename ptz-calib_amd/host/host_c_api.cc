@@ -715,6 +715,49 @@ int32_t ptzh_krt_solve_cov(const double* cam_ref15, double* cam_cur15, int32_t n
   return (ok ? 1 : 0) | (okc ? 2 : 0) | (oks ? 4 : 0);
 }
 
+// KRTOptimizer with or without SetTrimming (trim = NULL: never called): Solve(), then MatchResiduals (err_px, kept [n_match]),
+// trim_report() and Covariance (cov needs room for 36 doubles).  Returns Solve() | MatchResiduals() << 1 | Covariance() << 2.
+int32_t ptzh_krt_solve_trimmed(const double* cam_ref15, double* cam_cur15, int32_t n_match, const float* uv_ref, const float* uv_cur,
+                               int32_t max_iter, double max_reproj_error, int32_t type, const ptz_krt_trim_options* trim, double* err_px,
+                               uint8_t* kept, ptz_krt_trim_report* report, double* cov, double* sigma0)
+{
+  Camera ref, cur;
+  ref.FromVector(std::vector<double>(cam_ref15, cam_ref15 + 15));
+  cur.FromVector(std::vector<double>(cam_cur15, cam_cur15 + 15));
+  std::vector<KeyPoint> kr(n_match), kc(n_match);
+  std::vector<DMatch> ms(n_match);
+  for (int m = 0; m < n_match; ++m) {
+    kr[m].pt = Point2f(uv_ref[2 * m], uv_ref[2 * m + 1]);
+    kc[m].pt = Point2f(uv_cur[2 * m], uv_cur[2 * m + 1]);
+    ms[m].queryIdx = m; ms[m].trainIdx = m;
+  }
+  KRTOptimizer opt(max_iter, max_reproj_error, static_cast<KRTOptimizer::FACTOR_TYPE>(type));
+  opt.SetInitParams(cur.K(), cur.R(), cur.t(), cur.dist());
+  opt.Add2d2dConstraints(ref, kr, kc, ms);
+  if (trim) opt.SetTrimming(*trim);
+  Mat33 K, R; Vec3 t; Vec5 dist;
+  const bool ok = opt.Solve(K, R, t, dist);
+  if (ok) {
+    const std::vector<double> v = Camera(K, R, t, dist).ToVector();
+    memcpy(cam_cur15, v.data(), sizeof(double) * 15);
+  }
+  std::vector<double> e, c;
+  std::vector<uint8_t> k;
+  const bool okr = opt.MatchResiduals(e, k);
+  if (okr) {
+    memcpy(err_px, e.data(), sizeof(double) * e.size());
+    memcpy(kept, k.data(), k.size());
+  }
+  if (report) *report = opt.trim_report();
+  double s0 = 0;
+  const bool okc = opt.Covariance(c, s0);
+  if (okc) {
+    memcpy(cov, c.data(), sizeof(double) * c.size());
+    *sigma0 = s0;
+  }
+  return (ok ? 1 : 0) | (okr ? 2 : 0) | (okc ? 4 : 0);
+}
+
 // PTZRayOptimizer::Solve followed by Covariance / StdDevs (ann_ptr = NULL: no annotations).  cov needs room for 36 doubles per
 // candidate, std_devs for 6; before_solve = the answer of Covariance() on the object before Solve() (must be 0).  The packed_*
 // outputs are the problem and the SOLVED state the class handed to ptz_ba_covariance.  Returns Solve() | Covariance() << 1 |

@@ -57,9 +57,16 @@ bool KRTOptimizer::Solve(Mat33& K, Mat33& R, Vec3& t, Vec5& dist)
   opt.max_num_iterations = max_iter_;  // krt_optimizer.cc:388
   opt.device_id = device_id_;
   int32_t accepted = 0;
-  if (ptz_krt_solve_batch_2d3d(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, pts2d_.data(),
-                               pts3d_.data(), ref.data(), cur.data(), static_cast<int32_t>(factor_type_), max_reproj_error_,
-                               &opt, &summary_, &accepted, nullptr) != PTZ_OK)
+  if (trimming_) {
+    kept_.assign(uv_ref_.size() / 2, 0);
+    if (ptz_krt_solve_batch_trimmed(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, pts2d_.data(), pts3d_.data(),
+                                    ref.data(), cur.data(), static_cast<int32_t>(factor_type_), max_reproj_error_, nullptr, &trim_, &opt,
+                                    &summary_, &accepted, kept_.data(), &trim_report_, nullptr) != PTZ_OK)
+      return false;
+  }
+  else if (ptz_krt_solve_batch_2d3d(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, pts2d_.data(),
+                                    pts3d_.data(), ref.data(), cur.data(), static_cast<int32_t>(factor_type_), max_reproj_error_,
+                                    &opt, &summary_, &accepted, nullptr) != PTZ_OK)
     return false;
   num_iter_ = summary_.num_successful_steps;  // krt_optimizer.cc:396
   if (!accepted) return false;                // CheckResults, :504-533
@@ -85,12 +92,28 @@ bool KRTOptimizer::Covariance(std::vector<double>& cov, double& sigma0) const
   double s0 = 0;
   int32_t status = -1;
   if (ptz_krt_covariance_batch(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, p3 ? pts2d_.data() : nullptr,
-                               p3 ? pts3d_.data() : nullptr, ref.data(), cur.data(), static_cast<int32_t>(factor_type_), nullptr, nullptr,
-                               0.0, device_id_, c.data(), &s0, &status, nullptr) != PTZ_OK ||
+                               p3 ? pts3d_.data() : nullptr, ref.data(), cur.data(), static_cast<int32_t>(factor_type_),
+                               kept_.empty() ? nullptr : kept_.data(), nullptr, 0.0, device_id_, c.data(), &s0, &status, nullptr) != PTZ_OK ||
       status != PTZ_COV_OK)
     return false;
   cov.swap(c);
   sigma0 = s0;
+  return true;
+}
+
+bool KRTOptimizer::MatchResiduals(std::vector<double>& err_px, std::vector<uint8_t>& kept) const
+{
+  if (!solved_ || uv_ref_.empty()) return false;
+  const int64_t match_ptr[2] = {0, static_cast<int64_t>(uv_ref_.size() / 2)};
+  const std::vector<double> ref = cam_ref_.ToVector(), cur = cam_curr_world_.ToVector();
+  std::vector<double> e(uv_ref_.size() / 2, 0.0);
+  if (ptz_krt_residuals_batch(1, match_ptr, uv_ref_.data(), uv_cur_.data(), nullptr, nullptr, nullptr, ref.data(), cur.data(),
+                              static_cast<int32_t>(factor_type_), nullptr, nullptr, 0, device_id_, e.data(), nullptr, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr) != PTZ_OK)
+    return false;
+  err_px.swap(e);
+  if (kept_.empty()) kept.assign(uv_ref_.size() / 2, 1);
+  else kept = kept_;
   return true;
 }
 

@@ -3,6 +3,7 @@
 // entry point is what relocalization over many queries should call directly.
 #pragma once
 
+#include <cstdint>
 #include <vector>
 
 #include "../../include/ptz_calib_amd.h"
@@ -30,6 +31,14 @@ class KRTOptimizer {
   bool Covariance(std::vector<double>& cov, double& sigma0) const;
   // the square roots of its diagonal: focal length (fx) in pixels, rotation about x, y, z in radians
   bool StdDevs(double& sigma_f, double sigma_rot[3]) const;
+  // Outlier trimming (ptz_krt_solve_batch_trimmed with one query): after SetTrimming, Solve() runs the solve / report / rule loop of
+  // include/ptz_calib_amd.h over the 2D-2D matches and Covariance() is taken over the matches the last solve kept.  Never called:
+  // Solve() is ptz_krt_solve_batch, as before.
+  void SetTrimming(const ptz_krt_trim_options& trim) { trim_ = trim; trimming_ = true; }
+  const ptz_krt_trim_report& trim_report() const { return trim_report_; }
+  // After a Solve() that returned true: |e_m| of every match at the refined camera in the order of Add2d2dConstraints (-1: skipped by
+  // the border guard; ptz_krt_residuals_batch) and the matches of the last solve (all 1 without trimming).  false otherwise.
+  bool MatchResiduals(std::vector<double>& err_px, std::vector<uint8_t>& kept) const;
   void SetFixedFocal() { set_fixed_focal_ = true; }  // a flag nobody reads, as in the reference (krt_optimizer.cc:502)
   int num_iter_ = 0;
 
@@ -46,6 +55,10 @@ class KRTOptimizer {
   double max_reproj_error_;
   int device_id_ = 0;
   ptz_lm_summary summary_{};
+  bool trimming_ = false;
+  ptz_krt_trim_options trim_{};
+  ptz_krt_trim_report trim_report_{};
+  std::vector<uint8_t> kept_;  // of the last trimmed Solve(); empty without trimming
 };
 
 }  // namespace ptzcalib
