@@ -745,6 +745,58 @@ int32_t ptz_krt_solve_batch_trimmed_device(int32_t n_query, int64_t n_match, con
                                            ptz_lm_summary* d_summaries, int32_t* d_accepted, uint8_t* d_kept,
                                            ptz_krt_trim_report* d_report, void* d_workspace, int64_t workspace_bytes, void* hip_stream);
 
+/* ---- descriptor matching: the match table from features ------------------------------------------------------------------------
+ * What ReadColmapMatches (src/core/data_io.cc) reads from pairs_matches.txt, computed: mutual nearest neighbours of uint8
+ * descriptors under Lowe's ratio test, for a batch of image pairs.  The contract is csrc/ptz_desc_match.h, all integer:
+ * d2(i, j) = sum_k (a_ik - b_jk)^2 in int32; best(i) = the j of smallest d2, lowest j on a tie; second(i) = the smallest d2 over
+ * j != best(i), INT32_MAX if there is none.  (i, j) is a match when j = best_A(i); with cross_check, i = best_B(j); with ratio > 0,
+ * (double)d2 < ratio^2 * (double)second on A's side and, with cross_check, on B's side as well (so the matches of (B, A) are the
+ * transposed matches of (A, B)); and max_dist2 == 0 or d2 <= max_dist2.  A pair with fewer than min_matches matches has none.
+ * Matches of a pair are in ascending i, pairs in the caller's order; a pair's result depends on its two images only. */
+typedef struct ptz_desc_options {
+  double ratio;            /* 0.8; 0: no ratio test */
+  int32_t max_dist2;       /* 0: no bound */
+  int32_t cross_check;     /* 1 */
+  int32_t min_matches;     /* 0 */
+  int32_t device_id;       /* 0; must be the sets' device */
+  int64_t workspace_bytes; /* 256 MiB: bound on the top-2 state (12 bytes per feature and side) and keep bytes of the pairs in
+                              flight; the pair list is processed in chunks that stay below it (one pair at least, 2^20 pairs at most) */
+} ptz_desc_options;
+void ptz_desc_options_default(ptz_desc_options* o);
+
+/* The descriptors (and key points) of a set of images, packed and resident on the device.  Image m owns features
+ * [feat_ptr[m], feat_ptr[m + 1]) of desc [n_feat, D] (uint8, host) and of kp_xy [n_feat, 2] (float32 pixels, host, or NULL: the
+ * matches of this set then carry no pixels).
+ * PTZ_EINVAL: n_img < 0, feat_ptr[0] != 0 or decreasing, D outside 1 .. 512, NULL desc with features, device_id < 0;
+ * PTZ_ELIMIT: more than 2^31 - 1 features in one image. */
+typedef struct ptz_desc_set ptz_desc_set;
+int32_t ptz_desc_set_create(int32_t n_img, const int64_t* feat_ptr, const uint8_t* desc, int32_t D, const float* kp_xy,
+                            int32_t device_id, ptz_desc_set** out);
+void ptz_desc_set_destroy(ptz_desc_set* s);
+
+/* Matches of pair p = (image img_a[p] of set_a, image img_b[p] of set_b).  set_a == set_b and img_a[p] == img_b[p] are allowed.
+ * opt = NULL: the defaults.  PTZ_EINVAL, before any device work: NULL sets / out, n_pair < 0, different D or devices of the sets,
+ * opt->device_id not the sets' device, an image index out of range, ratio negative or not finite, max_dist2 / min_matches
+ * negative, workspace_bytes not positive.  n_pair = 0 and images without features are PTZ_OK. */
+typedef struct ptz_desc_matches ptz_desc_matches;
+int32_t ptz_desc_match_pairs(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair, const int32_t* img_a,
+                             const int32_t* img_b, const ptz_desc_options* opt, ptz_desc_matches** out);
+int64_t ptz_desc_matches_n_matches(const ptz_desc_matches* m);
+int32_t ptz_desc_matches_n_pairs(const ptz_desc_matches* m);
+double ptz_desc_matches_device_ms(const ptz_desc_matches* m); /* kernels of all chunks, between events on the call's stream */
+int32_t ptz_desc_matches_n_chunks(const ptz_desc_matches* m);
+/* every pointer nullable: match_ptr [n_pair + 1], idx_a / idx_b / dist2 [n_matches] int32, uv_a / uv_b [n_matches, 2] float32
+ * (PTZ_EINVAL if asked of a set created without key points) */
+int32_t ptz_desc_matches_download(const ptz_desc_matches* m, int64_t* match_ptr, int32_t* idx_a, int32_t* idx_b, int32_t* dist2,
+                                  float* uv_a, float* uv_b);
+/* the same arrays on the device, the result's until it is destroyed, in the layout ptz_match_gate_run_device and
+ * ptz_krt_solve_batch_device take (d_uv_* NULL without key points); every out pointer nullable */
+int32_t ptz_desc_matches_device_ptrs(const ptz_desc_matches* m, const int64_t** d_match_ptr, const int32_t** d_idx_a,
+                                     const int32_t** d_idx_b, const int32_t** d_dist2, const float** d_uv_a, const float** d_uv_b);
+void ptz_desc_matches_destroy(ptz_desc_matches* m);
+/* tests only: the full matrix d2 [n_a, n_b] (host) of one pair, from the matcher's own matrix-core tile code */
+int32_t ptz_debug_desc_dist2(const ptz_desc_set* set_a, int32_t img_a, const ptz_desc_set* set_b, int32_t img_b, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

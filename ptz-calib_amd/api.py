@@ -35,7 +35,10 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_ba_covariance_georef", "ptz_ba_batch_residuals", "ptz_ba_batch_trim_select", "ptz_ba_problem_trim",
            "ptz_trim_options_default", "ptz_ba_solve_trimmed_batch", "ptz_ba_solve_trimmed", "ptz_krt_residuals_batch",
            "ptz_krt_residuals_batch_device", "ptz_krt_trim_options_default", "ptz_krt_trim_workspace_bytes", "ptz_krt_solve_batch_trimmed",
-           "ptz_krt_solve_batch_trimmed_device"]
+           "ptz_krt_solve_batch_trimmed_device", "ptz_desc_options_default", "ptz_desc_set_create", "ptz_desc_set_destroy",
+           "ptz_desc_match_pairs", "ptz_desc_matches_n_matches", "ptz_desc_matches_n_pairs", "ptz_desc_matches_device_ms",
+           "ptz_desc_matches_n_chunks", "ptz_desc_matches_download", "ptz_desc_matches_device_ptrs", "ptz_desc_matches_destroy",
+           "ptz_debug_desc_dist2"]
 
 
 class PtzError(RuntimeError):
@@ -1104,3 +1107,137 @@ def hbm_bandwidth(device_id=0):
     r, c = C.c_double(), C.c_double()
     _check(lib().ptz_hbm_bandwidth(int(device_id), C.byref(r), C.byref(c)), "ptz_hbm_bandwidth")
     return r.value, c.value
+
+
+# ---- descriptor matching: the match table from features ----------------------------------------------------------------------
+class DescOptions(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("max_dist2", C.c_int32), ("cross_check", C.c_int32), ("min_matches", C.c_int32),
+                ("device_id", C.c_int32), ("workspace_bytes", C.c_int64)]
+
+
+def desc_options(**kw) -> DescOptions:
+    o = DescOptions()
+    lib().ptz_desc_options_default.restype = None
+    lib().ptz_desc_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown descriptor matching option {k}")
+        setattr(o, k, v)
+    return o
+
+
+class DescSet:
+    """ptz_desc_set: the uint8 descriptors [n_feat, D] (and key points [n_feat, 2], optional) of a set of images, image m owning
+    features feat_ptr[m] .. feat_ptr[m + 1], packed and resident on the device."""
+
+    def __init__(self, feat_ptr, desc, kp_xy=None, device_id=0):
+        self.feat_ptr = np.ascontiguousarray(feat_ptr, dtype=np.int64)
+        d = np.ascontiguousarray(desc, dtype=np.uint8)
+        if d.ndim != 2:
+            raise ValueError("desc: [n_feat, D]")
+        kp = None if kp_xy is None else np.ascontiguousarray(kp_xy, dtype=np.float32).reshape(-1, 2)
+        if len(self.feat_ptr) < 1 or int(self.feat_ptr[-1]) != d.shape[0] or (kp is not None and len(kp) != d.shape[0]):
+            raise ValueError("feat_ptr, desc and kp_xy disagree on the number of features")
+        self.n_img, self.D, self.device_id = len(self.feat_ptr) - 1, int(d.shape[1]), int(device_id)
+        self.handle = C.c_void_p()
+        lib().ptz_desc_set_destroy.restype = None
+        _check(lib().ptz_desc_set_create(self.n_img, _p(self.feat_ptr), _p(d) if d.size else None, self.D, _p(kp) if kp is not None and kp.size else None,
+                                         self.device_id, C.byref(self.handle)), "ptz_desc_set_create")
+        self.has_kp = kp is not None and kp.size > 0
+
+    def close(self):
+        if self.handle:
+            lib().ptz_desc_set_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DescMatches:
+    """ptz_desc_matches: the result of match_descriptors, resident on the device until closed."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        L = lib()
+        L.ptz_desc_matches_n_matches.restype = C.c_int64
+        L.ptz_desc_matches_device_ms.restype = C.c_double
+        L.ptz_desc_matches_destroy.restype = None
+        self.n_matches = int(L.ptz_desc_matches_n_matches(handle))
+        self.n_pairs = int(L.ptz_desc_matches_n_pairs(handle))
+        self.n_chunks = int(L.ptz_desc_matches_n_chunks(handle))
+        self.device_ms = float(L.ptz_desc_matches_device_ms(handle))
+
+    def download(self, uv=True):
+        """dict of numpy arrays: match_ptr [n_pair + 1], idx_a / idx_b / dist2 [n_matches], uv_a / uv_b [n_matches, 2] (uv=True)."""
+        n = self.n_matches
+        ptr = np.zeros(self.n_pairs + 1, dtype=np.int64)
+        ia, ib, d2 = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        ua, ub = (np.zeros((n, 2), dtype=np.float32) for _ in range(2)) if uv else (None, None)
+        _check(lib().ptz_desc_matches_download(self.handle, _p(ptr), _p(ia), _p(ib), _p(d2), _p(ua), _p(ub)), "ptz_desc_matches_download")
+        out = dict(match_ptr=ptr, idx_a=ia, idx_b=ib, dist2=d2, device_ms=self.device_ms, n_chunks=self.n_chunks)
+        if uv:
+            out.update(uv_a=ua, uv_b=ub)
+        return out
+
+    def device_ptrs(self):
+        """Integer device addresses (match_ptr, idx_a, idx_b, dist2, uv_a, uv_b), the result's until it is closed."""
+        p = [C.c_void_p() for _ in range(6)]
+        _check(lib().ptz_desc_matches_device_ptrs(self.handle, *[C.byref(x) for x in p]), "ptz_desc_matches_device_ptrs")
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_desc_matches_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_descriptors(set_a, set_b, img_a, img_b, resident=False, **options):
+    """ptz_desc_match_pairs: mutual nearest neighbours under the ratio test for the pairs (img_a[p] of set_a, img_b[p] of set_b).
+    options: ratio (0.8), max_dist2 (0), cross_check (1), min_matches (0), workspace_bytes (256 MiB).  Returns the CSR arrays as a
+    dict (DescMatches.download; pixels if both sets carry key points), or with resident=True the DescMatches itself."""
+    ia = np.ascontiguousarray(img_a, dtype=np.int32)
+    ib = np.ascontiguousarray(img_b, dtype=np.int32)
+    if ia.shape != ib.shape or ia.ndim != 1:
+        raise ValueError("img_a and img_b: two index lists of equal length")
+    options.setdefault("device_id", set_a.device_id)
+    o = desc_options(**options)
+    h = C.c_void_p()
+    _check(lib().ptz_desc_match_pairs(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), C.byref(o), C.byref(h)), "ptz_desc_match_pairs")
+    m = DescMatches(h)
+    if resident:
+        return m
+    try:
+        return m.download(uv=set_a.has_kp and set_b.has_kp)
+    finally:
+        m.close()
+
+
+def desc_dist2(set_a, img_a, set_b, img_b):
+    """ptz_debug_desc_dist2: the int32 matrix d2 [n_a, n_b] of one pair, from the matcher's own tile code (tests)."""
+    na = int(set_a.feat_ptr[img_a + 1] - set_a.feat_ptr[img_a])
+    nb = int(set_b.feat_ptr[img_b + 1] - set_b.feat_ptr[img_b])
+    out = np.zeros((na, nb), dtype=np.int32)
+    _check(lib().ptz_debug_desc_dist2(set_a.handle, int(img_a), set_b.handle, int(img_b), _p(out) if out.size else None), "ptz_debug_desc_dist2")
+    return out

@@ -14,6 +14,9 @@
 // PTZRayOptimizer::SetTrimming (solve, residual report, one rejected observation per offending track, re-pack, solve again).  A side
 // file <output>/<basename(images)>_residuals.json then holds the rounds, the last threshold, the observations removed and, per
 // registered image, rms_px / max_px / n_obs / n_removed of the georeferencing fit.  Without the flag nothing changes.
+// --match_descriptors (with --match_ratio, --match_min, --match_window, --save_matches; not in the reference) builds the match table
+// from the descriptors of the feature files on the GPU (MatchDescriptors) instead of reading pairs_matches.txt: every pair (i, j),
+// i != j, of the sorted file names; the blocks go through the same loader as a file's.  Without the flag nothing changes.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -185,6 +188,11 @@ int main(int argc, char** argv)
   parser.Add("trim_px", '\0', "Trim outlying observations in the georeferencing / uncertainty solves: threshold floor in pixels (off unless given)", false);
   parser.Add("trim_sigma", '\0', "With --trim_px: threshold = max(trim_px, trim_sigma * robust sigma) (default 3; 0: trim_px alone)", false);
   parser.Add("trim_rounds", '\0', "With --trim_px: solves at most (default 8)", false);
+  parser.AddFlag("match_descriptors", "Build the match table from the descriptors of the feature files on the GPU; pairs_matches.txt is not read");
+  parser.Add("match_ratio", '\0', "With --match_descriptors: Lowe's ratio (default 0.8; 0: no ratio test)", false);
+  parser.Add("match_min", '\0', "With --match_descriptors: matches a pair needs to keep any (default 8)", false);
+  parser.Add("match_window", '\0', "With --match_descriptors: only pairs of cyclic index distance <= k in the sorted file names (default: all)", false);
+  parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
   parser.ParseCheck(argc, argv);
   TrimArgs trim;
   if (parser.Exist("trim_px")) {
@@ -213,11 +221,42 @@ int main(int argc, char** argv)
   std::vector<MatchesInfo> matches_info;
   const std::string matches_path = parser.Get("features") + "/pairs_matches.txt";
   const bool gpu_h = parser.Exist("gpu_homography");
-  const bool loaded = parser.Exist("inlier_matches") ? LoadInlierMatchesInfo(matches_path, fnames, features, matches_info, gpu_h ? 0 : -1, min_inliers)
-                      : gpu_h                        ? LoadMatchesInfo(matches_path, fnames, features, matches_info, 0)
-                                                     : LoadMatchesInfo(matches_path, fnames, features, matches_info);
+  bool loaded;
+  if (parser.Exist("match_descriptors")) {
+    // every unordered pair once on the device, (j, i) as its transpose; the blocks then go where a file's blocks go
+    DescMatchOptions mo;
+    if (parser.Exist("match_ratio")) mo.ratio = atof(parser.Get("match_ratio").c_str());
+    if (parser.Exist("match_min")) mo.min_matches = atoi(parser.Get("match_min").c_str());
+    const long n_img = static_cast<long>(fnames.size());
+    const long window = parser.Exist("match_window") ? atol(parser.Get("match_window").c_str()) : n_img;
+    if (!(mo.ratio >= 0.0) || !std::isfinite(mo.ratio) || mo.min_matches < 0 || window < 1) {
+      fprintf(stderr, "--match_ratio must not be negative, --match_min not negative, --match_window at least 1\n");
+      return 1;
+    }
+    std::vector<std::pair<long, long>> pairs;
+    for (long i = 0; i < n_img; ++i)
+      for (long j = i + 1; j < n_img; ++j)
+        if (std::min(j - i, n_img - (j - i)) <= window) pairs.push_back({i, j});
+    std::vector<std::vector<DMatch>> pairs_matches;
+    std::vector<std::pair<std::string, std::string>> img_pairs_name;
+    if (!MatchDescriptors(parser.Get("features"), fnames, parser.Get("features"), fnames, pairs, mo, true, pairs_matches, img_pairs_name)) {
+      fprintf(stderr, "Error matching the descriptors of %s. Exiting ...\n", parser.Get("features").c_str());
+      return -1;
+    }
+    if (parser.Exist("save_matches") && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
+      fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
+      return -1;
+    }
+    loaded = LoadMatchesInfoFromBlocks(pairs_matches, img_pairs_name, fnames, features, matches_info, gpu_h ? 0 : -1, parser.Exist("inlier_matches"),
+                                       min_inliers);
+  }
+  else
+    loaded = parser.Exist("inlier_matches") ? LoadInlierMatchesInfo(matches_path, fnames, features, matches_info, gpu_h ? 0 : -1, min_inliers)
+             : gpu_h                        ? LoadMatchesInfo(matches_path, fnames, features, matches_info, 0)
+                                            : LoadMatchesInfo(matches_path, fnames, features, matches_info);
   if (!loaded) {
-    fprintf(stderr, "Error loading matches from %s. Exiting ...\n", matches_path.c_str());
+    if (parser.Exist("match_descriptors")) fprintf(stderr, "Error building the match table from the matched descriptors. Exiting ...\n");
+    else fprintf(stderr, "Error loading matches from %s. Exiting ...\n", matches_path.c_str());
     return -1;
   }
   fprintf(stderr, "================== PTZ-IBA Begin ==========================\n");

@@ -55,6 +55,11 @@ int main(int argc, char** argv)
                               "max(trim_px, trim_sigma * median / 1.1774) pixels, solve again, until nothing changes", false);
   parser.Add("trim_sigma", '\0', "With --trim_px: the threshold's multiple of the robust pixel noise (default 3, 0: trim_px alone)", false);
   parser.Add("trim_rounds", '\0', "With --trim_px: solves per test image at most (default 8)", false);
+  parser.AddFlag("match_descriptors", "Match every test image against every reference image by the descriptors of the feature files, on "
+                 "the GPU; pairs_matches.txt is not read");
+  parser.Add("match_ratio", '\0', "With --match_descriptors: Lowe's ratio (default 0.8; 0: no ratio test)", false);
+  parser.Add("match_min", '\0', "With --match_descriptors: matches a pair needs to keep any (default 8)", false);
+  parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -88,7 +93,30 @@ int main(int argc, char** argv)
   }
   std::vector<std::vector<DMatch>> pairs_matches;
   std::vector<std::pair<std::string, std::string>> img_pairs_name;
-  ReadColmapMatches(parser.Get("test_features") + "/pairs_matches.txt", pairs_matches, img_pairs_name);
+  if (parser.Exist("match_descriptors")) {
+    // blocks test image by test image, the references in ref_fnames order: FindBestMatch's first-wins tie picks the lowest reference
+    DescMatchOptions mo;
+    if (parser.Exist("match_ratio")) mo.ratio = atof(parser.Get("match_ratio").c_str());
+    if (parser.Exist("match_min")) mo.min_matches = atoi(parser.Get("match_min").c_str());
+    if (!(mo.ratio >= 0.0) || !std::isfinite(mo.ratio) || mo.min_matches < 0) {
+      fprintf(stderr, "--match_ratio and --match_min must not be negative\n");
+      return 1;
+    }
+    std::vector<std::pair<long, long>> pairs;
+    for (size_t t = 0; t < test_fnames.size(); ++t)
+      for (size_t r = 0; r < ref_fnames.size(); ++r) pairs.push_back({static_cast<long>(r), static_cast<long>(t)});
+    if (!MatchDescriptors(parser.Get("ref_features"), ref_fnames, parser.Get("test_features"), test_fnames, pairs, mo, false, pairs_matches,
+                          img_pairs_name)) {
+      fprintf(stderr, "Error matching the descriptors of the test images against the references. Exiting ...\n");
+      return -1;
+    }
+    if (parser.Exist("save_matches") && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
+      fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
+      return -1;
+    }
+  }
+  else
+    ReadColmapMatches(parser.Get("test_features") + "/pairs_matches.txt", pairs_matches, img_pairs_name);
   std::vector<Camera> ref_cameras;
   if (!ReadCamFromJson(parser.Get("ref_params"), ref_fnames, ref_cameras)) {
     fprintf(stderr, "Error loading reference camera parameters. Exiting ...\n");

@@ -1,0 +1,603 @@
+// ptz_desc_match.hip -- the match table from features: mutual nearest neighbours of uint8 descriptors under Lowe's ratio test for a
+// batch of image pairs (ptz_desc_match_pairs).  The contract is ptz_desc_match.h; everything here is integer arithmetic, so a
+// pair's matches are the bits of the brute-force restatement whatever the batch, the tiling or the chunking.
+//
+//   pack      a byte xor 0x80 is (a - 128) as int8; the bias cancels in a - b, so d2 = |a'|^2 + |b'|^2 - 2 a'.b'.  Rows are padded
+//             with zeros to DP = a multiple of 64 bytes, images to a multiple of 64 rows (zero rows, norm INT32_MAX: the dot
+//             product of a padding row is exactly 0, its key INT32_MAX, and it never beats the empty state).
+//   top-2     one workgroup = (pair, direction, 128 query rows): each of its four waves holds two tiles of 16 queries for the whole
+//             DP in registers (the B operand of v_mfma_i32_16x16x64_i8) and streams the other image in tiles of 16 rows (the A
+//             operand) straight from global memory, one tile ahead.  Lane l of the result holds C[row 4 (l >> 4) + r][col l & 15]:
+//             ONE query per lane, four candidates per step, so the running (best, best j, second) of a query tile is three
+//             registers.  Candidates reach a lane in ascending j, so `<` keeps the lowest j there; the four lanes of a query
+//             are merged once at the end with the header's rule.  The DP x n product is never written.
+//   join      the acceptance rule per feature of A -> a keep byte; counting, scan and scatter are ptz_gate_compact.h's kernels
+//             (min_matches as `need`); a gather writes indices, distances and the pixels of the resident key points.
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "ptz_common.h"
+#include "ptz_desc_match.h"
+#include "ptz_gate_compact.h"
+#include "ptz_pool.h"
+
+namespace ptz {
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int DESC_WG = 256;     // four waves
+constexpr int DESC_QT = 2;       // query tiles of 16 per wave
+constexpr int DESC_WG_Q = (DESC_WG / WAVE) * DESC_QT * 16;  // 128 queries per workgroup
+constexpr int DESC_ROW_PAD = 64; // rows of an image are padded to this
+constexpr int DESC_CHUNK_PAIRS = 1 << 20;  // most pairs of a chunk: its launches have a workgroup row per pair and direction
+
+struct DescPair {
+  int64_t row_a, row_b;  // first packed row of the two images
+  int64_t kp_a, kp_b;    // first key point
+  int64_t soff;          // first top-2 state of the pair in its chunk: A's n_a, then B's n_b
+  int64_t aoff;          // first keep byte (position of A's feature 0 in the chunk's list of A features)
+  int32_t n_a, n_b;
+};
+
+// one thread per packed row of image blockIdx.x (the last "image" is the slack behind the set: no features, 64 rows)
+__global__ __launch_bounds__(256) void k_desc_pack(const int64_t* __restrict__ feat_ptr, const int64_t* __restrict__ row_off,
+                                                   const uint8_t* __restrict__ raw, int D, int DP, uint32_t* __restrict__ desc,
+                                                   int32_t* __restrict__ norm)
+{
+  const int m = blockIdx.x;
+  const int64_t f0 = feat_ptr[m], n = feat_ptr[m + 1] - f0, r0 = row_off[m], np = row_off[m + 1] - r0;
+  for (int64_t r = (int64_t)blockIdx.y * blockDim.x + threadIdx.x; r < np; r += (int64_t)gridDim.y * blockDim.x) {
+    uint32_t* o = desc + (r0 + r) * (DP / 4);
+    int32_t sum = INT32_MAX;
+    if (r < n) {
+      const uint8_t* src = raw + (f0 + r) * D;
+      sum = 0;
+      for (int k = 0; k < DP; k += 4) {
+        uint32_t w = 0;
+        for (int b = 0; b < 4; ++b) {
+          const int v = k + b < D ? (int)src[k + b] - 128 : 0;
+          w |= (uint32_t)(v & 255) << (8 * b);
+          sum += v * v;
+        }
+        o[k / 4] = w;
+      }
+    }
+    else {
+      for (int k = 0; k < DP; k += 4) o[k / 4] = 0u;
+    }
+    norm[r0 + r] = sum;
+  }
+}
+
+// blockIdx.x = pair * dirs + direction (0: A's features ask B, 1: B's ask A), blockIdx.y (strided) = tile of 128 queries.
+// DUMP: the distances themselves to dump [n_q, n_s] instead of the top-2 (ptz_debug_desc_dist2: the same fragments, the same map).
+template <int KS, bool DUMP>
+__global__ __launch_bounds__(DESC_WG) void k_desc_top2(const DescPair* __restrict__ pairs, int dirs, const int8_t* __restrict__ desc_a,
+                                                       const int32_t* __restrict__ norm_a, const int8_t* __restrict__ desc_b,
+                                                       const int32_t* __restrict__ norm_b, DescTop2* __restrict__ state,
+                                                       int32_t* __restrict__ dump)
+{
+  constexpr int DP = KS * 64;
+  const DescPair P = pairs[blockIdx.x / dirs];
+  const int dir = blockIdx.x % dirs;
+  const int nq = dir ? P.n_b : P.n_a, ns = dir ? P.n_a : P.n_b;
+  const int8_t* qd = dir ? desc_b + P.row_b * DP : desc_a + P.row_a * DP;
+  const int32_t* qn = dir ? norm_b + P.row_b : norm_a + P.row_a;
+  const int8_t* sdp = dir ? desc_a + P.row_a * DP : desc_b + P.row_b * DP;
+  const int32_t* sn = dir ? norm_a + P.row_a : norm_b + P.row_b;
+  DescTop2* out = DUMP ? nullptr : state + P.soff + (dir ? P.n_a : 0);
+  const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, c = lane & 15, g = lane >> 4;
+  const int nt = (ns + 15) >> 4;  // streamed tiles; rows up to 16 nt <= the image's padded rows
+
+  for (int64_t tile = blockIdx.y; tile * DESC_WG_Q < nq; tile += gridDim.y) {
+    const int q0 = (int)(tile * DESC_WG_Q) + wave * (DESC_QT * 16);
+    if (q0 >= nq) continue;  // (one value per wave; rows q0 .. q0 + 31 lie inside the image's padded rows)
+    v4i qf[DESC_QT][KS];
+#pragma unroll
+    for (int t = 0; t < DESC_QT; ++t)
+#pragma unroll
+      for (int s = 0; s < KS; ++s) qf[t][s] = *reinterpret_cast<const v4i*>(qd + (int64_t)(q0 + 16 * t + c) * DP + s * 64 + g * 16);
+    int32_t bd[DESC_QT], bj[DESC_QT], sd[DESC_QT];
+#pragma unroll
+    for (int t = 0; t < DESC_QT; ++t) bd[t] = bj[t] = sd[t] = kDescNone;
+
+    v4i sf[KS], nf[KS], skey, nkey;
+    if (nt > 0) {
+#pragma unroll
+      for (int s = 0; s < KS; ++s) sf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)c * DP + s * 64 + g * 16);
+      skey = *reinterpret_cast<const v4i*>(sn + 4 * g);
+    }
+    for (int jt = 0; jt < nt; ++jt) {
+      const int jn = min(jt + 1, nt - 1);  // the tile ahead (the last one reads itself again)
+#pragma unroll
+      for (int s = 0; s < KS; ++s) nf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)(16 * jn + c) * DP + s * 64 + g * 16);
+      nkey = *reinterpret_cast<const v4i*>(sn + 16 * jn + 4 * g);
+#pragma unroll
+      for (int t = 0; t < DESC_QT; ++t) {
+        v4i acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(sf[s], qf[t][s], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int32_t key = skey[r] - 2 * acc[r];  // d2 less the query's norm, which every candidate of a query shares
+          const int32_t jj = 16 * jt + 4 * g + r;
+          if (DUMP) {
+            const int q = q0 + 16 * t + c;
+            if (q < nq && jj < ns) dump[(int64_t)q * ns + jj] = key + qn[q];
+          }
+          else {
+            sd[t] = min(sd[t], max(bd[t], key));
+            bj[t] = key < bd[t] ? jj : bj[t];
+            bd[t] = min(bd[t], key);
+          }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < KS; ++s) sf[s] = nf[s];
+      skey = nkey;
+    }
+    if (!DUMP) {
+#pragma unroll
+      for (int t = 0; t < DESC_QT; ++t) {
+        const int q = q0 + 16 * t + c;
+        const int32_t nq2 = q < nq ? qn[q] : 0;  // (a padding row's result is not stored)
+        DescTop2 T;
+        T.d = bd[t] == kDescNone ? kDescNone : bd[t] + nq2;
+        T.j = bj[t];
+        T.s = sd[t] == kDescNone ? kDescNone : sd[t] + nq2;
+#pragma unroll
+        for (int d = 16; d <= 32; d <<= 1) {
+          DescTop2 O;
+          O.d = __shfl_xor(T.d, d);
+          O.j = __shfl_xor(T.j, d);
+          O.s = __shfl_xor(T.s, d);
+          T = desc_top2_merge(T, O);
+        }
+        if (g == 0 && q < nq) out[q] = T;
+      }
+    }
+  }
+}
+
+// the keep byte of every feature of A
+__global__ __launch_bounds__(256) void k_desc_join(const DescPair* __restrict__ pairs, const DescTop2* __restrict__ state, DescRule rule,
+                                                   uint8_t* __restrict__ keep)
+{
+  const DescPair P = pairs[blockIdx.x];
+  const DescTop2* sa = state + P.soff;
+  const DescTop2* sb = sa + P.n_a;
+  for (int64_t i = (int64_t)blockIdx.y * blockDim.x + threadIdx.x; i < P.n_a; i += (int64_t)gridDim.y * blockDim.x) {
+    const DescTop2 ta = sa[i];
+    DescTop2 tb = desc_top2_empty();
+    if (rule.cross_check && ta.j != kDescNone) tb = sb[ta.j];
+    keep[P.aoff + i] = desc_accept(rule, (int32_t)i, ta, tb) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_desc_fill(int n, int32_t v, int32_t* __restrict__ x)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+
+// one thread per kept match of the chunk: its pair by bisection of the chunk's offsets, then the match's five outputs
+__global__ __launch_bounds__(256) void k_desc_gather(int n_pair, const DescPair* __restrict__ pairs, const int64_t* __restrict__ out_ptr,
+                                                     const int32_t* __restrict__ out_index, const DescTop2* __restrict__ state,
+                                                     const float2* __restrict__ kp_a, const float2* __restrict__ kp_b,
+                                                     int32_t* __restrict__ idx_a, int32_t* __restrict__ idx_b, int32_t* __restrict__ dist2,
+                                                     float2* __restrict__ uv_a, float2* __restrict__ uv_b)
+{
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= out_ptr[n_pair]) return;
+  int lo = 0, hi = n_pair;  // the last p with out_ptr[p] <= o
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (out_ptr[mid] <= o) lo = mid;
+    else hi = mid;
+  }
+  const DescPair P = pairs[lo];
+  const int32_t i = (int32_t)(out_index[o] - P.aoff);
+  const DescTop2 ta = state[P.soff + i];
+  idx_a[o] = i;
+  idx_b[o] = ta.j;
+  dist2[o] = ta.d;
+  if (uv_a) {
+    uv_a[o] = kp_a[P.kp_a + i];
+    uv_b[o] = kp_b[P.kp_b + ta.j];
+  }
+}
+
+template <bool DUMP>
+void launch_top2(int KS, dim3 grid, hipStream_t st, const DescPair* pairs, int dirs, const int8_t* da, const int32_t* na, const int8_t* db,
+                 const int32_t* nb, DescTop2* state, int32_t* dump)
+{
+  switch (KS) {
+#define PTZ_DESC_CASE(K) \
+  case K: hipLaunchKernelGGL((k_desc_top2<K, DUMP>), grid, dim3(DESC_WG), 0, st, pairs, dirs, da, na, db, nb, state, dump); break;
+    PTZ_DESC_CASE(1) PTZ_DESC_CASE(2) PTZ_DESC_CASE(3) PTZ_DESC_CASE(4) PTZ_DESC_CASE(5) PTZ_DESC_CASE(6) PTZ_DESC_CASE(7) PTZ_DESC_CASE(8)
+#undef PTZ_DESC_CASE
+  }
+}
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline unsigned tiles_y(int64_t n, int per) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + per - 1) / per, 1), 65535); }
+
+// a call's stream and timing events, from the pool
+struct DescStream {
+  int dev = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t open(int device)
+  {
+    dev = device;
+    hipError_t e = ptzpool::stream_acquire(dev, &st);
+    if (e == hipSuccess) e = ptzpool::event_acquire(dev, true, &e0);
+    if (e == hipSuccess) e = ptzpool::event_acquire(dev, true, &e1);
+    return e;
+  }
+  ~DescStream()
+  {
+    if (st) (void)stream_wait(st);
+    ptzpool::stream_release(dev, st);
+    ptzpool::event_release(dev, true, e0);
+    ptzpool::event_release(dev, true, e1);
+  }
+};
+struct DescBlock {  // a pooled device block, released with its owner
+  int dev = 0;
+  char* p = nullptr;
+  hipError_t get(int device, size_t bytes) { dev = device; return ptzpool::dev_acquire(dev, std::max<size_t>(bytes, 256), (void**)&p); }
+  ~DescBlock() { ptzpool::dev_release(dev, p); }
+  DescBlock() = default;
+  DescBlock(const DescBlock&) = delete;
+  DescBlock& operator=(const DescBlock&) = delete;
+};
+
+}  // namespace
+}  // namespace ptz
+
+struct ptz_desc_set {
+  int device = 0;
+  int32_t n_img = 0, D = 0, KS = 0;
+  int64_t n_feat = 0;
+  std::vector<int64_t> feat_ptr, row_off;  // [n_img + 1]
+  ptz::DescBlock blk;
+  int8_t* d_desc = nullptr;   // [rows + slack][64 KS]
+  int32_t* d_norm = nullptr;  // [rows + slack]
+  float2* d_kp = nullptr;     // [n_feat] or nullptr
+};
+
+struct ptz_desc_matches {
+  int device = 0;
+  int32_t n_pair = 0, n_chunks = 0;
+  int64_t n_match = 0;
+  double device_ms = 0;
+  bool has_uv = false;
+  std::vector<int64_t> match_ptr;  // [n_pair + 1]
+  ptz::DescBlock blk;
+  int64_t* d_match_ptr = nullptr;
+  int32_t *d_idx_a = nullptr, *d_idx_b = nullptr, *d_dist2 = nullptr;
+  float2 *d_uv_a = nullptr, *d_uv_b = nullptr;
+};
+
+extern "C" void ptz_desc_options_default(ptz_desc_options* o)
+{
+  if (!o) return;
+  o->ratio = 0.8;
+  o->max_dist2 = 0;
+  o->cross_check = 1;
+  o->min_matches = 0;
+  o->device_id = 0;
+  o->workspace_bytes = (int64_t)256 << 20;
+}
+
+extern "C" int32_t ptz_desc_set_create(int32_t n_img, const int64_t* feat_ptr, const uint8_t* desc, int32_t D, const float* kp_xy,
+                                       int32_t device_id, ptz_desc_set** out)
+{
+  using namespace ptz;
+  if (!out) return PTZ_EINVAL;
+  *out = nullptr;
+  if (n_img < 0 || !feat_ptr || feat_ptr[0] != 0 || D < 1 || D > kDescMaxDim || device_id < 0) return PTZ_EINVAL;
+  for (int m = 0; m < n_img; ++m)
+    if (feat_ptr[m + 1] < feat_ptr[m]) return PTZ_EINVAL;
+  for (int m = 0; m < n_img; ++m)
+    if (feat_ptr[m + 1] - feat_ptr[m] > INT32_MAX) return PTZ_ELIMIT;
+  const int64_t nf = feat_ptr[n_img];
+  if (nf > 0 && !desc) return PTZ_EINVAL;
+  clear_stale_error(__func__);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) return PTZ_ENODEVICE;
+  PTZ_DEVICE_GUARD(device_id);
+
+  std::unique_ptr<ptz_desc_set> s(new ptz_desc_set());
+  s->device = device_id; s->n_img = n_img; s->D = D; s->KS = (D + 63) / 64; s->n_feat = nf;
+  s->feat_ptr.assign(feat_ptr, feat_ptr + n_img + 1);
+  s->row_off.resize(n_img + 1);
+  s->row_off[0] = 0;
+  for (int m = 0; m < n_img; ++m)
+    s->row_off[m + 1] = s->row_off[m] + (feat_ptr[m + 1] - feat_ptr[m] + DESC_ROW_PAD - 1) / DESC_ROW_PAD * DESC_ROW_PAD;
+  const int DP = 64 * s->KS;
+  const size_t rows = (size_t)s->row_off[n_img] + DESC_ROW_PAD;  // the slack is the pack kernel's image n_img
+  const size_t o_desc = 0, o_norm = o_desc + up256(rows * DP), o_kp = o_norm + up256(rows * sizeof(int32_t)),
+               total = o_kp + up256(kp_xy ? (size_t)nf * sizeof(float2) : 0);
+  if (s->blk.get(device_id, total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  s->d_desc = (int8_t*)(s->blk.p + o_desc);
+  s->d_norm = (int32_t*)(s->blk.p + o_norm);
+  s->d_kp = kp_xy ? (float2*)(s->blk.p + o_kp) : nullptr;
+
+  // the raw bytes and the two offset tables, for the pack kernel only
+  std::vector<int64_t> fp(s->feat_ptr), ro(s->row_off);
+  fp.push_back(nf);
+  ro.push_back((int64_t)rows);
+  const size_t t_fp = 0, t_ro = t_fp + up256(sizeof(int64_t) * fp.size()), t_raw = t_ro + up256(sizeof(int64_t) * ro.size()),
+               t_total = t_raw + up256((size_t)nf * D);
+  DescBlock tmp;
+  if (tmp.get(device_id, t_total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  DescStream ds;
+  PTZ_HIP_TRY(ds.open(device_id));
+  PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_fp, fp.data(), sizeof(int64_t) * fp.size(), hipMemcpyHostToDevice, ds.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_ro, ro.data(), sizeof(int64_t) * ro.size(), hipMemcpyHostToDevice, ds.st));
+  if (nf > 0) PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_raw, desc, (size_t)nf * D, hipMemcpyHostToDevice, ds.st));
+  if (nf > 0 && kp_xy) PTZ_HIP_TRY(hipMemcpyAsync(s->d_kp, kp_xy, (size_t)nf * sizeof(float2), hipMemcpyHostToDevice, ds.st));
+  int64_t most = DESC_ROW_PAD;
+  for (int m = 0; m < n_img; ++m) most = std::max(most, s->row_off[m + 1] - s->row_off[m]);
+  hipLaunchKernelGGL(k_desc_pack, dim3(n_img + 1, tiles_y(most, 256)), dim3(256), 0, ds.st, (const int64_t*)(tmp.p + t_fp),
+                     (const int64_t*)(tmp.p + t_ro), (const uint8_t*)(tmp.p + t_raw), D, DP, (uint32_t*)s->d_desc, s->d_norm);
+  PTZ_HIP_TRY(hipGetLastError());
+  PTZ_HIP_TRY(stream_wait(ds.st));
+  *out = s.release();
+  return PTZ_OK;
+}
+
+extern "C" void ptz_desc_set_destroy(ptz_desc_set* s)
+{
+  if (!s) return;
+  ptz::DeviceGuard g(s->device);
+  delete s;
+}
+
+extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                                        const int32_t* img_b, const ptz_desc_options* opt, ptz_desc_matches** out)
+{
+  using namespace ptz;
+  if (!out) return PTZ_EINVAL;
+  *out = nullptr;
+  ptz_desc_options o;
+  ptz_desc_options_default(&o);
+  if (opt) o = *opt;
+  else if (A) o.device_id = A->device;
+  if (!A || !B || n_pair < 0 || (n_pair > 0 && (!img_a || !img_b))) return PTZ_EINVAL;
+  if (A->device != B->device || o.device_id != A->device || A->D != B->D) return PTZ_EINVAL;
+  if (!(std::isfinite(o.ratio) && o.ratio >= 0) || o.max_dist2 < 0 || o.min_matches < 0 || o.workspace_bytes <= 0) return PTZ_EINVAL;
+  for (int p = 0; p < n_pair; ++p)
+    if (img_a[p] < 0 || img_a[p] >= A->n_img || img_b[p] < 0 || img_b[p] >= B->n_img) return PTZ_EINVAL;
+  clear_stale_error(__func__);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= A->device) return PTZ_ENODEVICE;
+  const int dev = A->device;
+  PTZ_DEVICE_GUARD(dev);
+
+  std::unique_ptr<ptz_desc_matches> res(new ptz_desc_matches());
+  res->device = dev; res->n_pair = n_pair; res->has_uv = A->d_kp && B->d_kp;
+  res->match_ptr.assign((size_t)n_pair + 1, 0);
+  const DescRule rule = {o.ratio * o.ratio, o.max_dist2, o.cross_check ? 1 : 0};
+  const int dirs = rule.cross_check ? 2 : 1;
+
+  // the pair table, offsets relative to each pair's chunk; chunks = runs of pairs whose state and keep bytes stay under the bound
+  std::vector<DescPair> tab((size_t)n_pair);
+  struct Chunk { int p0, p1; int64_t n_state, n_a; int most_q; };
+  std::vector<Chunk> chunks;
+  {
+    Chunk c = {0, 0, 0, 0, 0};
+    int64_t bytes = 0;
+    for (int p = 0; p < n_pair; ++p) {
+      const int ia = img_a[p], ib = img_b[p];
+      const int64_t na = A->feat_ptr[ia + 1] - A->feat_ptr[ia], nb = B->feat_ptr[ib + 1] - B->feat_ptr[ib];
+      const int64_t cost = (int64_t)sizeof(DescTop2) * (na + nb) + na;
+      if (c.p1 > c.p0 && (bytes + cost > o.workspace_bytes || c.n_a + na > INT32_MAX || c.p1 - c.p0 >= DESC_CHUNK_PAIRS)) {
+        chunks.push_back(c);
+        c = {p, p, 0, 0, 0};
+        bytes = 0;
+      }
+      tab[p] = DescPair{A->row_off[ia], B->row_off[ib], A->feat_ptr[ia], B->feat_ptr[ib], c.n_state, c.n_a, (int32_t)na, (int32_t)nb};
+      c.n_state += na + nb;
+      c.n_a += na;
+      c.most_q = (int)std::max<int64_t>(c.most_q, std::max(na, nb));
+      c.p1 = p + 1;
+      bytes += cost;
+    }
+    if (c.p1 > c.p0) chunks.push_back(c);
+  }
+  res->n_chunks = (int32_t)chunks.size();
+  int64_t ws_state = 1, ws_a = 1;
+  int ws_pairs = 1;
+  for (const Chunk& c : chunks) {
+    ws_state = std::max(ws_state, c.n_state);
+    ws_a = std::max(ws_a, c.n_a);
+    ws_pairs = std::max(ws_pairs, c.p1 - c.p0);
+  }
+
+  const size_t o_tab = 0, o_state = o_tab + up256(sizeof(DescPair) * std::max<size_t>(tab.size(), 1)),
+               o_keep = o_state + up256(sizeof(DescTop2) * ws_state), o_index = o_keep + up256(ws_a),
+               o_aptr = o_index + up256(sizeof(int32_t) * ws_a), o_found = o_aptr + up256(sizeof(int64_t) * (ws_pairs + 1)),
+               o_cnt = o_found + up256(sizeof(int32_t) * ws_pairs), o_optr = o_cnt + up256(sizeof(int32_t) * ws_pairs),
+               ws_total = o_optr + up256(sizeof(int64_t) * (ws_pairs + 1));
+  // a chunk's matches wait in a block of their own until the total is known
+  struct Part { std::unique_ptr<DescBlock> blk; int64_t n; };
+  // the stream is declared after every block its kernels write: on an early return it is waited for before they go back to the pool
+  DescBlock ws;
+  std::vector<Part> parts;
+  std::vector<int64_t> aptr, optr;  // a chunk's offsets, up and down
+  DescStream ds;
+  if (ws.get(dev, ws_total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  PTZ_HIP_TRY(ds.open(dev));
+  DescPair* d_tab = (DescPair*)(ws.p + o_tab);
+  DescTop2* d_state = (DescTop2*)(ws.p + o_state);
+  uint8_t* d_keep = (uint8_t*)(ws.p + o_keep);
+  int32_t* d_index = (int32_t*)(ws.p + o_index);
+  int64_t* d_aptr = (int64_t*)(ws.p + o_aptr);
+  int32_t* d_found = (int32_t*)(ws.p + o_found);
+  int32_t* d_cnt = (int32_t*)(ws.p + o_cnt);
+  int64_t* d_optr = (int64_t*)(ws.p + o_optr);
+  if (n_pair > 0) {
+    PTZ_HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DescPair) * tab.size(), hipMemcpyHostToDevice, ds.st));
+    hipLaunchKernelGGL(k_desc_fill, dim3((ws_pairs + 255) / 256), dim3(256), 0, ds.st, ws_pairs, 1, d_found);
+  }
+
+  auto carve = [](char* base, int64_t n, bool uv, int32_t*& ia, int32_t*& ib, int32_t*& d2, float2*& ua, float2*& ub) {
+    const size_t w = up256(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)), w2 = up256(sizeof(float2) * (size_t)std::max<int64_t>(n, 1));
+    ia = (int32_t*)base; ib = (int32_t*)(base + w); d2 = (int32_t*)(base + 2 * w);
+    ua = uv ? (float2*)(base + 3 * w) : nullptr;
+    ub = uv ? (float2*)(base + 3 * w + w2) : nullptr;
+    return 3 * w + (uv ? 2 * w2 : 0);
+  };
+  double ms_sum = 0;
+  for (const Chunk& c : chunks) {
+    const int npc = c.p1 - c.p0;
+    aptr.resize(npc + 1);
+    for (int p = 0; p < npc; ++p) aptr[p] = tab[c.p0 + p].aoff;
+    aptr[npc] = c.n_a;
+    PTZ_HIP_TRY(hipMemcpyAsync(d_aptr, aptr.data(), sizeof(int64_t) * (npc + 1), hipMemcpyHostToDevice, ds.st));
+    PTZ_HIP_TRY(hipEventRecord(ds.e0, ds.st));
+    launch_top2<false>(A->KS, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG_Q)), ds.st, d_tab + c.p0, dirs, A->d_desc, A->d_norm,
+                       B->d_desc, B->d_norm, d_state, nullptr);
+    hipLaunchKernelGGL(k_desc_join, dim3(npc, tiles_y(c.most_q, 256)), dim3(256), 0, ds.st, (const DescPair*)(d_tab + c.p0),
+                       (const DescTop2*)d_state, rule, d_keep);
+    enqueue_compact(npc, d_aptr, d_found, d_keep, o.min_matches, d_cnt, d_optr, nullptr, nullptr, nullptr, nullptr, d_index, ds.st);
+    PTZ_HIP_TRY(hipGetLastError());
+    PTZ_HIP_TRY(hipEventRecord(ds.e1, ds.st));
+    optr.resize(npc + 1);
+    PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d_optr, sizeof(int64_t) * (npc + 1), hipMemcpyDeviceToHost, ds.st));
+    PTZ_HIP_TRY(stream_wait(ds.st));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ds.e0, ds.e1);
+    ms_sum += ms;
+    const int64_t nc = optr[npc], base = res->match_ptr[c.p0];
+    for (int p = 0; p < npc; ++p) res->match_ptr[c.p0 + p + 1] = base + optr[p + 1];
+    Part part;
+    part.n = nc;
+    part.blk.reset(new DescBlock());
+    int32_t *ia, *ib, *d2;
+    float2 *ua, *ub;
+    const size_t bytes = carve(nullptr, nc, res->has_uv, ia, ib, d2, ua, ub);
+    if (part.blk->get(dev, bytes) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+    if (nc > 0) {
+      carve(part.blk->p, nc, res->has_uv, ia, ib, d2, ua, ub);
+      PTZ_HIP_TRY(hipEventRecord(ds.e0, ds.st));
+      hipLaunchKernelGGL(k_desc_gather, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ds.st, npc, (const DescPair*)(d_tab + c.p0),
+                         (const int64_t*)d_optr, (const int32_t*)d_index, (const DescTop2*)d_state, (const float2*)A->d_kp,
+                         (const float2*)B->d_kp, ia, ib, d2, ua, ub);
+      PTZ_HIP_TRY(hipGetLastError());
+      PTZ_HIP_TRY(hipEventRecord(ds.e1, ds.st));
+      PTZ_HIP_TRY(stream_wait(ds.st));
+      (void)hipEventElapsedTime(&ms, ds.e0, ds.e1);
+      ms_sum += ms;
+    }
+    parts.push_back(std::move(part));
+  }
+
+  // one block behind the result: the offsets, then the five arrays, chunk after chunk
+  const int64_t nm = res->match_ptr[n_pair];
+  res->n_match = nm;
+  res->device_ms = ms_sum;
+  int32_t *ia, *ib, *d2;
+  float2 *ua, *ub;
+  const size_t o_ptr_bytes = up256(sizeof(int64_t) * ((size_t)n_pair + 1));
+  const size_t arr_bytes = carve(nullptr, nm, res->has_uv, ia, ib, d2, ua, ub);
+  if (res->blk.get(dev, o_ptr_bytes + arr_bytes) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  res->d_match_ptr = (int64_t*)res->blk.p;
+  carve(res->blk.p + o_ptr_bytes, nm, res->has_uv, res->d_idx_a, res->d_idx_b, res->d_dist2, res->d_uv_a, res->d_uv_b);
+  PTZ_HIP_TRY(hipMemcpyAsync(res->d_match_ptr, res->match_ptr.data(), sizeof(int64_t) * ((size_t)n_pair + 1), hipMemcpyHostToDevice, ds.st));
+  int64_t at = 0;
+  for (const Part& part : parts) {
+    if (part.n == 0) continue;
+    carve(part.blk->p, part.n, res->has_uv, ia, ib, d2, ua, ub);
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_a + at, ia, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_b + at, ib, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_dist2 + at, d2, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
+    if (res->has_uv) {
+      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_a + at, ua, sizeof(float2) * part.n, hipMemcpyDeviceToDevice, ds.st));
+      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_b + at, ub, sizeof(float2) * part.n, hipMemcpyDeviceToDevice, ds.st));
+    }
+    at += part.n;
+  }
+  PTZ_HIP_TRY(stream_wait(ds.st));
+  PTZ_HIP_TRY(hipGetLastError());
+  *out = res.release();
+  return PTZ_OK;
+}
+
+extern "C" int64_t ptz_desc_matches_n_matches(const ptz_desc_matches* m) { return m ? m->n_match : 0; }
+extern "C" int32_t ptz_desc_matches_n_pairs(const ptz_desc_matches* m) { return m ? m->n_pair : 0; }
+extern "C" double ptz_desc_matches_device_ms(const ptz_desc_matches* m) { return m ? m->device_ms : 0.0; }
+extern "C" int32_t ptz_desc_matches_n_chunks(const ptz_desc_matches* m) { return m ? m->n_chunks : 0; }
+
+extern "C" int32_t ptz_desc_matches_download(const ptz_desc_matches* m, int64_t* match_ptr, int32_t* idx_a, int32_t* idx_b, int32_t* dist2,
+                                             float* uv_a, float* uv_b)
+{
+  using namespace ptz;
+  if (!m || ((uv_a || uv_b) && !m->has_uv)) return PTZ_EINVAL;
+  if (match_ptr) memcpy(match_ptr, m->match_ptr.data(), sizeof(int64_t) * m->match_ptr.size());
+  const int64_t n = m->n_match;
+  if (n == 0 || !(idx_a || idx_b || dist2 || uv_a || uv_b)) return PTZ_OK;
+  PTZ_DEVICE_GUARD(m->device);
+  DescStream ds;
+  PTZ_HIP_TRY(ds.open(m->device));
+  if (idx_a) PTZ_HIP_TRY(hipMemcpyAsync(idx_a, m->d_idx_a, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
+  if (idx_b) PTZ_HIP_TRY(hipMemcpyAsync(idx_b, m->d_idx_b, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
+  if (dist2) PTZ_HIP_TRY(hipMemcpyAsync(dist2, m->d_dist2, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
+  if (uv_a) PTZ_HIP_TRY(hipMemcpyAsync(uv_a, m->d_uv_a, sizeof(float2) * n, hipMemcpyDeviceToHost, ds.st));
+  if (uv_b) PTZ_HIP_TRY(hipMemcpyAsync(uv_b, m->d_uv_b, sizeof(float2) * n, hipMemcpyDeviceToHost, ds.st));
+  PTZ_HIP_TRY(stream_wait(ds.st));
+  return PTZ_OK;
+}
+
+extern "C" int32_t ptz_desc_matches_device_ptrs(const ptz_desc_matches* m, const int64_t** d_match_ptr, const int32_t** d_idx_a,
+                                                const int32_t** d_idx_b, const int32_t** d_dist2, const float** d_uv_a, const float** d_uv_b)
+{
+  if (!m) return PTZ_EINVAL;
+  if (d_match_ptr) *d_match_ptr = m->d_match_ptr;
+  if (d_idx_a) *d_idx_a = m->d_idx_a;
+  if (d_idx_b) *d_idx_b = m->d_idx_b;
+  if (d_dist2) *d_dist2 = m->d_dist2;
+  if (d_uv_a) *d_uv_a = (const float*)m->d_uv_a;
+  if (d_uv_b) *d_uv_b = (const float*)m->d_uv_b;
+  return PTZ_OK;
+}
+
+extern "C" void ptz_desc_matches_destroy(ptz_desc_matches* m)
+{
+  if (!m) return;
+  ptz::DeviceGuard g(m->device);
+  delete m;
+}
+
+extern "C" int32_t ptz_debug_desc_dist2(const ptz_desc_set* A, int32_t img_a, const ptz_desc_set* B, int32_t img_b, int32_t* out)
+{
+  using namespace ptz;
+  if (!A || !B || A->device != B->device || A->D != B->D) return PTZ_EINVAL;
+  if (img_a < 0 || img_a >= A->n_img || img_b < 0 || img_b >= B->n_img) return PTZ_EINVAL;
+  const int64_t na = A->feat_ptr[img_a + 1] - A->feat_ptr[img_a], nb = B->feat_ptr[img_b + 1] - B->feat_ptr[img_b];
+  if (na * nb == 0) return PTZ_OK;
+  if (!out) return PTZ_EINVAL;
+  if (na * nb > INT32_MAX) return PTZ_ELIMIT;
+  clear_stale_error(__func__);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= A->device) return PTZ_ENODEVICE;
+  PTZ_DEVICE_GUARD(A->device);
+  const DescPair P = {A->row_off[img_a], B->row_off[img_b], 0, 0, 0, 0, (int32_t)na, (int32_t)nb};
+  const size_t o_dump = up256(sizeof(DescPair));
+  DescBlock ws;
+  if (ws.get(A->device, o_dump + sizeof(int32_t) * (size_t)(na * nb)) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  DescStream ds;
+  PTZ_HIP_TRY(ds.open(A->device));
+  PTZ_HIP_TRY(hipMemcpyAsync(ws.p, &P, sizeof(P), hipMemcpyHostToDevice, ds.st));
+  launch_top2<true>(A->KS, dim3(1, tiles_y(na, DESC_WG_Q)), ds.st, (const DescPair*)ws.p, 1, A->d_desc, A->d_norm, B->d_desc, B->d_norm,
+                    nullptr, (int32_t*)(ws.p + o_dump));
+  PTZ_HIP_TRY(hipGetLastError());
+  PTZ_HIP_TRY(hipMemcpyAsync(out, ws.p + o_dump, sizeof(int32_t) * (size_t)(na * nb), hipMemcpyDeviceToHost, ds.st));
+  PTZ_HIP_TRY(stream_wait(ds.st));
+  return PTZ_OK;
+}

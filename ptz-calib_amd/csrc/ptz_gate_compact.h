@@ -8,7 +8,8 @@
 namespace ptz {
 
 // d_cnt[p] = the non-zero mask bytes of pair p if d_found[p] == 1 and there are at least `need` of them, else 0;
-// d_out_ptr [n_pair + 1] = their exclusive scan; d_out_a / d_out_b (and d_out_index, nullable: the source positions) = the kept
+// d_out_ptr [n_pair + 1] = their exclusive scan; d_out_a / d_out_b (nullable together, d_a / d_b are then not read; and d_out_index,
+// nullable: the source positions) = the kept
 // matches of the pairs with d_cnt[p] > 0.  d_live (nullable): a device counter of the pairs that have work; where it reads 0 the three
 // launches return at once and write nothing -- for a caller that enqueues more rounds than its data may need and reads the
 // outputs of a round only for pairs that had work in it.

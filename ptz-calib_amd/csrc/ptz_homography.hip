@@ -286,8 +286,10 @@ __global__ __launch_bounds__(GATE_WG) void k_gate_scatter(int n_pair, const int6
     const unsigned long long bal = __ballot(in);
     if (in) {
       const int64_t at = o + __popcll(bal & ((1ull << lane) - 1ull));
-      out_a[at] = uv_a[base + i];
-      out_b[at] = uv_b[base + i];
+      if (out_a) {  // (nullable as a pair: the descriptor matcher compacts positions only)
+        out_a[at] = uv_a[base + i];
+        out_b[at] = uv_b[base + i];
+      }
       if (out_index) out_index[at] = static_cast<int32_t>(base + i);
     }
     o += __popcll(bal);

@@ -26,14 +26,21 @@ def image_name(i: int, ext: str = ".png") -> str:
     return f"img_{i:05d}{ext}"
 
 
-def write_features(feature_dir: str, names, kp_ptr, kp_xy, desc_dim: int = 0) -> None:
+def write_features(feature_dir: str, names, kp_ptr, kp_xy, desc_dim: int = 0, desc=None) -> None:
+    """desc: uint8 [n_kp, D] descriptors written behind the key points (COLMAP text SIFT); None: desc_dim zeros."""
     os.makedirs(feature_dir, exist_ok=True)
     for i, name in enumerate(names):
         pts = kp_xy[kp_ptr[i]:kp_ptr[i + 1]]
         with open(os.path.join(feature_dir, name + ".txt"), "w") as f:
-            f.write(f"{len(pts)} {desc_dim}\n")
-            for x, y in pts:
-                f.write(f"{float(x):.9g} {float(y):.9g} 1 0" + " 0" * desc_dim + "\n")
+            if desc is None:
+                f.write(f"{len(pts)} {desc_dim}\n")
+                for x, y in pts:
+                    f.write(f"{float(x):.9g} {float(y):.9g} 1 0" + " 0" * desc_dim + "\n")
+            else:
+                rows = np.asarray(desc[kp_ptr[i]:kp_ptr[i + 1]])
+                f.write(f"{len(pts)} {rows.shape[1]}\n")
+                for (x, y), d in zip(pts, rows):
+                    f.write(f"{float(x):.9g} {float(y):.9g} 1 0 " + " ".join(map(str, d.tolist())) + "\n")
 
 
 def write_matches(path: str, pairs, trailing_blank: bool = True) -> None:

@@ -4,6 +4,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -135,6 +136,161 @@ void ReadColmapMatches(const std::string& filepath, std::vector<std::vector<DMat
       }
     }
   }
+}
+
+bool ReadColmapDescriptors(const std::string& filepath, std::vector<unsigned char>& desc, int& dim)
+{
+  desc.clear();
+  std::ifstream fin(filepath);
+  if (!fin.good()) return false;
+  long num_kpts = 0, desc_dim = 0;
+  fin >> num_kpts >> desc_dim;
+  if (!fin || num_kpts < 0 || desc_dim < 0) return false;
+  if (num_kpts > 0 && dim != 0 && desc_dim != dim) return false;  // (an image without features fits any dimension)
+  std::vector<double> v(static_cast<size_t>(num_kpts) * static_cast<size_t>(desc_dim));
+  bool integral = true;
+  double x, y, scale, orientation;
+  for (long i = 0; i < num_kpts; ++i) {
+    fin >> x >> y >> scale >> orientation;
+    for (long j = 0; j < desc_dim; ++j) {
+      double& d = v[static_cast<size_t>(i * desc_dim + j)];
+      fin >> d;
+      integral = integral && d >= 0.0 && d <= 255.0 && d == std::floor(d);
+    }
+  }
+  if (!fin) return false;  // a short file
+  if (!integral) {
+    static bool warned = false;
+    if (!warned) fprintf(stderr, "[ptzcalib] ReadColmapDescriptors: %s holds values that are not integers in 0 .. 255; such files are quantised as clamp(rint(128 + 127 v), 0, 255)\n", filepath.c_str());
+    warned = true;
+  }
+  desc.resize(v.size());
+  for (size_t k = 0; k < v.size(); ++k)
+    desc[k] = static_cast<unsigned char>(integral ? v[k] : std::min(255.0, std::max(0.0, std::rint(128.0 + 127.0 * v[k]))));
+  if (num_kpts > 0 || dim == 0) dim = static_cast<int>(desc_dim);
+  return true;
+}
+
+bool WriteColmapMatches(const std::string& filepath, const std::vector<std::vector<DMatch>>& pairs_matches,
+                        const std::vector<std::pair<std::string, std::string>>& img_pairs_name)
+{
+  FILE* f = fopen(filepath.c_str(), "w");
+  if (!f) return false;
+  for (size_t p = 0; p < pairs_matches.size(); ++p) {
+    fprintf(f, "%s %s\n", img_pairs_name[p].first.c_str(), img_pairs_name[p].second.c_str());
+    for (const DMatch& m : pairs_matches[p]) fprintf(f, "%d %d\n", m.queryIdx, m.trainIdx);
+    fputc('\n', f);
+  }
+  return fclose(f) == 0;
+}
+
+namespace {
+
+// the descriptors of a list of images as one resident set (features of image m: ptr[m] .. ptr[m + 1])
+bool LoadDescSet(const std::string& dir, const std::vector<std::string>& fnames, int device_id, int& dim, std::vector<int64_t>& ptr,
+                 ptz_desc_set** set)
+{
+  std::vector<unsigned char> all, one;
+  ptr.assign(1, 0);
+  for (const std::string& fname : fnames) {
+    const std::string path = dir + "/" + fname + ".txt";
+    if (!ReadColmapDescriptors(path, one, dim)) {
+      fprintf(stderr, "[ptzcalib] MatchDescriptors: cannot read the descriptors of %s (missing or short file, or another dimension than the images before it)\n", path.c_str());
+      return false;
+    }
+    all.insert(all.end(), one.begin(), one.end());
+    ptr.push_back(ptr.back() + static_cast<int64_t>(dim > 0 ? one.size() / static_cast<size_t>(dim) : 0));
+  }
+  if (dim < 1) {
+    fprintf(stderr, "[ptzcalib] MatchDescriptors: the feature files of %s carry no descriptors\n", dir.c_str());
+    return false;
+  }
+  const int32_t rc = ptz_desc_set_create(static_cast<int32_t>(fnames.size()), ptr.data(), all.data(), dim, nullptr, device_id, set);
+  if (rc != PTZ_OK) fprintf(stderr, "[ptzcalib] MatchDescriptors: ptz_desc_set_create failed (%d)\n", rc);
+  return rc == PTZ_OK;
+}
+
+}  // namespace
+
+bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& fnames_a, const std::string& dir_b,
+                      const std::vector<std::string>& fnames_b, const std::vector<std::pair<long, long>>& pairs, const DescMatchOptions& options,
+                      bool transpose_back, std::vector<std::vector<DMatch>>& pairs_matches,
+                      std::vector<std::pair<std::string, std::string>>& img_pairs_name)
+{
+  pairs_matches.clear();
+  img_pairs_name.clear();
+  const bool one_set = dir_a == dir_b && fnames_a == fnames_b;
+  if (transpose_back && !one_set) return false;
+  int dim = 0;
+  std::vector<int64_t> ptr_a, ptr_b;
+  ptz_desc_set *set_a = nullptr, *set_b = nullptr;
+  if (!LoadDescSet(dir_a, fnames_a, options.device_id, dim, ptr_a, &set_a)) return false;
+  if (one_set) set_b = set_a;
+  else if (!LoadDescSet(dir_b, fnames_b, options.device_id, dim, ptr_b, &set_b)) { ptz_desc_set_destroy(set_a); return false; }
+  std::vector<int32_t> ia, ib;
+  for (const std::pair<long, long>& p : pairs) { ia.push_back(static_cast<int32_t>(p.first)); ib.push_back(static_cast<int32_t>(p.second)); }
+  ptz_desc_options o;
+  ptz_desc_options_default(&o);
+  o.ratio = options.ratio;
+  o.min_matches = options.min_matches;
+  o.device_id = options.device_id;
+  ptz_desc_matches* res = nullptr;
+  int32_t rc = ptz_desc_match_pairs(set_a, set_b, static_cast<int32_t>(pairs.size()), ia.data(), ib.data(), &o, &res);
+  std::vector<int64_t> mptr(pairs.size() + 1, 0);
+  std::vector<int32_t> qa, tb;
+  if (rc == PTZ_OK) {
+    const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(res));
+    qa.resize(std::max<size_t>(n, 1));
+    tb.resize(std::max<size_t>(n, 1));
+    rc = ptz_desc_matches_download(res, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
+  }
+  ptz_desc_matches_destroy(res);
+  if (!one_set) ptz_desc_set_destroy(set_b);
+  ptz_desc_set_destroy(set_a);
+  if (rc != PTZ_OK) {
+    fprintf(stderr, "[ptzcalib] MatchDescriptors: the device matcher failed (%d)\n", rc);
+    return false;
+  }
+  for (size_t p = 0; p < pairs.size(); ++p) {
+    if (mptr[p + 1] == mptr[p]) continue;  // a block without matches is not a block (ReadColmapMatches drops it)
+    std::vector<DMatch> ms;
+    for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) {
+      DMatch m;
+      m.queryIdx = qa[static_cast<size_t>(k)];
+      m.trainIdx = tb[static_cast<size_t>(k)];
+      ms.push_back(m);
+    }
+    pairs_matches.push_back(ms);
+    img_pairs_name.push_back({fnames_a[static_cast<size_t>(pairs[p].first)], fnames_b[static_cast<size_t>(pairs[p].second)]});
+  }
+  if (transpose_back) {  // + every block's (second, first) form, then all of them in table order (row = first image)
+    std::vector<std::pair<long, long>> key;
+    for (size_t p = 0; p < pairs.size(); ++p)
+      if (mptr[p + 1] != mptr[p]) key.push_back(pairs[p]);
+    const size_t n = pairs_matches.size();
+    for (size_t p = 0; p < n; ++p) {
+      std::vector<DMatch> ms;
+      for (const DMatch& m : pairs_matches[p]) {
+        DMatch t = m;
+        t.queryIdx = m.trainIdx;
+        t.trainIdx = m.queryIdx;
+        ms.push_back(t);
+      }
+      std::sort(ms.begin(), ms.end(), [](const DMatch& x, const DMatch& y) { return x.queryIdx < y.queryIdx; });  // (mutual matches: unique)
+      pairs_matches.push_back(ms);
+      img_pairs_name.push_back({img_pairs_name[p].second, img_pairs_name[p].first});
+      key.push_back({key[p].second, key[p].first});
+    }
+    std::vector<size_t> order(key.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&key](size_t x, size_t y) { return key[x] < key[y]; });
+    std::vector<std::vector<DMatch>> pm;
+    std::vector<std::pair<std::string, std::string>> nm;
+    for (size_t k : order) { pm.push_back(pairs_matches[k]); nm.push_back(img_pairs_name[k]); }
+    pairs_matches.swap(pm);
+    img_pairs_name.swap(nm);
+  }
+  return true;
 }
 
 // ---- camera JSON ------------------------------------------------------------------------------------------------------
@@ -309,12 +465,10 @@ void FillCellMatches(MatchesInfo& mi, const std::vector<DMatch>& ms, bool gated,
   mi.confidence = static_cast<int>(n) >= kMaxNumMatches ? 1.0f : static_cast<float>(n) / static_cast<float>(kMaxNumMatches);
 }
 
-bool LoadMatchesInfoHost(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
-                         std::vector<MatchesInfo>& matches_info, bool inliers, int min_inliers)
+bool BlocksToMatchesInfoHost(const std::vector<std::vector<DMatch>>& pairs_matches,
+                             const std::vector<std::pair<std::string, std::string>>& img_pairs_name, const std::vector<std::string>& fnames,
+                             const std::vector<ImageFeatures>& features, std::vector<MatchesInfo>& matches_info, bool inliers, int min_inliers)
 {
-  std::vector<std::vector<DMatch>> pairs_matches;
-  std::vector<std::pair<std::string, std::string>> img_pairs_name;
-  ReadColmapMatches(matches_path, pairs_matches, img_pairs_name);
   matches_info.clear();
   const size_t num_images = fnames.size();
   matches_info.resize(num_images * num_images);  // value-initialised cells: (0, 0), no matches, empty H, confidence 0
@@ -344,12 +498,20 @@ bool LoadMatchesInfoHost(const std::string& matches_path, const std::vector<std:
   return true;
 }
 
-bool LoadMatchesInfoDevice(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
-                           std::vector<MatchesInfo>& matches_info, int device_id, bool inliers, int min_inliers)
+bool LoadMatchesInfoHost(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                         std::vector<MatchesInfo>& matches_info, bool inliers, int min_inliers)
 {
   std::vector<std::vector<DMatch>> pairs_matches;
   std::vector<std::pair<std::string, std::string>> img_pairs_name;
   ReadColmapMatches(matches_path, pairs_matches, img_pairs_name);
+  return BlocksToMatchesInfoHost(pairs_matches, img_pairs_name, fnames, features, matches_info, inliers, min_inliers);
+}
+
+bool BlocksToMatchesInfoDevice(const std::vector<std::vector<DMatch>>& pairs_matches,
+                               const std::vector<std::pair<std::string, std::string>>& img_pairs_name, const std::vector<std::string>& fnames,
+                               const std::vector<ImageFeatures>& features, std::vector<MatchesInfo>& matches_info, int device_id, bool inliers,
+                               int min_inliers)
+{
   matches_info.clear();
   const size_t num_images = fnames.size();
   matches_info.resize(num_images * num_images);
@@ -405,7 +567,25 @@ bool LoadMatchesInfoDevice(const std::string& matches_path, const std::vector<st
   return true;
 }
 
+bool LoadMatchesInfoDevice(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                           std::vector<MatchesInfo>& matches_info, int device_id, bool inliers, int min_inliers)
+{
+  std::vector<std::vector<DMatch>> pairs_matches;
+  std::vector<std::pair<std::string, std::string>> img_pairs_name;
+  ReadColmapMatches(matches_path, pairs_matches, img_pairs_name);
+  return BlocksToMatchesInfoDevice(pairs_matches, img_pairs_name, fnames, features, matches_info, device_id, inliers, min_inliers);
+}
+
 }  // namespace
+
+bool LoadMatchesInfoFromBlocks(const std::vector<std::vector<DMatch>>& pairs_matches,
+                               const std::vector<std::pair<std::string, std::string>>& img_pairs_name, const std::vector<std::string>& fnames,
+                               const std::vector<ImageFeatures>& features, std::vector<MatchesInfo>& matches_info, int device_id, bool inliers,
+                               int min_inliers)
+{
+  return device_id < 0 ? BlocksToMatchesInfoHost(pairs_matches, img_pairs_name, fnames, features, matches_info, inliers, min_inliers)
+                       : BlocksToMatchesInfoDevice(pairs_matches, img_pairs_name, fnames, features, matches_info, device_id, inliers, min_inliers);
+}
 
 bool LoadMatchesInfo(const std::string& matches_path, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
                      std::vector<MatchesInfo>& matches_info)

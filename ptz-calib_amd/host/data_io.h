@@ -19,6 +19,35 @@ namespace ptzcalib {
 void ReadColmapFeatures(const std::string& filepath, std::vector<KeyPoint>& kpts);
 void ReadColmapMatches(const std::string& filepath, std::vector<std::vector<DMatch>>& pairs_matches,
                        std::vector<std::pair<std::string, std::string>>& img_pairs_name);
+// The uint8 descriptors behind the key points of a COLMAP text feature file, [n, dim] row-major.  A file whose values are all
+// integers in 0 .. 255 is taken as it is; any other (unit-norm float descriptors) is quantised as clamp(rint(128 + 127 v), 0, 255),
+// with one warning on stderr per run.  dim: 0 on entry takes the file's, otherwise the file's must equal it.  false: no file, a
+// short file, or a dimension mismatch.
+bool ReadColmapDescriptors(const std::string& filepath, std::vector<unsigned char>& desc, int& dim);
+// The inverse of ReadColmapMatches: a block "name_a name_b", its "queryIdx trainIdx" lines, a blank line -- after the last block too.
+bool WriteColmapMatches(const std::string& filepath, const std::vector<std::vector<DMatch>>& pairs_matches,
+                        const std::vector<std::pair<std::string, std::string>>& img_pairs_name);
+// The descriptor matcher on device `device_id` (ptz_desc_match_pairs): fills what ReadColmapMatches fills.  Pair p matches image
+// pairs[p].first of (dir_a, fnames_a) with image pairs[p].second of (dir_b, fnames_b); queryIdx is the feature of the first image,
+// trainIdx that of the second; blocks come in the pairs' order and a pair without matches has no block, as in a file.
+// transpose_back: also emit every pair's (second, first) block -- its matches swapped and sorted by the feature of the second
+// image (the matcher's (B, A) result: the rule is symmetric under cross_check) -- and put all blocks in table order (first image,
+// then second); needs dir_a == dir_b.
+struct DescMatchOptions {
+  double ratio = 0.8;
+  int min_matches = 8;
+  int device_id = 0;
+};
+bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& fnames_a, const std::string& dir_b,
+                      const std::vector<std::string>& fnames_b, const std::vector<std::pair<long, long>>& pairs, const DescMatchOptions& options,
+                      bool transpose_back, std::vector<std::vector<DMatch>>& pairs_matches,
+                      std::vector<std::pair<std::string, std::string>>& img_pairs_name);
+// LoadMatchesInfo / LoadInlierMatchesInfo on blocks already in memory (what they read from matches_path): device_id < 0: the host
+// estimator; inliers: the gated table.
+bool LoadMatchesInfoFromBlocks(const std::vector<std::vector<DMatch>>& pairs_matches,
+                               const std::vector<std::pair<std::string, std::string>>& img_pairs_name, const std::vector<std::string>& fnames,
+                               const std::vector<ImageFeatures>& features, std::vector<MatchesInfo>& matches_info, int device_id, bool inliers,
+                               int min_inliers);
 bool SaveToJson(const std::vector<Camera>& cameras, const std::vector<std::string>& names,
                 const std::vector<std::vector<Point2f>>& pixels_gt, const std::vector<std::vector<Point3d>>& pts3d_gt,
                 const std::string& filepath);

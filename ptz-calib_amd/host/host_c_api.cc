@@ -397,6 +397,8 @@ static char* DupText(const std::string& s)
 // cmd = "rewrite": a = camera json in, b = camera json out (ReadFromJson -> SaveToJson)  -> {ok, names}
 // cmd = "image_size": a = file -> {ok, width, height}
 // cmd = "json": a = JSON text -> {ok, dump}
+// cmd = "descriptors": a = feature file, b = expected dimension or "" -> {ok, dim, desc (flat)}
+// cmd = "rewrite_matches": a = matches file in, b = matches file out (ReadColmapMatches -> WriteColmapMatches) -> {ok, blocks}
 char* ptzh_io_probe(const char* cmd_c, const char* a_c, const char* b_c)
 {
   std::string cmd = cmd_c ? cmd_c : "";
@@ -578,6 +580,23 @@ char* ptzh_io_probe(const char* cmd_c, const char* a_c, const char* b_c)
     Json jn = Json::Array();
     for (const std::string& n : names) jn.push_back(Json::String(n));
     out["names"] = jn;
+  }
+  else if (cmd == "descriptors") {  // a = feature file, b = the dimension expected ("" or "0": the file's) -> {ok, dim, desc}
+    std::vector<unsigned char> desc;
+    int dim = atoi(b.c_str());
+    const bool ok = ReadColmapDescriptors(a, desc, dim);
+    out["ok"] = Json::Bool(ok);
+    out["dim"] = Json::Int(dim);
+    Json jd = Json::Array();
+    for (unsigned char v : desc) jd.push_back(Json::Int(v));
+    out["desc"] = jd;
+  }
+  else if (cmd == "rewrite_matches") {  // a = matches file in, b = matches file out (ReadColmapMatches -> WriteColmapMatches) -> {ok, blocks}
+    std::vector<std::vector<DMatch>> pm;
+    std::vector<std::pair<std::string, std::string>> names;
+    ReadColmapMatches(a, pm, names);
+    out["ok"] = Json::Bool(WriteColmapMatches(b, pm, names));
+    out["blocks"] = Json::Int(static_cast<long long>(pm.size()));
   }
   else out["ok"] = Json::Bool(false);
   return DupText(out.dump(4));

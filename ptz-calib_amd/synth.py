@@ -896,3 +896,53 @@ _MT_SCENES, _MT_KW = None, None
 
 def _match_table_job(i):
     return make_match_table(_MT_SCENES[i], **_MT_KW)
+
+
+# ------------------------------------------------------------------------------------------ descriptors (matcher input)
+def _feature_tracks(scene_or_table):
+    """(kp_ptr, kp_xy, track id per feature, image size) in the feature order of make_match_table.  A Scene knows its tracks; for a
+    MatchTable they are the connected components of its matches."""
+    if isinstance(scene_or_table, Scene):
+        sc = scene_or_table
+        counts = np.bincount(sc.obs_cam, minlength=sc.n_cam)
+        kp_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        order = np.argsort(sc.obs_cam, kind="stable")
+        return kp_ptr, np.ascontiguousarray(sc.obs_uv[order], dtype=np.float32), np.asarray(sc.obs_ray)[order].astype(np.int64), (sc.width, sc.height)
+    tb = scene_or_table
+    n = int(tb.kp_ptr[-1])
+    parent = np.arange(n, dtype=np.int64)
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    pair_of = np.repeat(np.arange(tb.n_pairs), np.diff(tb.match_ptr))
+    fa = tb.kp_ptr[tb.src[pair_of]] + tb.q
+    fb = tb.kp_ptr[tb.dst[pair_of]] + tb.t
+    for x, y in zip(fa.tolist(), fb.tolist()):
+        rx, ry = find(x), find(y)
+        if rx != ry:
+            parent[max(rx, ry)] = min(rx, ry)
+    roots = np.array([find(x) for x in range(n)], dtype=np.int64)
+    return tb.kp_ptr, tb.kp_xy, np.unique(roots, return_inverse=True)[1].astype(np.int64), (int(tb.img_wh[0, 0]), int(tb.img_wh[0, 1]))
+
+
+def make_descriptors(scene_or_table, D: int = 128, noise: int = 12, n_distractors: int = 50, seed: int = 0):
+    """uint8 descriptors for the features of a scene's match table: one uniform random descriptor per track, every observation a
+    copy with uniform integer noise in [-noise, noise], clipped to 0..255; n_distractors unmatched random features (uniform
+    descriptors, uniform pixels) are appended to every image, so the table's feature indices stay valid.
+    Returns (feat_ptr int64 [n_img + 1], desc uint8 [n_feat, D], kp_xy float32 [n_feat, 2])."""
+    kp_ptr, kp_xy, track, (w, h) = _feature_tracks(scene_or_table)
+    rng = np.random.default_rng(seed)
+    n_img = len(kp_ptr) - 1
+    base = rng.integers(0, 256, (int(track.max()) + 1 if len(track) else 0, D), dtype=np.int64)
+    obs = np.clip(base[track] + rng.integers(-noise, noise + 1, (len(track), D)), 0, 255).astype(np.uint8)
+    descs, kps = [], []
+    for i in range(n_img):
+        sl = slice(int(kp_ptr[i]), int(kp_ptr[i + 1]))
+        descs += [obs[sl], rng.integers(0, 256, (n_distractors, D), dtype=np.uint8)]
+        kps += [kp_xy[sl], rng.uniform([0, 0], [w, h], (n_distractors, 2)).astype(np.float32)]
+    feat_ptr = (np.asarray(kp_ptr, dtype=np.int64) + n_distractors * np.arange(n_img + 1)).astype(np.int64)
+    return feat_ptr, np.concatenate(descs) if descs else np.zeros((0, D), np.uint8), \
+        np.concatenate(kps).astype(np.float32) if kps else np.zeros((0, 2), np.float32)
