@@ -29,6 +29,7 @@
 
 #include "ptz_common.h"
 #include "ptz_pool.h"
+#include "ptz_host_batch.h"
 #include "ptz_ba_cov.h"
 #include "ptz_ba_cov_georef.h"
 
@@ -677,7 +678,7 @@ size_t cov_layout(const CovVariant& v, size_t count, size_t np, size_t cams, siz
 {
   const size_t nt = np / NB, ne = (size_t)v.nf * v.nf, geo = v.centre ? 1 : 0, D = sizeof(double);
   size_t o = 0;
-  auto take = [&o](size_t& slot, size_t bytes) { slot = o; o += (bytes + 255) & ~(size_t)255; };
+  auto take = [&o](size_t& slot, size_t bytes) { slot = o; o += up256(bytes); };
   take(l.A, D * count * np * np); take(l.T, D * count * np * np); take(l.X, D * count * np * np); take(l.Si, D * count * np * np);
   take(l.Ldiag, D * count * nt * NB * NB);
   take(l.Linv, D * count * nt * NB * NB);
@@ -702,17 +703,6 @@ size_t cov_layout(const CovVariant& v, size_t count, size_t np, size_t cams, siz
   return o;
 }
 
-// what a run holds until it returns: the group's workspace and the two timing events, released once the stream is idle
-struct CovHeld {
-  int dev; void* base = nullptr; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~CovHeld()
-  {
-    (void)stream_wait(st);
-    if (base) ptzpool::dev_release(dev, base);
-    if (e0) ptzpool::event_release(dev, true, e0);
-    if (e1) ptzpool::event_release(dev, true, e1);
-  }
-};
 // bytes of workspace per group of problems (PTZ_BA_COV_MAX_MB, default 2048)
 size_t cov_budget()
 {
@@ -726,10 +716,7 @@ int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const Ba
 {
   const int NE = v.nf * v.nf;
   const size_t budget = cov_budget();
-  CovHeld h;
-  h.dev = in.device; h.st = st;
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  CallHeld h(st);  // a group's workspace and the two timing events, released once the stream is idle
   double total_ms = 0;
   for (int first = 0; first < in.n_scene;) {
     // the group: problems first .. first + count - 1, as many as the budget holds (one at least)
@@ -751,8 +738,11 @@ int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const Ba
     w.max_waves = (max_ray + 63) / 64 + 1;
     w.pixel_sigma = pixel_sigma; w.annotation_sigma = annotation_sigma;
     (void)cov_layout(v, (size_t)count, (size_t)w.np, cams, obs, o3, (size_t)w.max_waves, l);
-    if (ptzpool::dev_acquire(h.dev, bytes, &h.base) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-    char* base = static_cast<char*>(h.base);
+    if (const int rc = h.acquire(in.device, bytes)) {  // (the group before gives its workspace back here)
+      if (rc == PTZ_ENOMEM) (void)hipGetLastError();
+      return rc;
+    }
+    char* base = h.base;
     auto at = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
     w.A = at(l.A); w.T = at(l.T); w.X = at(l.X); w.Si = at(l.Si);
     w.Linv = at(l.Linv); w.dsc = at(l.dsc); w.camblk = at(l.camblk); w.EY = at(l.EY); w.Dg = at(l.Dg);
@@ -766,9 +756,9 @@ int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const Ba
     PTZ_HIP_TRY(hipMemsetAsync(ints, 0, sizeof(int) * l.n_ints, st));
     PTZ_HIP_TRY(hipMemcpyAsync(ints + l.i_gauge, hg.data(), sizeof(int) * count, hipMemcpyHostToDevice, st));
     PTZ_HIP_TRY(hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)count * w.np * w.np, st));
-    PTZ_HIP_TRY(hipEventRecord(h.e0, st));
+    PTZ_HIP_TRY(hipEventRecord(h.ev[0], st));
     v.enqueue(in, geo, w, cb, at(l.x), max_cam, max_ray, max_n, st);
-    PTZ_HIP_TRY(hipEventRecord(h.e1, st));
+    PTZ_HIP_TRY(hipEventRecord(h.ev[1], st));
     // the group's results come back into buffers of their own: only problems whose status is OK reach the caller's arrays
     std::vector<double> hc(cams * NE), hsig((size_t)v.n_sig * count), hcen(v.centre ? 9 * (size_t)count : 0);
     std::vector<int> hi(l.n_ints);
@@ -778,9 +768,7 @@ int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const Ba
     PTZ_HIP_TRY(hipMemcpyAsync(hi.data(), ints, sizeof(int) * hi.size(), hipMemcpyDeviceToHost, st));
     PTZ_HIP_TRY(stream_wait(st));
     PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-    total_ms += ms;
+    total_ms += h.elapsed_ms();
     for (int k = 0; k < count; ++k) {
       const BaCovScene& s = hs[first + k];
       const int fail = hi[l.i_fail + k], flags = hi[l.i_flags + k], n_ann = v.centre ? hi[l.i_n_ann + k] : 0;
@@ -792,8 +780,6 @@ int cov_run(const CovVariant& v, const BaCovIn& in, const BaGeoIn& geo, const Ba
       if (v.centre) memcpy(cov_centre + 9 * (size_t)(first + k), hcen.data() + 9 * (size_t)k, sizeof(double) * 9);
       memcpy(sigma0 + (size_t)v.n_sig * (first + k), hsig.data() + (size_t)v.n_sig * k, sizeof(double) * v.n_sig);
     }
-    ptzpool::dev_release(h.dev, h.base);
-    h.base = nullptr;
     first += count;
   }
   if (device_ms) *device_ms = total_ms;

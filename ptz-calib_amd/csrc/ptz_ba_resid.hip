@@ -10,6 +10,7 @@
 
 #include "ptz_common.h"
 #include "ptz_pool.h"
+#include "ptz_host_batch.h"
 #include "ptz_ba_resid.h"
 
 namespace ptz {
@@ -233,17 +234,6 @@ __global__ __launch_bounds__(PROBLEM_BLOCK) void k_resid_problem(BaCovIn in, Res
   if (tid == 0) { w.thr[g] = t; w.nrej[g] = s_cnt; }
 }
 
-struct ResidHeld {
-  int dev; void* base = nullptr; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~ResidHeld()
-  {
-    (void)stream_wait(st);
-    if (base) ptzpool::dev_release(dev, base);
-    if (e0) ptzpool::event_release(dev, true, e0);
-    if (e1) ptzpool::event_release(dev, true, e1);
-  }
-};
-
 }  // namespace
 
 int ba_resid_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, const int* ray_perm, hipStream_t st, const BaResidOut& out,
@@ -262,19 +252,19 @@ int ba_resid_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, co
   }
   // one block: results first (they come back in one copy), scratch behind
   size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  auto take = [&o](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
   const size_t D = sizeof(double), I = sizeof(int);
   const size_t o_err = take(D * TO), o_rmax = take(D * TR), o_vrms = take(D * TC), o_vmax = take(D * TC), o_rms = take(D * n), o_med = take(D * n),
                o_rms3 = take(D * n), o_thr = take(D * n), o_e3 = take(D * T3), o_rworst = take(I * TR), o_vcnt = take(I * TC), o_nrej = take(I * n),
                o_rej = take(TO);
   const size_t result_bytes = o;
   const size_t o_camblk = take(D * TC * CAMBLK), o_tlw = take(D * (size_t)n * TLWBLK), o_eint = take(D * TO), o_cstart = take(I * TR);
-  ResidHeld h;
-  h.dev = in.device; h.st = st;
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
-  if (ptzpool::dev_acquire(h.dev, std::max<size_t>(o, 256), &h.base) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  char* base = static_cast<char*>(h.base);
+  CallHeld h(st);
+  if (const int rc = h.acquire(in.device, std::max<size_t>(o, 256))) {
+    if (rc == PTZ_ENOMEM) (void)hipGetLastError();
+    return rc;
+  }
+  char* base = h.base;
   ResidWork w;
   auto dp = [&](size_t off) { return reinterpret_cast<double*>(base + off); };
   auto ip = [&](size_t off) { return reinterpret_cast<int*>(base + off); };
@@ -288,7 +278,7 @@ int ba_resid_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, co
   w.want_median = (out.median || (out.select && trim_needs_median(out.rule))) ? 1 : 0;
   w.has_o3 = (geo.tlw_x && T3 > 0) ? 1 : 0;
   PTZ_HIP_TRY(hipMemsetAsync(base, 0, o, st));
-  PTZ_HIP_TRY(hipEventRecord(h.e0, st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], st));
   if (n > 0 && TO > 0) {
     hipLaunchKernelGGL(k_resid_cam, dim3((max_cam + 63) / 64, n), dim3(64), 0, st, in, geo, w);
     hipLaunchKernelGGL(k_resid_order, dim3(n), dim3(256), 0, st, in, w);
@@ -305,14 +295,12 @@ int ba_resid_run(const BaCovIn& in, const BaGeoIn& geo, const BaCovScene* hs, co
     }
     hipLaunchKernelGGL(k_resid_problem, dim3(n), dim3(PROBLEM_BLOCK), 0, st, in, w);
   }
-  PTZ_HIP_TRY(hipEventRecord(h.e1, st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], st));
   std::vector<char> hb(result_bytes);
   PTZ_HIP_TRY(hipMemcpyAsync(hb.data(), base, result_bytes, hipMemcpyDeviceToHost, st));
   PTZ_HIP_TRY(stream_wait(st));
   PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   // to the caller's arrays: concatenated at the real extents
   auto hd = [&](size_t off) { return reinterpret_cast<const double*>(hb.data() + off); };
   auto hi = [&](size_t off) { return reinterpret_cast<const int*>(hb.data() + off); };

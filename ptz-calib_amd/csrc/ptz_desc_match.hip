@@ -21,6 +21,7 @@
 #include "ptz_desc_match.h"
 #include "ptz_gate_compact.h"
 #include "ptz_pool.h"
+#include "ptz_block_layout.h"
 
 namespace ptz {
 namespace {
@@ -221,7 +222,6 @@ void launch_top2(int KS, dim3 grid, hipStream_t st, const DescPair* pairs, int d
   }
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned tiles_y(int64_t n, int per) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + per - 1) / per, 1), 65535); }
 
 // a call's stream and timing events, from the pool

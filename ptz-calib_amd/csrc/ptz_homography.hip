@@ -25,6 +25,7 @@
 #include "ptz_homography.h"
 #include "ptz_gate_compact.h"
 #include "ptz_pool.h"
+#include "ptz_host_batch.h"
 
 namespace ptz {
 namespace {
@@ -402,29 +403,14 @@ extern "C" int32_t ptz_homography_ransac_batch(int32_t n_pair, const int64_t* ma
   std::vector<int32_t> tab, order;
   host_bounds_and_order(n_pair, match_ptr, boff, tab, order);
 
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nmx = nm > 0 ? (size_t)nm : 1;
-  const size_t o_ptr = 0, o_ord = o_ptr + up(sizeof(int64_t) * (n_pair + 1)), o_boff = o_ord + up(sizeof(int32_t) * n_pair),
-               o_tab = o_boff + up(sizeof(int64_t) * n_pair), o_src = o_tab + up(sizeof(int32_t) * tab.size()),
-               o_dst = o_src + up(sizeof(float) * 2 * nmx), o_H = o_dst + up(sizeof(float) * 2 * nmx),
-               o_found = o_H + up(sizeof(double) * 9 * n_pair), o_mask = o_found + up(sizeof(int32_t) * n_pair),
-               o_inl = o_mask + up(nmx), total = o_inl + up(sizeof(int32_t) * nmx);
-  struct Held {
-    int dev; char* base = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-    }
-  } h;
-  h.dev = device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  const size_t o_ptr = 0, o_ord = o_ptr + up256(sizeof(int64_t) * (n_pair + 1)), o_boff = o_ord + up256(sizeof(int32_t) * n_pair),
+               o_tab = o_boff + up256(sizeof(int64_t) * n_pair), o_src = o_tab + up256(sizeof(int32_t) * tab.size()),
+               o_dst = o_src + up256(sizeof(float) * 2 * nmx), o_H = o_dst + up256(sizeof(float) * 2 * nmx),
+               o_found = o_H + up256(sizeof(double) * 9 * n_pair), o_mask = o_found + up256(sizeof(int32_t) * n_pair),
+               o_inl = o_mask + up256(nmx), total = o_inl + up256(sizeof(int32_t) * nmx);
+  CallHeld h;
+  if (const int32_t rc = h.acquire(device_id, total)) return rc;
   char* b = h.base;
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_ptr, match_ptr, sizeof(int64_t) * (n_pair + 1), hipMemcpyHostToDevice, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_ord, order.data(), sizeof(int32_t) * n_pair, hipMemcpyHostToDevice, h.st));
@@ -435,13 +421,13 @@ extern "C" int32_t ptz_homography_ransac_batch(int32_t n_pair, const int64_t* ma
     PTZ_HIP_TRY(hipMemcpyAsync(b + o_dst, dst_uv, sizeof(float) * 2 * nm, hipMemcpyHostToDevice, h.st));
   }
   uint8_t* d_mask = inlier_mask ? (uint8_t*)(b + o_mask) : nullptr;
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
   hipLaunchKernelGGL(k_homography_ransac, dim3(n_pair), dim3(HB), 0, h.st, (const int64_t*)(b + o_ptr), (const int32_t*)(b + o_ord),
                      (const float*)(b + o_src), (const float*)(b + o_dst), ransac_thresh * ransac_thresh,
                      (const int64_t*)(b + o_boff), (const int32_t*)(b + o_tab), (double*)(b + o_H), (int32_t*)(b + o_found), d_mask,
                      (int32_t*)(b + o_inl), INT32_MAX, nm);
   PTZ_HIP_TRY(hipGetLastError());
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   std::vector<double> Hd(9 * (size_t)n_pair);
   std::vector<uint8_t> md(inlier_mask ? nmx : 0);
   PTZ_HIP_TRY(hipMemcpyAsync(Hd.data(), b + o_H, sizeof(double) * 9 * n_pair, hipMemcpyDeviceToHost, h.st));
@@ -449,9 +435,7 @@ extern "C" int32_t ptz_homography_ransac_batch(int32_t n_pair, const int64_t* ma
   if (inlier_mask && nm > 0) PTZ_HIP_TRY(hipMemcpyAsync(md.data(), d_mask, nm, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   // H and mask of a pair that is not found stay untouched, as with the host estimator
   for (int p = 0; p < n_pair; ++p) {
     if (!found[p]) continue;
@@ -505,11 +489,10 @@ extern "C" int32_t ptz_match_gate_create(int32_t max_pairs, int64_t max_matches,
   PTZ_DEVICE_GUARD(device_id);
   std::vector<int32_t> tab;
   gate_table(max_pair_matches, tab);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nmx = (size_t)std::max<int64_t>(max_matches, 1);
-  const size_t o_tab = 0, o_boff = o_tab + up(sizeof(int32_t) * tab.size()), o_cnt = o_boff + up(sizeof(int64_t) * max_pairs),
-               o_inl = o_cnt + up(sizeof(int32_t) * max_pairs), o_mask = o_inl + up(sizeof(int32_t) * nmx), o_H = o_mask + up(nmx),
-               total = o_H + up(sizeof(double) * 9 * max_pairs);
+  const size_t o_tab = 0, o_boff = o_tab + up256(sizeof(int32_t) * tab.size()), o_cnt = o_boff + up256(sizeof(int64_t) * max_pairs),
+               o_inl = o_cnt + up256(sizeof(int32_t) * max_pairs), o_mask = o_inl + up256(sizeof(int32_t) * nmx), o_H = o_mask + up256(nmx),
+               total = o_H + up256(sizeof(double) * 9 * max_pairs);
   std::unique_ptr<ptz_match_gate> g(new ptz_match_gate());
   g->device = device_id; g->max_pairs = max_pairs; g->max_matches = max_matches; g->max_pair_matches = max_pair_matches;
   void* blk = nullptr;
@@ -580,41 +563,26 @@ extern "C" int32_t ptz_match_gate_run(ptz_match_gate* g, int32_t n_pair, const i
   if (device_ms) *device_ms = 0;
   clear_stale_error(__func__);
   PTZ_DEVICE_GUARD(g->device);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nmx = nm > 0 ? (size_t)nm : 1, np1 = (size_t)n_pair + 1;
-  const size_t o_ptr = 0, o_a = o_ptr + up(sizeof(int64_t) * np1), o_b = o_a + up(sizeof(float) * 2 * nmx),
-               o_H = o_b + up(sizeof(float) * 2 * nmx), o_found = o_H + up(sizeof(double) * 9 * np1), o_mask = o_found + up(sizeof(int32_t) * np1),
-               o_optr = o_mask + up(nmx), o_oa = o_optr + up(sizeof(int64_t) * np1), o_ob = o_oa + up(sizeof(float) * 2 * nmx),
-               o_oi = o_ob + up(sizeof(float) * 2 * nmx), total = o_oi + up(sizeof(int32_t) * nmx);
-  struct Held {
-    int dev; char* base = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-    }
-  } h;
-  h.dev = g->device;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  const size_t o_ptr = 0, o_a = o_ptr + up256(sizeof(int64_t) * np1), o_b = o_a + up256(sizeof(float) * 2 * nmx),
+               o_H = o_b + up256(sizeof(float) * 2 * nmx), o_found = o_H + up256(sizeof(double) * 9 * np1), o_mask = o_found + up256(sizeof(int32_t) * np1),
+               o_optr = o_mask + up256(nmx), o_oa = o_optr + up256(sizeof(int64_t) * np1), o_ob = o_oa + up256(sizeof(float) * 2 * nmx),
+               o_oi = o_ob + up256(sizeof(float) * 2 * nmx), total = o_oi + up256(sizeof(int32_t) * nmx);
+  CallHeld h;
+  if (const int32_t rc = h.acquire(g->device, total)) return rc;
   char* b = h.base;
   if (n_pair > 0) PTZ_HIP_TRY(hipMemcpyAsync(b + o_ptr, match_ptr, sizeof(int64_t) * np1, hipMemcpyHostToDevice, h.st));
   if (nm > 0) {
     PTZ_HIP_TRY(hipMemcpyAsync(b + o_a, uv_a, sizeof(float) * 2 * nm, hipMemcpyHostToDevice, h.st));
     PTZ_HIP_TRY(hipMemcpyAsync(b + o_b, uv_b, sizeof(float) * 2 * nm, hipMemcpyHostToDevice, h.st));
   }
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
   if (const int32_t rc = ptz_match_gate_run_device(g, n_pair, (const int64_t*)(b + o_ptr), (const float*)(b + o_a), (const float*)(b + o_b),
                                                    ransac_thresh, min_inliers, (double*)(b + o_H), (int32_t*)(b + o_found),
                                                    (uint8_t*)(b + o_mask), (int64_t*)(b + o_optr), (float*)(b + o_oa), (float*)(b + o_ob),
                                                    (int32_t*)(b + o_oi), h.st))
     return rc;
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   std::vector<double> Hd(H ? 9 * (size_t)n_pair : 0);
   std::vector<uint8_t> md(mask ? nmx : 0);
   if (H && n_pair > 0) PTZ_HIP_TRY(hipMemcpyAsync(Hd.data(), b + o_H, sizeof(double) * 9 * n_pair, hipMemcpyDeviceToHost, h.st));
@@ -631,9 +599,7 @@ extern "C" int32_t ptz_match_gate_run(ptz_match_gate* g, int32_t n_pair, const i
     if (out_index) PTZ_HIP_TRY(hipMemcpyAsync(out_index, b + o_oi, sizeof(int32_t) * kept, hipMemcpyDeviceToHost, h.st));
     PTZ_HIP_TRY(stream_wait(h.st));
   }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   // H and mask of a pair without a model stay untouched, as with ptz_homography_ransac_batch
   for (int p = 0; p < n_pair; ++p) {
     if (found[p] != 1) continue;
@@ -671,35 +637,19 @@ extern "C" int32_t ptz_krt_solve_batch_gated(int32_t n_query, const int64_t* mat
 
   // one pooled block: [offsets | order | table offsets | tables | pixels | H | found | mask | inlier lists | kept counts |
   //                    compacted CSR | cameras | summaries | accepted]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nmx = nm > 0 ? (size_t)nm : 1, nq = (size_t)n_query;
-  const size_t o_ptr = 0, o_ord = o_ptr + up(sizeof(int64_t) * (nq + 1)), o_boff = o_ord + up(sizeof(int32_t) * nq),
-               o_tab = o_boff + up(sizeof(int64_t) * nq), o_ref = o_tab + up(sizeof(int32_t) * tab.size()),
-               o_cur = o_ref + up(sizeof(float) * 2 * nmx), o_H = o_cur + up(sizeof(float) * 2 * nmx),
-               o_found = o_H + up(sizeof(double) * 9 * nq), o_mask = o_found + up(sizeof(int32_t) * nq), o_inl = o_mask + up(nmx),
-               o_cnt = o_inl + up(sizeof(int32_t) * nmx), o_optr = o_cnt + up(sizeof(int32_t) * nq),
-               o_oref = o_optr + up(sizeof(int64_t) * (nq + 1)), o_ocur = o_oref + up(sizeof(float) * 2 * nmx),
-               o_cref = o_ocur + up(sizeof(float) * 2 * nmx), o_ccur = o_cref + up(sizeof(double) * 15 * nq),
-               o_sum = o_ccur + up(sizeof(double) * 15 * nq), o_acc = o_sum + up(sizeof(ptz_lm_summary) * nq),
-               total = o_acc + up(sizeof(int32_t) * nq);
-  struct Held {
-    int dev; char* base = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-      ptzpool::event_release(dev, true, e2);
-    }
-  } h;
-  h.dev = o.device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e2));
+  const size_t o_ptr = 0, o_ord = o_ptr + up256(sizeof(int64_t) * (nq + 1)), o_boff = o_ord + up256(sizeof(int32_t) * nq),
+               o_tab = o_boff + up256(sizeof(int64_t) * nq), o_ref = o_tab + up256(sizeof(int32_t) * tab.size()),
+               o_cur = o_ref + up256(sizeof(float) * 2 * nmx), o_H = o_cur + up256(sizeof(float) * 2 * nmx),
+               o_found = o_H + up256(sizeof(double) * 9 * nq), o_mask = o_found + up256(sizeof(int32_t) * nq), o_inl = o_mask + up256(nmx),
+               o_cnt = o_inl + up256(sizeof(int32_t) * nmx), o_optr = o_cnt + up256(sizeof(int32_t) * nq),
+               o_oref = o_optr + up256(sizeof(int64_t) * (nq + 1)), o_ocur = o_oref + up256(sizeof(float) * 2 * nmx),
+               o_cref = o_ocur + up256(sizeof(float) * 2 * nmx), o_ccur = o_cref + up256(sizeof(double) * 15 * nq),
+               o_sum = o_ccur + up256(sizeof(double) * 15 * nq), o_acc = o_sum + up256(sizeof(ptz_lm_summary) * nq),
+               total = o_acc + up256(sizeof(int32_t) * nq);
+  CallHeld h;
+  if (const int32_t rc = h.acquire(o.device_id, total)) return rc;
+  PTZ_HIP_TRY(h.third_event());
   char* b = h.base;
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_ptr, match_ptr, sizeof(int64_t) * (nq + 1), hipMemcpyHostToDevice, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_ord, order.data(), sizeof(int32_t) * nq, hipMemcpyHostToDevice, h.st));
@@ -711,19 +661,19 @@ extern "C" int32_t ptz_krt_solve_batch_gated(int32_t n_query, const int64_t* mat
   }
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_cref, cam_ref, sizeof(double) * 15 * nq, hipMemcpyHostToDevice, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(b + o_ccur, cam_cur, sizeof(double) * 15 * nq, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
   enqueue_gate(n_query, (const int64_t*)(b + o_ptr), (const int32_t*)(b + o_ord), (const int64_t*)(b + o_boff), (const int32_t*)(b + o_tab),
                (const float*)(b + o_ref), (const float*)(b + o_cur), ransac_thresh, INT32_MAX, nm, min_inliers, (double*)(b + o_H),
                (int32_t*)(b + o_found), (uint8_t*)(b + o_mask), (int32_t*)(b + o_inl), (int32_t*)(b + o_cnt), (int64_t*)(b + o_optr),
                (float*)(b + o_oref), (float*)(b + o_ocur), nullptr, h.st);
   PTZ_HIP_TRY(hipGetLastError());
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   // the LM of ptz_krt_solve_batch on the compacted CSR: same launch path, same stream
   if (const int32_t rc = ptz_krt_solve_batch_device(n_query, (const int64_t*)(b + o_optr), (const float*)(b + o_oref), (const float*)(b + o_ocur),
                                                     nullptr, nullptr, nullptr, (const double*)(b + o_cref), (double*)(b + o_ccur), factor_type,
                                                     max_reproj_error, &o, (ptz_lm_summary*)(b + o_sum), (int32_t*)(b + o_acc), h.st))
     return rc;
-  PTZ_HIP_TRY(hipEventRecord(h.e2, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[2], h.st));
   std::vector<double> Hd(H ? 9 * nq : 0);
   std::vector<int32_t> fd(nq);
   std::vector<uint8_t> md(inlier_mask ? nmx : 0);
@@ -736,11 +686,7 @@ extern "C" int32_t ptz_krt_solve_batch_gated(int32_t n_query, const int64_t* mat
   PTZ_HIP_TRY(hipMemcpyAsync(accepted, b + o_acc, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a solve
-  float ms = 0;
-  if (device_ms) {
-    (void)hipEventElapsedTime(&ms, h.e0, h.e1); device_ms[0] = ms;
-    (void)hipEventElapsedTime(&ms, h.e1, h.e2); device_ms[1] = ms;
-  }
+  if (device_ms) { device_ms[0] = h.elapsed_ms(0); device_ms[1] = h.elapsed_ms(1); }
   // H of a query without a model stays untouched, as with ptz_homography_ransac_batch; inlier_mask is the KEPT set: the
   // estimator's mask of a query that passes, zeros for every other query
   for (int q = 0; q < n_query; ++q) {

@@ -389,21 +389,21 @@ inline int group_size(int n_query, int requested)
   return n_query >= 16384 ? 16 : 64;
 }
 
-// one launch over device-resident queries (all pointers are device pointers; d_pptr = nullptr: no 2D-3D constraints)
-void launch_krt(int n_query, const long long* d_ptr, const float2* d_ref, const float2* d_cur, const long long* d_pptr,
-                const float2* d_puv, const double* d_pxyz, const double* d_cref, double* d_ccur, int factor_type, const KrtOpt& ko,
-                ptz_lm_summary* d_sum, int* d_acc, hipStream_t st, const long long* d_delta = nullptr, const int* d_active = nullptr)
+// one launch over a device-resident batch; d_delta (nullable): per query, where its uv_cur range lies from its uv_ref range
+void launch_krt(const KrtBatch& in, int factor_type, const KrtOpt& ko, ptz_lm_summary* d_sum, int* d_acc, hipStream_t st,
+                const long long* d_delta = nullptr, const int* d_active = nullptr)
 {
+  const int n_query = in.n_query;
   const int G = group_size(n_query, ko.lanes_per_query);
   const int qpb = 256 / G;
   const dim3 grid((n_query + qpb - 1) / qpb), block(256);
-  const bool p3 = d_pptr != nullptr;
+  const bool p3 = in.point_ptr != nullptr;
 #define PTZ_KRT_LAUNCH(T, P)                                                                                                   \
   do {                                                                                                                         \
-    if (G == 16) hipLaunchKernelGGL((k_krt<T, P, 16>), grid, block, 0, st, n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, \
-                                    d_cref, d_ccur, ko, d_sum, d_acc, d_delta, d_active);                                      \
-    else hipLaunchKernelGGL((k_krt<T, P, 64>), grid, block, 0, st, n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, d_cref, \
-                            d_ccur, ko, d_sum, d_acc, d_delta, d_active);                                                      \
+    if (G == 16) hipLaunchKernelGGL((k_krt<T, P, 16>), grid, block, 0, st, n_query, in.match_ptr, in.uv_ref, in.uv_cur,  \
+                                    in.point_ptr, in.pt_uv, in.pt_xyz, in.cam_ref, in.cam_cur, ko, d_sum, d_acc, d_delta, d_active); \
+    else hipLaunchKernelGGL((k_krt<T, P, 64>), grid, block, 0, st, n_query, in.match_ptr, in.uv_ref, in.uv_cur, in.point_ptr,  \
+                            in.pt_uv, in.pt_xyz, in.cam_ref, in.cam_cur, ko, d_sum, d_acc, d_delta, d_active);                 \
   } while (0)
   switch (factor_type * 2 + (p3 ? 1 : 0)) {
     case 0: PTZ_KRT_LAUNCH(0, false); break;
@@ -422,15 +422,67 @@ void launch_krt(int n_query, const long long* d_ptr, const float2* d_ref, const 
 
 int krt_group_size(int n_query, int requested) { return group_size(n_query, requested); }
 
-void krt_enqueue(int n_query, const long long* d_match_ptr, const float2* d_uv_ref, const float2* d_uv_cur, const long long* d_point_ptr,
-                 const float2* d_pts2d, const double* d_pts3d, const double* d_cam_ref, double* d_cam_cur, int factor_type,
-                 const ptz_lm_options& o, double max_reproj_error, int lanes, ptz_lm_summary* d_summaries, int* d_accepted,
-                 const int* d_active, hipStream_t st)
+void krt_enqueue(const KrtBatch& in, int factor_type, const ptz_lm_options& o, double max_reproj_error, int lanes,
+                 ptz_lm_summary* d_summaries, int* d_accepted, const int* d_active, hipStream_t st)
 {
   KrtOpt ko = make_krt_opt(o, max_reproj_error);
   ko.lanes_per_query = lanes;
-  launch_krt(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur, factor_type, ko, d_summaries,
-             d_accepted, st, nullptr, d_active);
+  launch_krt(in, factor_type, ko, d_summaries, d_accepted, st, nullptr, d_active);
+}
+
+static bool csr_ok(int n, const int64_t* ptr, bool any_base)
+{
+  if (!any_base && ptr[0] != 0) return false;
+  for (int q = 0; q < n; ++q)
+    if (ptr[q + 1] < ptr[q]) return false;
+  return true;
+}
+
+int check_host_batch(const KrtHostBatch& hb, unsigned what)
+{
+  const bool any_base = (what & kKrtAnyBase) != 0;
+  if (what & kKrtCheckMatches) {
+    if (!hb.match_ptr || !hb.cam_ref || !hb.cam_cur || !csr_ok(hb.n_query, hb.match_ptr, any_base)) return PTZ_EINVAL;
+    if (hb.n_match() > 0 && (!hb.uv_ref || !hb.uv_cur)) return PTZ_EINVAL;
+  }
+  if ((what & kKrtCheckPoints) && hb.point_ptr) {
+    if (!csr_ok(hb.n_query, hb.point_ptr, any_base)) return PTZ_EINVAL;
+    if (hb.n_point() > 0 && (!hb.pts2d || !hb.pts3d)) return PTZ_EINVAL;
+  }
+  return PTZ_OK;
+}
+
+hipError_t krt_batch_upload(const KrtHostBatch& hb, const uint8_t* match_mask, const int32_t* accepted, const KrtBatchSlots& s,
+                            const CallHeld& h, bool staged, KrtBatch* out)
+{
+  const size_t nq = (size_t)hb.n_query, nm = (size_t)hb.n_match(), np = (size_t)hb.n_point();
+  // each array to its slot: of the pinned mirror, which then goes over in one copy, or of the block by a copy of its own
+  hipError_t e = hipSuccess;
+  staged = staged && h.pinned;
+  char* to = staged ? (char*)h.pinned : h.base;
+  auto put = [&](size_t slot, const void* src, size_t bytes) {
+    if (bytes == 0 || e != hipSuccess) return;
+    if (staged) memcpy(to + slot, src, bytes);
+    else e = hipMemcpyAsync(to + slot, src, bytes, hipMemcpyHostToDevice, h.st);
+  };
+  put(s.match_ptr, hb.match_ptr, sizeof(long long) * (nq + 1));
+  put(s.uv_ref, hb.uv_ref, sizeof(float2) * nm);
+  put(s.uv_cur, hb.uv_cur, sizeof(float2) * nm);
+  put(s.cam_ref, hb.cam_ref, sizeof(double) * 15 * nq);
+  if (hb.point_ptr) {
+    put(s.point_ptr, hb.point_ptr, sizeof(long long) * (nq + 1));
+    put(s.pt_uv, hb.pts2d, sizeof(float2) * np);
+    put(s.pt_xyz, hb.pts3d, sizeof(double) * 3 * np);
+  }
+  if (match_mask) put(s.mask, match_mask, nm);
+  if (accepted) put(s.accepted, accepted, sizeof(int) * nq);
+  put(s.cam_cur, hb.cam_cur, sizeof(double) * 15 * nq);
+  if (staged) e = hipMemcpyAsync(h.base + s.begin, to + s.begin, s.end - s.begin, hipMemcpyHostToDevice, h.st);
+  char* b = h.base;
+  *out = {hb.n_query, (const long long*)(b + s.match_ptr), (const float2*)(b + s.uv_ref), (const float2*)(b + s.uv_cur),
+          hb.point_ptr ? (const long long*)(b + s.point_ptr) : nullptr, (const float2*)(b + s.pt_uv), (const double*)(b + s.pt_xyz),
+          (const double*)(b + s.cam_ref), (double*)(b + s.cam_cur)};
+  return e;
 }
 
 }  // namespace ptz
@@ -449,27 +501,12 @@ extern "C" int32_t ptz_krt_solve_batch_device(int32_t n_query, const int64_t* d_
   ptz_lm_options o;
   if (opt) o = *opt; else ptz_lm_options_default(&o);
   clear_stale_error(__func__);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PTZ_ENODEVICE;
-  // The launch goes to the device that owns the caller's buffers, on the caller's stream: a caller holding tensors and a
-  // stream on GPU 1 must not need to repeat that in opt->device_id.  An explicit, different device_id is a contradiction.
   int device = -1;
-  {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_cam_cur) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-    device = attr.device;
-    if (hip_stream) {
-      hipDevice_t sdev = -1;
-      if (hipStreamGetDevice((hipStream_t)hip_stream, &sdev) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-      if ((int)sdev != device) return PTZ_EINVAL;  // stream and buffers live on different devices
-    }
-    if (device < 0 || device >= ndev) return PTZ_EINVAL;
-    if (opt && opt->device_id != 0 && opt->device_id != device) return PTZ_EINVAL;
-  }
+  if (const int rc = owning_device(d_cam_cur, hip_stream, &device)) return rc;
+  if (opt && opt->device_id != 0 && opt->device_id != device) return PTZ_EINVAL;  // an explicit, different device_id is a contradiction
   PTZ_DEVICE_GUARD(device);
-  launch_krt(n_query, (const long long*)d_match_ptr, (const float2*)d_uv_ref, (const float2*)d_uv_cur, (const long long*)d_point_ptr,
-             (const float2*)d_pts2d, d_pts3d, d_cam_ref, d_cam_cur, factor_type, make_krt_opt(o, max_reproj_error), d_summaries, d_accepted,
-             (hipStream_t)hip_stream);
+  launch_krt(krt_batch_of(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur), factor_type,
+             make_krt_opt(o, max_reproj_error), d_summaries, d_accepted, (hipStream_t)hip_stream);
   PTZ_HIP_TRY(hipGetLastError());
   return PTZ_OK;
 }
@@ -489,89 +526,32 @@ extern "C" int32_t ptz_krt_solve_batch_2d3d(int32_t n_query, const int64_t* matc
                                             int32_t* accepted, double* device_ms)
 {
   if (n_query <= 0 || !match_ptr || !uv_ref || !uv_cur || !cam_ref || !cam_cur || !summaries || !accepted) return PTZ_EINVAL;
-  const bool p3 = point_ptr != nullptr;
-  if (p3 && (!pts2d || !pts3d)) return PTZ_EINVAL;
-  if (p3)
-    for (int q = 0; q < n_query; ++q)
-      if (point_ptr[q + 1] < point_ptr[q]) return PTZ_EINVAL;
-  const int64_t np = p3 ? point_ptr[n_query] : 0;
+  if (point_ptr && (!pts2d || !pts3d)) return PTZ_EINVAL;
+  const KrtHostBatch hb = {n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur};
+  if (const int rc = check_host_batch(hb, kKrtCheckPoints | kKrtAnyBase)) return rc;
   if (factor_type < PTZ_KRT_F || factor_type > PTZ_KRT_FxfyDist) return PTZ_EUNSUPPORTED;
   ptz_lm_options o;
   if (opt) o = *opt; else ptz_lm_options_default(&o);
-  for (int q = 0; q < n_query; ++q)
-    if (match_ptr[q + 1] < match_ptr[q]) return PTZ_EINVAL;
+  if (const int rc = check_host_batch(hb, kKrtCheckMatches | kKrtAnyBase)) return rc;
   clear_stale_error(__func__);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= o.device_id) return PTZ_ENODEVICE;
   PTZ_DEVICE_GUARD(o.device_id);
-  const int64_t nm = match_ptr[n_query];
   // one pooled device block for everything the launch touches: [inputs | cam_cur (in/out) | summaries | accepted]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_ptr = 0, o_ref = o_ptr + up(sizeof(long long) * (n_query + 1)), o_cur = o_ref + up(sizeof(float2) * (nm > 0 ? nm : 1)),
-               o_cref = o_cur + up(sizeof(float2) * (nm > 0 ? nm : 1)), o_pptr = o_cref + up(sizeof(double) * 15 * n_query),
-               o_puv = o_pptr + up(sizeof(long long) * (n_query + 1)), o_pxyz = o_puv + up(sizeof(float2) * (np > 0 ? np : 1)),
-               o_ccur = o_pxyz + up(sizeof(double) * 3 * (np > 0 ? np : 1)), o_sum = o_ccur + up(sizeof(double) * 15 * n_query),
-               o_acc = o_sum + up(sizeof(ptz_lm_summary) * n_query), total = o_acc + up(sizeof(int) * n_query);
-  struct Held {
-    int dev; char* base = nullptr; void* pinned = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::pinned_release(pinned);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-    }
-  } h;
-  h.dev = o.device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
-  long long* d_ptr = (long long*)(h.base + o_ptr);
-  float2 *d_ref = (float2*)(h.base + o_ref), *d_cur = (float2*)(h.base + o_cur);
-  double *d_cref = (double*)(h.base + o_cref), *d_ccur = (double*)(h.base + o_ccur);
-  ptz_lm_summary* d_sum = (ptz_lm_summary*)(h.base + o_sum);
-  int* d_acc = (int*)(h.base + o_acc);
-  long long* d_pptr = p3 ? (long long*)(h.base + o_pptr) : nullptr;
-  float2* d_puv = (float2*)(h.base + o_puv);
-  double* d_pxyz = (double*)(h.base + o_pxyz);
+  BlockLayout lay;
+  const KrtBatchSlots slots = krt_batch_reserve(lay, n_query, hb.n_match(), hb.n_point(), false, false);
+  const size_t o_ccur = slots.cam_cur, o_sum = lay.take(sizeof(ptz_lm_summary) * n_query), o_acc = lay.take(sizeof(int) * n_query);
+  const size_t total = lay.total();
   // Small launches (a registration, a handful of queries) go through one pinned staging buffer: one copy in, one copy out,
   // instead of eight synchronous-by-nature pageable copies of 10-15 us each.  Large ones keep the per-array copies.
-  const bool staged = total <= ((size_t)64 << 20) && ptzpool::pinned_acquire(total, &h.pinned) == hipSuccess;
-  if (!staged) (void)hipGetLastError();
-  if (staged) {
-    char* ps = (char*)h.pinned;
-    memcpy(ps + o_ptr, match_ptr, sizeof(long long) * (n_query + 1));
-    if (nm > 0) { memcpy(ps + o_ref, uv_ref, sizeof(float2) * nm); memcpy(ps + o_cur, uv_cur, sizeof(float2) * nm); }
-    memcpy(ps + o_cref, cam_ref, sizeof(double) * 15 * n_query);
-    memcpy(ps + o_ccur, cam_cur, sizeof(double) * 15 * n_query);
-    if (p3) {
-      memcpy(ps + o_pptr, point_ptr, sizeof(long long) * (n_query + 1));
-      if (np > 0) { memcpy(ps + o_puv, pts2d, sizeof(float2) * np); memcpy(ps + o_pxyz, pts3d, sizeof(double) * 3 * np); }
-    }
-    PTZ_HIP_TRY(hipMemcpyAsync(h.base, ps, o_sum, hipMemcpyHostToDevice, h.st));
-  }
-  else {
-    if (p3) {
-      PTZ_HIP_TRY(hipMemcpyAsync(d_pptr, point_ptr, sizeof(long long) * (n_query + 1), hipMemcpyHostToDevice, h.st));
-      if (np > 0) {
-        PTZ_HIP_TRY(hipMemcpyAsync(d_puv, pts2d, sizeof(float2) * np, hipMemcpyHostToDevice, h.st));
-        PTZ_HIP_TRY(hipMemcpyAsync(d_pxyz, pts3d, sizeof(double) * 3 * np, hipMemcpyHostToDevice, h.st));
-      }
-    }
-    PTZ_HIP_TRY(hipMemcpyAsync(d_ptr, match_ptr, sizeof(long long) * (n_query + 1), hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(d_ref, uv_ref, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(d_cur, uv_cur, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(d_cref, cam_ref, sizeof(double) * 15 * n_query, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(d_ccur, cam_cur, sizeof(double) * 15 * n_query, hipMemcpyHostToDevice, h.st));
-  }
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
-  launch_krt(n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, d_cref, d_ccur, factor_type, make_krt_opt(o, max_reproj_error), d_sum,
-             d_acc, h.st);
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
-  if (staged) {
+  CallHeld h;
+  if (const int rc = h.acquire(o.device_id, total, total <= ((size_t)64 << 20))) return rc;
+  KrtBatch in;
+  PTZ_HIP_TRY(krt_batch_upload(hb, nullptr, nullptr, slots, h, true, &in));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
+  launch_krt(in, factor_type, make_krt_opt(o, max_reproj_error), (ptz_lm_summary*)(h.base + o_sum), (int*)(h.base + o_acc), h.st);
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
+  if (h.pinned) {
     char* ps = (char*)h.pinned;
     PTZ_HIP_TRY(hipMemcpyAsync(ps + o_ccur, h.base + o_ccur, total - o_ccur, hipMemcpyDeviceToHost, h.st));
     PTZ_HIP_TRY(stream_wait(h.st));
@@ -581,15 +561,13 @@ extern "C" int32_t ptz_krt_solve_batch_2d3d(int32_t n_query, const int64_t* matc
     memcpy(accepted, ps + o_acc, sizeof(int) * n_query);
   }
   else {
-    PTZ_HIP_TRY(hipMemcpyAsync(cam_cur, d_ccur, sizeof(double) * 15 * n_query, hipMemcpyDeviceToHost, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(summaries, d_sum, sizeof(ptz_lm_summary) * n_query, hipMemcpyDeviceToHost, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(accepted, d_acc, sizeof(int) * n_query, hipMemcpyDeviceToHost, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(cam_cur, h.base + o_ccur, sizeof(double) * 15 * n_query, hipMemcpyDeviceToHost, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(summaries, h.base + o_sum, sizeof(ptz_lm_summary) * n_query, hipMemcpyDeviceToHost, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(accepted, h.base + o_acc, sizeof(int) * n_query, hipMemcpyDeviceToHost, h.st));
     PTZ_HIP_TRY(stream_wait(h.st));
     PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a solve
   }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   return PTZ_OK;
 }
 
@@ -669,28 +647,13 @@ extern "C" int32_t ptz_krt_solve_attempts(int32_t n_query, const ptz_krt_attempt
   clear_stale_error(__func__);
   PTZ_DEVICE_GUARD(device);
   // one pooled device block, one pinned staging block: [ranges | deltas | cam_ref | cam_cur (in / out) | summaries | accepted]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_rng = 0, o_del = o_rng + up(sizeof(long long) * 2 * n_query), o_cref = o_del + up(sizeof(long long) * n_query),
-               o_ccur = o_cref + up(sizeof(double) * 15 * n_query), o_sum = o_ccur + up(sizeof(double) * 15 * n_query),
-               o_acc = o_sum + up(sizeof(ptz_lm_summary) * n_query), total = o_acc + up(sizeof(int) * n_query);
-  struct Held {
-    int dev; char* base = nullptr; void* pinned = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::pinned_release(pinned);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-    }
-  } h;
-  h.dev = device;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  if (ptzpool::pinned_acquire(total, &h.pinned) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  BlockLayout lay;
+  const size_t o_rng = lay.take(sizeof(long long) * 2 * n_query), o_del = lay.take(sizeof(long long) * n_query),
+               o_cref = lay.take(sizeof(double) * 15 * n_query), o_ccur = lay.take(sizeof(double) * 15 * n_query),
+               o_sum = lay.take(sizeof(ptz_lm_summary) * n_query), o_acc = lay.take(sizeof(int) * n_query), total = lay.total();
+  CallHeld h;
+  if (const int rc = h.acquire(device, total, true)) return rc;
+  if (!h.pinned) return PTZ_ENOMEM;
   char* ps = (char*)h.pinned;
   long long* rng = (long long*)(ps + o_rng);
   long long* del = (long long*)(ps + o_del);
@@ -709,20 +672,20 @@ extern "C" int32_t ptz_krt_solve_attempts(int32_t n_query, const ptz_krt_attempt
   memcpy(ps + o_cref, cam_ref, sizeof(double) * 15 * n_query);
   memcpy(ps + o_ccur, cam_cur, sizeof(double) * 15 * n_query);
   PTZ_HIP_TRY(hipMemcpyAsync(h.base, ps, o_sum, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
-  launch_krt(n_query, (const long long*)(h.base + o_rng), t0->d_ref, t0->d_cur, nullptr, nullptr, nullptr, (const double*)(h.base + o_cref),
-             (double*)(h.base + o_ccur), factor_type, make_krt_opt(o, max_reproj_error), (ptz_lm_summary*)(h.base + o_sum), (int*)(h.base + o_acc), h.st,
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
+  // (ranges, not a CSR: query q's matches are rng[2 q] .. rng[2 q + 1], which k_krt takes from match_ptr where it is given deltas)
+  const KrtBatch in = {n_query, (const long long*)(h.base + o_rng), t0->d_ref, t0->d_cur, nullptr, nullptr, nullptr,
+                       (const double*)(h.base + o_cref), (double*)(h.base + o_ccur)};
+  launch_krt(in, factor_type, make_krt_opt(o, max_reproj_error), (ptz_lm_summary*)(h.base + o_sum), (int*)(h.base + o_acc), h.st,
              (const long long*)(h.base + o_del));
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(ps + o_ccur, h.base + o_ccur, total - o_ccur, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a solve
   memcpy(cam_cur, ps + o_ccur, sizeof(double) * 15 * n_query);
   memcpy(summaries, ps + o_sum, sizeof(ptz_lm_summary) * n_query);
   memcpy(accepted, ps + o_acc, sizeof(int) * n_query);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   return PTZ_OK;
 }
 

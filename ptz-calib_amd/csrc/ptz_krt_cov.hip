@@ -97,16 +97,15 @@ __global__ __launch_bounds__(256, (KrtCovOcc<KTYPE, P3>::WAVES)) void k_krt_cov(
   }
 }
 
-// one launch over device-resident queries (all pointers are device pointers; d_pptr = nullptr: no 2D-3D constraints)
-void launch_krt_cov(int n_query, const long long* d_ptr, const float2* d_ref, const float2* d_cur, const long long* d_pptr, const float2* d_puv,
-                    const double* d_pxyz, const double* d_cref, const double* d_ccur, int factor_type, const unsigned char* d_mask,
-                    const int* d_acc, double pixel_sigma, double* d_cov, double* d_s0, int* d_status, hipStream_t st)
+// one launch over a device-resident batch
+void launch_krt_cov(const KrtBatch& in, int factor_type, const unsigned char* d_mask, const int* d_acc, double pixel_sigma, double* d_cov,
+                    double* d_s0, int* d_status, hipStream_t st)
 {
-  const dim3 grid((n_query + COV_QPB - 1) / COV_QPB), block(256);
+  const dim3 grid((in.n_query + COV_QPB - 1) / COV_QPB), block(256);
 #define PTZ_COV_LAUNCH(T, P)                                                                                                          \
-  hipLaunchKernelGGL((k_krt_cov<T, P>), grid, block, 0, st, n_query, d_ptr, d_ref, d_cur, d_pptr, d_puv, d_pxyz, d_cref, d_ccur, d_mask, \
-                     d_acc, pixel_sigma, d_cov, d_s0, d_status)
-  switch (factor_type * 2 + (d_pptr ? 1 : 0)) {
+  hipLaunchKernelGGL((k_krt_cov<T, P>), grid, block, 0, st, in.n_query, in.match_ptr, in.uv_ref, in.uv_cur, in.point_ptr, in.pt_uv,     \
+                     in.pt_xyz, in.cam_ref, in.cam_cur, d_mask, d_acc, pixel_sigma, d_cov, d_s0, d_status)
+  switch (factor_type * 2 + (in.point_ptr ? 1 : 0)) {
     case 0: PTZ_COV_LAUNCH(0, false); break;
     case 1: PTZ_COV_LAUNCH(0, true); break;
     case 2: PTZ_COV_LAUNCH(1, false); break;
@@ -149,25 +148,11 @@ extern "C" int32_t ptz_krt_covariance_batch_device(int32_t n_query, const int64_
   if (n_query == 0) return PTZ_OK;
   if (!d_match_ptr || !d_uv_ref || !d_uv_cur || !d_cam_ref || !d_cam_cur || !d_cov || !d_sigma0 || !d_status) return PTZ_EINVAL;
   clear_stale_error(__func__);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PTZ_ENODEVICE;
-  // the launch goes to the device that owns the caller's buffers, on the caller's stream (as ptz_krt_solve_batch_device)
   int device = -1;
-  {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_cam_cur) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-    device = attr.device;
-    if (hip_stream) {
-      hipDevice_t sdev = -1;
-      if (hipStreamGetDevice((hipStream_t)hip_stream, &sdev) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-      if ((int)sdev != device) return PTZ_EINVAL;  // stream and buffers live on different devices
-    }
-    if (device < 0 || device >= ndev) return PTZ_EINVAL;
-  }
+  if (const int rc = owning_device(d_cam_cur, hip_stream, &device)) return rc;
   PTZ_DEVICE_GUARD(device);
-  launch_krt_cov(n_query, (const long long*)d_match_ptr, (const float2*)d_uv_ref, (const float2*)d_uv_cur, (const long long*)d_point_ptr,
-                 (const float2*)d_pts2d, d_pts3d, d_cam_ref, d_cam_cur, factor_type, d_match_mask, d_accepted, pixel_sigma, d_cov, d_sigma0,
-                 d_status, (hipStream_t)hip_stream);
+  launch_krt_cov(krt_batch_of(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur), factor_type,
+                 d_match_mask, d_accepted, pixel_sigma, d_cov, d_sigma0, d_status, (hipStream_t)hip_stream);
   PTZ_HIP_TRY(hipGetLastError());
   return PTZ_OK;
 }
@@ -179,76 +164,31 @@ extern "C" int32_t ptz_krt_covariance_batch(int32_t n_query, const int64_t* matc
                                             double* device_ms)
 {
   if (n_query < 0 || !(pixel_sigma >= 0.0) || !std::isfinite(pixel_sigma)) return PTZ_EINVAL;
-  const bool p3 = point_ptr != nullptr;
-  if (p3 && (!pts2d || !pts3d)) return PTZ_EINVAL;
+  if (point_ptr && (!pts2d || !pts3d)) return PTZ_EINVAL;
   const int nf = free_dim(factor_type);
   if (nf < 0) return PTZ_EUNSUPPORTED;
   if (n_query == 0) return PTZ_OK;
-  if (!match_ptr || !cam_ref || !cam_cur || !cov || !sigma0 || !status || device_id < 0) return PTZ_EINVAL;
-  if (match_ptr[0] != 0) return PTZ_EINVAL;
-  for (int q = 0; q < n_query; ++q)
-    if (match_ptr[q + 1] < match_ptr[q]) return PTZ_EINVAL;
-  const int64_t nm = match_ptr[n_query];
-  if (nm > 0 && (!uv_ref || !uv_cur)) return PTZ_EINVAL;
-  if (p3) {
-    if (point_ptr[0] != 0) return PTZ_EINVAL;
-    for (int q = 0; q < n_query; ++q)
-      if (point_ptr[q + 1] < point_ptr[q]) return PTZ_EINVAL;
-  }
-  const int64_t np = p3 ? point_ptr[n_query] : 0;
+  if (!cov || !sigma0 || !status || device_id < 0) return PTZ_EINVAL;
+  const KrtHostBatch hb = {n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur};
+  if (const int rc = check_host_batch(hb, kKrtCheckAll)) return rc;
   clear_stale_error(__func__);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) return PTZ_ENODEVICE;
   PTZ_DEVICE_GUARD(device_id);
   // one pooled device block: [inputs | cov | sigma0 | status]
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t nn = (size_t)nf * nf;
-  const size_t o_ptr = 0, o_ref = o_ptr + up(sizeof(long long) * (n_query + 1)), o_cur = o_ref + up(sizeof(float2) * (nm > 0 ? nm : 1)),
-               o_cref = o_cur + up(sizeof(float2) * (nm > 0 ? nm : 1)), o_ccur = o_cref + up(sizeof(double) * 15 * n_query),
-               o_pptr = o_ccur + up(sizeof(double) * 15 * n_query), o_puv = o_pptr + up(sizeof(long long) * (n_query + 1)),
-               o_pxyz = o_puv + up(sizeof(float2) * (np > 0 ? np : 1)), o_mask = o_pxyz + up(sizeof(double) * 3 * (np > 0 ? np : 1)),
-               o_acc = o_mask + up(nm > 0 ? nm : 1), o_cov = o_acc + up(sizeof(int) * n_query),
-               o_s0 = o_cov + up(sizeof(double) * nn * n_query), o_st = o_s0 + up(sizeof(double) * n_query),
-               total = o_st + up(sizeof(int) * n_query);
-  struct Held {
-    int dev; char* base = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Held()
-    {
-      if (st) (void)stream_wait(st);
-      ptzpool::dev_release(dev, base);
-      ptzpool::stream_release(dev, st);
-      ptzpool::event_release(dev, true, e0);
-      ptzpool::event_release(dev, true, e1);
-    }
-  } h;
-  h.dev = device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
-  PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_ptr, match_ptr, sizeof(long long) * (n_query + 1), hipMemcpyHostToDevice, h.st));
-  if (nm > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_ref, uv_ref, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_cur, uv_cur, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    if (match_mask) PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_mask, match_mask, (size_t)nm, hipMemcpyHostToDevice, h.st));
-  }
-  PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_cref, cam_ref, sizeof(double) * 15 * n_query, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_ccur, cam_cur, sizeof(double) * 15 * n_query, hipMemcpyHostToDevice, h.st));
-  if (p3) {
-    PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_pptr, point_ptr, sizeof(long long) * (n_query + 1), hipMemcpyHostToDevice, h.st));
-    if (np > 0) {
-      PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_puv, pts2d, sizeof(float2) * np, hipMemcpyHostToDevice, h.st));
-      PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_pxyz, pts3d, sizeof(double) * 3 * np, hipMemcpyHostToDevice, h.st));
-    }
-  }
-  if (accepted) PTZ_HIP_TRY(hipMemcpyAsync(h.base + o_acc, accepted, sizeof(int) * n_query, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
-  launch_krt_cov(n_query, (const long long*)(h.base + o_ptr), (const float2*)(h.base + o_ref), (const float2*)(h.base + o_cur),
-                 p3 ? (const long long*)(h.base + o_pptr) : nullptr, (const float2*)(h.base + o_puv), (const double*)(h.base + o_pxyz),
-                 (const double*)(h.base + o_cref), (const double*)(h.base + o_ccur), factor_type,
-                 match_mask ? (const unsigned char*)(h.base + o_mask) : nullptr, accepted ? (const int*)(h.base + o_acc) : nullptr,
-                 pixel_sigma, (double*)(h.base + o_cov), (double*)(h.base + o_s0), (int*)(h.base + o_st), h.st);
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  BlockLayout lay;
+  const KrtBatchSlots slots = krt_batch_reserve(lay, n_query, hb.n_match(), hb.n_point(), match_mask != nullptr, accepted != nullptr);
+  const size_t o_cov = lay.take(sizeof(double) * nn * n_query), o_s0 = lay.take(sizeof(double) * n_query), o_st = lay.take(sizeof(int) * n_query);
+  CallHeld h;
+  if (const int rc = h.acquire(device_id, lay.total())) return rc;
+  KrtBatch in;
+  PTZ_HIP_TRY(krt_batch_upload(hb, match_mask, accepted, slots, h, false, &in));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
+  launch_krt_cov(in, factor_type, match_mask ? (const unsigned char*)(h.base + slots.mask) : nullptr,
+                 accepted ? (const int*)(h.base + slots.accepted) : nullptr, pixel_sigma, (double*)(h.base + o_cov), (double*)(h.base + o_s0),
+                 (int*)(h.base + o_st), h.st);
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   // cov and sigma0 of a query whose status is not PTZ_COV_OK stay as the caller had them: the device's copies come back into a
   // buffer of their own and only the rows of computed queries are copied out
   std::vector<double> hc(nn * n_query), hs(n_query);
@@ -262,8 +202,6 @@ extern "C" int32_t ptz_krt_covariance_batch(int32_t n_query, const int64_t* matc
     memcpy(cov + nn * q, hc.data() + nn * q, sizeof(double) * nn);
     sigma0[q] = hs[q];
   }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   return PTZ_OK;
 }

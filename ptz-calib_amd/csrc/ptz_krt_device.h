@@ -1,9 +1,12 @@
 // ptz_krt_device.h -- device helpers shared by the single-view kernels: k_krt (ptz_krt.hip), k_krt_cov (ptz_krt_cov.hip) and the
-// residual report / trimming step (ptz_krt_resid.hip); and the host-side launch of k_krt those files share.
+// residual report / trimming step (ptz_krt_resid.hip); and, host side, the one description of a relocalization batch those files
+// share: its checks, its upload and the launch of k_krt.
 #pragma once
 
 #include "ptz_common.h"
 #include "ptz_factor.h"
+#include "ptz_host_batch.h"
+#include "ptz_krt_batch_layout.h"
 
 namespace ptz {
 
@@ -111,15 +114,68 @@ template <int G> __device__ __forceinline__ double group_max(double v)  // (the 
   return v;
 }
 
-// ---- host side: the one launch path of k_krt (ptz_krt.hip) ---------------------------------------------------------------------
+// ---- one description of a relocalization batch ---------------------------------------------------------------------------------
+// The device-resident batch: what the kernels and their launches take (device pointers; point_ptr = nullptr: no 2D-3D constraints).
+// cam_cur is read and written by the solves; the reports and the covariance only read it.
+struct KrtBatch {
+  int n_query;
+  const long long* match_ptr;
+  const float2 *uv_ref, *uv_cur;
+  const long long* point_ptr;
+  const float2* pt_uv;
+  const double* pt_xyz;
+  const double* cam_ref;
+  double* cam_cur;
+};
+inline KrtBatch krt_batch_of(int n_query, const int64_t* d_match_ptr, const float* d_uv_ref, const float* d_uv_cur, const int64_t* d_point_ptr,
+                             const float* d_pts2d, const double* d_pts3d, const double* d_cam_ref, const double* d_cam_cur)
+{
+  return {n_query, (const long long*)d_match_ptr, (const float2*)d_uv_ref, (const float2*)d_uv_cur, (const long long*)d_point_ptr,
+          (const float2*)d_pts2d, d_pts3d, d_cam_ref, const_cast<double*>(d_cam_cur)};
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+// The same batch in the caller's host arrays, as the four host-form entry points get it.
+struct KrtHostBatch {
+  int n_query;
+  const int64_t* match_ptr;
+  const float *uv_ref, *uv_cur;
+  const int64_t* point_ptr;  // nullptr: no 2D-3D constraints
+  const float* pts2d;
+  const double* pts3d;
+  const double *cam_ref, *cam_cur;
+  int64_t n_match() const { return match_ptr[n_query]; }
+  int64_t n_point() const { return point_ptr ? point_ptr[n_query] : 0; }
+};
+// Checks of the CSR arrays before any device work, n_query > 0: PTZ_OK or PTZ_EINVAL.  kKrtCheckMatches: match_ptr, cam_ref, cam_cur
+// given; match_ptr starts at 0 and does not decrease; the pixel arrays given if there is a match.  kKrtCheckPoints: the same of
+// point_ptr, pts2d, pts3d where point_ptr is given.  kKrtAnyBase: the offset arrays may start anywhere.
+//
+// The four callers do NOT validate alike, and each keeps what it answered when it was written (tests/golden/krt_return_codes.json):
+//                                n_query == 0   offsets start at 0   null pixels, no match   point_ptr order is checked   device_id < 0
+//   ptz_krt_solve_batch_2d3d     PTZ_EINVAL     not required         PTZ_EINVAL              before factor_type           not checked
+//   ptz_krt_covariance_batch     PTZ_OK         required             accepted                after factor_type            PTZ_EINVAL
+//   ptz_krt_residuals_batch      PTZ_OK         required             accepted                after factor_type            PTZ_EINVAL
+//   ptz_krt_solve_batch_trimmed  PTZ_OK         required             accepted                after factor_type            PTZ_EINVAL
+// (so a decreasing point_ptr with an unknown factor_type is PTZ_EINVAL to the plain solve and PTZ_EUNSUPPORTED to the others; all four
+//  ask hipGetDeviceCount only after every argument check, which on a machine without a device decides between PTZ_EINVAL and
+//  PTZ_ENODEVICE)
+enum : unsigned { kKrtCheckMatches = 1, kKrtCheckPoints = 2, kKrtCheckAll = 3, kKrtAnyBase = 4 };
+int check_host_batch(const KrtHostBatch& hb, unsigned what);
+
+// The inputs of `hb` into the block of `h` at the slots krt_batch_reserve() gave them (match_mask / accepted: nullable, as the slots
+// were reserved), enqueued on h.st; *out: the batch as the launches take it.  staged: through the pinned block of `h` where it has
+// one -- one copy of slots.begin .. slots.end instead of a pageable copy per array, the win of a registration-sized call; only
+// ptz_krt_solve_batch_2d3d asks for it (probably a win for the other three as well, but not measured: a change of its own).
+hipError_t krt_batch_upload(const KrtHostBatch& hb, const uint8_t* match_mask, const int32_t* accepted, const KrtBatchSlots& slots,
+                            const CallHeld& h, bool staged, KrtBatch* out);
+
 // lanes per query of a launch of n_query queries: `requested` (ptz_lm_options::krt_lanes_per_query) if 16 or 64, else PTZ_KRT_GROUP,
 // else by launch size
 int krt_group_size(int n_query, int requested);
-// k_krt over device-resident queries on `st` (d_point_ptr = nullptr: no 2D-3D constraints).  lanes: the group size, 16 or 64.
+// k_krt over a device-resident batch on `st`.  lanes: the group size, 16 or 64.
 // d_active (nullable): queries whose entry is 0 are left alone -- camera, summary and accepted as they were.
-void krt_enqueue(int n_query, const long long* d_match_ptr, const float2* d_uv_ref, const float2* d_uv_cur, const long long* d_point_ptr,
-                 const float2* d_pts2d, const double* d_pts3d, const double* d_cam_ref, double* d_cam_cur, int factor_type,
-                 const ptz_lm_options& o, double max_reproj_error, int lanes, ptz_lm_summary* d_summaries, int* d_accepted,
-                 const int* d_active, hipStream_t st);
+void krt_enqueue(const KrtBatch& in, int factor_type, const ptz_lm_options& o, double max_reproj_error, int lanes,
+                 ptz_lm_summary* d_summaries, int* d_accepted, const int* d_active, hipStream_t st);
 
 }  // namespace ptz

@@ -37,15 +37,6 @@ static_assert(kKrtTrimMaxRounds == PTZ_TRIM_MAX_ROUNDS && kKrtTrimMinKeep == PTZ
 constexpr int TRIM_ROUNDS_LIMIT = 64;  // rounds one call enqueues at most
 constexpr int RESID_E = 8;  // errors of a query a lane keeps in registers: 128 matches at G = 16, 512 at G = 64
 
-struct KrtResidIn {
-  int n_query;
-  const long long* match_ptr;
-  const float2 *uv_ref, *uv_cur;
-  const long long* point_ptr;
-  const float2* pt_uv;
-  const double* pt_xyz;
-  const double *cam_ref, *cam_cur;
-};
 struct KrtResidOut {
   double *err, *err3, *rms, *mx, *median, *rms3;
   int* count;
@@ -69,7 +60,7 @@ template <int G> __device__ __forceinline__ double group_sum64(const double (&p)
 // The report of query q by its group.  mask (nullable): the matches that count; err / err3 (nullable): err_px / err3d_px of the whole
 // batch.  want_median needs err when the query has more than RESID_E * G matches.  Every lane of the group returns the same st.
 template <int KTYPE, bool P3, int G>
-__device__ __forceinline__ void krt_resid_query(const KrtResidIn& in, int q, int lane, const unsigned char* mask, double* err, double* err3,
+__device__ __forceinline__ void krt_resid_query(const KrtBatch& in, int q, int lane, const unsigned char* mask, double* err, double* err3,
                                                 bool want_median, ResidLane& ln, ResidStats& st)
 {
   constexpr int NF = KrtDims<KTYPE>::NF, NV = 64 / G;
@@ -179,7 +170,7 @@ __device__ __forceinline__ void krt_resid_query(const KrtResidIn& in, int q, int
 }
 
 template <int KTYPE, bool P3, int G>
-__global__ __launch_bounds__(256) void k_krt_resid(KrtResidIn in, const unsigned char* __restrict__ mask, const int* __restrict__ accepted,
+__global__ __launch_bounds__(256) void k_krt_resid(KrtBatch in, const unsigned char* __restrict__ mask, const int* __restrict__ accepted,
                                                    KrtResidOut out)
 {
   const int q = blockIdx.x * (256 / G) + (int)threadIdx.x / G;
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(256) void k_krt_resid(KrtResidIn in, const unsigned
 // One round's report and rule for the queries still active, behind their solve: in.cam_cur = the loop's working cameras.
 // umask (nullable): the universe; kmask: the kept set, the round's solve ran on it -- replaced by K' only if the query goes on.
 template <int KTYPE, bool P3, int G>
-__global__ __launch_bounds__(256) void k_krt_trim_step(KrtResidIn in, const unsigned char* __restrict__ umask, unsigned char* kmask, double* err,
+__global__ __launch_bounds__(256) void k_krt_trim_step(KrtBatch in, const unsigned char* __restrict__ umask, unsigned char* kmask, double* err,
                                                        const int* __restrict__ acc_round, int* __restrict__ active, KrtTrimRule rule, int round,
                                                        ptz_krt_trim_report* __restrict__ rep, int* __restrict__ live)
 {
@@ -330,7 +321,7 @@ __global__ void k_krt_trim_finish_match(long long n_match, const unsigned char* 
     }                                                                    \
   } while (0)
 
-void launch_krt_resid(const KrtResidIn& in, int factor_type, int G, const unsigned char* d_mask, const int* d_acc, const KrtResidOut& out,
+void launch_krt_resid(const KrtBatch& in, int factor_type, int G, const unsigned char* d_mask, const int* d_acc, const KrtResidOut& out,
                       hipStream_t st)
 {
   const int qpb = 256 / G;
@@ -340,7 +331,7 @@ void launch_krt_resid(const KrtResidIn& in, int factor_type, int G, const unsign
 #undef PTZ_RESID_LAUNCH
 }
 
-void launch_krt_trim_step(const KrtResidIn& in, int factor_type, int G, const unsigned char* d_umask, unsigned char* d_kmask, double* d_err,
+void launch_krt_trim_step(const KrtBatch& in, int factor_type, int G, const unsigned char* d_umask, unsigned char* d_kmask, double* d_err,
                           const int* d_acc_round, int* d_active, const KrtTrimRule& rule, int round, ptz_krt_trim_report* d_rep, int* d_live,
                           hipStream_t st)
 {
@@ -352,8 +343,6 @@ void launch_krt_trim_step(const KrtResidIn& in, int factor_type, int G, const un
   PTZ_KRT_BY_TYPE(PTZ_STEP_LAUNCH, factor_type, in.point_ptr != nullptr, G);
 #undef PTZ_STEP_LAUNCH
 }
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the loop's device state, cut from one block
 struct TrimWork {
@@ -369,8 +358,8 @@ struct TrimWork {
 size_t trim_work_cut(int n_query, long long n_match, char* base, TrimWork* w)
 {
   const size_t n = (size_t)n_query, nm = (size_t)(n_match > 0 ? n_match : 1);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return base ? base + at : nullptr; };
+  BlockLayout lay;
+  auto take = [&](size_t bytes) { const size_t at = lay.take(bytes); return base ? base + at : nullptr; };
   char* p_cam = take(sizeof(double) * 15 * n);
   char* p_err = take(sizeof(double) * nm);
   char* p_k = take(nm);
@@ -387,7 +376,7 @@ size_t trim_work_cut(int n_query, long long n_match, char* base, TrimWork* w)
     w->cnt = (int*)p_cnt; w->optr = (long long*)p_optr; w->oref = (float2*)p_oref; w->ocur = (float2*)p_ocur; w->rep = (ptz_krt_trim_report*)p_rep;
     w->live = (int*)p_live;
   }
-  return o;
+  return lay.total();
 }
 
 // Every round of the trimmed solve on `st`, device pointers throughout: [compaction of the kept sets | k_krt with the open bound on
@@ -395,7 +384,7 @@ size_t trim_work_cut(int n_query, long long n_match, char* base, TrimWork* w)
 // acceptance.  A query that is finished is left alone by every kernel (`active`); a round no query reaches costs its launches only:
 // w.live[r] counts the queries that go into round r, and the compaction -- whose scan walks all n counts in one workgroup --
 // returns at once where it reads 0.
-void enqueue_trimmed(KrtResidIn in, long long n_match, double* d_cam_cur, int factor_type, double max_reproj_error, const unsigned char* d_umask,
+void enqueue_trimmed(const KrtBatch& in, long long n_match, int factor_type, double max_reproj_error, const unsigned char* d_umask,
                      const KrtTrimRule& rule, const ptz_lm_options& o, ptz_lm_summary* d_sum, int* d_acc, unsigned char* d_kept,
                      ptz_krt_trim_report* d_rep, const TrimWork& w, hipStream_t st)
 {
@@ -403,77 +392,27 @@ void enqueue_trimmed(KrtResidIn in, long long n_match, double* d_cam_cur, int fa
   const int G = krt_group_size(n, o.krt_lanes_per_query);  // of the CALL's size, every round
   ptz_krt_trim_report* rep = d_rep ? d_rep : w.rep;
   const unsigned mgrid = (unsigned)((n_match + 255) / 256);
-  hipLaunchKernelGGL(k_krt_trim_init_query, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)d_cam_cur, w.cam, w.active, w.acc_round, rep, w.live);
+  hipLaunchKernelGGL(k_krt_trim_init_query, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)in.cam_cur, w.cam, w.active, w.acc_round, rep, w.live);
   if (n_match > 0) hipLaunchKernelGGL(k_krt_trim_init_match, dim3(mgrid), dim3(256), 0, st, n_match, d_umask, w.kmask);
-  KrtResidIn at = in;
+  KrtBatch at = in;
   at.cam_cur = w.cam;
   for (int r = 0; r < rule.max_rounds; ++r) {
-    if (r == 0 && !d_umask) {  // the kept set is every match: the caller's arrays ARE the packed ones
-      krt_enqueue(n, in.match_ptr, in.uv_ref, in.uv_cur, in.point_ptr, in.pt_uv, in.pt_xyz, in.cam_ref, w.cam, factor_type, o, 1e300, G, d_sum,
-                  w.acc_round, w.active, st);
-    }
-    else {
+    KrtBatch kept = at;
+    if (r > 0 || d_umask) {  // (else the kept set is every match: the caller's arrays ARE the packed ones)
       // the kept matches of the active queries from the ORIGINAL arrays, in their order (a finished query packs nothing)
       enqueue_compact(n, (const int64_t*)in.match_ptr, (const int32_t*)w.active, w.kmask, 0, w.cnt, (int64_t*)w.optr, in.uv_ref, in.uv_cur,
                       w.oref, w.ocur, nullptr, st, w.live + r);
-      krt_enqueue(n, w.optr, w.oref, w.ocur, in.point_ptr, in.pt_uv, in.pt_xyz, in.cam_ref, w.cam, factor_type, o, 1e300, G, d_sum, w.acc_round,
-                  w.active, st);
+      kept.match_ptr = w.optr; kept.uv_ref = w.oref; kept.uv_cur = w.ocur;
     }
+    krt_enqueue(kept, factor_type, o, 1e300, G, d_sum, w.acc_round, w.active, st);
     launch_krt_trim_step(at, factor_type, G, d_umask, w.kmask, w.err, w.acc_round, w.active, rule, r, rep, w.live, st);
   }
   hipLaunchKernelGGL(k_krt_trim_finish_query, dim3((n + 255) / 256), dim3(256), 0, st, n, (const double*)w.cam, (const ptz_lm_summary*)d_sum,
-                     (const int*)w.acc_round, max_reproj_error, d_cam_cur, d_acc);
+                     (const int*)w.acc_round, max_reproj_error, in.cam_cur, d_acc);
   if (d_kept && n_match > 0) hipLaunchKernelGGL(k_krt_trim_finish_match, dim3(mgrid), dim3(256), 0, st, n_match, (const unsigned char*)w.kmask, d_kept);
 }
 
 inline bool factor_type_ok(int factor_type) { return factor_type >= PTZ_KRT_F && factor_type <= PTZ_KRT_FxfyDist; }
-
-// the device that owns `p`, checked against the stream's (as ptz_krt_solve_batch_device); PTZ_OK or the error to return
-int owning_device(const void* p, void* hip_stream, int* device)
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PTZ_ENODEVICE;
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-  *device = attr.device;
-  if (hip_stream) {
-    hipDevice_t sdev = -1;
-    if (hipStreamGetDevice((hipStream_t)hip_stream, &sdev) != hipSuccess) { (void)hipGetLastError(); return PTZ_EINVAL; }
-    if ((int)sdev != *device) return PTZ_EINVAL;  // stream and buffers live on different devices
-  }
-  if (*device < 0 || *device >= ndev) return PTZ_EINVAL;
-  return PTZ_OK;
-}
-
-// host-side checks of a CSR batch, before any device work (as ptz_krt_covariance_batch); n_query > 0
-int check_host_batch(int n_query, const int64_t* match_ptr, const float* uv_ref, const float* uv_cur, const int64_t* point_ptr,
-                     const float* pts2d, const double* pts3d, const double* cam_ref, const double* cam_cur)
-{
-  if (!match_ptr || !cam_ref || !cam_cur) return PTZ_EINVAL;
-  if (match_ptr[0] != 0) return PTZ_EINVAL;
-  for (int q = 0; q < n_query; ++q)
-    if (match_ptr[q + 1] < match_ptr[q]) return PTZ_EINVAL;
-  if (match_ptr[n_query] > 0 && (!uv_ref || !uv_cur)) return PTZ_EINVAL;
-  if (point_ptr) {
-    if (point_ptr[0] != 0) return PTZ_EINVAL;
-    for (int q = 0; q < n_query; ++q)
-      if (point_ptr[q + 1] < point_ptr[q]) return PTZ_EINVAL;
-    if (point_ptr[n_query] > 0 && (!pts2d || !pts3d)) return PTZ_EINVAL;
-  }
-  return PTZ_OK;
-}
-
-struct Held {
-  int dev; char* base = nullptr; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~Held()
-  {
-    if (st) (void)stream_wait(st);
-    ptzpool::dev_release(dev, base);
-    ptzpool::stream_release(dev, st);
-    ptzpool::event_release(dev, true, e0);
-    ptzpool::event_release(dev, true, e1);
-  }
-};
 
 }  // namespace
 }  // namespace ptz
@@ -498,8 +437,7 @@ extern "C" int32_t ptz_krt_residuals_batch_device(int32_t n_query, const int64_t
   int device = -1;
   if (const int rc = owning_device(d_cam_cur, hip_stream, &device)) return rc;
   PTZ_DEVICE_GUARD(device);
-  const KrtResidIn in = {n_query, (const long long*)d_match_ptr, (const float2*)d_uv_ref, (const float2*)d_uv_cur, (const long long*)d_point_ptr,
-                         (const float2*)d_pts2d, d_pts3d, d_cam_ref, d_cam_cur};
+  const KrtBatch in = krt_batch_of(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur);
   const KrtResidOut out = {d_err_px, d_point_ptr ? d_err3d_px : nullptr, d_rms, d_max, d_median, d_rms3d, d_count};
   launch_krt_resid(in, factor_type, krt_group_size(n_query, lanes_per_query), d_match_mask, d_accepted, out, (hipStream_t)hip_stream);
   PTZ_HIP_TRY(hipGetLastError());
@@ -519,63 +457,38 @@ extern "C" int32_t ptz_krt_residuals_batch(int32_t n_query, const int64_t* match
   if (!factor_type_ok(factor_type)) return PTZ_EUNSUPPORTED;
   if (n_query == 0) return PTZ_OK;
   if (device_id < 0) return PTZ_EINVAL;
-  if (const int rc = check_host_batch(n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur)) return rc;
-  const int64_t nm = match_ptr[n_query], np = p3 ? point_ptr[n_query] : 0;
+  const KrtHostBatch hb = {n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur};
+  if (const int rc = check_host_batch(hb, kKrtCheckAll)) return rc;
   clear_stale_error(__func__);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) return PTZ_ENODEVICE;
   PTZ_DEVICE_GUARD(device_id);
   // one pooled device block: [inputs | results]
-  const size_t nq = (size_t)n_query, nmx = (size_t)(nm > 0 ? nm : 1), npx = (size_t)(np > 0 ? np : 1), D = sizeof(double);
-  size_t o = 0;
-  auto take = [&o](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
-  const size_t o_ptr = take(sizeof(long long) * (nq + 1)), o_ref = take(sizeof(float2) * nmx), o_cur = take(sizeof(float2) * nmx),
-               o_cref = take(D * 15 * nq), o_ccur = take(D * 15 * nq), o_pptr = take(sizeof(long long) * (nq + 1)), o_puv = take(sizeof(float2) * npx),
-               o_pxyz = take(D * 3 * npx), o_mask = take(nmx), o_acc = take(sizeof(int) * nq);
-  const size_t o_res = o;
-  const size_t o_err = take(D * nmx), o_e3 = take(D * npx), o_rms = take(D * nq), o_max = take(D * nq), o_med = take(D * nq), o_rms3 = take(D * nq),
-               o_cnt = take(sizeof(int) * nq);
-  const size_t total = o;
-  Held h;
-  h.dev = device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  const size_t nq = (size_t)n_query, nmx = (size_t)std::max<int64_t>(hb.n_match(), 1), npx = (size_t)std::max<int64_t>(hb.n_point(), 1), D = sizeof(double);
+  BlockLayout lay;
+  const KrtBatchSlots slots = krt_batch_reserve(lay, n_query, hb.n_match(), hb.n_point(), match_mask != nullptr, accepted != nullptr);
+  const size_t o_res = lay.total();
+  const size_t o_err = lay.take(D * nmx), o_e3 = lay.take(D * npx), o_rms = lay.take(D * nq), o_max = lay.take(D * nq), o_med = lay.take(D * nq),
+               o_rms3 = lay.take(D * nq), o_cnt = lay.take(sizeof(int) * nq), total = lay.total();
+  CallHeld h;
+  if (const int rc = h.acquire(device_id, total)) return rc;
   char* b = h.base;
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_ptr, match_ptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h.st));
-  if (nm > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_ref, uv_ref, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_cur, uv_cur, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    if (match_mask) PTZ_HIP_TRY(hipMemcpyAsync(b + o_mask, match_mask, (size_t)nm, hipMemcpyHostToDevice, h.st));
-  }
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_cref, cam_ref, D * 15 * nq, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_ccur, cam_cur, D * 15 * nq, hipMemcpyHostToDevice, h.st));
-  if (p3) {
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_pptr, point_ptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h.st));
-    if (np > 0) {
-      PTZ_HIP_TRY(hipMemcpyAsync(b + o_puv, pts2d, sizeof(float2) * np, hipMemcpyHostToDevice, h.st));
-      PTZ_HIP_TRY(hipMemcpyAsync(b + o_pxyz, pts3d, D * 3 * np, hipMemcpyHostToDevice, h.st));
-    }
-  }
-  if (accepted) PTZ_HIP_TRY(hipMemcpyAsync(b + o_acc, accepted, sizeof(int) * nq, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
-  const KrtResidIn in = {n_query, (const long long*)(b + o_ptr), (const float2*)(b + o_ref), (const float2*)(b + o_cur),
-                         p3 ? (const long long*)(b + o_pptr) : nullptr, (const float2*)(b + o_puv), (const double*)(b + o_pxyz),
-                         (const double*)(b + o_cref), (const double*)(b + o_ccur)};
+  KrtBatch in;
+  PTZ_HIP_TRY(krt_batch_upload(hb, match_mask, accepted, slots, h, false, &in));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
   // err_px is always taken on the device: the median of a long query reads it back
   const KrtResidOut out = {(double*)(b + o_err), p3 ? (double*)(b + o_e3) : nullptr, (double*)(b + o_rms), (double*)(b + o_max),
                            median ? (double*)(b + o_med) : nullptr, (double*)(b + o_rms3), (int*)(b + o_cnt)};
-  launch_krt_resid(in, factor_type, krt_group_size(n_query, lanes_per_query), match_mask ? (const unsigned char*)(b + o_mask) : nullptr,
-                   accepted ? (const int*)(b + o_acc) : nullptr, out, h.st);
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  launch_krt_resid(in, factor_type, krt_group_size(n_query, lanes_per_query), match_mask ? (const unsigned char*)(b + slots.mask) : nullptr,
+                   accepted ? (const int*)(b + slots.accepted) : nullptr, out, h.st);
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   // the outputs of a query with accepted = 0 stay as the caller had them: the device's copies come back into a buffer of their own
-  std::vector<char> hb(total - o_res);
-  PTZ_HIP_TRY(hipMemcpyAsync(hb.data(), b + o_res, total - o_res, hipMemcpyDeviceToHost, h.st));
+  std::vector<char> hr(total - o_res);
+  PTZ_HIP_TRY(hipMemcpyAsync(hr.data(), b + o_res, total - o_res, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a result
-  auto hd = [&](size_t off) { return reinterpret_cast<const double*>(hb.data() + (off - o_res)); };
-  const int* hcnt = reinterpret_cast<const int*>(hb.data() + (o_cnt - o_res));
+  auto hd = [&](size_t off) { return reinterpret_cast<const double*>(hr.data() + (off - o_res)); };
+  const int* hcnt = reinterpret_cast<const int*>(hr.data() + (o_cnt - o_res));
   for (int q = 0; q < n_query; ++q) {
     if (accepted && accepted[q] == 0) continue;
     const int64_t a = match_ptr[q], m = match_ptr[q + 1] - a;
@@ -587,9 +500,7 @@ extern "C" int32_t ptz_krt_residuals_batch(int32_t n_query, const int64_t* match
     if (count) count[q] = hcnt[q];
     if (rms3d) rms3d[q] = hd(o_rms3)[q];
   }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   return PTZ_OK;
 }
 
@@ -639,9 +550,8 @@ extern "C" int32_t ptz_krt_solve_batch_trimmed_device(int32_t n_query, int64_t n
   PTZ_DEVICE_GUARD(device);
   TrimWork w;
   trim_work_cut(n_query, n_match, (char*)d_workspace, &w);
-  const KrtResidIn in = {n_query, (const long long*)d_match_ptr, (const float2*)d_uv_ref, (const float2*)d_uv_cur, (const long long*)d_point_ptr,
-                         (const float2*)d_pts2d, d_pts3d, d_cam_ref, d_cam_cur};
-  enqueue_trimmed(in, n_match, d_cam_cur, factor_type, max_reproj_error, d_match_mask, rule, o, d_summaries, d_accepted, d_kept, d_report, w,
+  const KrtBatch in = krt_batch_of(n_query, d_match_ptr, d_uv_ref, d_uv_cur, d_point_ptr, d_pts2d, d_pts3d, d_cam_ref, d_cam_cur);
+  enqueue_trimmed(in, n_match, factor_type, max_reproj_error, d_match_mask, rule, o, d_summaries, d_accepted, d_kept, d_report, w,
                   (hipStream_t)hip_stream);
   PTZ_HIP_TRY(hipGetLastError());
   return PTZ_OK;
@@ -654,63 +564,39 @@ extern "C" int32_t ptz_krt_solve_batch_trimmed(int32_t n_query, const int64_t* m
                                                int32_t* accepted, uint8_t* kept, ptz_krt_trim_report* report, double* device_ms)
 {
   if (n_query < 0) return PTZ_EINVAL;
-  const bool p3 = point_ptr != nullptr;
-  if (p3 && (!pts2d || !pts3d)) return PTZ_EINVAL;
+  if (point_ptr && (!pts2d || !pts3d)) return PTZ_EINVAL;
   KrtTrimRule rule;
   if (!trim_rule_from(trim, &rule)) return PTZ_EINVAL;
   if (!factor_type_ok(factor_type)) return PTZ_EUNSUPPORTED;
   if (n_query == 0) return PTZ_OK;
   if (!summaries || !accepted) return PTZ_EINVAL;
-  if (const int rc = check_host_batch(n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur)) return rc;
+  const KrtHostBatch hb = {n_query, match_ptr, uv_ref, uv_cur, point_ptr, pts2d, pts3d, cam_ref, cam_cur};
+  if (const int rc = check_host_batch(hb, kKrtCheckAll)) return rc;
   ptz_lm_options o;
   if (opt) o = *opt; else ptz_lm_options_default(&o);
   if (o.device_id < 0) return PTZ_EINVAL;
-  const int64_t nm = match_ptr[n_query], np = p3 ? point_ptr[n_query] : 0;
   clear_stale_error(__func__);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= o.device_id) return PTZ_ENODEVICE;
   PTZ_DEVICE_GUARD(o.device_id);
   // one pooled device block: [inputs | cam_cur (in / out) | summaries | accepted | kept | report | the loop's state]
-  const size_t nq = (size_t)n_query, nmx = (size_t)(nm > 0 ? nm : 1), npx = (size_t)(np > 0 ? np : 1), D = sizeof(double);
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
-  const size_t o_ptr = take(sizeof(long long) * (nq + 1)), o_ref = take(sizeof(float2) * nmx), o_cur = take(sizeof(float2) * nmx),
-               o_cref = take(D * 15 * nq), o_pptr = take(sizeof(long long) * (nq + 1)), o_puv = take(sizeof(float2) * npx),
-               o_pxyz = take(D * 3 * npx), o_mask = take(nmx), o_ccur = take(D * 15 * nq), o_sum = take(sizeof(ptz_lm_summary) * nq),
-               o_acc = take(sizeof(int) * nq), o_kept = take(nmx), o_rep = take(sizeof(ptz_krt_trim_report) * nq),
-               o_work = take(trim_work_cut(n_query, nm, nullptr, nullptr));
-  const size_t total = off;
-  Held h;
-  h.dev = o.device_id;
-  if (ptzpool::dev_acquire(h.dev, total, (void**)&h.base) != hipSuccess) return PTZ_ENOMEM;
-  PTZ_HIP_TRY(ptzpool::stream_acquire(h.dev, &h.st));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e0));
-  PTZ_HIP_TRY(ptzpool::event_acquire(h.dev, true, &h.e1));
+  const int64_t nm = hb.n_match();
+  const size_t nq = (size_t)n_query, nmx = (size_t)std::max<int64_t>(nm, 1), D = sizeof(double);
+  BlockLayout lay;
+  const KrtBatchSlots slots = krt_batch_reserve(lay, n_query, nm, hb.n_point(), match_mask != nullptr, false);
+  const size_t o_ccur = slots.cam_cur, o_sum = lay.take(sizeof(ptz_lm_summary) * nq), o_acc = lay.take(sizeof(int) * nq), o_kept = lay.take(nmx),
+               o_rep = lay.take(sizeof(ptz_krt_trim_report) * nq), o_work = lay.take(trim_work_cut(n_query, nm, nullptr, nullptr));
+  CallHeld h;
+  if (const int rc = h.acquire(o.device_id, lay.total())) return rc;
   char* b = h.base;
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_ptr, match_ptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h.st));
-  if (nm > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_ref, uv_ref, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_cur, uv_cur, sizeof(float2) * nm, hipMemcpyHostToDevice, h.st));
-    if (match_mask) PTZ_HIP_TRY(hipMemcpyAsync(b + o_mask, match_mask, (size_t)nm, hipMemcpyHostToDevice, h.st));
-  }
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_cref, cam_ref, D * 15 * nq, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(b + o_ccur, cam_cur, D * 15 * nq, hipMemcpyHostToDevice, h.st));
-  if (p3) {
-    PTZ_HIP_TRY(hipMemcpyAsync(b + o_pptr, point_ptr, sizeof(long long) * (nq + 1), hipMemcpyHostToDevice, h.st));
-    if (np > 0) {
-      PTZ_HIP_TRY(hipMemcpyAsync(b + o_puv, pts2d, sizeof(float2) * np, hipMemcpyHostToDevice, h.st));
-      PTZ_HIP_TRY(hipMemcpyAsync(b + o_pxyz, pts3d, D * 3 * np, hipMemcpyHostToDevice, h.st));
-    }
-  }
-  PTZ_HIP_TRY(hipEventRecord(h.e0, h.st));
+  KrtBatch in;
+  PTZ_HIP_TRY(krt_batch_upload(hb, match_mask, nullptr, slots, h, false, &in));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
   TrimWork w;
   trim_work_cut(n_query, nm, b + o_work, &w);
-  const KrtResidIn in = {n_query, (const long long*)(b + o_ptr), (const float2*)(b + o_ref), (const float2*)(b + o_cur),
-                         p3 ? (const long long*)(b + o_pptr) : nullptr, (const float2*)(b + o_puv), (const double*)(b + o_pxyz),
-                         (const double*)(b + o_cref), (const double*)(b + o_ccur)};
-  enqueue_trimmed(in, nm, (double*)(b + o_ccur), factor_type, max_reproj_error, match_mask ? (const unsigned char*)(b + o_mask) : nullptr, rule, o,
+  enqueue_trimmed(in, nm, factor_type, max_reproj_error, match_mask ? (const unsigned char*)(b + slots.mask) : nullptr, rule, o,
                   (ptz_lm_summary*)(b + o_sum), (int*)(b + o_acc), (unsigned char*)(b + o_kept), (ptz_krt_trim_report*)(b + o_rep), w, h.st);
-  PTZ_HIP_TRY(hipEventRecord(h.e1, h.st));
+  PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(cam_cur, b + o_ccur, D * 15 * nq, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(summaries, b + o_sum, sizeof(ptz_lm_summary) * nq, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(accepted, b + o_acc, sizeof(int) * nq, hipMemcpyDeviceToHost, h.st));
@@ -718,8 +604,6 @@ extern "C" int32_t ptz_krt_solve_batch_trimmed(int32_t n_query, const int64_t* m
   if (report) PTZ_HIP_TRY(hipMemcpyAsync(report, b + o_rep, sizeof(ptz_krt_trim_report) * nq, hipMemcpyDeviceToHost, h.st));
   PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());  // a refused kernel launch must not pass for a solve
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, h.e0, h.e1);
-  if (device_ms) *device_ms = ms;
+  if (device_ms) *device_ms = h.elapsed_ms();
   return PTZ_OK;
 }
