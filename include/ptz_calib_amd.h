@@ -794,6 +794,33 @@ int32_t ptz_desc_matches_download(const ptz_desc_matches* m, int64_t* match_ptr,
 int32_t ptz_desc_matches_device_ptrs(const ptz_desc_matches* m, const int64_t** d_match_ptr, const int32_t** d_idx_a,
                                      const int32_t** d_idx_b, const int32_t** d_dist2, const float** d_uv_a, const float** d_uv_b);
 void ptz_desc_matches_destroy(ptz_desc_matches* m);
+
+/* Homography-guided matching: the rule of ptz_desc_match_pairs over the candidates pair p's homography admits (the second pass of
+ * COLMAP's guided_matching and of OpenCV's stitching matcher, for texture that repeats).  H [9 n_pair] row-major, b ~ H a, as
+ * ptz_homography_ransac_batch returns it for src = A's pixels, dst = B's.  Contract (csrc/ptz_desc_match.h): feature i of A is
+ * warped in double, X = H0 x + H1 y + H2 and Y, Z likewise, left to right without fma; ok(i) = Z > 0 and X, Y, Z finite; the pair
+ * (i, j) is ADMISSIBLE iff ok(i) and, in float without fma, (wx - bx)^2 + (wy - by)^2 <= (float)(radius_px^2), inclusive, with
+ * (wx, wy) = ((float)(X / Z), (float)(Y / Z)) and (bx, by) the pixel of B's feature j.  B's features ask A over the SAME admissible
+ * set (the error is measured in B's image in both directions), so best, second (INT32_MAX with fewer than two admissible
+ * candidates), ties, the ratio test, cross_check, max_dist2 and min_matches are ptz_desc_match_pairs's over the admissible
+ * candidates only, and:
+ *   - the matches of (B, A) under the same H and roles are the transposed matches of (A, B); a call with the sets swapped and
+ *     H^-1 measures the error in the other image, is another predicate and need not return the transpose;
+ *   - a pair's result depends on its two images and its H only (not on the batch, its order or the chunking);
+ *   - a radius that admits every candidate returns ptz_desc_match_pairs's arrays.
+ * found [n_pair] or NULL (= all 1): a pair with found[p] != 1 has no matches and its H is not read.  A non-finite H is not an
+ * error: that pair has no admissible candidate.  The result is an ordinary ptz_desc_matches.
+ * PTZ_EINVAL, before any device work: the list of ptz_desc_match_pairs, a set with features but without key points, NULL H with
+ * n_pair > 0, a radius that is not finite and positive.
+ * ptz_desc_match_pairs_guided_device: d_H and d_found are DEVICE pointers on the sets' device, as ptz_match_gate_run_device leaves
+ * them; the call runs on a stream of its own, so the work that writes them must have completed (synchronise its stream first). */
+int32_t ptz_desc_match_pairs_guided(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair, const int32_t* img_a,
+                                    const int32_t* img_b, const double* H /* [9 n_pair], b ~ H a */,
+                                    const int32_t* found /* [n_pair] or NULL = all 1 */, double radius_px,
+                                    const ptz_desc_options* opt, ptz_desc_matches** out);
+int32_t ptz_desc_match_pairs_guided_device(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair, const int32_t* img_a,
+                                           const int32_t* img_b, const double* d_H, const int32_t* d_found /* or NULL */,
+                                           double radius_px, const ptz_desc_options* opt, ptz_desc_matches** out);
 /* tests only: the full matrix d2 [n_a, n_b] (host) of one pair, from the matcher's own matrix-core tile code */
 int32_t ptz_debug_desc_dist2(const ptz_desc_set* set_a, int32_t img_a, const ptz_desc_set* set_b, int32_t img_b, int32_t* out);
 

@@ -38,7 +38,7 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_batch_trimmed_device", "ptz_desc_options_default", "ptz_desc_set_create", "ptz_desc_set_destroy",
            "ptz_desc_match_pairs", "ptz_desc_matches_n_matches", "ptz_desc_matches_n_pairs", "ptz_desc_matches_device_ms",
            "ptz_desc_matches_n_chunks", "ptz_desc_matches_download", "ptz_desc_matches_device_ptrs", "ptz_desc_matches_destroy",
-           "ptz_debug_desc_dist2"]
+           "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device"]
 
 
 class PtzError(RuntimeError):
@@ -1225,6 +1225,41 @@ def match_descriptors(set_a, set_b, img_a, img_b, resident=False, **options):
     o = desc_options(**options)
     h = C.c_void_p()
     _check(lib().ptz_desc_match_pairs(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), C.byref(o), C.byref(h)), "ptz_desc_match_pairs")
+    m = DescMatches(h)
+    if resident:
+        return m
+    try:
+        return m.download(uv=set_a.has_kp and set_b.has_kp)
+    finally:
+        m.close()
+
+
+def match_descriptors_guided(set_a, set_b, img_a, img_b, H, found=None, radius_px=4.0, resident=False, **options):
+    """ptz_desc_match_pairs_guided: match_descriptors over the candidates pair p's homography H[p] (b ~ H a, [n_pair, 9] or
+    [n_pair, 3, 3]) admits within radius_px, the error measured in B's image; found [n_pair] or None (all 1): a pair whose found is
+    not 1 has no matches.  H and found may also be DEVICE buffers (torch tensors or integer addresses) on the sets' device (what MatchGate.run_device leaves,
+    its stream synchronised): ptz_desc_match_pairs_guided_device.  Both sets need key points.  Returns what match_descriptors does."""
+    ia = np.ascontiguousarray(img_a, dtype=np.int32)
+    ib = np.ascontiguousarray(img_b, dtype=np.int32)
+    if ia.shape != ib.shape or ia.ndim != 1:
+        raise ValueError("img_a and img_b: two index lists of equal length")
+    options.setdefault("device_id", set_a.device_id)
+    o = desc_options(**options)
+    h = C.c_void_p()
+    if isinstance(H, int) or hasattr(H, "data_ptr"):
+        if found is not None and not (isinstance(found, int) or hasattr(found, "data_ptr")):
+            raise ValueError("a device H goes with a device found (or None)")
+        _check(lib().ptz_desc_match_pairs_guided_device(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _dptr(H), _dptr(found),
+                                                        C.c_double(radius_px), C.byref(o), C.byref(h)),
+               "ptz_desc_match_pairs_guided_device")
+    else:
+        Hh = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        fh = None if found is None else np.ascontiguousarray(found, dtype=np.int32)
+        if len(Hh) != len(ia) or (fh is not None and fh.shape != ia.shape):
+            raise ValueError("H: one 3 x 3 matrix per pair, found: one flag per pair")
+        _check(lib().ptz_desc_match_pairs_guided(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _p(Hh) if len(ia) else None,
+                                                 _p(fh) if fh is not None and len(ia) else None, C.c_double(radius_px), C.byref(o),
+                                                 C.byref(h)), "ptz_desc_match_pairs_guided")
     m = DescMatches(h)
     if resident:
         return m

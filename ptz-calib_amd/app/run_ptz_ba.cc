@@ -193,6 +193,8 @@ int main(int argc, char** argv)
   parser.Add("match_min", '\0', "With --match_descriptors: matches a pair needs to keep any (default 8)", false);
   parser.Add("match_window", '\0', "With --match_descriptors: only pairs of cyclic index distance <= k in the sorted file names (default: all)", false);
   parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
+  parser.Add("match_guided", '\0', "With --match_descriptors: match every pair again within this many pixels of its RANSAC homography "
+                                   "and keep these matches instead; a pair without a verified model keeps none (off unless given)", false);
   parser.ParseCheck(argc, argv);
   TrimArgs trim;
   if (parser.Exist("trim_px")) {
@@ -218,6 +220,10 @@ int main(int argc, char** argv)
     fprintf(stderr, "Error loading images and features. Exiting ...\n");
     return -1;
   }
+  if (parser.Exist("match_guided") && !parser.Exist("match_descriptors")) {
+    fprintf(stderr, "--match_guided needs --match_descriptors\n");
+    return 1;
+  }
   std::vector<MatchesInfo> matches_info;
   const std::string matches_path = parser.Get("features") + "/pairs_matches.txt";
   const bool gpu_h = parser.Exist("gpu_homography");
@@ -232,6 +238,14 @@ int main(int argc, char** argv)
     if (!(mo.ratio >= 0.0) || !std::isfinite(mo.ratio) || mo.min_matches < 0 || window < 1) {
       fprintf(stderr, "--match_ratio must not be negative, --match_min not negative, --match_window at least 1\n");
       return 1;
+    }
+    if (parser.Exist("match_guided")) {
+      mo.guided_radius = atof(parser.Get("match_guided").c_str());
+      mo.min_inliers = min_inliers;
+      if (!(mo.guided_radius > 0.0) || !std::isfinite(mo.guided_radius)) {
+        fprintf(stderr, "--match_guided must be a positive number of pixels\n");
+        return 1;
+      }
     }
     std::vector<std::pair<long, long>> pairs;
     for (long i = 0; i < n_img; ++i)

@@ -60,6 +60,8 @@ int main(int argc, char** argv)
   parser.Add("match_ratio", '\0', "With --match_descriptors: Lowe's ratio (default 0.8; 0: no ratio test)", false);
   parser.Add("match_min", '\0', "With --match_descriptors: matches a pair needs to keep any (default 8)", false);
   parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
+  parser.Add("match_guided", '\0', "With --match_descriptors: match every pair again within this many pixels of its RANSAC homography "
+                                   "and keep these matches instead; a pair without a verified model keeps none (off unless given)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -67,6 +69,10 @@ int main(int argc, char** argv)
     return 1;
   }
 
+  if (parser.Exist("match_guided") && !parser.Exist("match_descriptors")) {
+    fprintf(stderr, "--match_guided needs --match_descriptors\n");
+    return 1;
+  }
   const bool trimming = parser.Exist("trim_px");
   ptz_krt_trim_options trim;
   ptz_krt_trim_options_default(&trim);
@@ -101,6 +107,14 @@ int main(int argc, char** argv)
     if (!(mo.ratio >= 0.0) || !std::isfinite(mo.ratio) || mo.min_matches < 0) {
       fprintf(stderr, "--match_ratio and --match_min must not be negative\n");
       return 1;
+    }
+    if (parser.Exist("match_guided")) {
+      mo.guided_radius = atof(parser.Get("match_guided").c_str());
+      mo.min_inliers = min_inliers;
+      if (!(mo.guided_radius > 0.0) || !std::isfinite(mo.guided_radius)) {
+        fprintf(stderr, "--match_guided must be a positive number of pixels\n");
+        return 1;
+      }
     }
     std::vector<std::pair<long, long>> pairs;
     for (size_t t = 0; t < test_fnames.size(); ++t)

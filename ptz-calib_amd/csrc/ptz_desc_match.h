@@ -70,4 +70,58 @@ PTZ_HD bool desc_accept(const DescRule& r, int32_t i, const DescTop2& ta, const 
   return r.max_dist2 == 0 || ta.d <= r.max_dist2;
 }
 
+// ---- guided matching (ptz_desc_match_pairs_guided): the same rule over the candidates a pair homography admits -------------------
+// The pair (i of A, j of B) is ADMISSIBLE under H (b ~ H a, row-major) and a radius when H puts a_i in front of the camera and within
+// the radius of b_j, the error measured in B's image:
+//   warp        X = H0 x + H1 y + H2 in double, left to right, every product and sum rounded on its own (no fma); Y and Z likewise;
+//               ok = Z > 0 and X, Y, Z finite; wx = (float)(X / Z), wy = (float)(Y / Z);
+//   admissible  dx = wx - bx, dy = wy - by, e2 = dx dx + dy dy in float (three roundings, no fma), e2 <= r2f -- inclusive, false for
+//               a NaN; r2f = (float)(radius_px * radius_px), computed once on the host.
+// ONE predicate serves both directions: B's features ask A over the same admissible set (A's warped points against b_j), so
+//   * best, second, ties, the ratio test, cross_check, max_dist2 and min_matches are the rules above over the admissible candidates
+//     only (second = INT32_MAX with fewer than two of them);
+//   * the matches of (B, A) under the SAME H and roles are the transposed matches of (A, B); a call with the roles swapped and
+//     H^-1 measures the error in the other image, is another predicate and need not be;
+//   * a pair's result depends on its two images and its H only;
+//   * a radius that admits every candidate gives the unguided result, array-equal.
+#if defined(__clang__)
+#pragma clang fp contract(off)  // every product and sum rounds on its own, as numpy's
+#endif
+
+struct DescWarp {
+  float x, y;
+  bool ok;
+};
+
+PTZ_HD bool desc_finite(double v) { return v - v == 0.0; }  // (inf - inf and NaN - NaN are NaN)
+
+PTZ_HD DescWarp desc_guide_warp(const double* H, float x, float y)
+{
+  const double ax = x, ay = y;
+  const double X = H[0] * ax + H[1] * ay + H[2];
+  const double Y = H[3] * ax + H[4] * ay + H[5];
+  const double Z = H[6] * ax + H[7] * ay + H[8];
+  DescWarp w;
+  w.ok = Z > 0.0 && desc_finite(X) && desc_finite(Y) && desc_finite(Z);
+  w.x = (float)(X / Z);
+  w.y = (float)(Y / Z);
+  return w;
+}
+
+PTZ_HD float desc_guide_err2(float wx, float wy, float bx, float by)
+{
+  const float dx = wx - bx, dy = wy - by;
+  return dx * dx + dy * dy;
+}
+
+PTZ_HD bool desc_guide_admissible(float wx, float wy, float bx, float by, float r2f) { return desc_guide_err2(wx, wy, bx, by) <= r2f; }
+
+// d2 of two packed rows (ptz_desc_match.hip's pack: bytes are a - 128 as int8, zero padding) from their norms: |a'|^2 + |b'|^2 - 2 a'.b'
+PTZ_HD int32_t desc_dot_i8x4(uint32_t a, uint32_t b)
+{
+  int32_t s = 0;
+  for (int k = 0; k < 4; ++k) s += (int32_t)(int8_t)(a >> (8 * k)) * (int32_t)(int8_t)(b >> (8 * k));
+  return s;
+}
+
 }  // namespace ptz

@@ -11,6 +11,9 @@
 //             ONE query per lane, four candidates per step, so the running (best, best j, second) of a query tile is three
 //             registers.  Candidates reach a lane in ascending j, so `<` keeps the lowest j there; the four lanes of a query
 //             are merged once at the end with the header's rule.  The DP x n product is never written.
+//   guided    ptz_desc_match_pairs_guided: the same top-2 over the candidates within a radius of where the pair's homography puts
+//             the feature (the header's predicate) -- a radius search over positions staged in LDS, one query per lane, the exact
+//             d2 from the packed rows only on a hit; the state, and everything behind it, is the dense pass's.
 //   join      the acceptance rule per feature of A -> a keep byte; counting, scan and scatter are ptz_gate_compact.h's kernels
 //             (min_matches as `need`); a gather writes indices, distances and the pixels of the resident key points.
 #include <cmath>
@@ -32,6 +35,8 @@ constexpr int DESC_WG = 256;     // four waves
 constexpr int DESC_QT = 2;       // query tiles of 16 per wave
 constexpr int DESC_WG_Q = (DESC_WG / WAVE) * DESC_QT * 16;  // 128 queries per workgroup
 constexpr int DESC_ROW_PAD = 64; // rows of an image are padded to this
+constexpr int DESC_G_TILE = 1024; // positions of the other image a guided workgroup stages in LDS at a time (8 KB)
+constexpr int DESC_G_UNROLL = 8;  // candidates a lane tests between two looks for a hit (divides DESC_G_TILE)
 constexpr int DESC_CHUNK_PAIRS = 1 << 20;  // most pairs of a chunk: its launches have a workgroup row per pair and direction
 
 struct DescPair {
@@ -159,6 +164,107 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2(const DescPair* __restric
         if (g == 0 && q < nq) out[q] = T;
       }
     }
+  }
+}
+
+// The guided pass: the top-2 over the candidates a pair homography admits (the header's predicate), a radius search instead of a
+// masked product -- at a few pixels' radius about one candidate per query is admissible.  The grid of k_desc_top2 (blockIdx.x =
+// pair * dirs + direction, blockIdx.y strided over query tiles), ONE query per thread.  The workgroup stages the other image's
+// positions through LDS in tiles of DESC_G_TILE -- direction 0: B's key points as they are, the query is A's warped point;
+// direction 1: A's warped points (NaN where the warp is not ok: never admissible), the query is B's key point -- and every lane scans
+// them in ascending index, all lanes reading one address.  On a hit the lane forms the exact d2 from the two packed rows and their
+// norms; candidates arrive in ascending j, so the dense kernel's update keeps the lowest j on a tie.  Key points are indexed by
+// FEATURE (d_kp is not padded).  A pair whose found is not 1 and a query whose warp is not ok get the empty state: the chunk's state
+// array is reused and k_desc_join reads all of it.  No thread leaves the tile loop before its last barrier.
+__global__ __launch_bounds__(DESC_WG) void k_desc_top2_guided(const DescPair* __restrict__ pairs, int dirs, int DPW,
+                                                              const uint32_t* __restrict__ desc_a, const int32_t* __restrict__ norm_a,
+                                                              const uint32_t* __restrict__ desc_b, const int32_t* __restrict__ norm_b,
+                                                              const float2* __restrict__ kp_a, const float2* __restrict__ kp_b,
+                                                              const double* __restrict__ Hs, const int32_t* __restrict__ found, float r2f,
+                                                              DescTop2* __restrict__ state)
+{
+  __shared__ float2 pos[DESC_G_TILE];
+  const int p = blockIdx.x / dirs, dir = blockIdx.x % dirs;
+  const DescPair P = pairs[p];
+  const int nq = dir ? P.n_b : P.n_a, ns = dir ? P.n_a : P.n_b;
+  DescTop2* out = state + P.soff + (dir ? P.n_a : 0);
+  // one value per workgroup, before any barrier
+  if ((found && found[p] != 1) || ns == 0) {
+    for (int64_t q = (int64_t)blockIdx.y * DESC_WG + threadIdx.x; q < nq; q += (int64_t)gridDim.y * DESC_WG) out[q] = desc_top2_empty();
+    return;
+  }
+  double H[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) H[k] = Hs[9 * (int64_t)p + k];
+  const uint32_t* qd = dir ? desc_b + P.row_b * DPW : desc_a + P.row_a * DPW;
+  const int32_t* qn = dir ? norm_b + P.row_b : norm_a + P.row_a;
+  const uint32_t* sdp = dir ? desc_a + P.row_a * DPW : desc_b + P.row_b * DPW;
+  const int32_t* sn = dir ? norm_a + P.row_a : norm_b + P.row_b;
+  const float2* ka = kp_a + P.kp_a;
+  const float2* kb = kp_b + P.kp_b;
+  const float qnan = __int_as_float(0x7fc00000);
+
+  for (int64_t tile = blockIdx.y; tile * DESC_WG < nq; tile += gridDim.y) {
+    const int64_t q = tile * DESC_WG + threadIdx.x;
+    bool scan = q < nq;  // (a lane without a query, or whose warp is not ok, stages and waits with the others)
+    float qx = 0.f, qy = 0.f;
+    if (scan) {
+      if (dir == 0) {
+        const float2 a = ka[q];
+        const DescWarp w = desc_guide_warp(H, a.x, a.y);
+        scan = w.ok; qx = w.x; qy = w.y;
+      }
+      else {
+        const float2 b = kb[q];
+        qx = b.x; qy = b.y;
+      }
+    }
+    int32_t bd = kDescNone, bj = kDescNone, sd = kDescNone;
+    for (int s0 = 0; s0 < ns; s0 += DESC_G_TILE) {
+      const int cnt = min(DESC_G_TILE, ns - s0), cntu = (cnt + DESC_G_UNROLL - 1) & ~(DESC_G_UNROLL - 1);  // the tail: never admissible
+      __syncthreads();  // the tile before this one has been scanned
+      for (int k = threadIdx.x; k < cntu; k += DESC_WG) {
+        float2 v = make_float2(qnan, qnan);
+        if (k < cnt) {
+          if (dir == 0) v = kb[s0 + k];
+          else {
+            const float2 a = ka[s0 + k];
+            const DescWarp w = desc_guide_warp(H, a.x, a.y);
+            if (w.ok) v = make_float2(w.x, w.y);
+          }
+        }
+        pos[k] = v;
+      }
+      __syncthreads();
+      if (scan) {
+        for (int k0 = 0; k0 < cntu; k0 += DESC_G_UNROLL) {
+          float e2[DESC_G_UNROLL], least = __int_as_float(0x7f800000);  // +inf
+#pragma unroll
+          for (int u = 0; u < DESC_G_UNROLL; ++u) {
+            // one form for both directions: (q - c) is exactly -(c - q), so the squares and their sum are the header's bits
+            // whichever of the two is the warped point -- and the loop has no branch on the direction
+            const float2 c = pos[k0 + u];
+            e2[u] = desc_guide_err2(qx, qy, c.x, c.y);
+            least = fminf(least, e2[u]);  // (fminf drops a NaN: an error that is NaN never looks like a hit)
+          }
+          if (!(least <= r2f)) continue;  // no hit among these: the common case costs one comparison, not one per candidate
+#pragma unroll
+          for (int u = 0; u < DESC_G_UNROLL; ++u) {
+            if (!(e2[u] <= r2f)) continue;
+            const int32_t j = s0 + k0 + u;
+            const uint32_t* x = qd + q * DPW;
+            const uint32_t* y = sdp + (int64_t)j * DPW;
+            int32_t dot = 0;
+            for (int w = 0; w < DPW; ++w) dot += desc_dot_i8x4(x[w], y[w]);
+            const int32_t key = qn[q] + sn[j] - 2 * dot;
+            sd = min(sd, max(bd, key));
+            bj = key < bd ? j : bj;
+            bd = min(bd, key);
+          }
+        }
+      }
+    }
+    if (q < nq) out[q] = DescTop2{bd, bj, sd};
   }
 }
 
@@ -358,10 +464,21 @@ extern "C" void ptz_desc_set_destroy(ptz_desc_set* s)
   delete s;
 }
 
-extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
-                                        const int32_t* img_b, const ptz_desc_options* opt, ptz_desc_matches** out)
+namespace ptz {
+namespace {
+
+// the guide of ptz_desc_match_pairs_guided: one H per pair, found nullable (all 1), host or device arrays
+struct DescGuide {
+  const double* H;
+  const int32_t* found;
+  bool on_device;
+  double radius_px;
+};
+
+// the chunk loop of both matchers; guide = nullptr: the dense pass
+int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                       const int32_t* img_b, const DescGuide* guide, const ptz_desc_options* opt, ptz_desc_matches** out)
 {
-  using namespace ptz;
   if (!out) return PTZ_EINVAL;
   *out = nullptr;
   ptz_desc_options o;
@@ -373,7 +490,12 @@ extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_se
   if (!(std::isfinite(o.ratio) && o.ratio >= 0) || o.max_dist2 < 0 || o.min_matches < 0 || o.workspace_bytes <= 0) return PTZ_EINVAL;
   for (int p = 0; p < n_pair; ++p)
     if (img_a[p] < 0 || img_a[p] >= A->n_img || img_b[p] < 0 || img_b[p] >= B->n_img) return PTZ_EINVAL;
-  clear_stale_error(__func__);
+  if (guide) {
+    if ((A->n_feat > 0 && !A->d_kp) || (B->n_feat > 0 && !B->d_kp) || (n_pair > 0 && !guide->H)) return PTZ_EINVAL;
+    if (!(std::isfinite(guide->radius_px) && guide->radius_px > 0)) return PTZ_EINVAL;
+  }
+  const float r2f = guide ? (float)(guide->radius_px * guide->radius_px) : 0.f;
+  clear_stale_error(who);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= A->device) return PTZ_ENODEVICE;
   const int dev = A->device;
@@ -423,7 +545,9 @@ extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_se
                o_keep = o_state + up256(sizeof(DescTop2) * ws_state), o_index = o_keep + up256(ws_a),
                o_aptr = o_index + up256(sizeof(int32_t) * ws_a), o_found = o_aptr + up256(sizeof(int64_t) * (ws_pairs + 1)),
                o_cnt = o_found + up256(sizeof(int32_t) * ws_pairs), o_optr = o_cnt + up256(sizeof(int32_t) * ws_pairs),
-               ws_total = o_optr + up256(sizeof(int64_t) * (ws_pairs + 1));
+               o_gh = o_optr + up256(sizeof(int64_t) * (ws_pairs + 1)),  // a host guide's copy: H, then found, of ALL pairs
+               o_gf = o_gh + up256(guide && !guide->on_device ? sizeof(double) * 9 * (size_t)n_pair : 0),
+               ws_total = o_gf + up256(guide && !guide->on_device && guide->found ? sizeof(int32_t) * (size_t)n_pair : 0);
   // a chunk's matches wait in a block of their own until the total is known
   struct Part { std::unique_ptr<DescBlock> blk; int64_t n; };
   // the stream is declared after every block its kernels write: on an early return it is waited for before they go back to the pool
@@ -445,6 +569,16 @@ extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_se
     PTZ_HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DescPair) * tab.size(), hipMemcpyHostToDevice, ds.st));
     hipLaunchKernelGGL(k_desc_fill, dim3((ws_pairs + 255) / 256), dim3(256), 0, ds.st, ws_pairs, 1, d_found);
   }
+  const double* g_H = guide ? guide->H : nullptr;
+  const int32_t* g_found = guide ? guide->found : nullptr;
+  if (guide && !guide->on_device && n_pair > 0) {
+    PTZ_HIP_TRY(hipMemcpyAsync(ws.p + o_gh, guide->H, sizeof(double) * 9 * (size_t)n_pair, hipMemcpyHostToDevice, ds.st));
+    g_H = (const double*)(ws.p + o_gh);
+    if (guide->found) {
+      PTZ_HIP_TRY(hipMemcpyAsync(ws.p + o_gf, guide->found, sizeof(int32_t) * (size_t)n_pair, hipMemcpyHostToDevice, ds.st));
+      g_found = (const int32_t*)(ws.p + o_gf);
+    }
+  }
 
   auto carve = [](char* base, int64_t n, bool uv, int32_t*& ia, int32_t*& ib, int32_t*& d2, float2*& ua, float2*& ub) {
     const size_t w = up256(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)), w2 = up256(sizeof(float2) * (size_t)std::max<int64_t>(n, 1));
@@ -461,8 +595,14 @@ extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_se
     aptr[npc] = c.n_a;
     PTZ_HIP_TRY(hipMemcpyAsync(d_aptr, aptr.data(), sizeof(int64_t) * (npc + 1), hipMemcpyHostToDevice, ds.st));
     PTZ_HIP_TRY(hipEventRecord(ds.e0, ds.st));
-    launch_top2<false>(A->KS, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG_Q)), ds.st, d_tab + c.p0, dirs, A->d_desc, A->d_norm,
-                       B->d_desc, B->d_norm, d_state, nullptr);
+    if (guide)
+      hipLaunchKernelGGL(k_desc_top2_guided, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG)), dim3(DESC_WG), 0, ds.st,
+                         (const DescPair*)(d_tab + c.p0), dirs, 16 * A->KS, (const uint32_t*)A->d_desc, (const int32_t*)A->d_norm,
+                         (const uint32_t*)B->d_desc, (const int32_t*)B->d_norm, (const float2*)A->d_kp, (const float2*)B->d_kp,
+                         g_H + 9 * (size_t)c.p0, g_found ? g_found + c.p0 : nullptr, r2f, d_state);
+    else
+      launch_top2<false>(A->KS, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG_Q)), ds.st, d_tab + c.p0, dirs, A->d_desc, A->d_norm,
+                         B->d_desc, B->d_norm, d_state, nullptr);
     hipLaunchKernelGGL(k_desc_join, dim3(npc, tiles_y(c.most_q, 256)), dim3(256), 0, ds.st, (const DescPair*)(d_tab + c.p0),
                        (const DescTop2*)d_state, rule, d_keep);
     enqueue_compact(npc, d_aptr, d_found, d_keep, o.min_matches, d_cnt, d_optr, nullptr, nullptr, nullptr, nullptr, d_index, ds.st);
@@ -527,6 +667,31 @@ extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_se
   PTZ_HIP_TRY(hipGetLastError());
   *out = res.release();
   return PTZ_OK;
+}
+
+}  // namespace
+}  // namespace ptz
+
+extern "C" int32_t ptz_desc_match_pairs(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                                        const int32_t* img_b, const ptz_desc_options* opt, ptz_desc_matches** out)
+{
+  return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, nullptr, opt, out);
+}
+
+extern "C" int32_t ptz_desc_match_pairs_guided(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                                               const int32_t* img_b, const double* H, const int32_t* found, double radius_px,
+                                               const ptz_desc_options* opt, ptz_desc_matches** out)
+{
+  const ptz::DescGuide g = {H, found, false, radius_px};
+  return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
+}
+
+extern "C" int32_t ptz_desc_match_pairs_guided_device(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                                                      const int32_t* img_b, const double* d_H, const int32_t* d_found, double radius_px,
+                                                      const ptz_desc_options* opt, ptz_desc_matches** out)
+{
+  const ptz::DescGuide g = {d_H, d_found, true, radius_px};
+  return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
 }
 
 extern "C" int64_t ptz_desc_matches_n_matches(const ptz_desc_matches* m) { return m ? m->n_match : 0; }

@@ -187,13 +187,20 @@ bool WriteColmapMatches(const std::string& filepath, const std::vector<std::vect
 namespace {
 
 // the descriptors of a list of images as one resident set (features of image m: ptr[m] .. ptr[m + 1])
-bool LoadDescSet(const std::string& dir, const std::vector<std::string>& fnames, int device_id, int& dim, std::vector<int64_t>& ptr,
-                 ptz_desc_set** set)
+// with_kp: the key points of the files go into the set as well (the guided pass needs them)
+bool LoadDescSet(const std::string& dir, const std::vector<std::string>& fnames, int device_id, bool with_kp, int& dim,
+                 std::vector<int64_t>& ptr, ptz_desc_set** set)
 {
   std::vector<unsigned char> all, one;
+  std::vector<float> kp_xy;
   ptr.assign(1, 0);
   for (const std::string& fname : fnames) {
     const std::string path = dir + "/" + fname + ".txt";
+    if (with_kp) {
+      std::vector<KeyPoint> kpts;
+      ReadColmapFeatures(path, kpts);
+      for (const KeyPoint& k : kpts) { kp_xy.push_back(k.pt.x); kp_xy.push_back(k.pt.y); }
+    }
     if (!ReadColmapDescriptors(path, one, dim)) {
       fprintf(stderr, "[ptzcalib] MatchDescriptors: cannot read the descriptors of %s (missing or short file, or another dimension than the images before it)\n", path.c_str());
       return false;
@@ -205,7 +212,12 @@ bool LoadDescSet(const std::string& dir, const std::vector<std::string>& fnames,
     fprintf(stderr, "[ptzcalib] MatchDescriptors: the feature files of %s carry no descriptors\n", dir.c_str());
     return false;
   }
-  const int32_t rc = ptz_desc_set_create(static_cast<int32_t>(fnames.size()), ptr.data(), all.data(), dim, nullptr, device_id, set);
+  if (with_kp && kp_xy.size() != 2 * static_cast<size_t>(ptr.back())) {
+    fprintf(stderr, "[ptzcalib] MatchDescriptors: the feature files of %s do not hold one key point per descriptor\n", dir.c_str());
+    return false;
+  }
+  const int32_t rc = ptz_desc_set_create(static_cast<int32_t>(fnames.size()), ptr.data(), all.data(), dim, with_kp ? kp_xy.data() : nullptr,
+                                         device_id, set);
   if (rc != PTZ_OK) fprintf(stderr, "[ptzcalib] MatchDescriptors: ptz_desc_set_create failed (%d)\n", rc);
   return rc == PTZ_OK;
 }
@@ -224,9 +236,10 @@ bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& 
   int dim = 0;
   std::vector<int64_t> ptr_a, ptr_b;
   ptz_desc_set *set_a = nullptr, *set_b = nullptr;
-  if (!LoadDescSet(dir_a, fnames_a, options.device_id, dim, ptr_a, &set_a)) return false;
+  const bool guided = options.guided_radius > 0.0;
+  if (!LoadDescSet(dir_a, fnames_a, options.device_id, guided, dim, ptr_a, &set_a)) return false;
   if (one_set) set_b = set_a;
-  else if (!LoadDescSet(dir_b, fnames_b, options.device_id, dim, ptr_b, &set_b)) { ptz_desc_set_destroy(set_a); return false; }
+  else if (!LoadDescSet(dir_b, fnames_b, options.device_id, guided, dim, ptr_b, &set_b)) { ptz_desc_set_destroy(set_a); return false; }
   std::vector<int32_t> ia, ib;
   for (const std::pair<long, long>& p : pairs) { ia.push_back(static_cast<int32_t>(p.first)); ib.push_back(static_cast<int32_t>(p.second)); }
   ptz_desc_options o;
@@ -235,8 +248,32 @@ bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& 
   o.min_matches = options.min_matches;
   o.device_id = options.device_id;
   ptz_desc_matches* res = nullptr;
-  int32_t rc = ptz_desc_match_pairs(set_a, set_b, static_cast<int32_t>(pairs.size()), ia.data(), ib.data(), &o, &res);
+  const int32_t n_pair = static_cast<int32_t>(pairs.size());
+  int32_t rc = ptz_desc_match_pairs(set_a, set_b, n_pair, ia.data(), ib.data(), &o, &res);
   std::vector<int64_t> mptr(pairs.size() + 1, 0);
+  if (rc == PTZ_OK && guided) {
+    // the pair homographies of the first pass's pixel pairs, then the guided pass over the pairs a model verified
+    const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(res));
+    std::vector<float> ua(2 * std::max<size_t>(n, 1)), ub(2 * std::max<size_t>(n, 1));
+    std::vector<uint8_t> mask(std::max<size_t>(n, 1), 0);
+    std::vector<double> H(9 * std::max<size_t>(pairs.size(), 1), 0.0);
+    std::vector<int32_t> found(std::max<size_t>(pairs.size(), 1), 0);
+    rc = ptz_desc_matches_download(res, mptr.data(), nullptr, nullptr, nullptr, ua.data(), ub.data());
+    if (rc == PTZ_OK)
+      rc = ptz_homography_ransac_batch(n_pair, mptr.data(), ua.data(), ub.data(), options.ransac_thresh, options.device_id, H.data(),
+                                       found.data(), mask.data(), nullptr);
+    ptz_desc_matches_destroy(res);
+    res = nullptr;
+    if (rc == PTZ_OK) {
+      const int64_t need = std::max(options.min_inliers, 4);
+      for (int32_t p = 0; p < n_pair; ++p) {
+        int64_t ones = 0;
+        for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) ones += found[p] == 1 && mask[static_cast<size_t>(k)] != 0;
+        found[p] = found[p] == 1 && ones >= need ? 1 : 0;
+      }
+      rc = ptz_desc_match_pairs_guided(set_a, set_b, n_pair, ia.data(), ib.data(), H.data(), found.data(), options.guided_radius, &o, &res);
+    }
+  }
   std::vector<int32_t> qa, tb;
   if (rc == PTZ_OK) {
     const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(res));

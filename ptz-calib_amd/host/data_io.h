@@ -33,10 +33,18 @@ bool WriteColmapMatches(const std::string& filepath, const std::vector<std::vect
 // transpose_back: also emit every pair's (second, first) block -- its matches swapped and sorted by the feature of the second
 // image (the matcher's (B, A) result: the rule is symmetric under cross_check) -- and put all blocks in table order (first image,
 // then second); needs dir_a == dir_b.
+// guided_radius > 0: a second, homography-guided pass (ptz_desc_match_pairs_guided) for texture that repeats.  The first pass's
+// pixel pairs go through ptz_homography_ransac_batch (ransac_thresh); a pair with a model and at least max(min_inliers, 4) mask-1
+// matches is matched again over the candidates within guided_radius pixels of where its H puts the feature, and these matches
+// REPLACE the pair's; a pair without such a model keeps none (the gate's rule: a first-pass pair no model verified is where the
+// wrong matches live).  The feature files' key points are then loaded with the descriptors.
 struct DescMatchOptions {
   double ratio = 0.8;
   int min_matches = 8;
   int device_id = 0;
+  double guided_radius = 0.0;  // pixels; 0: off
+  double ransac_thresh = 4.0;
+  int min_inliers = 6;         // kDefaultMinInliers
 };
 bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& fnames_a, const std::string& dir_b,
                       const std::vector<std::string>& fnames_b, const std::vector<std::pair<long, long>>& pairs, const DescMatchOptions& options,

@@ -946,3 +946,31 @@ def make_descriptors(scene_or_table, D: int = 128, noise: int = 12, n_distractor
     feat_ptr = (np.asarray(kp_ptr, dtype=np.int64) + n_distractors * np.arange(n_img + 1)).astype(np.int64)
     return feat_ptr, np.concatenate(descs) if descs else np.zeros((0, D), np.uint8), \
         np.concatenate(kps).astype(np.float32) if kps else np.zeros((0, 2), np.float32)
+
+
+def make_repeated_descriptors(scene_or_table, D: int = 128, noise: int = 12, n_distractors: int = 50, repeat_share: float = 0.7,
+                              repeat_group: int = 4, repeat_noise: int = 6, seed: int = 0):
+    """make_descriptors for texture that repeats (pitch markings, seats, windows): repeat_share of the tracks, chosen at random, are
+    put in groups of repeat_group that share ONE base descriptor, each track of a group a copy of it with uniform integer
+    perturbation in [-repeat_noise, repeat_noise]; the other tracks keep a descriptor of their own.  Observations, distractors,
+    feature order and the return value are make_descriptors's, so the table's feature indices stay valid -- but a feature's
+    look-alikes sit elsewhere in the other image, which the ratio test over all features cannot tell from its partner."""
+    kp_ptr, kp_xy, track, (w, h) = _feature_tracks(scene_or_table)
+    rng = np.random.default_rng(seed)
+    n_img = len(kp_ptr) - 1
+    n_track = int(track.max()) + 1 if len(track) else 0
+    base = rng.integers(0, 256, (n_track, D), dtype=np.int64)
+    g = max(int(repeat_group), 1)
+    n_rep = int(repeat_share * n_track) // g * g
+    groups = rng.permutation(n_track)[:n_rep].reshape(-1, g)
+    if len(groups):
+        base[groups] = np.clip(base[groups[:, 0]][:, None, :] + rng.integers(-repeat_noise, repeat_noise + 1, (len(groups), g, D)), 0, 255)
+    obs = np.clip(base[track] + rng.integers(-noise, noise + 1, (len(track), D)), 0, 255).astype(np.uint8)
+    descs, kps = [], []
+    for i in range(n_img):
+        sl = slice(int(kp_ptr[i]), int(kp_ptr[i + 1]))
+        descs += [obs[sl], rng.integers(0, 256, (n_distractors, D), dtype=np.uint8)]
+        kps += [kp_xy[sl], rng.uniform([0, 0], [w, h], (n_distractors, 2)).astype(np.float32)]
+    feat_ptr = (np.asarray(kp_ptr, dtype=np.int64) + n_distractors * np.arange(n_img + 1)).astype(np.int64)
+    return feat_ptr, np.concatenate(descs) if descs else np.zeros((0, D), np.uint8), \
+        np.concatenate(kps).astype(np.float32) if kps else np.zeros((0, 2), np.float32)
