@@ -824,6 +824,116 @@ int32_t ptz_desc_match_pairs_guided_device(const ptz_desc_set* set_a, const ptz_
 /* tests only: the full matrix d2 [n_a, n_b] (host) of one pair, from the matcher's own matrix-core tile code */
 int32_t ptz_debug_desc_dist2(const ptz_desc_set* set_a, int32_t img_a, const ptz_desc_set* set_b, int32_t img_b, int32_t* out);
 
+/* ---- relocalization assembly: from the match table of every (reference, query) pair to the solve's inputs ----------------------
+ * What run_ptz_reloc.cc does on the host between the matcher and the solve -- FindBestMatch, the initial camera, the query's CSR --
+ * on the device, and for the K = max_refs best references of a query instead of one.  The contract is csrc/ptz_reloc_assemble.h:
+ * a query's pairs are ranked by (match count descending, position in its list ascending), pairs without matches never rank; slots
+ * 0 .. n_sel - 1 (n_sel <= K) take the first K, slot 0 is the anchor.  cam_cur = [f, f, 0.5 w, 0.5 h, rvec, t, dist] of the anchor.
+ * K = 1: the output CSR is a copy of the anchor pair's matches and cam_ref the anchor's camera -- the arrays the tool builds, so every
+ * downstream call returns the bits it returns today.  K > 1: cam_ref is the virtual anchor [fa, fa, S, S, rvec_a, t_a, 0 x 5],
+ * S = 8192, and every match of every selected pair is re-expressed as a pixel of it (undistorted in its own view for factor_type & 1
+ * and dropped where that view's border guard would skip it; rotated R_a R_r^T; dropped behind the anchor or outside [0, 2S)^2).  All
+ * references are assumed to share one projection centre (the library's rotation-only model).
+ * Inputs: the match CSR over n_pair pairs in the layout of ptz_desc_matches_device_ptrs; pair_ref [n_pair] the reference image of
+ * each pair; query_ptr [n_query + 1] the contiguous pair list of each query (query_ptr[0] = 0, query_ptr[n_query] = n_pair);
+ * ref_cams [15 n_ref]; ref_R [9 n_ref] row-major, from ptz_reloc_ref_rotations (host logic only: Rodrigues of every reference, once);
+ * query_wh [2 n_query] the queries' image sizes.
+ * Outputs: sel_pair [K n_query] (pair index, -1 for an unused slot), n_sel [n_query] (0: unusable query, empty range, finite cameras:
+ * those of the first reference of its list, reference 0 for an empty list), out_ptr [n_query + 1], out_uv_ref / out_uv_cur
+ * [n_match, 2] and out_src [n_match] (index of each kept match in the input arrays) of which the first out_ptr[n_query] entries are
+ * written, kept matches slot after slot in each pair's order; cam_ref / cam_cur [15 n_query].
+ * A query's output depends on its own pairs only: not on the batch, the order of the queries or the launch.
+ * ptz_reloc_assemble (host arrays: upload, run, download).  PTZ_EINVAL, before any device work: negative extents, max_refs < 1,
+ * offsets that do not start at 0, decrease or do not cover the pairs, pair_ref outside [0, n_ref), missing arrays, an image size
+ * that is not positive, device_id < 0; PTZ_EUNSUPPORTED: an unknown factor_type; PTZ_ELIMIT: more than 2^31 - 1 matches or slots;
+ * n_query = 0 is PTZ_OK.
+ * ptz_reloc_assemble_device: the same on DEVICE pointers of the device that owns d_cam_cur, enqueued on `hip_stream`, returns without
+ * synchronising.  Nothing on the device is validated (a malformed list is an empty one, a pair whose reference is out of range never
+ * ranks).  d_workspace: 256-byte aligned device memory of at least ptz_reloc_assemble_workspace_bytes(n_query, n_match) bytes, the
+ * caller's until the stream has run the call. */
+int32_t ptz_reloc_ref_rotations(int32_t n_ref, const double* ref_cams, double* ref_R);
+int64_t ptz_reloc_assemble_workspace_bytes(int32_t n_query, int64_t n_match);
+int32_t ptz_reloc_assemble_device(int32_t n_query, int32_t n_pair, int64_t n_match, int32_t n_ref, const int64_t* d_match_ptr,
+                                  const float* d_uv_ref, const float* d_uv_cur, const int32_t* d_pair_ref, const int64_t* d_query_ptr,
+                                  const double* d_ref_cams, const double* d_ref_R, const int32_t* d_query_wh, int32_t factor_type,
+                                  int32_t max_refs, int32_t* d_sel_pair, int32_t* d_n_sel, int64_t* d_out_ptr, float* d_out_uv_ref,
+                                  float* d_out_uv_cur, int32_t* d_out_src, double* d_cam_ref, double* d_cam_cur, void* d_workspace,
+                                  int64_t workspace_bytes, void* hip_stream);
+int32_t ptz_reloc_assemble(int32_t n_query, int32_t n_pair, int32_t n_ref, const int64_t* match_ptr, const float* uv_ref,
+                           const float* uv_cur, const int32_t* pair_ref, const int64_t* query_ptr, const double* ref_cams,
+                           const double* ref_R, const int32_t* query_wh, int32_t factor_type, int32_t max_refs, int32_t device_id,
+                           int32_t* sel_pair, int32_t* n_sel, int64_t* out_ptr, float* out_uv_ref, float* out_uv_cur, int32_t* out_src,
+                           double* cam_ref, double* cam_cur, double* device_ms /* or NULL */);
+
+/* ---- the resident serving loop of relocalization ---------------------------------------------------------------------------------
+ * What joins the device entry points above.  The references stay on the device: their descriptor set (the caller's, with key
+ * points, alive as long as the relocalizer) and their cameras ref_cams [15 n_ref] (image m of the set is camera m).  A run takes the
+ * n_query images of query_set (with key points; query_wh [2 n_query] their sizes) through, in this order, every array in between on
+ * the device:
+ *   1. ptz_desc_match_pairs over all (reference, query) pairs, test image by test image, the references in their order;
+ *   2. guided_radius > 0: ptz_match_gate_run_device on all pairs (ransac_thresh, min_inliers) and ptz_desc_match_pairs_guided_device
+ *      with the H it leaves and found = (the gate kept matches of the pair), exactly as MatchDescriptors composes the host forms;
+ *   3. ptz_reloc_assemble_device (max_refs, factor_type);
+ *   4. inlier_matches: ptz_match_gate_run_device on the assembled queries;
+ *   5. trim = 0: ptz_krt_solve_batch_device, on the gate's compacted CSR if inlier_matches; trim != 0:
+ *      ptz_krt_solve_batch_trimmed_device over the assembled arrays, the gate's kept set as its universe if inlier_matches;
+ *   6. uncertainty: ptz_krt_covariance_batch_device over the matches a query kept (the trimming loop's set, else the gate's, else all).
+ * The composition is run_ptz_reloc's, so with max_refs = 1 every per-query output is the bits of the path through
+ * ptz_krt_solve_batch / _gated / _trimmed and ptz_krt_covariance_batch on the host-selected arrays.  The host reads one word in
+ * between (the extent of the assembled arrays) and, at the end, per-query results only -- any pointer of the result may be NULL:
+ * cam [15 n_query] (the solve's cam_cur: the initial camera where the query was not accepted), accepted, summaries, sel_ref
+ * [max_refs n_query] (reference image of each slot, -1 unused), n_sel, n_matches (assembled), n_inliers (kept by the gate;
+ * n_matches without it), trim_report (trim != 0), cov [NF NF n_query] / sigma0 / cov_status (uncertainty), and stage_ms [6]: device
+ * time of the stages above (2: the gate's launches plus the guided matcher's).  A query with n_sel = 0 is solved on no matches.
+ * gate_max_pair_matches (2048, at most 4096): the pair size the gates' bound tables are built for; a pair (stage 2) or a query
+ * (stage 4) with more matches does not pass.  The gate object is kept and grows with the runs.
+ * ptz_relocalizer_matches downloads the last run's assembled matches (tests): match_ptr [n_query + 1], uv_ref / uv_cur
+ * [ptz_relocalizer_n_matches, 2], src (index in the matcher's table), any may be NULL.
+ * ptz_relocalizer_table: the last run's match table of all pairs (the guided pass's, if it ran), the relocalizer's until its next run
+ * or its end: one ptz_desc_matches_download of it is what --save_matches writes.
+ * PTZ_EINVAL, before any device work: NULL relocalizer / sets / result, n_ref < 1, n_query < 0, an image size that is not positive,
+ * max_refs < 1, min_inliers < 0, a radius or threshold that is negative or not finite, a device_id in the options that is not the
+ * relocalizer's; PTZ_EUNSUPPORTED: factor_type; the stages' own codes otherwise.  Runs on one relocalizer are the caller's to order. */
+typedef struct ptz_reloc_options {
+  ptz_desc_options match;        /* stage 1 (and 2) */
+  double guided_radius;          /* 0: no guided pass */
+  double ransac_thresh;          /* 4.0 */
+  int32_t min_inliers;           /* 6 */
+  int32_t inlier_matches;        /* 0 */
+  int32_t trim;                  /* 0 */
+  int32_t uncertainty;           /* 0 */
+  ptz_krt_trim_options trim_options;
+  int32_t max_refs;              /* 1 */
+  int32_t factor_type;           /* PTZ_KRT_F */
+  double max_reproj_error;       /* 100 */
+  int32_t gate_max_pair_matches; /* 2048 */
+  int32_t reserved_;
+  ptz_lm_options lm;
+} ptz_reloc_options;
+void ptz_reloc_options_default(ptz_reloc_options* o);
+typedef struct ptz_reloc_result {
+  double* cam;
+  int32_t* accepted;
+  ptz_lm_summary* summaries;
+  int32_t* sel_ref;
+  int32_t* n_sel;
+  int32_t* n_matches;
+  int32_t* n_inliers;
+  ptz_krt_trim_report* trim_report;
+  double* cov;
+  double* sigma0;
+  int32_t* cov_status;
+  double stage_ms[6];
+} ptz_reloc_result;
+typedef struct ptz_relocalizer ptz_relocalizer;
+int32_t ptz_relocalizer_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t device_id, ptz_relocalizer** out);
+void ptz_relocalizer_destroy(ptz_relocalizer* r);
+int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                            const ptz_reloc_options* options, ptz_reloc_result* result);
+const ptz_desc_matches* ptz_relocalizer_table(const ptz_relocalizer* r);
+int64_t ptz_relocalizer_n_matches(const ptz_relocalizer* r);
+int32_t ptz_relocalizer_matches(const ptz_relocalizer* r, int64_t* match_ptr, float* uv_ref, float* uv_cur, int32_t* src);
+
 #ifdef __cplusplus
 }
 #endif

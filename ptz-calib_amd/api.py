@@ -38,7 +38,9 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_batch_trimmed_device", "ptz_desc_options_default", "ptz_desc_set_create", "ptz_desc_set_destroy",
            "ptz_desc_match_pairs", "ptz_desc_matches_n_matches", "ptz_desc_matches_n_pairs", "ptz_desc_matches_device_ms",
            "ptz_desc_matches_n_chunks", "ptz_desc_matches_download", "ptz_desc_matches_device_ptrs", "ptz_desc_matches_destroy",
-           "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device"]
+           "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device", "ptz_reloc_ref_rotations",
+           "ptz_reloc_assemble_workspace_bytes", "ptz_reloc_assemble_device", "ptz_reloc_assemble", "ptz_reloc_options_default",
+           "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table"]
 
 
 class PtzError(RuntimeError):
@@ -1276,3 +1278,154 @@ def desc_dist2(set_a, img_a, set_b, img_b):
     out = np.zeros((na, nb), dtype=np.int32)
     _check(lib().ptz_debug_desc_dist2(set_a.handle, int(img_a), set_b.handle, int(img_b), _p(out) if out.size else None), "ptz_debug_desc_dist2")
     return out
+
+
+# ---- relocalization assembly (csrc/ptz_reloc_assemble.h) ----------------------------------------------------------------------------
+def reloc_ref_rotations(ref_cams):
+    """ptz_reloc_ref_rotations (host logic only): Rodrigues of every reference camera [n_ref, 15] -> [n_ref, 9] row-major."""
+    cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+    R = np.zeros((len(cams), 9))
+    _check(lib().ptz_reloc_ref_rotations(len(cams), _p(cams), _p(R)), "ptz_reloc_ref_rotations")
+    return R
+
+
+def reloc_assemble_workspace_bytes(n_query, n_match) -> int:
+    lib().ptz_reloc_assemble_workspace_bytes.restype = C.c_int64
+    return int(lib().ptz_reloc_assemble_workspace_bytes(int(n_query), C.c_int64(int(n_match))))
+
+
+def reloc_assemble(match_ptr, uv_ref, uv_cur, pair_ref, query_ptr, ref_cams, query_wh, factor_type=0, max_refs=1, ref_R=None, device_id=0):
+    """ptz_reloc_assemble: from the match CSR of every (reference, query) pair to the solve's inputs, for the max_refs best references
+    of every query.  pair_ref [n_pair]: the reference of each pair; query_ptr [n_query + 1]: the contiguous pair list of each query;
+    ref_cams [n_ref, 15]; query_wh [n_query, 2]; ref_R: reloc_ref_rotations(ref_cams) unless given.
+    Returns a dict: sel_pair [n_query, K] (-1: unused slot), n_sel [n_query], match_ptr [n_query + 1], uv_ref / uv_cur [n_kept, 2],
+    src [n_kept] (index in the input arrays), cam_ref / cam_init [n_query, 15], device_ms."""
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    a = np.ascontiguousarray(uv_ref, dtype=np.float32).reshape(-1, 2)
+    b = np.ascontiguousarray(uv_cur, dtype=np.float32).reshape(-1, 2)
+    pref = np.ascontiguousarray(pair_ref, dtype=np.int32)
+    qptr = np.ascontiguousarray(query_ptr, dtype=np.int64)
+    cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+    wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
+    R = reloc_ref_rotations(cams) if ref_R is None else np.ascontiguousarray(ref_R, dtype=np.float64).reshape(-1, 9)
+    nq, npair, nm, K = len(qptr) - 1, len(ptr) - 1, len(a), int(max_refs)
+    if len(pref) != npair or len(wh) != nq or len(R) != len(cams) or len(b) != nm:
+        raise ValueError("pair_ref: one reference per pair, query_wh: one size per query, ref_R: one matrix per reference")
+    sel = np.full((nq, max(K, 1)), -1, dtype=np.int32)
+    nsel = np.zeros(nq, dtype=np.int32)
+    optr = np.zeros(nq + 1, dtype=np.int64)
+    oa, ob = np.zeros((nm, 2), dtype=np.float32), np.zeros((nm, 2), dtype=np.float32)
+    osrc = np.zeros(nm, dtype=np.int32)
+    cref, ccur = np.zeros((nq, 15)), np.zeros((nq, 15))
+    ms = C.c_double()
+    _check(lib().ptz_reloc_assemble(nq, npair, len(cams), _p(ptr), _p(a) if nm else None, _p(b) if nm else None, _p(pref) if npair else None,
+                                    _p(qptr), _p(cams), _p(R), _p(wh), int(factor_type), K, int(device_id), _p(sel), _p(nsel), _p(optr),
+                                    _p(oa) if nm else None, _p(ob) if nm else None, _p(osrc) if nm else None, _p(cref), _p(ccur),
+                                    C.byref(ms)), "ptz_reloc_assemble")
+    k = int(optr[-1])
+    return dict(sel_pair=sel, n_sel=nsel, match_ptr=optr, uv_ref=oa[:k], uv_cur=ob[:k], src=osrc[:k], cam_ref=cref, cam_init=ccur,
+                device_ms=ms.value)
+
+
+def reloc_assemble_device(n_query, n_pair, n_match, n_ref, d_match_ptr, d_uv_ref, d_uv_cur, d_pair_ref, d_query_ptr, d_ref_cams, d_ref_R,
+                          d_query_wh, d_sel_pair, d_n_sel, d_out_ptr, d_out_uv_ref, d_out_uv_cur, d_out_src, d_cam_ref, d_cam_cur,
+                          d_workspace, workspace_bytes, factor_type=0, max_refs=1, stream=None):
+    """ptz_reloc_assemble_device: every d_* is a device buffer (torch tensor or integer address); d_workspace needs
+    reloc_assemble_workspace_bytes(n_query, n_match) bytes.  Enqueues on `stream` and returns without synchronising."""
+    _check(lib().ptz_reloc_assemble_device(int(n_query), int(n_pair), C.c_int64(int(n_match)), int(n_ref), _dptr(d_match_ptr), _dptr(d_uv_ref),
+                                           _dptr(d_uv_cur), _dptr(d_pair_ref), _dptr(d_query_ptr), _dptr(d_ref_cams), _dptr(d_ref_R),
+                                           _dptr(d_query_wh), int(factor_type), int(max_refs), _dptr(d_sel_pair), _dptr(d_n_sel),
+                                           _dptr(d_out_ptr), _dptr(d_out_uv_ref), _dptr(d_out_uv_cur), _dptr(d_out_src), _dptr(d_cam_ref),
+                                           _dptr(d_cam_cur), _dptr(d_workspace), C.c_int64(int(workspace_bytes)),
+                                           C.c_void_p(stream) if stream else None), "ptz_reloc_assemble_device")
+
+
+# ---- the resident serving loop (ptz_relocalizer_*) ---------------------------------------------------------------------------------
+class RelocOptions(C.Structure):
+    _fields_ = [("match", DescOptions), ("guided_radius", C.c_double), ("ransac_thresh", C.c_double), ("min_inliers", C.c_int32),
+                ("inlier_matches", C.c_int32), ("trim", C.c_int32), ("uncertainty", C.c_int32), ("trim_options", KrtTrimOptions),
+                ("max_refs", C.c_int32), ("factor_type", C.c_int32), ("max_reproj_error", C.c_double), ("gate_max_pair_matches", C.c_int32),
+                ("reserved_", C.c_int32), ("lm", LmOptions)]
+
+
+class RelocResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("cam", "accepted", "summaries", "sel_ref", "n_sel", "n_matches", "n_inliers", "trim_report", "cov",
+                                          "sigma0", "cov_status")] + [("stage_ms", C.c_double * 6)]
+
+
+class Relocalizer:
+    """ptz_relocalizer: relocalization from features with the references resident on the device.  ref_set: a DescSet with key points
+    (kept alive by this object), ref_cams [n_ref, 15] (image m of the set is camera m)."""
+
+    def __init__(self, ref_set, ref_cams, device_id=None):
+        self.ref_set = ref_set
+        self.ref_cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+        self.device_id = ref_set.device_id if device_id is None else int(device_id)
+        self.handle = C.c_void_p()
+        lib().ptz_relocalizer_destroy.restype = None
+        lib().ptz_relocalizer_n_matches.restype = C.c_int64
+        _check(lib().ptz_relocalizer_create(ref_set.handle, _p(self.ref_cams), len(self.ref_cams), self.device_id, C.byref(self.handle)),
+               "ptz_relocalizer_create")
+
+    def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, **lm):
+        """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
+        krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
+        arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
+        None), cov / sigma0 / cov_status (or None), stage_ms [6]."""
+        wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
+        n, K = len(wh), int(max_refs)
+        o = RelocOptions()
+        lib().ptz_reloc_options_default(C.byref(o))
+        for k, v in dict(match or {}, device_id=self.device_id).items():
+            setattr(o.match, k, v)
+        for k, v in (trim or {}).items():
+            setattr(o.trim_options, k, v)
+        for k, v in lm.items():
+            setattr(o.lm, k, v)
+        o.guided_radius, o.ransac_thresh, o.min_inliers, o.inlier_matches = float(guided_radius), float(ransac_thresh), int(min_inliers), int(bool(inlier_matches))
+        o.trim, o.uncertainty, o.max_refs, o.factor_type = int(trim is not None), int(bool(uncertainty)), K, int(factor_type)
+        o.max_reproj_error, o.gate_max_pair_matches = float(max_reproj_error), int(gate_max_pair_matches)
+        nf = krt_free_dim(factor_type)
+        cam, acc = np.zeros((n, 15)), np.zeros(n, dtype=np.int32)
+        summ, rep = (LmSummary * max(n, 1))(), (KrtTrimReport * max(n, 1))()
+        sel = np.full((n, max(K, 1)), -1, dtype=np.int32)
+        nsel, nmat, ninl = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        cov, s0, cst = np.zeros((n, nf, nf)), np.zeros(n), np.full(n, -1, dtype=np.int32)
+        r = RelocResult()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p).value
+        r.cam, r.accepted, r.sel_ref, r.n_sel, r.n_matches, r.n_inliers = vp(cam), vp(acc), vp(sel), vp(nsel), vp(nmat), vp(ninl)
+        r.summaries, r.trim_report = C.addressof(summ), C.addressof(rep)
+        r.cov, r.sigma0, r.cov_status = vp(cov), vp(s0), vp(cst)
+        _check(lib().ptz_relocalizer_run(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)), "ptz_relocalizer_run")
+        self._last_n = n
+        return dict(cam=cam, accepted=acc, summaries=[summ[i].as_dict() for i in range(n)], sel_ref=sel, n_sel=nsel, n_matches=nmat, n_inliers=ninl,
+                    trim_report=[rep[i].as_dict() for i in range(n)] if trim is not None else None, cov=cov if uncertainty else None,
+                    sigma0=s0 if uncertainty else None, cov_status=cst if uncertainty else None, stage_ms=np.array(list(r.stage_ms)))
+
+    def matches(self):
+        """The last run's assembled matches (tests): dict of match_ptr, uv_ref, uv_cur, src."""
+        k = int(lib().ptz_relocalizer_n_matches(self.handle))
+        n = self._last_n
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        a, b, s = np.zeros((k, 2), dtype=np.float32), np.zeros((k, 2), dtype=np.float32), np.zeros(k, dtype=np.int32)
+        _check(lib().ptz_relocalizer_matches(self.handle, _p(ptr), _p(a) if k else None, _p(b) if k else None, _p(s) if k else None),
+               "ptz_relocalizer_matches")
+        return dict(match_ptr=ptr, uv_ref=a, uv_cur=b, src=s)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_relocalizer_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -7,6 +7,7 @@
 // --trim_px <px> (not in the reference; with --trim_sigma, --trim_rounds) solves every test image with the outlier-trimming loop of
 // ptz_krt_solve_batch_trimmed: with --inlier_matches the gate's inliers are the loop's universe, with --uncertainty the covariance is
 // taken over the matches the last solve kept, and every record gains rms_px, n_matches, n_removed, trim_rounds.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -37,6 +38,29 @@ static BestMatchT FindBestMatch(const std::string& fname, const std::vector<std:
   return best;
 }
 
+// the descriptors of the feature files and the key points already loaded, as one resident set (image m: features ptr[m] .. ptr[m + 1])
+static bool BuildDescSet(const std::string& dir, const std::vector<std::string>& fnames, const std::vector<ImageFeatures>& features,
+                         ptz_desc_set** set)
+{
+  std::vector<unsigned char> all, one;
+  std::vector<float> kp_xy;
+  std::vector<int64_t> ptr(1, 0);
+  int dim = 0;
+  for (size_t i = 0; i < fnames.size(); ++i) {
+    const std::string path = dir + "/" + fnames[i] + ".txt";
+    if (!ReadColmapDescriptors(path, one, dim) || dim < 1 || one.size() / static_cast<size_t>(dim) != features[i].keypoints.size()) {
+      fprintf(stderr, "Error reading the descriptors of %s (missing, of another dimension, or not one per key point)\n", path.c_str());
+      return false;
+    }
+    all.insert(all.end(), one.begin(), one.end());
+    for (const KeyPoint& k : features[i].keypoints) { kp_xy.push_back(k.pt.x); kp_xy.push_back(k.pt.y); }
+    ptr.push_back(ptr.back() + static_cast<int64_t>(features[i].keypoints.size()));
+  }
+  const int32_t rc = ptz_desc_set_create(static_cast<int32_t>(fnames.size()), ptr.data(), all.data(), dim, kp_xy.data(), 0, set);
+  if (rc != PTZ_OK) fprintf(stderr, "ptz_desc_set_create failed with status %d (no usable HIP device?)\n", rc);
+  return rc == PTZ_OK;
+}
+
 int main(int argc, char** argv)
 {
   ptzapp::Args parser;
@@ -62,6 +86,10 @@ int main(int argc, char** argv)
   parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
   parser.Add("match_guided", '\0', "With --match_descriptors: match every pair again within this many pixels of its RANSAC homography "
                                    "and keep these matches instead; a pair without a verified model keeps none (off unless given)", false);
+  parser.AddFlag("on_device", "With --match_descriptors: keep the match table on the GPU -- reference selection, the initial camera, the gate, "
+                              "the solve and the covariance run there and only per-image results come back; the output is the same");
+  parser.Add("multi_ref", '\0', "With --match_descriptors: solve each test image against its K best reference images at once (implies "
+                                "--on_device); every record gains n_refs and n_matches", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -71,6 +99,16 @@ int main(int argc, char** argv)
 
   if (parser.Exist("match_guided") && !parser.Exist("match_descriptors")) {
     fprintf(stderr, "--match_guided needs --match_descriptors\n");
+    return 1;
+  }
+  const int multi_ref = parser.Exist("multi_ref") ? atoi(parser.Get("multi_ref").c_str()) : 0;
+  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref");
+  if (on_device && !parser.Exist("match_descriptors")) {
+    fprintf(stderr, "--on_device and --multi_ref need --match_descriptors\n");
+    return 1;
+  }
+  if (parser.Exist("multi_ref") && multi_ref < 1) {
+    fprintf(stderr, "--multi_ref must be at least 1\n");
     return 1;
   }
   const bool trimming = parser.Exist("trim_px");
@@ -99,7 +137,10 @@ int main(int argc, char** argv)
   }
   std::vector<std::vector<DMatch>> pairs_matches;
   std::vector<std::pair<std::string, std::string>> img_pairs_name;
-  if (parser.Exist("match_descriptors")) {
+  if (on_device) {
+    // (the table stays on the GPU: below, once the reference cameras are read)
+  }
+  else if (parser.Exist("match_descriptors")) {
     // blocks test image by test image, the references in ref_fnames order: FindBestMatch's first-wins tie picks the lowest reference
     DescMatchOptions mo;
     if (parser.Exist("match_ratio")) mo.ratio = atof(parser.Get("match_ratio").c_str());
@@ -142,7 +183,7 @@ int main(int argc, char** argv)
   std::vector<int64_t> match_ptr{0};
   std::vector<float> uv_ref, uv_cur;
   std::vector<double> cam_ref, cam_cur;
-  for (size_t test_idx = 0; test_idx < test_fnames.size(); ++test_idx) {
+  for (size_t test_idx = 0; !on_device && test_idx < test_fnames.size(); ++test_idx) {
     const BestMatchT best = FindBestMatch(test_fnames[test_idx], img_pairs_name, pairs_matches);
     const long ref_idx = FindImgIndex(ref_fnames, best.first);
     bool usable = ref_idx != -1 && !best.second.empty();
@@ -177,6 +218,119 @@ int main(int argc, char** argv)
   std::vector<Sigma> sigmas(test_fnames.size());
   struct Trimmed { double rms = 0; int n_matches = 0, n_removed = 0, rounds = 0; };
   std::vector<Trimmed> trimmed(test_fnames.size());
+  std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0);
+  if (on_device && !test_fnames.empty()) {
+    // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
+    // guided pass, the assembly, the gate, the solve or the trimming loop, the covariance -- in the order of the code below
+    ptz_reloc_options ro;
+    ptz_reloc_options_default(&ro);
+    const DescMatchOptions defaults;
+    ro.match.ratio = parser.Exist("match_ratio") ? atof(parser.Get("match_ratio").c_str()) : defaults.ratio;
+    ro.match.min_matches = parser.Exist("match_min") ? atoi(parser.Get("match_min").c_str()) : defaults.min_matches;
+    if (!(ro.match.ratio >= 0.0) || !std::isfinite(ro.match.ratio) || ro.match.min_matches < 0) {
+      fprintf(stderr, "--match_ratio and --match_min must not be negative\n");
+      return 1;
+    }
+    if (parser.Exist("match_guided")) {
+      ro.guided_radius = atof(parser.Get("match_guided").c_str());
+      if (!(ro.guided_radius > 0.0) || !std::isfinite(ro.guided_radius)) {
+        fprintf(stderr, "--match_guided must be a positive number of pixels\n");
+        return 1;
+      }
+    }
+    ro.ransac_thresh = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
+    ro.min_inliers = min_inliers;
+    ro.inlier_matches = parser.Exist("inlier_matches") ? 1 : 0;
+    ro.trim = trimming ? 1 : 0;
+    ro.trim_options = trim;
+    ro.uncertainty = uncertainty ? 1 : 0;
+    ro.max_refs = multi_ref > 0 ? multi_ref : 1;
+    ro.factor_type = parser.Exist("dist") ? PTZ_KRT_FDist : PTZ_KRT_F;
+    ro.max_reproj_error = 100.0;
+    ro.lm.max_num_iterations = 200;
+    const int32_t nq = static_cast<int32_t>(test_fnames.size()), n_ref = static_cast<int32_t>(ref_fnames.size()), K = ro.max_refs;
+    const int32_t nf = ptz_krt_free_dim(ro.factor_type);
+    ptz_desc_set *ref_set = nullptr, *test_set = nullptr;
+    ptz_relocalizer* rl = nullptr;
+    std::vector<double> ref_cams;
+    for (const Camera& c : ref_cameras) {
+      const std::vector<double> v = c.ToVector();
+      ref_cams.insert(ref_cams.end(), v.begin(), v.end());
+    }
+    std::vector<int32_t> wh;
+    for (const Size& s : test_sizes) { wh.push_back(s.width); wh.push_back(s.height); }
+    std::vector<double> cam(15 * static_cast<size_t>(nq)), cov(static_cast<size_t>(nf) * nf * nq, 0.0), sigma0(nq, 0.0);
+    std::vector<int32_t> accepted(nq, 0), n_sel(nq, 0), n_matches(nq, 0), n_inliers(nq, 0), status(nq, -1), sel_ref(static_cast<size_t>(K) * nq, -1);
+    std::vector<ptz_lm_summary> summaries(nq);
+    std::vector<ptz_krt_trim_report> reports(nq);
+    ptz_reloc_result rr;
+    rr.cam = cam.data(); rr.accepted = accepted.data(); rr.summaries = summaries.data(); rr.sel_ref = sel_ref.data(); rr.n_sel = n_sel.data();
+    rr.n_matches = n_matches.data(); rr.n_inliers = n_inliers.data(); rr.trim_report = reports.data(); rr.cov = cov.data();
+    rr.sigma0 = sigma0.data(); rr.cov_status = status.data();
+    bool ok = n_ref > 0 && static_cast<size_t>(n_ref) == ref_cameras.size() && BuildDescSet(parser.Get("ref_features"), ref_fnames, ref_features, &ref_set) &&
+              BuildDescSet(parser.Get("test_features"), test_fnames, test_features, &test_set);
+    int32_t rc = PTZ_OK;
+    if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
+    if (ok && rc == PTZ_OK) rc = ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
+    if (ok && rc == PTZ_OK && parser.Exist("save_matches")) {
+      // the table comes to the host once, for the file alone: blocks in the pairs' order, a pair without matches has none
+      const ptz_desc_matches* t = ptz_relocalizer_table(rl);
+      const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(t));
+      std::vector<int64_t> mptr(static_cast<size_t>(nq) * n_ref + 1, 0);
+      std::vector<int32_t> qa(std::max<size_t>(n, 1)), tb(std::max<size_t>(n, 1));
+      rc = ptz_desc_matches_download(t, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
+      for (size_t p = 0; rc == PTZ_OK && p + 1 < mptr.size(); ++p) {
+        if (mptr[p + 1] == mptr[p]) continue;
+        std::vector<DMatch> ms;
+        for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) {
+          DMatch m;
+          m.queryIdx = qa[static_cast<size_t>(k)];
+          m.trainIdx = tb[static_cast<size_t>(k)];
+          ms.push_back(m);
+        }
+        pairs_matches.push_back(ms);
+        img_pairs_name.push_back({ref_fnames[p % n_ref], test_fnames[p / n_ref]});
+      }
+      if (rc == PTZ_OK && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
+        fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
+        ok = false;
+      }
+    }
+    ptz_relocalizer_destroy(rl);
+    ptz_desc_set_destroy(test_set);
+    ptz_desc_set_destroy(ref_set);
+    if (!ok) return -1;
+    if (rc != PTZ_OK) {
+      fprintf(stderr, "ptz_relocalizer_run failed with status %d (no usable HIP device?)\n", rc);
+      return -1;
+    }
+    const bool gated = ro.inlier_matches != 0;
+    for (int32_t q = 0; q < nq; ++q) {
+      multi_n_refs[q] = n_sel[q];
+      multi_n_matches[q] = n_matches[q];
+      if (n_sel[q] > 0 && accepted[q] && (!gated || n_inliers[q] > 0)) {
+        test_cameras[q].FromVector(std::vector<double>(cam.begin() + 15 * q, cam.begin() + 15 * (q + 1)));
+        success_ids.insert(static_cast<long>(q));
+        fprintf(stderr, "Running ptz-reloc success: %s\n", test_fnames[q].c_str());
+      }
+      else fprintf(stderr, "Running ptz-reloc failed: %s\n", test_fnames[q].c_str());
+      if (trimming) {
+        Trimmed& t = trimmed[q];
+        t.rms = reports[q].rms_last;
+        t.n_matches = n_matches[q];
+        t.n_removed = t.n_matches - reports[q].n_kept;
+        t.rounds = reports[q].rounds;
+      }
+      if (uncertainty && status[q] == PTZ_COV_OK) {
+        Sigma& s = sigmas[q];
+        const double* c = cov.data() + static_cast<size_t>(nf) * nf * q;
+        s.ok = true;
+        s.f = std::sqrt(c[0]);
+        for (int k = 0; k < 3; ++k) s.rot_deg[k] = std::sqrt(c[(1 + k) * nf + 1 + k]) * 180.0 / M_PI;
+        s.s0 = sigma0[q];
+      }
+    }
+  }
   if (!query_image.empty()) {
     static const int MAX_ITER = 200;
     static const double MAX_REPROJ_ERROR = 100.0;
@@ -272,7 +426,7 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty || trimming) {
+  if (uncertainty || trimming || multi_ref > 0) {
     // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
@@ -292,6 +446,10 @@ int main(int argc, char** argv)
       SplitExt(test_fnames[i], &rootname, &ext);
       if (!cams.contains(rootname)) continue;
       Json& j = cams[rootname];
+      if (multi_ref > 0) {
+        j["n_refs"] = Json::Int(multi_n_refs[i]);
+        if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
+      }
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

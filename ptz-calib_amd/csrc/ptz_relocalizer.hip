@@ -1,0 +1,355 @@
+// ptz_relocalizer.hip -- the resident serving loop of the online half: what joins the device entry points.  References stay on the
+// device (their descriptor set is the caller's, their cameras and rotation matrices are uploaded once); a run takes a set of query
+// images through
+//   1. the matcher over all (reference, query) pairs            ptz_desc_match_pairs
+//   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
+//   3. the assembly                                              ptz_reloc_assemble_device
+//   4. optionally the gate on the assembled queries              ptz_match_gate_run_device
+//   5. the solve or the trimmed solve                            ptz_krt_solve_batch_device, ptz_krt_solve_batch_trimmed_device
+//   6. optionally the covariance                                 ptz_krt_covariance_batch_device
+// with every array between them on the device.  Nothing here computes: the stages are the library's own entry points, composed as
+// run_ptz_reloc and MatchDescriptors compose their host forms, so with max_refs = 1 a query's outputs are the bits of that path.
+// The two kernels of this file turn the gate's kept offsets into what the host code derives from its mask: a pair's `found` after
+// the min_inliers rule, and a mask that is zero for a query that does not pass.
+#include <cmath>
+#include <vector>
+
+#include "ptz_common.h"
+#include "ptz_host_batch.h"
+
+namespace ptz {
+namespace {
+
+// found[p] = 1 iff the gate kept matches of pair p (a model and at least max(min_inliers, 4) mask-1 matches), else 0
+__global__ void k_reloc_found(int n_pair, const int64_t* __restrict__ gate_ptr, int32_t* __restrict__ found)
+{
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n_pair) found[p] = gate_ptr[p + 1] > gate_ptr[p] ? 1 : 0;
+}
+
+// the mask bytes of a query the gate did not pass are whatever an earlier run left: zero them (one wave per query)
+__global__ void k_reloc_universe(int n_query, const int64_t* __restrict__ match_ptr, const int64_t* __restrict__ gate_ptr,
+                                 uint8_t* __restrict__ mask)
+{
+  const int q = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  if (q >= n_query || gate_ptr[q + 1] > gate_ptr[q]) return;
+  for (int64_t i = match_ptr[q] + threadIdx.x % WAVE; i < match_ptr[q + 1]; i += WAVE) mask[i] = 0;
+}
+
+struct Events {
+  int dev;
+  hipEvent_t e[8] = {};
+  explicit Events(int d) : dev(d) {}
+  ~Events() { for (hipEvent_t x : e) ptzpool::event_release(dev, true, x); }
+  hipError_t make() { for (hipEvent_t& x : e) { const hipError_t r = ptzpool::event_acquire(dev, true, &x); if (r != hipSuccess) return r; } return hipSuccess; }
+  double ms(int a, int b) const { float t = 0; (void)hipEventElapsedTime(&t, e[a], e[b]); return t; }
+};
+
+struct DevBlock {  // a pooled block that goes back when the scope ends
+  int dev;
+  char* p = nullptr;
+  explicit DevBlock(int d) : dev(d) {}
+  ~DevBlock() { ptzpool::dev_release(dev, p); }
+  hipError_t take(size_t bytes) { return ptzpool::dev_acquire(dev, bytes ? bytes : 256, (void**)&p); }
+};
+
+}  // namespace
+}  // namespace ptz
+
+struct ptz_relocalizer {
+  int device = 0;
+  int32_t n_ref = 0;
+  const ptz_desc_set* refs = nullptr;
+  char* d_const = nullptr;  // [ref_cams | ref_R]
+  double *d_cams = nullptr, *d_R = nullptr;
+  hipStream_t st = nullptr;
+  ptz_match_gate* gate = nullptr;  // grows with the runs: pairs, matches, matches of one pair
+  int32_t gate_pairs = 0, gate_pm = 0;
+  int64_t gate_matches = 0;
+  ptz_desc_matches* table = nullptr;  // the last run's match table of all pairs (the guided one, if that pass ran)
+  // the last run's block: the assembled matches stay until the next run
+  char* blk = nullptr;
+  int32_t n_query = 0;
+  int64_t kept = 0;
+  size_t o_optr = 0, o_oa = 0, o_ob = 0, o_osrc = 0;
+};
+
+extern "C" void ptz_reloc_options_default(ptz_reloc_options* o)
+{
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  ptz_desc_options_default(&o->match);
+  o->ransac_thresh = 4.0;
+  o->min_inliers = 6;
+  o->gate_max_pair_matches = 2048;
+  ptz_krt_trim_options_default(&o->trim_options);
+  o->max_refs = 1;
+  o->factor_type = PTZ_KRT_F;
+  o->max_reproj_error = 100.0;
+  ptz_lm_options_default(&o->lm);
+}
+
+extern "C" int32_t ptz_relocalizer_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t device_id,
+                                          ptz_relocalizer** out)
+{
+  using namespace ptz;
+  if (!out) return PTZ_EINVAL;
+  *out = nullptr;
+  if (!ref_set || !ref_cams || n_ref < 1 || device_id < 0) return PTZ_EINVAL;
+  clear_stale_error(__func__);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) return PTZ_ENODEVICE;
+  PTZ_DEVICE_GUARD(device_id);
+  std::vector<double> R(9 * (size_t)n_ref);
+  if (const int32_t rc = ptz_reloc_ref_rotations(n_ref, ref_cams, R.data())) return rc;
+  ptz_relocalizer* r = new ptz_relocalizer();
+  r->device = device_id; r->n_ref = n_ref; r->refs = ref_set;
+  const size_t o_R = up256(sizeof(double) * 15 * n_ref), total = o_R + up256(sizeof(double) * 9 * n_ref);
+  hipError_t e = ptzpool::dev_acquire(device_id, total, (void**)&r->d_const);
+  if (e == hipSuccess) e = ptzpool::stream_acquire(device_id, &r->st);
+  if (e == hipSuccess) {
+    r->d_cams = (double*)r->d_const; r->d_R = (double*)(r->d_const + o_R);
+    e = hipMemcpyAsync(r->d_cams, ref_cams, sizeof(double) * 15 * n_ref, hipMemcpyHostToDevice, r->st);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(r->d_R, R.data(), sizeof(double) * 9 * n_ref, hipMemcpyHostToDevice, r->st);
+  if (e == hipSuccess) e = stream_wait(r->st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ptz_relocalizer_destroy(r);
+    return e == hipErrorOutOfMemory ? PTZ_ENOMEM : PTZ_ENODEVICE;
+  }
+  *out = r;
+  return PTZ_OK;
+}
+
+extern "C" void ptz_relocalizer_destroy(ptz_relocalizer* r)
+{
+  if (!r) return;
+  ptz::DeviceGuard guard(r->device);
+  if (r->st) { (void)ptz::stream_wait(r->st); ptzpool::stream_release(r->device, r->st); }
+  ptz_match_gate_destroy(r->gate);
+  ptz_desc_matches_destroy(r->table);
+  ptzpool::dev_release(r->device, r->blk);
+  ptzpool::dev_release(r->device, r->d_const);
+  delete r;
+}
+
+static int32_t reloc_gate_for(ptz_relocalizer* r, int32_t pairs, int64_t matches, int32_t pm)
+{
+  if (r->gate && r->gate_pairs >= pairs && r->gate_matches >= matches && r->gate_pm >= pm) return PTZ_OK;
+  ptz_match_gate_destroy(r->gate);
+  r->gate = nullptr;
+  r->gate_pairs = pairs > r->gate_pairs ? pairs : r->gate_pairs;
+  r->gate_matches = matches > r->gate_matches ? matches : r->gate_matches;
+  r->gate_pm = pm > r->gate_pm ? pm : r->gate_pm;
+  return ptz_match_gate_create(r->gate_pairs, r->gate_matches, r->gate_pm, r->device, &r->gate);
+}
+
+extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                       const ptz_reloc_options* options, ptz_reloc_result* res)
+{
+  using namespace ptz;
+  if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
+  ptz_reloc_options o;
+  if (options) o = *options; else ptz_reloc_options_default(&o);
+  if (o.max_refs < 1 || o.min_inliers < 0 || !(o.guided_radius >= 0.0) || !std::isfinite(o.guided_radius) ||
+      !(std::isfinite(o.ransac_thresh) && o.ransac_thresh > 0) || o.gate_max_pair_matches < 0 || o.gate_max_pair_matches > 4096)
+    return PTZ_EINVAL;
+  for (int q = 0; q < n_query; ++q)
+    if (query_wh[2 * q] <= 0 || query_wh[2 * q + 1] <= 0) return PTZ_EINVAL;
+  if (o.factor_type < PTZ_KRT_F || o.factor_type > PTZ_KRT_FxfyDist) return PTZ_EUNSUPPORTED;
+  if (o.match.device_id != r->device || (o.lm.device_id != 0 && o.lm.device_id != r->device)) return PTZ_EINVAL;
+  for (double& t : res->stage_ms) t = 0;
+  if (n_query == 0) return PTZ_OK;
+  if ((int64_t)n_query * r->n_ref > INT32_MAX || (int64_t)n_query * o.max_refs > INT32_MAX) return PTZ_ELIMIT;
+  clear_stale_error(__func__);
+  PTZ_DEVICE_GUARD(r->device);
+  const int32_t n_ref = r->n_ref, npair = n_query * n_ref, K = o.max_refs;
+  const size_t nq = (size_t)n_query;
+  // the pairs test image by test image, the references in their order: FindBestMatch's first-wins tie picks the lowest reference
+  std::vector<int32_t> ia((size_t)npair), ib((size_t)npair);
+  std::vector<int64_t> qptr(nq + 1);
+  for (int q = 0; q < n_query; ++q) {
+    qptr[q] = (int64_t)q * n_ref;
+    for (int k = 0; k < n_ref; ++k) { ia[(size_t)q * n_ref + k] = k; ib[(size_t)q * n_ref + k] = q; }
+  }
+  qptr[nq] = npair;
+  hipStream_t st = r->st;
+  Events ev(r->device);
+  PTZ_HIP_TRY(ev.make());
+
+  // 1. pass 1 over all pairs
+  ptz_desc_matches_destroy(r->table);
+  r->table = nullptr;
+  ptz_desc_matches* m = nullptr;
+  if (const int32_t rc = ptz_desc_match_pairs(r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
+  struct Held { ptz_desc_matches*& m; ~Held() { ptz_desc_matches_destroy(m); } } held{m};
+  res->stage_ms[0] = ptz_desc_matches_device_ms(m);
+  int64_t nm = ptz_desc_matches_n_matches(m);
+  if (nm > INT32_MAX) return PTZ_ELIMIT;
+  const int64_t* d_ptr = nullptr;
+  const float *d_ua = nullptr, *d_ub = nullptr;
+  if (const int32_t rc = ptz_desc_matches_device_ptrs(m, &d_ptr, nullptr, nullptr, nullptr, &d_ua, &d_ub)) return rc;
+  if (nm > 0 && (!d_ua || !d_ub)) return PTZ_EINVAL;  // sets without key points
+
+  // 2. the gate on all pairs, then the guided pass with its device H / found, as MatchDescriptors composes them
+  if (o.guided_radius > 0.0) {
+    if (const int32_t rc = reloc_gate_for(r, npair, nm, o.gate_max_pair_matches)) return rc;
+    const size_t nmx = (size_t)(nm > 0 ? nm : 1);
+    BlockLayout b;
+    const size_t o_H = b.take(sizeof(double) * 9 * npair), o_f = b.take(sizeof(int32_t) * npair), o_p = b.take(sizeof(int64_t) * ((size_t)npair + 1)),
+                 o_a = b.take(sizeof(float) * 2 * nmx), o_b = b.take(sizeof(float) * 2 * nmx);
+    DevBlock t(r->device);
+    if (t.take(b.total()) != hipSuccess) return PTZ_ENOMEM;
+    PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
+    if (const int32_t rc = ptz_match_gate_run_device(r->gate, npair, d_ptr, d_ua, d_ub, o.ransac_thresh, o.min_inliers, (double*)(t.p + o_H),
+                                                     (int32_t*)(t.p + o_f), nullptr, (int64_t*)(t.p + o_p), (float*)(t.p + o_a),
+                                                     (float*)(t.p + o_b), nullptr, st))
+      return rc;
+    hipLaunchKernelGGL(k_reloc_found, dim3((npair + 255) / 256), dim3(256), 0, st, npair, (const int64_t*)(t.p + o_p), (int32_t*)(t.p + o_f));
+    PTZ_HIP_TRY(hipGetLastError());
+    PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
+    PTZ_HIP_TRY(stream_wait(st));  // the guided call runs on a stream of its own
+    ptz_desc_matches* g = nullptr;
+    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), (const double*)(t.p + o_H),
+                                                              (const int32_t*)(t.p + o_f), o.guided_radius, &o.match, &g))
+      return rc;
+    ptz_desc_matches_destroy(m);
+    m = g;
+    res->stage_ms[1] = ev.ms(0, 1) + ptz_desc_matches_device_ms(m);
+    nm = ptz_desc_matches_n_matches(m);
+    if (nm > INT32_MAX) return PTZ_ELIMIT;
+    if (const int32_t rc = ptz_desc_matches_device_ptrs(m, &d_ptr, nullptr, nullptr, nullptr, &d_ua, &d_ub)) return rc;
+  }
+
+  // the run's block
+  const bool gated = o.inlier_matches != 0, trimming = o.trim != 0, cov = o.uncertainty != 0;
+  const int nf = ptz_krt_free_dim(o.factor_type);
+  const size_t nmx = (size_t)(nm > 0 ? nm : 1);
+  const int64_t ws_asm = ptz_reloc_assemble_workspace_bytes(n_query, nm), ws_trim = trimming ? ptz_krt_trim_workspace_bytes(n_query, nm) : 0;
+  BlockLayout b;
+  const size_t o_pref = b.take(sizeof(int32_t) * npair), o_qptr = b.take(sizeof(int64_t) * (nq + 1)), o_wh = b.take(sizeof(int32_t) * 2 * nq),
+               o_sel = b.take(sizeof(int32_t) * K * nq), o_nsel = b.take(sizeof(int32_t) * nq), o_optr = b.take(sizeof(int64_t) * (nq + 1)),
+               o_oa = b.take(sizeof(float) * 2 * nmx), o_ob = b.take(sizeof(float) * 2 * nmx), o_osrc = b.take(sizeof(int32_t) * nmx),
+               o_cref = b.take(sizeof(double) * 15 * nq), o_ccur = b.take(sizeof(double) * 15 * nq), o_ws = b.take((size_t)ws_asm),
+               o_sum = b.take(sizeof(ptz_lm_summary) * nq), o_acc = b.take(sizeof(int32_t) * nq), o_H = b.take(sizeof(double) * 9 * nq),
+               o_found = b.take(sizeof(int32_t) * nq), o_mask = b.take(nmx), o_gptr = b.take(sizeof(int64_t) * (nq + 1)),
+               o_ga = b.take(sizeof(float) * 2 * nmx), o_gb = b.take(sizeof(float) * 2 * nmx), o_kept = b.take(nmx),
+               o_rep = b.take(sizeof(ptz_krt_trim_report) * nq), o_wst = b.take((size_t)ws_trim), o_cov = b.take(sizeof(double) * nf * nf * nq),
+               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq);
+  ptzpool::dev_release(r->device, r->blk);
+  r->blk = nullptr; r->n_query = 0; r->kept = 0;
+  if (ptzpool::dev_acquire(r->device, b.total(), (void**)&r->blk) != hipSuccess) return PTZ_ENOMEM;
+  char* d = r->blk;
+  PTZ_HIP_TRY(hipMemcpyAsync(d + o_pref, ia.data(), sizeof(int32_t) * npair, hipMemcpyHostToDevice, st));
+  PTZ_HIP_TRY(hipMemcpyAsync(d + o_qptr, qptr.data(), sizeof(int64_t) * (nq + 1), hipMemcpyHostToDevice, st));
+  PTZ_HIP_TRY(hipMemcpyAsync(d + o_wh, query_wh, sizeof(int32_t) * 2 * nq, hipMemcpyHostToDevice, st));
+
+  // 3. the assembly
+  PTZ_HIP_TRY(hipEventRecord(ev.e[2], st));
+  if (const int32_t rc = ptz_reloc_assemble_device(n_query, npair, nm, n_ref, d_ptr, d_ua, d_ub, (const int32_t*)(d + o_pref), (const int64_t*)(d + o_qptr),
+                                                   r->d_cams, r->d_R, (const int32_t*)(d + o_wh), o.factor_type, K, (int32_t*)(d + o_sel),
+                                                   (int32_t*)(d + o_nsel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
+                                                   (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
+    return rc;
+  PTZ_HIP_TRY(hipEventRecord(ev.e[3], st));
+  std::vector<int64_t> optr(nq + 1), gptr(nq + 1, 0);
+  PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d + o_optr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
+  PTZ_HIP_TRY(stream_wait(st));  // the one word the host needs: the extent of the assembled arrays
+  const int64_t kept = optr[nq];
+  if (kept < 0 || kept > nm) return PTZ_ENODEVICE;
+  const int64_t* a_ptr = (const int64_t*)(d + o_optr);
+  const float *a_ref = (const float*)(d + o_oa), *a_cur = (const float*)(d + o_ob);
+  const double* a_cref = (const double*)(d + o_cref);
+  double* a_ccur = (double*)(d + o_ccur);
+  ptz_lm_summary* d_sum = (ptz_lm_summary*)(d + o_sum);
+  int32_t* d_acc = (int32_t*)(d + o_acc);
+  uint8_t *d_mask = (uint8_t*)(d + o_mask), *d_kept = (uint8_t*)(d + o_kept);
+
+  // 4. the gate on the assembled queries
+  if (gated) {
+    if (const int32_t rc = reloc_gate_for(r, n_query, nm, o.gate_max_pair_matches)) return rc;
+    if (const int32_t rc = ptz_match_gate_run_device(r->gate, n_query, a_ptr, a_ref, a_cur, o.ransac_thresh, o.min_inliers, (double*)(d + o_H),
+                                                     (int32_t*)(d + o_found), d_mask, (int64_t*)(d + o_gptr), (float*)(d + o_ga),
+                                                     (float*)(d + o_gb), nullptr, st))
+      return rc;
+    hipLaunchKernelGGL(k_reloc_universe, dim3((n_query + 3) / 4), dim3(256), 0, st, n_query, a_ptr, (const int64_t*)(d + o_gptr), d_mask);
+    PTZ_HIP_TRY(hipGetLastError());
+    PTZ_HIP_TRY(hipMemcpyAsync(gptr.data(), d + o_gptr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
+  }
+  PTZ_HIP_TRY(hipEventRecord(ev.e[4], st));
+
+  // 5. the solve: on the gate's compacted CSR, or the trimming loop over the assembled arrays with the gate's set as its universe
+  if (trimming) {
+    PTZ_HIP_TRY(hipMemsetAsync(d + o_rep, 0, sizeof(ptz_krt_trim_report) * nq, st));
+    if (const int32_t rc = ptz_krt_solve_batch_trimmed_device(n_query, kept, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
+                                                              o.max_reproj_error, gated ? d_mask : nullptr, &o.trim_options, &o.lm, d_sum, d_acc,
+                                                              d_kept, (ptz_krt_trim_report*)(d + o_rep), d + o_wst, ws_trim, st))
+      return rc;
+  }
+  else if (const int32_t rc = gated ? ptz_krt_solve_batch_device(n_query, (const int64_t*)(d + o_gptr), (const float*)(d + o_ga), (const float*)(d + o_gb),
+                                                                  nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type, o.max_reproj_error, &o.lm,
+                                                                  d_sum, d_acc, st)
+                                    : ptz_krt_solve_batch_device(n_query, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
+                                                                  o.max_reproj_error, &o.lm, d_sum, d_acc, st))
+    return rc;
+  PTZ_HIP_TRY(hipEventRecord(ev.e[5], st));
+
+  // 6. the covariance over the matches a query kept
+  if (cov) {
+    PTZ_HIP_TRY(hipMemsetAsync(d + o_cov, 0, sizeof(double) * nf * nf * nq, st));
+    PTZ_HIP_TRY(hipMemsetAsync(d + o_s0, 0, sizeof(double) * nq, st));
+    if (const int32_t rc = ptz_krt_covariance_batch_device(n_query, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
+                                                           trimming ? d_kept : (gated ? d_mask : nullptr), d_acc, 0.0, (double*)(d + o_cov),
+                                                           (double*)(d + o_s0), (int32_t*)(d + o_cst), st))
+      return rc;
+  }
+  PTZ_HIP_TRY(hipEventRecord(ev.e[6], st));
+
+  // only per-query results reach the host
+  std::vector<int32_t> sel(res->sel_ref ? (size_t)K * nq : 0);
+  if (res->cam) PTZ_HIP_TRY(hipMemcpyAsync(res->cam, a_ccur, sizeof(double) * 15 * nq, hipMemcpyDeviceToHost, st));
+  if (res->accepted) PTZ_HIP_TRY(hipMemcpyAsync(res->accepted, d_acc, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+  if (res->summaries) PTZ_HIP_TRY(hipMemcpyAsync(res->summaries, d_sum, sizeof(ptz_lm_summary) * nq, hipMemcpyDeviceToHost, st));
+  if (res->sel_ref) PTZ_HIP_TRY(hipMemcpyAsync(sel.data(), d + o_sel, sizeof(int32_t) * K * nq, hipMemcpyDeviceToHost, st));
+  if (res->n_sel) PTZ_HIP_TRY(hipMemcpyAsync(res->n_sel, d + o_nsel, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+  if (res->trim_report && trimming) PTZ_HIP_TRY(hipMemcpyAsync(res->trim_report, d + o_rep, sizeof(ptz_krt_trim_report) * nq, hipMemcpyDeviceToHost, st));
+  if (cov) {
+    if (res->cov) PTZ_HIP_TRY(hipMemcpyAsync(res->cov, d + o_cov, sizeof(double) * nf * nf * nq, hipMemcpyDeviceToHost, st));
+    if (res->sigma0) PTZ_HIP_TRY(hipMemcpyAsync(res->sigma0, d + o_s0, sizeof(double) * nq, hipMemcpyDeviceToHost, st));
+    if (res->cov_status) PTZ_HIP_TRY(hipMemcpyAsync(res->cov_status, d + o_cst, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+  }
+  PTZ_HIP_TRY(stream_wait(st));
+  PTZ_HIP_TRY(hipGetLastError());
+  for (size_t q = 0; q < nq; ++q) {
+    if (res->n_matches) res->n_matches[q] = (int32_t)(optr[q + 1] - optr[q]);
+    if (res->n_inliers) res->n_inliers[q] = (int32_t)(gated ? gptr[q + 1] - gptr[q] : optr[q + 1] - optr[q]);
+    if (res->sel_ref)
+      for (int s = 0; s < K; ++s) { const int32_t p = sel[q * K + s]; res->sel_ref[q * K + s] = p < 0 ? -1 : p - (int32_t)q * n_ref; }
+  }
+  res->stage_ms[2] = ev.ms(2, 3); res->stage_ms[3] = gated ? ev.ms(3, 4) : 0; res->stage_ms[4] = ev.ms(4, 5); res->stage_ms[5] = cov ? ev.ms(5, 6) : 0;
+  r->n_query = n_query; r->kept = kept;
+  r->table = m;  // (kept for ptz_relocalizer_table)
+  m = nullptr;
+  r->o_optr = o_optr; r->o_oa = o_oa; r->o_ob = o_ob; r->o_osrc = o_osrc;
+  return PTZ_OK;
+}
+
+extern "C" const ptz_desc_matches* ptz_relocalizer_table(const ptz_relocalizer* r) { return r ? r->table : nullptr; }
+
+extern "C" int64_t ptz_relocalizer_n_matches(const ptz_relocalizer* r) { return r ? r->kept : 0; }
+
+extern "C" int32_t ptz_relocalizer_matches(const ptz_relocalizer* r, int64_t* match_ptr, float* uv_ref, float* uv_cur, int32_t* src)
+{
+  using namespace ptz;
+  if (!r || !r->blk || r->n_query <= 0) return PTZ_EINVAL;
+  PTZ_DEVICE_GUARD(r->device);
+  if (match_ptr) PTZ_HIP_TRY(hipMemcpyAsync(match_ptr, r->blk + r->o_optr, sizeof(int64_t) * ((size_t)r->n_query + 1), hipMemcpyDeviceToHost, r->st));
+  if (r->kept > 0) {
+    if (uv_ref) PTZ_HIP_TRY(hipMemcpyAsync(uv_ref, r->blk + r->o_oa, sizeof(float) * 2 * r->kept, hipMemcpyDeviceToHost, r->st));
+    if (uv_cur) PTZ_HIP_TRY(hipMemcpyAsync(uv_cur, r->blk + r->o_ob, sizeof(float) * 2 * r->kept, hipMemcpyDeviceToHost, r->st));
+    if (src) PTZ_HIP_TRY(hipMemcpyAsync(src, r->blk + r->o_osrc, sizeof(int32_t) * r->kept, hipMemcpyDeviceToHost, r->st));
+  }
+  PTZ_HIP_TRY(stream_wait(r->st));
+  return PTZ_OK;
+}
