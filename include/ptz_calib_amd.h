@@ -934,6 +934,65 @@ const ptz_desc_matches* ptz_relocalizer_table(const ptz_relocalizer* r);
 int64_t ptz_relocalizer_n_matches(const ptz_relocalizer* r);
 int32_t ptz_relocalizer_matches(const ptz_relocalizer* r, int64_t* match_ptr, float* uv_ref, float* uv_cur, int32_t* src);
 
+/* ---- reference shortlist: which references a query is worth matching against ----------------------------------------------------
+ * A retrieval step in front of the matcher.  The contract is csrc/ptz_desc_shortlist.h, all integer but desc_ratio_ok's multiply:
+ *   probes     a query image with n features has m = min(n, n_probes) probes: feature k if n <= n_probes, else feature
+ *              floor(k n / n_probes) in int64 -- strictly increasing, in file order;
+ *   vote       a probe votes for reference r when its top-2 over ALL features of r (ptz_desc_match_pairs's: lowest j on a tie,
+ *              second = INT32_MAX with one candidate) has a feature, passes the ratio test of desc_opt->ratio and, with
+ *              desc_opt->max_dist2 != 0, has d2 <= max_dist2.  One direction: cross_check and min_matches do not enter;
+ *   shortlist  the references are ranked by (votes descending, reference index ascending), one with fewer than max(min_votes, 1)
+ *              votes never ranks, the first min(max_refs, ranked) are taken and written in ASCENDING reference index.
+ * Every image of ref_set is a reference.  Query q is image query_img[q] of query_set.  Outputs: shortlist [max_refs n_query]
+ * (query q owns entries max_refs q .., -1 in unused slots), n_short [n_query], votes [n_query n_ref].  A query's output depends on
+ * its own image, the reference set and the options only: not on the batch, its order or the launch.  An empty query or reference
+ * has no votes.  Whenever a query's shortlist contains the references ptz_relocalizer_run would select, matching the shortlisted
+ * pairs alone gives that run's per-query bits (a pair's matches depend on its two images only).
+ * ptz_desc_shortlist (host arrays: run, download).  PTZ_EINVAL, before any device work: the list of ptz_desc_match_pairs (NULL sets,
+ * n_query < 0, different D or devices, desc_opt->device_id not the sets' device, ratio negative or not finite, max_dist2 /
+ * min_matches negative, workspace_bytes not positive), max_refs < 1, n_probes < 1, min_votes < 0, an image index out of range, a
+ * missing output; PTZ_ELIMIT: more than 2^31 - 1 shortlist slots or vote cells; n_query = 0 is PTZ_OK.  desc_opt / sl_opt = NULL: defaults.
+ * ptz_desc_shortlist_device: outputs (and d_query_img, or NULL: query q is image q) are DEVICE pointers on the sets' device; the
+ * call is enqueued on `hip_stream` and returns without synchronising.  An image index the device reads out of range is an empty
+ * query.  d_workspace: 256-byte aligned device memory of at least ptz_desc_shortlist_workspace_bytes(...) bytes, the caller's until
+ * the stream has run the call; whatever it holds before is never read. */
+typedef struct ptz_shortlist_options {
+  int32_t max_refs;  /* 8: R, the most references a query keeps */
+  int32_t n_probes;  /* 256: M, the most features of a query that vote */
+  int32_t min_votes; /* 1 */
+  int32_t reserved_;
+} ptz_shortlist_options;
+void ptz_shortlist_options_default(ptz_shortlist_options* o);
+int32_t ptz_desc_shortlist(const ptz_desc_set* ref_set, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_img,
+                           const ptz_desc_options* desc_opt, const ptz_shortlist_options* sl_opt, int32_t* shortlist, int32_t* n_short,
+                           int32_t* votes /* or NULL */, double* device_ms /* or NULL */);
+int64_t ptz_desc_shortlist_workspace_bytes(const ptz_desc_set* ref_set, const ptz_desc_set* query_set, int32_t n_query,
+                                           const ptz_shortlist_options* sl_opt);
+int32_t ptz_desc_shortlist_device(const ptz_desc_set* ref_set, const ptz_desc_set* query_set, int32_t n_query,
+                                  const int32_t* d_query_img /* or NULL */, const ptz_desc_options* desc_opt,
+                                  const ptz_shortlist_options* sl_opt, int32_t* d_shortlist, int32_t* d_n_short,
+                                  int32_t* d_votes /* or NULL */, void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+
+/* ptz_relocalizer_run with the shortlist in front: stage 0 is ptz_desc_shortlist_device of the query images against the resident
+ * references (options->match's ratio and max_dist2, sl_opt); the host downloads shortlist and n_short and builds the pair list,
+ * query-major, a query's references ascending; stages 1-6 are ptz_relocalizer_run's on that list.  The reference set must hold
+ * exactly the relocalizer's n_ref images.  result is ptz_relocalizer_run's (sel_ref stays a reference image index); sl_result (or
+ * NULL), every pointer nullable: shortlist [sl_opt->max_refs n_query], n_short [n_query], votes [n_query n_ref], shortlist_ms the
+ * device time of stage 0.  A query with n_short = 0 has no pairs and goes on as a query with n_sel = 0.  ptz_relocalizer_table is
+ * then the table of the shortlisted pairs.
+ * ptz_relocalizer_pairs: the pair list of the last run of either kind, *n_pair pairs, pair_ref [n_pair] the reference image of
+ * each, query_ptr [n_query + 1] each query's range; every pointer nullable (ask for n_pair first). */
+typedef struct ptz_shortlist_result {
+  int32_t* shortlist;
+  int32_t* n_short;
+  int32_t* votes;
+  double shortlist_ms;
+} ptz_shortlist_result;
+int32_t ptz_relocalizer_run_shortlisted(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                        const ptz_reloc_options* options, const ptz_shortlist_options* sl_opt, ptz_reloc_result* result,
+                                        ptz_shortlist_result* sl_result);
+int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,9 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_desc_matches_n_chunks", "ptz_desc_matches_download", "ptz_desc_matches_device_ptrs", "ptz_desc_matches_destroy",
            "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device", "ptz_reloc_ref_rotations",
            "ptz_reloc_assemble_workspace_bytes", "ptz_reloc_assemble_device", "ptz_reloc_assemble", "ptz_reloc_options_default",
-           "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table"]
+           "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table",
+           "ptz_shortlist_options_default", "ptz_desc_shortlist", "ptz_desc_shortlist_workspace_bytes", "ptz_desc_shortlist_device",
+           "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs"]
 
 
 class PtzError(RuntimeError):
@@ -1280,6 +1282,70 @@ def desc_dist2(set_a, img_a, set_b, img_b):
     return out
 
 
+# ---- reference shortlist (csrc/ptz_desc_shortlist.h) -------------------------------------------------------------------------------
+class ShortlistOptions(C.Structure):
+    _fields_ = [("max_refs", C.c_int32), ("n_probes", C.c_int32), ("min_votes", C.c_int32), ("reserved_", C.c_int32)]
+
+
+def shortlist_options(**kw) -> ShortlistOptions:
+    o = ShortlistOptions()
+    lib().ptz_shortlist_options_default.restype = None
+    lib().ptz_shortlist_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown shortlist option {k}")
+        setattr(o, k, int(v))
+    return o
+
+
+def _shortlist_split(options):
+    """The ShortlistOptions among one keyword dict, taken out of it (what stays are desc_options fields)"""
+    sl = {k: options.pop(k) for k in ("max_refs", "n_probes", "min_votes") if k in options}
+    return shortlist_options(**sl)
+
+
+def desc_shortlist(ref_set, query_set, query_img=None, **options):
+    """ptz_desc_shortlist: the references worth matching for each query image.  A query's first n_probes features in the index rule
+    of the header vote for the references in which their nearest neighbour passes the ratio test; the max_refs references with the
+    most votes (at least max(min_votes, 1)) are its shortlist, in ascending reference index.  query_img: image of query_set per query
+    (default: all, in order).  options: max_refs (8), n_probes (256), min_votes (1) and the fields of desc_options (ratio,
+    max_dist2).  Returns dict(shortlist [n_query, max_refs] with -1 in unused slots, n_short [n_query], votes [n_query, n_ref],
+    device_ms)."""
+    qi = np.arange(query_set.n_img, dtype=np.int32) if query_img is None else np.ascontiguousarray(query_img, dtype=np.int32)
+    if qi.ndim != 1:
+        raise ValueError("query_img: one image index per query")
+    sl = _shortlist_split(options)
+    options.setdefault("device_id", ref_set.device_id)
+    o = desc_options(**options)
+    n, R = len(qi), max(int(sl.max_refs), 1)
+    out = np.full((n, R), -1, dtype=np.int32)
+    ns = np.zeros(n, dtype=np.int32)
+    votes = np.zeros((n, ref_set.n_img), dtype=np.int32)
+    ms = C.c_double()
+    _check(lib().ptz_desc_shortlist(ref_set.handle, query_set.handle, n, _p(qi) if n else None, C.byref(o), C.byref(sl), _p(out) if n else None,
+                                    _p(ns) if n else None, _p(votes) if votes.size else None, C.byref(ms)), "ptz_desc_shortlist")
+    return dict(shortlist=out, n_short=ns, votes=votes, device_ms=ms.value)
+
+
+def desc_shortlist_workspace_bytes(ref_set, query_set, n_query, **sl) -> int:
+    lib().ptz_desc_shortlist_workspace_bytes.restype = C.c_int64
+    o = shortlist_options(**sl)
+    return int(lib().ptz_desc_shortlist_workspace_bytes(ref_set.handle, query_set.handle, int(n_query), C.byref(o)))
+
+
+def desc_shortlist_device(ref_set, query_set, n_query, d_shortlist, d_n_short, d_workspace, workspace_bytes, d_query_img=None, d_votes=None,
+                          stream=None, **options):
+    """ptz_desc_shortlist_device: every d_* is a device buffer (torch tensor or integer address) on the sets' device; d_workspace
+    needs desc_shortlist_workspace_bytes(...) bytes.  d_query_img = None: query q is image q.  Enqueues on `stream` and returns
+    without synchronising."""
+    sl = _shortlist_split(options)
+    options.setdefault("device_id", ref_set.device_id)
+    o = desc_options(**options)
+    _check(lib().ptz_desc_shortlist_device(ref_set.handle, query_set.handle, int(n_query), _dptr(d_query_img), C.byref(o), C.byref(sl),
+                                           _dptr(d_shortlist), _dptr(d_n_short), _dptr(d_votes), _dptr(d_workspace),
+                                           C.c_int64(int(workspace_bytes)), C.c_void_p(stream) if stream else None), "ptz_desc_shortlist_device")
+
+
 # ---- relocalization assembly (csrc/ptz_reloc_assemble.h) ----------------------------------------------------------------------------
 def reloc_ref_rotations(ref_cams):
     """ptz_reloc_ref_rotations (host logic only): Rodrigues of every reference camera [n_ref, 15] -> [n_ref, 9] row-major."""
@@ -1353,6 +1419,10 @@ class RelocResult(C.Structure):
                                           "sigma0", "cov_status")] + [("stage_ms", C.c_double * 6)]
 
 
+class ShortlistResult(C.Structure):
+    _fields_ = [("shortlist", C.c_void_p), ("n_short", C.c_void_p), ("votes", C.c_void_p), ("shortlist_ms", C.c_double)]
+
+
 class Relocalizer:
     """ptz_relocalizer: relocalization from features with the references resident on the device.  ref_set: a DescSet with key points
     (kept alive by this object), ref_cams [n_ref, 15] (image m of the set is camera m)."""
@@ -1368,11 +1438,14 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
-        None), cov / sigma0 / cov_status (or None), stage_ms [6]."""
+        None), cov / sigma0 / cov_status (or None), stage_ms [6].
+        shortlist: None (every reference of every query), or a dict of shortlist_options fields (max_refs, n_probes, min_votes; {} for
+        the defaults): ptz_relocalizer_run_shortlisted -- only the references the vote pass keeps are matched, and the result gains
+        shortlist [n, R], n_short [n], votes [n, n_ref] and shortlist_ms."""
         wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
         n, K = len(wh), int(max_refs)
         o = RelocOptions()
@@ -1397,11 +1470,45 @@ class Relocalizer:
         r.cam, r.accepted, r.sel_ref, r.n_sel, r.n_matches, r.n_inliers = vp(cam), vp(acc), vp(sel), vp(nsel), vp(nmat), vp(ninl)
         r.summaries, r.trim_report = C.addressof(summ), C.addressof(rep)
         r.cov, r.sigma0, r.cov_status = vp(cov), vp(s0), vp(cst)
-        _check(lib().ptz_relocalizer_run(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)), "ptz_relocalizer_run")
+        extra = {}
+        if shortlist is None:
+            _check(lib().ptz_relocalizer_run(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)), "ptz_relocalizer_run")
+        else:
+            so = shortlist_options(**shortlist)
+            sr = ShortlistResult()
+            sl = np.full((n, max(int(so.max_refs), 1)), -1, dtype=np.int32)
+            ns, votes = np.zeros(n, dtype=np.int32), np.zeros((n, len(self.ref_cams)), dtype=np.int32)
+            sr.shortlist, sr.n_short, sr.votes = vp(sl), vp(ns), vp(votes)
+            _check(lib().ptz_relocalizer_run_shortlisted(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(so), C.byref(r), C.byref(sr)),
+                   "ptz_relocalizer_run_shortlisted")
+            extra = dict(shortlist=sl, n_short=ns, votes=votes, shortlist_ms=sr.shortlist_ms)
         self._last_n = n
-        return dict(cam=cam, accepted=acc, summaries=[summ[i].as_dict() for i in range(n)], sel_ref=sel, n_sel=nsel, n_matches=nmat, n_inliers=ninl,
+        return dict(extra, cam=cam, accepted=acc, summaries=[summ[i].as_dict() for i in range(n)], sel_ref=sel, n_sel=nsel, n_matches=nmat, n_inliers=ninl,
                     trim_report=[rep[i].as_dict() for i in range(n)] if trim is not None else None, cov=cov if uncertainty else None,
                     sigma0=s0 if uncertainty else None, cov_status=cst if uncertainty else None, stage_ms=np.array(list(r.stage_ms)))
+
+    def pairs(self):
+        """The last run's pair list: dict of pair_ref [n_pair] (reference image of each pair), query_ptr [n_query + 1]."""
+        k = C.c_int32()
+        _check(lib().ptz_relocalizer_pairs(self.handle, C.byref(k), None, None), "ptz_relocalizer_pairs")
+        ref, ptr = np.zeros(k.value, dtype=np.int32), np.zeros(self._last_n + 1, dtype=np.int64)
+        _check(lib().ptz_relocalizer_pairs(self.handle, None, _p(ref) if k.value else None, _p(ptr)), "ptz_relocalizer_pairs")
+        return dict(pair_ref=ref, query_ptr=ptr)
+
+    def table(self):
+        """The last run's match table of its pairs (the relocalizer's own; downloaded): match_ptr, idx_a, idx_b, dist2, uv_a, uv_b."""
+        L = lib()
+        L.ptz_relocalizer_table.restype = C.c_void_p
+        L.ptz_desc_matches_n_matches.restype = C.c_int64
+        t = C.c_void_p(L.ptz_relocalizer_table(self.handle))
+        if not t:
+            raise ValueError("no run yet")
+        n, npair = int(L.ptz_desc_matches_n_matches(t)), int(L.ptz_desc_matches_n_pairs(t))
+        ptr = np.zeros(npair + 1, dtype=np.int64)
+        ia, ib, d2 = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        ua, ub = (np.zeros((n, 2), dtype=np.float32) for _ in range(2))
+        _check(L.ptz_desc_matches_download(t, _p(ptr), _p(ia), _p(ib), _p(d2), _p(ua) if n else None, _p(ub) if n else None), "ptz_desc_matches_download")
+        return dict(match_ptr=ptr, idx_a=ia, idx_b=ib, dist2=d2, uv_a=ua, uv_b=ub)
 
     def matches(self):
         """The last run's assembled matches (tests): dict of match_ptr, uv_ref, uv_cur, src."""

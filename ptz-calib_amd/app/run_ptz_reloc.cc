@@ -7,6 +7,9 @@
 // --trim_px <px> (not in the reference; with --trim_sigma, --trim_rounds) solves every test image with the outlier-trimming loop of
 // ptz_krt_solve_batch_trimmed: with --inlier_matches the gate's inliers are the loop's universe, with --uncertainty the covariance is
 // taken over the matches the last solve kept, and every record gains rms_px, n_matches, n_removed, trim_rounds.
+// --shortlist R (not in the reference; with --shortlist_probes, --shortlist_min_votes; implies --on_device) matches every test image
+// against the R reference images its probe features vote for instead of all of them (ptz_relocalizer_run_shortlisted); every record
+// gains n_shortlist.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -90,6 +93,10 @@ int main(int argc, char** argv)
                               "the solve and the covariance run there and only per-image results come back; the output is the same");
   parser.Add("multi_ref", '\0', "With --match_descriptors: solve each test image against its K best reference images at once (implies "
                                 "--on_device); every record gains n_refs and n_matches", false);
+  parser.Add("shortlist", '\0', "With --match_descriptors: match each test image against the R reference images that most of its probe "
+                                "features vote for instead of all of them (implies --on_device); every record gains n_shortlist", false);
+  parser.Add("shortlist_probes", '\0', "With --shortlist: features of a test image that vote (default 256)", false);
+  parser.Add("shortlist_min_votes", '\0', "With --shortlist: votes a reference image needs to be listed (default 1)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -102,10 +109,26 @@ int main(int argc, char** argv)
     return 1;
   }
   const int multi_ref = parser.Exist("multi_ref") ? atoi(parser.Get("multi_ref").c_str()) : 0;
-  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref");
+  const bool shortlisting = parser.Exist("shortlist");
+  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting;
   if (on_device && !parser.Exist("match_descriptors")) {
-    fprintf(stderr, "--on_device and --multi_ref need --match_descriptors\n");
+    fprintf(stderr, "--on_device, --multi_ref and --shortlist need --match_descriptors\n");
     return 1;
+  }
+  ptz_shortlist_options sl;
+  ptz_shortlist_options_default(&sl);
+  if (!shortlisting && (parser.Exist("shortlist_probes") || parser.Exist("shortlist_min_votes"))) {
+    fprintf(stderr, "--shortlist_probes and --shortlist_min_votes need --shortlist\n");
+    return 1;
+  }
+  if (shortlisting) {
+    sl.max_refs = atoi(parser.Get("shortlist").c_str());
+    if (parser.Exist("shortlist_probes")) sl.n_probes = atoi(parser.Get("shortlist_probes").c_str());
+    if (parser.Exist("shortlist_min_votes")) sl.min_votes = atoi(parser.Get("shortlist_min_votes").c_str());
+    if (sl.max_refs < 1 || sl.n_probes < 1 || sl.min_votes < 0) {
+      fprintf(stderr, "--shortlist and --shortlist_probes must be at least 1, --shortlist_min_votes not negative\n");
+      return 1;
+    }
   }
   if (parser.Exist("multi_ref") && multi_ref < 1) {
     fprintf(stderr, "--multi_ref must be at least 1\n");
@@ -218,7 +241,7 @@ int main(int argc, char** argv)
   std::vector<Sigma> sigmas(test_fnames.size());
   struct Trimmed { double rms = 0; int n_matches = 0, n_removed = 0, rounds = 0; };
   std::vector<Trimmed> trimmed(test_fnames.size());
-  std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0);
+  std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0), n_shortlist(test_fnames.size(), 0);
   if (on_device && !test_fnames.empty()) {
     // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
     // guided pass, the assembly, the gate, the solve or the trimming loop, the covariance -- in the order of the code below
@@ -271,15 +294,29 @@ int main(int argc, char** argv)
               BuildDescSet(parser.Get("test_features"), test_fnames, test_features, &test_set);
     int32_t rc = PTZ_OK;
     if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
-    if (ok && rc == PTZ_OK) rc = ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
+    std::vector<int32_t> n_short(nq, 0);
+    ptz_shortlist_result sr;
+    sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
+    if (ok && rc == PTZ_OK)
+      rc = shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
+                        : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
+    for (int32_t q = 0; q < nq; ++q) n_shortlist[q] = n_short[q];
     if (ok && rc == PTZ_OK && parser.Exist("save_matches")) {
       // the table comes to the host once, for the file alone: blocks in the pairs' order, a pair without matches has none
       const ptz_desc_matches* t = ptz_relocalizer_table(rl);
       const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(t));
-      std::vector<int64_t> mptr(static_cast<size_t>(nq) * n_ref + 1, 0);
+      // (the run's own pair list: every reference of every test image, or the shortlisted ones)
+      int32_t n_pair = 0;
+      rc = ptz_relocalizer_pairs(rl, &n_pair, nullptr, nullptr);
+      std::vector<int32_t> pair_ref(std::max<int32_t>(n_pair, 1));
+      std::vector<int64_t> query_ptr(static_cast<size_t>(nq) + 1, 0);
+      if (rc == PTZ_OK) rc = ptz_relocalizer_pairs(rl, nullptr, pair_ref.data(), query_ptr.data());
+      std::vector<int64_t> mptr(static_cast<size_t>(n_pair) + 1, 0);
       std::vector<int32_t> qa(std::max<size_t>(n, 1)), tb(std::max<size_t>(n, 1));
-      rc = ptz_desc_matches_download(t, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
+      if (rc == PTZ_OK) rc = ptz_desc_matches_download(t, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
+      size_t pq = 0;  // the test image of pair p
       for (size_t p = 0; rc == PTZ_OK && p + 1 < mptr.size(); ++p) {
+        while (static_cast<int64_t>(p) >= query_ptr[pq + 1]) ++pq;
         if (mptr[p + 1] == mptr[p]) continue;
         std::vector<DMatch> ms;
         for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) {
@@ -289,7 +326,7 @@ int main(int argc, char** argv)
           ms.push_back(m);
         }
         pairs_matches.push_back(ms);
-        img_pairs_name.push_back({ref_fnames[p % n_ref], test_fnames[p / n_ref]});
+        img_pairs_name.push_back({ref_fnames[pair_ref[p]], test_fnames[pq]});
       }
       if (rc == PTZ_OK && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
         fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
@@ -426,7 +463,7 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty || trimming || multi_ref > 0) {
+  if (uncertainty || trimming || multi_ref > 0 || shortlisting) {
     // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
@@ -450,6 +487,7 @@ int main(int argc, char** argv)
         j["n_refs"] = Json::Int(multi_n_refs[i]);
         if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
       }
+      if (shortlisting) j["n_shortlist"] = Json::Int(n_shortlist[i]);
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

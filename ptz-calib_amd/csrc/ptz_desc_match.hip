@@ -22,6 +22,7 @@
 
 #include "ptz_common.h"
 #include "ptz_desc_match.h"
+#include "ptz_desc_set.h"
 #include "ptz_gate_compact.h"
 #include "ptz_pool.h"
 #include "ptz_block_layout.h"
@@ -34,7 +35,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int DESC_WG = 256;     // four waves
 constexpr int DESC_QT = 2;       // query tiles of 16 per wave
 constexpr int DESC_WG_Q = (DESC_WG / WAVE) * DESC_QT * 16;  // 128 queries per workgroup
-constexpr int DESC_ROW_PAD = 64; // rows of an image are padded to this
 constexpr int DESC_G_TILE = 1024; // positions of the other image a guided workgroup stages in LDS at a time (8 KB)
 constexpr int DESC_G_UNROLL = 8;  // candidates a lane tests between two looks for a hit (divides DESC_G_TILE)
 constexpr int DESC_CHUNK_PAIRS = 1 << 20;  // most pairs of a chunk: its launches have a workgroup row per pair and direction
@@ -330,50 +330,8 @@ void launch_top2(int KS, dim3 grid, hipStream_t st, const DescPair* pairs, int d
 
 inline unsigned tiles_y(int64_t n, int per) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + per - 1) / per, 1), 65535); }
 
-// a call's stream and timing events, from the pool
-struct DescStream {
-  int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t open(int device)
-  {
-    dev = device;
-    hipError_t e = ptzpool::stream_acquire(dev, &st);
-    if (e == hipSuccess) e = ptzpool::event_acquire(dev, true, &e0);
-    if (e == hipSuccess) e = ptzpool::event_acquire(dev, true, &e1);
-    return e;
-  }
-  ~DescStream()
-  {
-    if (st) (void)stream_wait(st);
-    ptzpool::stream_release(dev, st);
-    ptzpool::event_release(dev, true, e0);
-    ptzpool::event_release(dev, true, e1);
-  }
-};
-struct DescBlock {  // a pooled device block, released with its owner
-  int dev = 0;
-  char* p = nullptr;
-  hipError_t get(int device, size_t bytes) { dev = device; return ptzpool::dev_acquire(dev, std::max<size_t>(bytes, 256), (void**)&p); }
-  ~DescBlock() { ptzpool::dev_release(dev, p); }
-  DescBlock() = default;
-  DescBlock(const DescBlock&) = delete;
-  DescBlock& operator=(const DescBlock&) = delete;
-};
-
 }  // namespace
 }  // namespace ptz
-
-struct ptz_desc_set {
-  int device = 0;
-  int32_t n_img = 0, D = 0, KS = 0;
-  int64_t n_feat = 0;
-  std::vector<int64_t> feat_ptr, row_off;  // [n_img + 1]
-  ptz::DescBlock blk;
-  int8_t* d_desc = nullptr;   // [rows + slack][64 KS]
-  int32_t* d_norm = nullptr;  // [rows + slack]
-  float2* d_kp = nullptr;     // [n_feat] or nullptr
-};
 
 struct ptz_desc_matches {
   int device = 0;
@@ -427,30 +385,32 @@ extern "C" int32_t ptz_desc_set_create(int32_t n_img, const int64_t* feat_ptr, c
   const int DP = 64 * s->KS;
   const size_t rows = (size_t)s->row_off[n_img] + DESC_ROW_PAD;  // the slack is the pack kernel's image n_img
   const size_t o_desc = 0, o_norm = o_desc + up256(rows * DP), o_kp = o_norm + up256(rows * sizeof(int32_t)),
-               total = o_kp + up256(kp_xy ? (size_t)nf * sizeof(float2) : 0);
+               o_fp = o_kp + up256(kp_xy ? (size_t)nf * sizeof(float2) : 0), o_ro = o_fp + up256(sizeof(int64_t) * ((size_t)n_img + 2)),
+               total = o_ro + up256(sizeof(int64_t) * ((size_t)n_img + 2));
   if (s->blk.get(device_id, total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
   s->d_desc = (int8_t*)(s->blk.p + o_desc);
   s->d_norm = (int32_t*)(s->blk.p + o_norm);
   s->d_kp = kp_xy ? (float2*)(s->blk.p + o_kp) : nullptr;
+  s->d_feat_ptr = (const int64_t*)(s->blk.p + o_fp);
+  s->d_row_off = (const int64_t*)(s->blk.p + o_ro);
 
-  // the raw bytes and the two offset tables, for the pack kernel only
+  // the two offset tables stay with the set (the pack kernel's "image" n_img is the slack); the raw bytes are the pack kernel's only
   std::vector<int64_t> fp(s->feat_ptr), ro(s->row_off);
   fp.push_back(nf);
   ro.push_back((int64_t)rows);
-  const size_t t_fp = 0, t_ro = t_fp + up256(sizeof(int64_t) * fp.size()), t_raw = t_ro + up256(sizeof(int64_t) * ro.size()),
-               t_total = t_raw + up256((size_t)nf * D);
+  const size_t t_raw = 0, t_total = t_raw + up256((size_t)nf * D);
   DescBlock tmp;
   if (tmp.get(device_id, t_total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
   DescStream ds;
   PTZ_HIP_TRY(ds.open(device_id));
-  PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_fp, fp.data(), sizeof(int64_t) * fp.size(), hipMemcpyHostToDevice, ds.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_ro, ro.data(), sizeof(int64_t) * ro.size(), hipMemcpyHostToDevice, ds.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_fp, fp.data(), sizeof(int64_t) * fp.size(), hipMemcpyHostToDevice, ds.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_ro, ro.data(), sizeof(int64_t) * ro.size(), hipMemcpyHostToDevice, ds.st));
   if (nf > 0) PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_raw, desc, (size_t)nf * D, hipMemcpyHostToDevice, ds.st));
   if (nf > 0 && kp_xy) PTZ_HIP_TRY(hipMemcpyAsync(s->d_kp, kp_xy, (size_t)nf * sizeof(float2), hipMemcpyHostToDevice, ds.st));
   int64_t most = DESC_ROW_PAD;
   for (int m = 0; m < n_img; ++m) most = std::max(most, s->row_off[m + 1] - s->row_off[m]);
-  hipLaunchKernelGGL(k_desc_pack, dim3(n_img + 1, tiles_y(most, 256)), dim3(256), 0, ds.st, (const int64_t*)(tmp.p + t_fp),
-                     (const int64_t*)(tmp.p + t_ro), (const uint8_t*)(tmp.p + t_raw), D, DP, (uint32_t*)s->d_desc, s->d_norm);
+  hipLaunchKernelGGL(k_desc_pack, dim3(n_img + 1, tiles_y(most, 256)), dim3(256), 0, ds.st, s->d_feat_ptr, s->d_row_off,
+                     (const uint8_t*)(tmp.p + t_raw), D, DP, (uint32_t*)s->d_desc, s->d_norm);
   PTZ_HIP_TRY(hipGetLastError());
   PTZ_HIP_TRY(stream_wait(ds.st));
   *out = s.release();

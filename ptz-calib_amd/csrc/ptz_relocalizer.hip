@@ -1,7 +1,8 @@
 // ptz_relocalizer.hip -- the resident serving loop of the online half: what joins the device entry points.  References stay on the
 // device (their descriptor set is the caller's, their cameras and rotation matrices are uploaded once); a run takes a set of query
 // images through
-//   1. the matcher over all (reference, query) pairs            ptz_desc_match_pairs
+//   0. (ptz_relocalizer_run_shortlisted) the vote pass that picks a query's references, read by the host   ptz_desc_shortlist_device
+//   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
 //   4. optionally the gate on the assembled queries              ptz_match_gate_run_device
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "ptz_common.h"
+#include "ptz_desc_set.h"
 #include "ptz_host_batch.h"
 
 namespace ptz {
@@ -66,7 +68,9 @@ struct ptz_relocalizer {
   ptz_match_gate* gate = nullptr;  // grows with the runs: pairs, matches, matches of one pair
   int32_t gate_pairs = 0, gate_pm = 0;
   int64_t gate_matches = 0;
-  ptz_desc_matches* table = nullptr;  // the last run's match table of all pairs (the guided one, if that pass ran)
+  ptz_desc_matches* table = nullptr;  // the last run's match table of its pairs (the guided one, if that pass ran)
+  std::vector<int32_t> pair_ref;      // the last run's pair list: the reference of each pair,
+  std::vector<int64_t> query_ptr;     // and each query's range of it
   // the last run's block: the assembled matches stay until the next run
   char* blk = nullptr;
   int32_t n_query = 0;
@@ -145,8 +149,9 @@ static int32_t reloc_gate_for(ptz_relocalizer* r, int32_t pairs, int64_t matches
   return ptz_match_gate_create(r->gate_pairs, r->gate_matches, r->gate_pm, r->device, &r->gate);
 }
 
-extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
-                                       const ptz_reloc_options* options, ptz_reloc_result* res)
+// both runs: sl = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references
+static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                         const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res)
 {
   using namespace ptz;
   if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
@@ -159,24 +164,67 @@ extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* q
     if (query_wh[2 * q] <= 0 || query_wh[2 * q + 1] <= 0) return PTZ_EINVAL;
   if (o.factor_type < PTZ_KRT_F || o.factor_type > PTZ_KRT_FxfyDist) return PTZ_EUNSUPPORTED;
   if (o.match.device_id != r->device || (o.lm.device_id != 0 && o.lm.device_id != r->device)) return PTZ_EINVAL;
+  if (sl && (sl->max_refs < 1 || sl->n_probes < 1 || sl->min_votes < 0 || r->refs->n_img != r->n_ref || n_query > query_set->n_img)) return PTZ_EINVAL;
   for (double& t : res->stage_ms) t = 0;
+  if (sl_res) sl_res->shortlist_ms = 0;
   if (n_query == 0) return PTZ_OK;
-  if ((int64_t)n_query * r->n_ref > INT32_MAX || (int64_t)n_query * o.max_refs > INT32_MAX) return PTZ_ELIMIT;
-  clear_stale_error(__func__);
+  const int32_t n_ref = r->n_ref, K = o.max_refs, per_query = sl ? (sl->max_refs < n_ref ? sl->max_refs : n_ref) : n_ref;
+  if ((int64_t)n_query * per_query > INT32_MAX || (int64_t)n_query * o.max_refs > INT32_MAX) return PTZ_ELIMIT;
+  clear_stale_error(who);
   PTZ_DEVICE_GUARD(r->device);
-  const int32_t n_ref = r->n_ref, npair = n_query * n_ref, K = o.max_refs;
   const size_t nq = (size_t)n_query;
-  // the pairs test image by test image, the references in their order: FindBestMatch's first-wins tie picks the lowest reference
-  std::vector<int32_t> ia((size_t)npair), ib((size_t)npair);
-  std::vector<int64_t> qptr(nq + 1);
-  for (int q = 0; q < n_query; ++q) {
-    qptr[q] = (int64_t)q * n_ref;
-    for (int k = 0; k < n_ref; ++k) { ia[(size_t)q * n_ref + k] = k; ib[(size_t)q * n_ref + k] = q; }
-  }
-  qptr[nq] = npair;
   hipStream_t st = r->st;
   Events ev(r->device);
   PTZ_HIP_TRY(ev.make());
+  // the pairs test image by test image, the references in ascending order: FindBestMatch's first-wins tie picks the lowest reference
+  std::vector<int32_t> ia, ib;
+  std::vector<int64_t> qptr(nq + 1, 0);
+  if (sl) {
+    // 0. the vote pass over the resident references; the host reads the lists and keeps their order
+    const size_t R = (size_t)sl->max_refs;
+    const int64_t ws = ptz_desc_shortlist_workspace_bytes(r->refs, query_set, n_query, sl);
+    BlockLayout b;
+    const size_t o_sl = b.take(sizeof(int32_t) * R * nq), o_ns = b.take(sizeof(int32_t) * nq), o_votes = b.take(sizeof(int32_t) * nq * n_ref),
+                 o_ws = b.take((size_t)ws);
+    DevBlock t(r->device);
+    if (t.take(b.total()) != hipSuccess) return PTZ_ENOMEM;
+    std::vector<int32_t> list(R * nq), n_short(nq);
+    PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
+    if (const int32_t rc = ptz_desc_shortlist_device(r->refs, query_set, n_query, nullptr, &o.match, sl, (int32_t*)(t.p + o_sl), (int32_t*)(t.p + o_ns),
+                                                     (int32_t*)(t.p + o_votes), t.p + o_ws, ws, st))
+      return rc;
+    PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
+    PTZ_HIP_TRY(hipMemcpyAsync(list.data(), t.p + o_sl, sizeof(int32_t) * R * nq, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(n_short.data(), t.p + o_ns, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+    if (sl_res && sl_res->votes) PTZ_HIP_TRY(hipMemcpyAsync(sl_res->votes, t.p + o_votes, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(stream_wait(st));
+    PTZ_HIP_TRY(hipGetLastError());
+    for (size_t q = 0; q < nq; ++q) {
+      const int32_t n = n_short[q];
+      if (n < 0 || n > per_query) return PTZ_ENODEVICE;  // (a kernel that did not run)
+      for (int32_t k = 0; k < n; ++k) {
+        const int32_t ref = list[q * R + k];
+        if (ref < 0 || ref >= n_ref) return PTZ_ENODEVICE;
+        ia.push_back(ref);
+        ib.push_back((int32_t)q);
+      }
+      qptr[q + 1] = (int64_t)ia.size();
+    }
+    if (sl_res) {
+      if (sl_res->shortlist) memcpy(sl_res->shortlist, list.data(), sizeof(int32_t) * R * nq);
+      if (sl_res->n_short) memcpy(sl_res->n_short, n_short.data(), sizeof(int32_t) * nq);
+      sl_res->shortlist_ms = ev.ms(0, 1);
+    }
+  }
+  else {
+    ia.resize((size_t)n_query * n_ref);
+    ib.resize(ia.size());
+    for (int q = 0; q < n_query; ++q) {
+      for (int k = 0; k < n_ref; ++k) { ia[(size_t)q * n_ref + k] = k; ib[(size_t)q * n_ref + k] = q; }
+      qptr[q + 1] = (int64_t)(q + 1) * n_ref;
+    }
+  }
+  const int32_t npair = (int32_t)ia.size();
 
   // 1. pass 1 over all pairs
   ptz_desc_matches_destroy(r->table);
@@ -193,7 +241,7 @@ extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* q
   if (nm > 0 && (!d_ua || !d_ub)) return PTZ_EINVAL;  // sets without key points
 
   // 2. the gate on all pairs, then the guided pass with its device H / found, as MatchDescriptors composes them
-  if (o.guided_radius > 0.0) {
+  if (o.guided_radius > 0.0 && npair > 0) {
     if (const int32_t rc = reloc_gate_for(r, npair, nm, o.gate_max_pair_matches)) return rc;
     const size_t nmx = (size_t)(nm > 0 ? nm : 1);
     BlockLayout b;
@@ -241,7 +289,7 @@ extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* q
   r->blk = nullptr; r->n_query = 0; r->kept = 0;
   if (ptzpool::dev_acquire(r->device, b.total(), (void**)&r->blk) != hipSuccess) return PTZ_ENOMEM;
   char* d = r->blk;
-  PTZ_HIP_TRY(hipMemcpyAsync(d + o_pref, ia.data(), sizeof(int32_t) * npair, hipMemcpyHostToDevice, st));
+  if (npair > 0) PTZ_HIP_TRY(hipMemcpyAsync(d + o_pref, ia.data(), sizeof(int32_t) * npair, hipMemcpyHostToDevice, st));
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_qptr, qptr.data(), sizeof(int64_t) * (nq + 1), hipMemcpyHostToDevice, st));
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_wh, query_wh, sizeof(int32_t) * 2 * nq, hipMemcpyHostToDevice, st));
 
@@ -325,13 +373,40 @@ extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* q
     if (res->n_matches) res->n_matches[q] = (int32_t)(optr[q + 1] - optr[q]);
     if (res->n_inliers) res->n_inliers[q] = (int32_t)(gated ? gptr[q + 1] - gptr[q] : optr[q + 1] - optr[q]);
     if (res->sel_ref)
-      for (int s = 0; s < K; ++s) { const int32_t p = sel[q * K + s]; res->sel_ref[q * K + s] = p < 0 ? -1 : p - (int32_t)q * n_ref; }
+      for (int s = 0; s < K; ++s) { const int32_t p = sel[q * K + s]; res->sel_ref[q * K + s] = p < 0 || p >= npair ? -1 : ia[p]; }
   }
   res->stage_ms[2] = ev.ms(2, 3); res->stage_ms[3] = gated ? ev.ms(3, 4) : 0; res->stage_ms[4] = ev.ms(4, 5); res->stage_ms[5] = cov ? ev.ms(5, 6) : 0;
   r->n_query = n_query; r->kept = kept;
   r->table = m;  // (kept for ptz_relocalizer_table)
   m = nullptr;
+  r->pair_ref.swap(ia);
+  r->query_ptr.swap(qptr);
   r->o_optr = o_optr; r->o_oa = o_oa; r->o_ob = o_ob; r->o_osrc = o_osrc;
+  return PTZ_OK;
+}
+
+extern "C" int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                       const ptz_reloc_options* options, ptz_reloc_result* res)
+{
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr);
+}
+
+extern "C" int32_t ptz_relocalizer_run_shortlisted(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                                   const ptz_reloc_options* options, const ptz_shortlist_options* sl_opt, ptz_reloc_result* res,
+                                                   ptz_shortlist_result* sl_res)
+{
+  ptz_shortlist_options s;
+  ptz_shortlist_options_default(&s);
+  if (sl_opt) s = *sl_opt;
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, &s, res, sl_res);
+}
+
+extern "C" int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr)
+{
+  if (!r || r->n_query <= 0) return PTZ_EINVAL;
+  if (n_pair) *n_pair = (int32_t)r->pair_ref.size();
+  if (pair_ref && !r->pair_ref.empty()) memcpy(pair_ref, r->pair_ref.data(), sizeof(int32_t) * r->pair_ref.size());
+  if (query_ptr) memcpy(query_ptr, r->query_ptr.data(), sizeof(int64_t) * r->query_ptr.size());
   return PTZ_OK;
 }
 
