@@ -2,18 +2,12 @@
 // batch of image pairs (ptz_desc_match_pairs).  The contract is ptz_desc_match.h; everything here is integer arithmetic, so a
 // pair's matches are the bits of the brute-force restatement whatever the batch, the tiling or the chunking.
 //
-//   pack      a byte xor 0x80 is (a - 128) as int8; the bias cancels in a - b, so d2 = |a'|^2 + |b'|^2 - 2 a'.b'.  Rows are padded
-//             with zeros to DP = a multiple of 64 bytes, images to a multiple of 64 rows (zero rows, norm INT32_MAX: the dot
-//             product of a padding row is exactly 0, its key INT32_MAX, and it never beats the empty state).
-//   top-2     one workgroup = (pair, direction, 128 query rows): each of its four waves holds two tiles of 16 queries for the whole
-//             DP in registers (the B operand of v_mfma_i32_16x16x64_i8) and streams the other image in tiles of 16 rows (the A
-//             operand) straight from global memory, one tile ahead.  Lane l of the result holds C[row 4 (l >> 4) + r][col l & 15]:
-//             ONE query per lane, four candidates per step, so the running (best, best j, second) of a query tile is three
-//             registers.  Candidates reach a lane in ascending j, so `<` keeps the lowest j there; the four lanes of a query
-//             are merged once at the end with the header's rule.  The DP x n product is never written.
-//   guided    ptz_desc_match_pairs_guided: the same top-2 over the candidates within a radius of where the pair's homography puts
-//             the feature (the header's predicate) -- a radius search over positions staged in LDS, one query per lane, the exact
-//             d2 from the packed rows only on a hit; the state, and everything behind it, is the dense pass's.
+//   pack      k_desc_pack writes the rows ptz_desc_sweep.h describes.
+//   top-2     one workgroup = (pair, direction, 128 query rows): each of its four waves holds two tiles of 16 queries and runs
+//             ptz_desc_sweep.h's sweep over the other image; the g == 0 lanes store the finished top-2.
+//   guided    ptz_desc_match_pairs_guided: the same running top-2 over the candidates within a radius of where the pair's
+//             homography puts the feature (the header's predicate) -- a radius search over positions staged in LDS, one query per
+//             lane, the exact d2 from the packed rows only on a hit; the state, and everything behind it, is the dense pass's.
 //   join      the acceptance rule per feature of A -> a keep byte; counting, scan and scatter are ptz_gate_compact.h's kernels
 //             (min_matches as `need`); a gather writes indices, distances and the pixels of the resident key points.
 #include <cmath>
@@ -23,14 +17,12 @@
 #include "ptz_common.h"
 #include "ptz_desc_match.h"
 #include "ptz_desc_set.h"
+#include "ptz_desc_sweep.h"
 #include "ptz_gate_compact.h"
-#include "ptz_pool.h"
-#include "ptz_block_layout.h"
+#include "ptz_host_batch.h"
 
 namespace ptz {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int DESC_WG = 256;     // four waves
 constexpr int DESC_QT = 2;       // query tiles of 16 per wave
@@ -95,7 +87,6 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2(const DescPair* __restric
   const int32_t* sn = dir ? norm_a + P.row_a : norm_b + P.row_b;
   DescTop2* out = DUMP ? nullptr : state + P.soff + (dir ? P.n_a : 0);
   const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, c = lane & 15, g = lane >> 4;
-  const int nt = (ns + 15) >> 4;  // streamed tiles; rows up to 16 nt <= the image's padded rows
 
   for (int64_t tile = blockIdx.y; tile * DESC_WG_Q < nq; tile += gridDim.y) {
     const int q0 = (int)(tile * DESC_WG_Q) + wave * (DESC_QT * 16);
@@ -104,65 +95,21 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2(const DescPair* __restric
 #pragma unroll
     for (int t = 0; t < DESC_QT; ++t)
 #pragma unroll
-      for (int s = 0; s < KS; ++s) qf[t][s] = *reinterpret_cast<const v4i*>(qd + (int64_t)(q0 + 16 * t + c) * DP + s * 64 + g * 16);
-    int32_t bd[DESC_QT], bj[DESC_QT], sd[DESC_QT];
-#pragma unroll
-    for (int t = 0; t < DESC_QT; ++t) bd[t] = bj[t] = sd[t] = kDescNone;
-
-    v4i sf[KS], nf[KS], skey, nkey;
-    if (nt > 0) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) sf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)c * DP + s * 64 + g * 16);
-      skey = *reinterpret_cast<const v4i*>(sn + 4 * g);
-    }
-    for (int jt = 0; jt < nt; ++jt) {
-      const int jn = min(jt + 1, nt - 1);  // the tile ahead (the last one reads itself again)
-#pragma unroll
-      for (int s = 0; s < KS; ++s) nf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)(16 * jn + c) * DP + s * 64 + g * 16);
-      nkey = *reinterpret_cast<const v4i*>(sn + 16 * jn + 4 * g);
-#pragma unroll
-      for (int t = 0; t < DESC_QT; ++t) {
-        v4i acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(sf[s], qf[t][s], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int32_t key = skey[r] - 2 * acc[r];  // d2 less the query's norm, which every candidate of a query shares
-          const int32_t jj = 16 * jt + 4 * g + r;
-          if (DUMP) {
-            const int q = q0 + 16 * t + c;
-            if (q < nq && jj < ns) dump[(int64_t)q * ns + jj] = key + qn[q];
-          }
-          else {
-            sd[t] = min(sd[t], max(bd[t], key));
-            bj[t] = key < bd[t] ? jj : bj[t];
-            bd[t] = min(bd[t], key);
-          }
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) sf[s] = nf[s];
-      skey = nkey;
-    }
-    if (!DUMP) {
-#pragma unroll
-      for (int t = 0; t < DESC_QT; ++t) {
+      for (int s = 0; s < KS; ++s) qf[t][s] = desc_frag<KS>(qd, q0 + 16 * t + c, s, g);
+    if (DUMP) {
+      desc_sweep<KS, DESC_QT>(qf, sdp, sn, ns, c, g, [&](int t, int32_t key, int32_t jj) {
         const int q = q0 + 16 * t + c;
-        const int32_t nq2 = q < nq ? qn[q] : 0;  // (a padding row's result is not stored)
-        DescTop2 T;
-        T.d = bd[t] == kDescNone ? kDescNone : bd[t] + nq2;
-        T.j = bj[t];
-        T.s = sd[t] == kDescNone ? kDescNone : sd[t] + nq2;
+        if (q < nq && jj < ns) dump[(int64_t)q * ns + jj] = key + qn[q];
+      });
+      continue;
+    }
+    DescRun run[DESC_QT];
+    desc_sweep<KS, DESC_QT>(qf, sdp, sn, ns, c, g, [&](int t, int32_t key, int32_t jj) { run[t].take(key, jj); });
 #pragma unroll
-        for (int d = 16; d <= 32; d <<= 1) {
-          DescTop2 O;
-          O.d = __shfl_xor(T.d, d);
-          O.j = __shfl_xor(T.j, d);
-          O.s = __shfl_xor(T.s, d);
-          T = desc_top2_merge(T, O);
-        }
-        if (g == 0 && q < nq) out[q] = T;
-      }
+    for (int t = 0; t < DESC_QT; ++t) {
+      const int q = q0 + 16 * t + c;
+      const DescTop2 T = desc_run_finish(run[t], q < nq ? qn[q] : 0);  // (a padding row's result is not stored)
+      if (g == 0 && q < nq) out[q] = T;
     }
   }
 }
@@ -219,7 +166,7 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2_guided(const DescPair* __
         qx = b.x; qy = b.y;
       }
     }
-    int32_t bd = kDescNone, bj = kDescNone, sd = kDescNone;
+    DescRun run;
     for (int s0 = 0; s0 < ns; s0 += DESC_G_TILE) {
       const int cnt = min(DESC_G_TILE, ns - s0), cntu = (cnt + DESC_G_UNROLL - 1) & ~(DESC_G_UNROLL - 1);  // the tail: never admissible
       __syncthreads();  // the tile before this one has been scanned
@@ -256,15 +203,12 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2_guided(const DescPair* __
             const uint32_t* y = sdp + (int64_t)j * DPW;
             int32_t dot = 0;
             for (int w = 0; w < DPW; ++w) dot += desc_dot_i8x4(x[w], y[w]);
-            const int32_t key = qn[q] + sn[j] - 2 * dot;
-            sd = min(sd, max(bd, key));
-            bj = key < bd ? j : bj;
-            bd = min(bd, key);
+            run.take(qn[q] + sn[j] - 2 * dot, j);
           }
         }
       }
     }
-    if (q < nq) out[q] = DescTop2{bd, bj, sd};
+    if (q < nq) out[q] = DescTop2{run.bd, run.bj, run.sd};
   }
 }
 
@@ -320,15 +264,27 @@ template <bool DUMP>
 void launch_top2(int KS, dim3 grid, hipStream_t st, const DescPair* pairs, int dirs, const int8_t* da, const int32_t* na, const int8_t* db,
                  const int32_t* nb, DescTop2* state, int32_t* dump)
 {
-  switch (KS) {
-#define PTZ_DESC_CASE(K) \
-  case K: hipLaunchKernelGGL((k_desc_top2<K, DUMP>), grid, dim3(DESC_WG), 0, st, pairs, dirs, da, na, db, nb, state, dump); break;
-    PTZ_DESC_CASE(1) PTZ_DESC_CASE(2) PTZ_DESC_CASE(3) PTZ_DESC_CASE(4) PTZ_DESC_CASE(5) PTZ_DESC_CASE(6) PTZ_DESC_CASE(7) PTZ_DESC_CASE(8)
-#undef PTZ_DESC_CASE
-  }
+  PTZ_DESC_FOR_KS(KS, hipLaunchKernelGGL((k_desc_top2<K, DUMP>), grid, dim3(DESC_WG), 0, st, pairs, dirs, da, na, db, nb, state, dump));
 }
 
 inline unsigned tiles_y(int64_t n, int per) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + per - 1) / per, 1), 65535); }
+
+// the five arrays of n matches as slots of a block (a chunk's part, the result): the pixels only where both sets have key points
+struct MatchArrays {
+  size_t o_ia, o_ib, o_d2, o_ua, o_ub;
+  bool has_uv;
+  MatchArrays(BlockLayout& b, int64_t n, bool uv) : has_uv(uv)
+  {
+    const size_t m = (size_t)std::max<int64_t>(n, 1);
+    o_ia = b.take(sizeof(int32_t) * m); o_ib = b.take(sizeof(int32_t) * m); o_d2 = b.take(sizeof(int32_t) * m);
+    o_ua = b.take(uv ? sizeof(float2) * m : 0); o_ub = b.take(uv ? sizeof(float2) * m : 0);
+  }
+  int32_t* idx_a(char* p) const { return (int32_t*)(p + o_ia); }
+  int32_t* idx_b(char* p) const { return (int32_t*)(p + o_ib); }
+  int32_t* dist2(char* p) const { return (int32_t*)(p + o_d2); }
+  float2* uv_a(char* p) const { return has_uv ? (float2*)(p + o_ua) : nullptr; }
+  float2* uv_b(char* p) const { return has_uv ? (float2*)(p + o_ub) : nullptr; }
+};
 
 }  // namespace
 }  // namespace ptz
@@ -340,7 +296,7 @@ struct ptz_desc_matches {
   double device_ms = 0;
   bool has_uv = false;
   std::vector<int64_t> match_ptr;  // [n_pair + 1]
-  ptz::DescBlock blk;
+  ptz::PoolBlock blk;
   int64_t* d_match_ptr = nullptr;
   int32_t *d_idx_a = nullptr, *d_idx_b = nullptr, *d_dist2 = nullptr;
   float2 *d_uv_a = nullptr, *d_uv_b = nullptr;
@@ -384,10 +340,10 @@ extern "C" int32_t ptz_desc_set_create(int32_t n_img, const int64_t* feat_ptr, c
     s->row_off[m + 1] = s->row_off[m] + (feat_ptr[m + 1] - feat_ptr[m] + DESC_ROW_PAD - 1) / DESC_ROW_PAD * DESC_ROW_PAD;
   const int DP = 64 * s->KS;
   const size_t rows = (size_t)s->row_off[n_img] + DESC_ROW_PAD;  // the slack is the pack kernel's image n_img
-  const size_t o_desc = 0, o_norm = o_desc + up256(rows * DP), o_kp = o_norm + up256(rows * sizeof(int32_t)),
-               o_fp = o_kp + up256(kp_xy ? (size_t)nf * sizeof(float2) : 0), o_ro = o_fp + up256(sizeof(int64_t) * ((size_t)n_img + 2)),
-               total = o_ro + up256(sizeof(int64_t) * ((size_t)n_img + 2));
-  if (s->blk.get(device_id, total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  BlockLayout b;
+  const size_t o_desc = b.take(rows * DP), o_norm = b.take(rows * sizeof(int32_t)), o_kp = b.take(kp_xy ? (size_t)nf * sizeof(float2) : 0),
+               o_fp = b.take(sizeof(int64_t) * ((size_t)n_img + 2)), o_ro = b.take(sizeof(int64_t) * ((size_t)n_img + 2));
+  if (s->blk.get(device_id, b.total()) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
   s->d_desc = (int8_t*)(s->blk.p + o_desc);
   s->d_norm = (int32_t*)(s->blk.p + o_norm);
   s->d_kp = kp_xy ? (float2*)(s->blk.p + o_kp) : nullptr;
@@ -398,21 +354,18 @@ extern "C" int32_t ptz_desc_set_create(int32_t n_img, const int64_t* feat_ptr, c
   std::vector<int64_t> fp(s->feat_ptr), ro(s->row_off);
   fp.push_back(nf);
   ro.push_back((int64_t)rows);
-  const size_t t_raw = 0, t_total = t_raw + up256((size_t)nf * D);
-  DescBlock tmp;
-  if (tmp.get(device_id, t_total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  DescStream ds;
-  PTZ_HIP_TRY(ds.open(device_id));
-  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_fp, fp.data(), sizeof(int64_t) * fp.size(), hipMemcpyHostToDevice, ds.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_ro, ro.data(), sizeof(int64_t) * ro.size(), hipMemcpyHostToDevice, ds.st));
-  if (nf > 0) PTZ_HIP_TRY(hipMemcpyAsync(tmp.p + t_raw, desc, (size_t)nf * D, hipMemcpyHostToDevice, ds.st));
-  if (nf > 0 && kp_xy) PTZ_HIP_TRY(hipMemcpyAsync(s->d_kp, kp_xy, (size_t)nf * sizeof(float2), hipMemcpyHostToDevice, ds.st));
+  CallHeld h;  // (declared after the set: the stream is waited for before a set that is not returned gives its block back)
+  if (const int32_t rc = h.acquire(device_id, (size_t)nf * D)) { (void)hipGetLastError(); return rc; }
+  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_fp, fp.data(), sizeof(int64_t) * fp.size(), hipMemcpyHostToDevice, h.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(s->blk.p + o_ro, ro.data(), sizeof(int64_t) * ro.size(), hipMemcpyHostToDevice, h.st));
+  if (nf > 0) PTZ_HIP_TRY(hipMemcpyAsync(h.base, desc, (size_t)nf * D, hipMemcpyHostToDevice, h.st));
+  if (nf > 0 && kp_xy) PTZ_HIP_TRY(hipMemcpyAsync(s->d_kp, kp_xy, (size_t)nf * sizeof(float2), hipMemcpyHostToDevice, h.st));
   int64_t most = DESC_ROW_PAD;
   for (int m = 0; m < n_img; ++m) most = std::max(most, s->row_off[m + 1] - s->row_off[m]);
-  hipLaunchKernelGGL(k_desc_pack, dim3(n_img + 1, tiles_y(most, 256)), dim3(256), 0, ds.st, s->d_feat_ptr, s->d_row_off,
-                     (const uint8_t*)(tmp.p + t_raw), D, DP, (uint32_t*)s->d_desc, s->d_norm);
+  hipLaunchKernelGGL(k_desc_pack, dim3(n_img + 1, tiles_y(most, 256)), dim3(256), 0, h.st, s->d_feat_ptr, s->d_row_off,
+                     (const uint8_t*)h.base, D, DP, (uint32_t*)s->d_desc, s->d_norm);
   PTZ_HIP_TRY(hipGetLastError());
-  PTZ_HIP_TRY(stream_wait(ds.st));
+  PTZ_HIP_TRY(stream_wait(h.st));
   *out = s.release();
   return PTZ_OK;
 }
@@ -442,12 +395,8 @@ int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_se
   if (!out) return PTZ_EINVAL;
   *out = nullptr;
   ptz_desc_options o;
-  ptz_desc_options_default(&o);
-  if (opt) o = *opt;
-  else if (A) o.device_id = A->device;
-  if (!A || !B || n_pair < 0 || (n_pair > 0 && (!img_a || !img_b))) return PTZ_EINVAL;
-  if (A->device != B->device || o.device_id != A->device || A->D != B->D) return PTZ_EINVAL;
-  if (!(std::isfinite(o.ratio) && o.ratio >= 0) || o.max_dist2 < 0 || o.min_matches < 0 || o.workspace_bytes <= 0) return PTZ_EINVAL;
+  if (const int32_t rc = desc_options_check(A, B, opt, &o)) return rc;
+  if (n_pair < 0 || (n_pair > 0 && (!img_a || !img_b))) return PTZ_EINVAL;
   for (int p = 0; p < n_pair; ++p)
     if (img_a[p] < 0 || img_a[p] >= A->n_img || img_b[p] < 0 || img_b[p] >= B->n_img) return PTZ_EINVAL;
   if (guide) {
@@ -501,129 +450,120 @@ int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_se
     ws_pairs = std::max(ws_pairs, c.p1 - c.p0);
   }
 
-  const size_t o_tab = 0, o_state = o_tab + up256(sizeof(DescPair) * std::max<size_t>(tab.size(), 1)),
-               o_keep = o_state + up256(sizeof(DescTop2) * ws_state), o_index = o_keep + up256(ws_a),
-               o_aptr = o_index + up256(sizeof(int32_t) * ws_a), o_found = o_aptr + up256(sizeof(int64_t) * (ws_pairs + 1)),
-               o_cnt = o_found + up256(sizeof(int32_t) * ws_pairs), o_optr = o_cnt + up256(sizeof(int32_t) * ws_pairs),
-               o_gh = o_optr + up256(sizeof(int64_t) * (ws_pairs + 1)),  // a host guide's copy: H, then found, of ALL pairs
-               o_gf = o_gh + up256(guide && !guide->on_device ? sizeof(double) * 9 * (size_t)n_pair : 0),
-               ws_total = o_gf + up256(guide && !guide->on_device && guide->found ? sizeof(int32_t) * (size_t)n_pair : 0);
+  const bool host_guide = guide && !guide->on_device;
+  BlockLayout wl;
+  const size_t o_tab = wl.take(sizeof(DescPair) * std::max<size_t>(tab.size(), 1)), o_state = wl.take(sizeof(DescTop2) * ws_state),
+               o_keep = wl.take(ws_a), o_index = wl.take(sizeof(int32_t) * ws_a), o_aptr = wl.take(sizeof(int64_t) * (ws_pairs + 1)),
+               o_found = wl.take(sizeof(int32_t) * ws_pairs), o_cnt = wl.take(sizeof(int32_t) * ws_pairs),
+               o_optr = wl.take(sizeof(int64_t) * (ws_pairs + 1)),
+               o_gh = wl.take(host_guide ? sizeof(double) * 9 * (size_t)n_pair : 0),  // a host guide's copy: H, then found, of ALL pairs
+               o_gf = wl.take(host_guide && guide->found ? sizeof(int32_t) * (size_t)n_pair : 0);
   // a chunk's matches wait in a block of their own until the total is known
-  struct Part { std::unique_ptr<DescBlock> blk; int64_t n; };
-  // the stream is declared after every block its kernels write: on an early return it is waited for before they go back to the pool
-  DescBlock ws;
+  struct Part { PoolBlock blk; int64_t n; };
+  // The ordering rule: on every return the stream is waited for before any block its kernels write goes back to the pool.  h's
+  // destructor waits and then releases the workspace; the parts and the result (res, above) are declared before h, so they go after.
   std::vector<Part> parts;
   std::vector<int64_t> aptr, optr;  // a chunk's offsets, up and down
-  DescStream ds;
-  if (ws.get(dev, ws_total) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  PTZ_HIP_TRY(ds.open(dev));
-  DescPair* d_tab = (DescPair*)(ws.p + o_tab);
-  DescTop2* d_state = (DescTop2*)(ws.p + o_state);
-  uint8_t* d_keep = (uint8_t*)(ws.p + o_keep);
-  int32_t* d_index = (int32_t*)(ws.p + o_index);
-  int64_t* d_aptr = (int64_t*)(ws.p + o_aptr);
-  int32_t* d_found = (int32_t*)(ws.p + o_found);
-  int32_t* d_cnt = (int32_t*)(ws.p + o_cnt);
-  int64_t* d_optr = (int64_t*)(ws.p + o_optr);
+  CallHeld h;
+  if (const int32_t rc = h.acquire(dev, wl.total())) { (void)hipGetLastError(); return rc; }
+  char* const ws = h.base;
+  DescPair* d_tab = (DescPair*)(ws + o_tab);
+  DescTop2* d_state = (DescTop2*)(ws + o_state);
+  uint8_t* d_keep = (uint8_t*)(ws + o_keep);
+  int32_t* d_index = (int32_t*)(ws + o_index);
+  int64_t* d_aptr = (int64_t*)(ws + o_aptr);
+  int32_t* d_found = (int32_t*)(ws + o_found);
+  int32_t* d_cnt = (int32_t*)(ws + o_cnt);
+  int64_t* d_optr = (int64_t*)(ws + o_optr);
   if (n_pair > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DescPair) * tab.size(), hipMemcpyHostToDevice, ds.st));
-    hipLaunchKernelGGL(k_desc_fill, dim3((ws_pairs + 255) / 256), dim3(256), 0, ds.st, ws_pairs, 1, d_found);
+    PTZ_HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DescPair) * tab.size(), hipMemcpyHostToDevice, h.st));
+    hipLaunchKernelGGL(k_desc_fill, dim3((ws_pairs + 255) / 256), dim3(256), 0, h.st, ws_pairs, 1, d_found);
   }
   const double* g_H = guide ? guide->H : nullptr;
   const int32_t* g_found = guide ? guide->found : nullptr;
-  if (guide && !guide->on_device && n_pair > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(ws.p + o_gh, guide->H, sizeof(double) * 9 * (size_t)n_pair, hipMemcpyHostToDevice, ds.st));
-    g_H = (const double*)(ws.p + o_gh);
+  if (host_guide && n_pair > 0) {
+    PTZ_HIP_TRY(hipMemcpyAsync(ws + o_gh, guide->H, sizeof(double) * 9 * (size_t)n_pair, hipMemcpyHostToDevice, h.st));
+    g_H = (const double*)(ws + o_gh);
     if (guide->found) {
-      PTZ_HIP_TRY(hipMemcpyAsync(ws.p + o_gf, guide->found, sizeof(int32_t) * (size_t)n_pair, hipMemcpyHostToDevice, ds.st));
-      g_found = (const int32_t*)(ws.p + o_gf);
+      PTZ_HIP_TRY(hipMemcpyAsync(ws + o_gf, guide->found, sizeof(int32_t) * (size_t)n_pair, hipMemcpyHostToDevice, h.st));
+      g_found = (const int32_t*)(ws + o_gf);
     }
   }
 
-  auto carve = [](char* base, int64_t n, bool uv, int32_t*& ia, int32_t*& ib, int32_t*& d2, float2*& ua, float2*& ub) {
-    const size_t w = up256(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)), w2 = up256(sizeof(float2) * (size_t)std::max<int64_t>(n, 1));
-    ia = (int32_t*)base; ib = (int32_t*)(base + w); d2 = (int32_t*)(base + 2 * w);
-    ua = uv ? (float2*)(base + 3 * w) : nullptr;
-    ub = uv ? (float2*)(base + 3 * w + w2) : nullptr;
-    return 3 * w + (uv ? 2 * w2 : 0);
-  };
   double ms_sum = 0;
   for (const Chunk& c : chunks) {
     const int npc = c.p1 - c.p0;
     aptr.resize(npc + 1);
     for (int p = 0; p < npc; ++p) aptr[p] = tab[c.p0 + p].aoff;
     aptr[npc] = c.n_a;
-    PTZ_HIP_TRY(hipMemcpyAsync(d_aptr, aptr.data(), sizeof(int64_t) * (npc + 1), hipMemcpyHostToDevice, ds.st));
-    PTZ_HIP_TRY(hipEventRecord(ds.e0, ds.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(d_aptr, aptr.data(), sizeof(int64_t) * (npc + 1), hipMemcpyHostToDevice, h.st));
+    PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
     if (guide)
-      hipLaunchKernelGGL(k_desc_top2_guided, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG)), dim3(DESC_WG), 0, ds.st,
+      hipLaunchKernelGGL(k_desc_top2_guided, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG)), dim3(DESC_WG), 0, h.st,
                          (const DescPair*)(d_tab + c.p0), dirs, 16 * A->KS, (const uint32_t*)A->d_desc, (const int32_t*)A->d_norm,
                          (const uint32_t*)B->d_desc, (const int32_t*)B->d_norm, (const float2*)A->d_kp, (const float2*)B->d_kp,
                          g_H + 9 * (size_t)c.p0, g_found ? g_found + c.p0 : nullptr, r2f, d_state);
     else
-      launch_top2<false>(A->KS, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG_Q)), ds.st, d_tab + c.p0, dirs, A->d_desc, A->d_norm,
+      launch_top2<false>(A->KS, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG_Q)), h.st, d_tab + c.p0, dirs, A->d_desc, A->d_norm,
                          B->d_desc, B->d_norm, d_state, nullptr);
-    hipLaunchKernelGGL(k_desc_join, dim3(npc, tiles_y(c.most_q, 256)), dim3(256), 0, ds.st, (const DescPair*)(d_tab + c.p0),
+    hipLaunchKernelGGL(k_desc_join, dim3(npc, tiles_y(c.most_q, 256)), dim3(256), 0, h.st, (const DescPair*)(d_tab + c.p0),
                        (const DescTop2*)d_state, rule, d_keep);
-    enqueue_compact(npc, d_aptr, d_found, d_keep, o.min_matches, d_cnt, d_optr, nullptr, nullptr, nullptr, nullptr, d_index, ds.st);
+    enqueue_compact(npc, d_aptr, d_found, d_keep, o.min_matches, d_cnt, d_optr, nullptr, nullptr, nullptr, nullptr, d_index, h.st);
     PTZ_HIP_TRY(hipGetLastError());
-    PTZ_HIP_TRY(hipEventRecord(ds.e1, ds.st));
+    PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
     optr.resize(npc + 1);
-    PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d_optr, sizeof(int64_t) * (npc + 1), hipMemcpyDeviceToHost, ds.st));
-    PTZ_HIP_TRY(stream_wait(ds.st));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ds.e0, ds.e1);
-    ms_sum += ms;
+    PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d_optr, sizeof(int64_t) * (npc + 1), hipMemcpyDeviceToHost, h.st));
+    PTZ_HIP_TRY(stream_wait(h.st));
+    ms_sum += h.elapsed_ms();
     const int64_t nc = optr[npc], base = res->match_ptr[c.p0];
     for (int p = 0; p < npc; ++p) res->match_ptr[c.p0 + p + 1] = base + optr[p + 1];
-    Part part;
+    parts.emplace_back();
+    Part& part = parts.back();
     part.n = nc;
-    part.blk.reset(new DescBlock());
-    int32_t *ia, *ib, *d2;
-    float2 *ua, *ub;
-    const size_t bytes = carve(nullptr, nc, res->has_uv, ia, ib, d2, ua, ub);
-    if (part.blk->get(dev, bytes) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+    BlockLayout pl;
+    const MatchArrays pa(pl, nc, res->has_uv);
+    if (part.blk.get(dev, pl.total()) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
     if (nc > 0) {
-      carve(part.blk->p, nc, res->has_uv, ia, ib, d2, ua, ub);
-      PTZ_HIP_TRY(hipEventRecord(ds.e0, ds.st));
-      hipLaunchKernelGGL(k_desc_gather, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ds.st, npc, (const DescPair*)(d_tab + c.p0),
+      char* const pp = part.blk.p;
+      PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
+      hipLaunchKernelGGL(k_desc_gather, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h.st, npc, (const DescPair*)(d_tab + c.p0),
                          (const int64_t*)d_optr, (const int32_t*)d_index, (const DescTop2*)d_state, (const float2*)A->d_kp,
-                         (const float2*)B->d_kp, ia, ib, d2, ua, ub);
+                         (const float2*)B->d_kp, pa.idx_a(pp), pa.idx_b(pp), pa.dist2(pp), pa.uv_a(pp), pa.uv_b(pp));
       PTZ_HIP_TRY(hipGetLastError());
-      PTZ_HIP_TRY(hipEventRecord(ds.e1, ds.st));
-      PTZ_HIP_TRY(stream_wait(ds.st));
-      (void)hipEventElapsedTime(&ms, ds.e0, ds.e1);
-      ms_sum += ms;
+      PTZ_HIP_TRY(hipEventRecord(h.ev[1], h.st));
+      PTZ_HIP_TRY(stream_wait(h.st));
+      ms_sum += h.elapsed_ms();
     }
-    parts.push_back(std::move(part));
   }
 
   // one block behind the result: the offsets, then the five arrays, chunk after chunk
   const int64_t nm = res->match_ptr[n_pair];
   res->n_match = nm;
   res->device_ms = ms_sum;
-  int32_t *ia, *ib, *d2;
-  float2 *ua, *ub;
-  const size_t o_ptr_bytes = up256(sizeof(int64_t) * ((size_t)n_pair + 1));
-  const size_t arr_bytes = carve(nullptr, nm, res->has_uv, ia, ib, d2, ua, ub);
-  if (res->blk.get(dev, o_ptr_bytes + arr_bytes) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  res->d_match_ptr = (int64_t*)res->blk.p;
-  carve(res->blk.p + o_ptr_bytes, nm, res->has_uv, res->d_idx_a, res->d_idx_b, res->d_dist2, res->d_uv_a, res->d_uv_b);
-  PTZ_HIP_TRY(hipMemcpyAsync(res->d_match_ptr, res->match_ptr.data(), sizeof(int64_t) * ((size_t)n_pair + 1), hipMemcpyHostToDevice, ds.st));
+  BlockLayout rl;
+  const size_t o_ptr = rl.take(sizeof(int64_t) * ((size_t)n_pair + 1));
+  const MatchArrays ra(rl, nm, res->has_uv);
+  if (res->blk.get(dev, rl.total()) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
+  char* const rp = res->blk.p;
+  res->d_match_ptr = (int64_t*)(rp + o_ptr);
+  res->d_idx_a = ra.idx_a(rp); res->d_idx_b = ra.idx_b(rp); res->d_dist2 = ra.dist2(rp); res->d_uv_a = ra.uv_a(rp); res->d_uv_b = ra.uv_b(rp);
+  PTZ_HIP_TRY(hipMemcpyAsync(res->d_match_ptr, res->match_ptr.data(), sizeof(int64_t) * ((size_t)n_pair + 1), hipMemcpyHostToDevice, h.st));
   int64_t at = 0;
   for (const Part& part : parts) {
     if (part.n == 0) continue;
-    carve(part.blk->p, part.n, res->has_uv, ia, ib, d2, ua, ub);
-    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_a + at, ia, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_b + at, ib, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(res->d_dist2 + at, d2, sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, ds.st));
+    BlockLayout pl;
+    const MatchArrays pa(pl, part.n, res->has_uv);
+    char* const pp = part.blk.p;
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_a + at, pa.idx_a(pp), sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_idx_b + at, pa.idx_b(pp), sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(res->d_dist2 + at, pa.dist2(pp), sizeof(int32_t) * part.n, hipMemcpyDeviceToDevice, h.st));
     if (res->has_uv) {
-      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_a + at, ua, sizeof(float2) * part.n, hipMemcpyDeviceToDevice, ds.st));
-      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_b + at, ub, sizeof(float2) * part.n, hipMemcpyDeviceToDevice, ds.st));
+      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_a + at, pa.uv_a(pp), sizeof(float2) * part.n, hipMemcpyDeviceToDevice, h.st));
+      PTZ_HIP_TRY(hipMemcpyAsync(res->d_uv_b + at, pa.uv_b(pp), sizeof(float2) * part.n, hipMemcpyDeviceToDevice, h.st));
     }
     at += part.n;
   }
-  PTZ_HIP_TRY(stream_wait(ds.st));
+  PTZ_HIP_TRY(stream_wait(h.st));
   PTZ_HIP_TRY(hipGetLastError());
   *out = res.release();
   return PTZ_OK;
@@ -668,14 +608,14 @@ extern "C" int32_t ptz_desc_matches_download(const ptz_desc_matches* m, int64_t*
   const int64_t n = m->n_match;
   if (n == 0 || !(idx_a || idx_b || dist2 || uv_a || uv_b)) return PTZ_OK;
   PTZ_DEVICE_GUARD(m->device);
-  DescStream ds;
-  PTZ_HIP_TRY(ds.open(m->device));
-  if (idx_a) PTZ_HIP_TRY(hipMemcpyAsync(idx_a, m->d_idx_a, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
-  if (idx_b) PTZ_HIP_TRY(hipMemcpyAsync(idx_b, m->d_idx_b, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
-  if (dist2) PTZ_HIP_TRY(hipMemcpyAsync(dist2, m->d_dist2, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ds.st));
-  if (uv_a) PTZ_HIP_TRY(hipMemcpyAsync(uv_a, m->d_uv_a, sizeof(float2) * n, hipMemcpyDeviceToHost, ds.st));
-  if (uv_b) PTZ_HIP_TRY(hipMemcpyAsync(uv_b, m->d_uv_b, sizeof(float2) * n, hipMemcpyDeviceToHost, ds.st));
-  PTZ_HIP_TRY(stream_wait(ds.st));
+  CallHeld h;
+  if (const int32_t rc = h.open(m->device)) return rc;
+  if (idx_a) PTZ_HIP_TRY(hipMemcpyAsync(idx_a, m->d_idx_a, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h.st));
+  if (idx_b) PTZ_HIP_TRY(hipMemcpyAsync(idx_b, m->d_idx_b, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h.st));
+  if (dist2) PTZ_HIP_TRY(hipMemcpyAsync(dist2, m->d_dist2, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h.st));
+  if (uv_a) PTZ_HIP_TRY(hipMemcpyAsync(uv_a, m->d_uv_a, sizeof(float2) * n, hipMemcpyDeviceToHost, h.st));
+  if (uv_b) PTZ_HIP_TRY(hipMemcpyAsync(uv_b, m->d_uv_b, sizeof(float2) * n, hipMemcpyDeviceToHost, h.st));
+  PTZ_HIP_TRY(stream_wait(h.st));
   return PTZ_OK;
 }
 
@@ -713,16 +653,16 @@ extern "C" int32_t ptz_debug_desc_dist2(const ptz_desc_set* A, int32_t img_a, co
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= A->device) return PTZ_ENODEVICE;
   PTZ_DEVICE_GUARD(A->device);
   const DescPair P = {A->row_off[img_a], B->row_off[img_b], 0, 0, 0, 0, (int32_t)na, (int32_t)nb};
-  const size_t o_dump = up256(sizeof(DescPair));
-  DescBlock ws;
-  if (ws.get(A->device, o_dump + sizeof(int32_t) * (size_t)(na * nb)) != hipSuccess) { (void)hipGetLastError(); return PTZ_ENOMEM; }
-  DescStream ds;
-  PTZ_HIP_TRY(ds.open(A->device));
-  PTZ_HIP_TRY(hipMemcpyAsync(ws.p, &P, sizeof(P), hipMemcpyHostToDevice, ds.st));
-  launch_top2<true>(A->KS, dim3(1, tiles_y(na, DESC_WG_Q)), ds.st, (const DescPair*)ws.p, 1, A->d_desc, A->d_norm, B->d_desc, B->d_norm,
-                    nullptr, (int32_t*)(ws.p + o_dump));
+  BlockLayout b;
+  const size_t o_pair = b.take(sizeof(DescPair)), o_dump = b.take(sizeof(int32_t) * (size_t)(na * nb));
+  CallHeld h;
+  if (const int32_t rc = h.acquire(A->device, b.total())) { (void)hipGetLastError(); return rc; }
+  char* const ws = h.base;
+  PTZ_HIP_TRY(hipMemcpyAsync(ws + o_pair, &P, sizeof(P), hipMemcpyHostToDevice, h.st));
+  launch_top2<true>(A->KS, dim3(1, tiles_y(na, DESC_WG_Q)), h.st, (const DescPair*)(ws + o_pair), 1, A->d_desc, A->d_norm, B->d_desc, B->d_norm,
+                    nullptr, (int32_t*)(ws + o_dump));
   PTZ_HIP_TRY(hipGetLastError());
-  PTZ_HIP_TRY(hipMemcpyAsync(out, ws.p + o_dump, sizeof(int32_t) * (size_t)(na * nb), hipMemcpyDeviceToHost, ds.st));
-  PTZ_HIP_TRY(stream_wait(ds.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(out, ws + o_dump, sizeof(int32_t) * (size_t)(na * nb), hipMemcpyDeviceToHost, h.st));
+  PTZ_HIP_TRY(stream_wait(h.st));
   return PTZ_OK;
 }

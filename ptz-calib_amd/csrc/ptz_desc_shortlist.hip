@@ -3,12 +3,11 @@
 // the only ones the matcher then sees.  The contract is ptz_desc_shortlist.h; everything here is integer arithmetic on the packed
 // rows of ptz_desc_set.h, so a query's votes are the bits of the brute-force restatement whatever the batch or the launch.
 //
-//   votes      k_desc_votes is k_desc_top2's inner loop (ptz_desc_match.hip) with another outer shape: a workgroup owns 128 probe
-//              slots of ONE query -- four waves of two 16-probe tiles, gathered once by the index rule into the B operand of
-//              v_mfma_i32_16x16x64_i8 -- and walks a strided group of references, streaming each reference's rows as the A operand,
-//              one tile ahead, with the running (best, best j, second) of a tile in three registers.  At the end of a reference the
-//              four lane groups merge by the header's rule, the g == 0 lanes apply the vote rule, and a ballot's popcount is the
-//              wave's count: 12 bytes of top-2 state per feature and side become one int32.  No state, keep byte, scan or gather.
+//   votes      k_desc_votes is the matcher's sweep (ptz_desc_sweep.h) with another outer shape: a workgroup owns 128 probe slots of
+//              ONE query -- four waves of two 16-probe tiles, gathered once by the index rule -- and walks a strided group of
+//              references, one sweep per reference.  On a reference's finished top-2 the g == 0 lanes apply the vote rule, and a
+//              ballot's popcount is the wave's count: 12 bytes of top-2 state per feature and side become one int32.  No state,
+//              keep byte, scan or gather.
 //   partials   a wave writes its count to a cell of its own, [query][slot of 32 probes][reference]: no atomics; k_desc_shortlist
 //              sums a query's slots in ascending order.  Every cell that is read has been written by exactly one wave of the same
 //              call, so the workspace needs no clearing.
@@ -16,18 +15,15 @@
 //              that share an XCD's L2 walk the same reference group.  The references are split into enough groups for a full
 //              machine's worth of workgroups when there is one query only.
 //   shortlist  one wave per query: sum, rank by counting (the header's sl_takes, O(n_ref^2) per query), write in ascending index.
-#include <cmath>
-
 #include "ptz_common.h"
 #include "ptz_desc_set.h"
 #include "ptz_desc_shortlist.h"
+#include "ptz_desc_sweep.h"
 #include "ptz_host_batch.h"
 #include "ptz_xcd_map.h"
 
 namespace ptz {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int SL_WG = 256;                       // four waves
 constexpr int SL_QT = 2;                         // probe tiles of 16 per wave
@@ -83,64 +79,18 @@ __global__ __launch_bounds__(SL_WG) void k_desc_votes(SlSide R, SlSide Q, const 
     const int64_t row = live[t] ? qi.row0 + sl_probe_feature(slot, qi.n, M) : slack;
     qn2[t] = live[t] ? Q.norm[row] : 0;
 #pragma unroll
-    for (int s = 0; s < KS; ++s) qf[t][s] = *reinterpret_cast<const v4i*>(Q.desc + row * DP + s * 64 + g * 16);
+    for (int s = 0; s < KS; ++s) qf[t][s] = desc_frag<KS>(Q.desc, row, s, g);
   }
 
   for (int r = (int)it.by; r < n_ref; r += (int)gy) {
     const int64_t rr = R.row_off[r];
-    const int ns = (int)(R.feat_ptr[r + 1] - R.feat_ptr[r]);
-    const int8_t* sdp = R.desc + rr * DP;
-    const int32_t* sn = R.norm + rr;
-    const int nt = (ns + 15) >> 4;  // streamed tiles; rows up to 16 nt <= the image's padded rows
-    int32_t bd[SL_QT], bj[SL_QT], sd[SL_QT];
-#pragma unroll
-    for (int t = 0; t < SL_QT; ++t) bd[t] = bj[t] = sd[t] = kDescNone;
-
-    v4i sf[KS], nf[KS], skey, nkey;
-    if (nt > 0) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) sf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)c * DP + s * 64 + g * 16);
-      skey = *reinterpret_cast<const v4i*>(sn + 4 * g);
-    }
-    for (int jt = 0; jt < nt; ++jt) {
-      const int jn = min(jt + 1, nt - 1);  // the tile ahead (the last one reads itself again)
-#pragma unroll
-      for (int s = 0; s < KS; ++s) nf[s] = *reinterpret_cast<const v4i*>(sdp + (int64_t)(16 * jn + c) * DP + s * 64 + g * 16);
-      nkey = *reinterpret_cast<const v4i*>(sn + 16 * jn + 4 * g);
-#pragma unroll
-      for (int t = 0; t < SL_QT; ++t) {
-        v4i acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(sf[s], qf[t][s], acc, 0, 0, 0);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int32_t key = skey[k] - 2 * acc[k];  // d2 less the probe's norm, which every candidate of a probe shares
-          const int32_t jj = 16 * jt + 4 * g + k;
-          sd[t] = min(sd[t], max(bd[t], key));
-          bj[t] = key < bd[t] ? jj : bj[t];
-          bd[t] = min(bd[t], key);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < KS; ++s) sf[s] = nf[s];
-      skey = nkey;
-    }
-
+    DescRun run[SL_QT];
+    desc_sweep<KS, SL_QT>(qf, R.desc + rr * DP, R.norm + rr, (int)(R.feat_ptr[r + 1] - R.feat_ptr[r]), c, g,
+                          [&](int t, int32_t key, int32_t jj) { run[t].take(key, jj); });
     int32_t count = 0;
 #pragma unroll
     for (int t = 0; t < SL_QT; ++t) {
-      DescTop2 T;
-      T.d = bd[t] == kDescNone ? kDescNone : bd[t] + qn2[t];
-      T.j = bj[t];
-      T.s = sd[t] == kDescNone ? kDescNone : sd[t] + qn2[t];
-#pragma unroll
-      for (int d = 16; d <= 32; d <<= 1) {
-        DescTop2 O;
-        O.d = __shfl_xor(T.d, d);
-        O.j = __shfl_xor(T.j, d);
-        O.s = __shfl_xor(T.s, d);
-        T = desc_top2_merge(T, O);
-      }
+      const DescTop2 T = desc_run_finish(run[t], qn2[t]);
       const bool vote = g == 0 && live[t] && sl_votes_for(r2, max_dist2, T);
       count += __popcll(__ballot(vote));
     }
@@ -181,13 +131,6 @@ __global__ __launch_bounds__(SL_WG) void k_desc_shortlist(SlSide Q, const int32_
   if (lane == 0) n_short[q] = taken;
 }
 
-template <int KS>
-void launch_votes_ks(unsigned grid, hipStream_t st, const SlSide& R, const SlSide& Q, const int32_t* query_img, int n_ref, int M, int tiles,
-                     int n_slot, unsigned gx, unsigned gy, double r2, int32_t max_dist2, int32_t* partial)
-{
-  hipLaunchKernelGGL((k_desc_votes<KS>), dim3(grid), dim3(SL_WG), 0, st, R, Q, query_img, n_ref, M, tiles, n_slot, gx, gy, r2, max_dist2, partial);
-}
-
 // the extents of one call: the probe slots any query of the set can use, the workspace
 struct SlWork {
   int cap, tiles, n_slot;
@@ -213,16 +156,11 @@ SlSide sl_side(const ptz_desc_set* s) { return SlSide{s->d_desc, s->d_norm, s->d
 int32_t sl_check(const ptz_desc_set* refs, const ptz_desc_set* queries, int32_t n_query, const ptz_desc_options* desc_opt,
                  const ptz_shortlist_options* sl_opt, ptz_desc_options* d, ptz_shortlist_options* s)
 {
-  ptz_desc_options_default(d);
   ptz_shortlist_options_default(s);
-  if (desc_opt) *d = *desc_opt;
-  else if (refs) d->device_id = refs->device;
   if (sl_opt) *s = *sl_opt;
-  if (!refs || !queries || n_query < 0) return PTZ_EINVAL;
-  if (refs->device != queries->device || d->device_id != refs->device || refs->D != queries->D) return PTZ_EINVAL;
-  if (!(std::isfinite(d->ratio) && d->ratio >= 0) || d->max_dist2 < 0 || d->min_matches < 0 || d->workspace_bytes <= 0) return PTZ_EINVAL;
-  if (s->max_refs < 1 || s->n_probes < 1 || s->min_votes < 0) return PTZ_EINVAL;
-  return PTZ_OK;
+  if (const int32_t rc = desc_options_check(refs, queries, desc_opt, d)) return rc;
+  if (n_query < 0) return PTZ_EINVAL;
+  return shortlist_options_check(*s);
 }
 
 int32_t sl_limits(const ptz_desc_set* refs, const ptz_desc_set* queries, int32_t n_query, const ptz_shortlist_options& s)
@@ -245,12 +183,8 @@ void sl_enqueue(const ptz_desc_set* refs, const ptz_desc_set* queries, int n_que
     const unsigned gx = (unsigned)n_query * (unsigned)w.tiles;
     const unsigned gy = std::min<unsigned>((unsigned)n_ref, std::max<unsigned>((SL_TARGET_WGS + gx - 1) / gx, 1u));
     const double r2 = d.ratio * d.ratio;
-    switch (refs->KS) {
-#define PTZ_SL_CASE(K) \
-  case K: launch_votes_ks<K>(gx * gy, st, R, Q, d_query_img, n_ref, M, w.tiles, w.n_slot, gx, gy, r2, d.max_dist2, partial); break;
-      PTZ_SL_CASE(1) PTZ_SL_CASE(2) PTZ_SL_CASE(3) PTZ_SL_CASE(4) PTZ_SL_CASE(5) PTZ_SL_CASE(6) PTZ_SL_CASE(7) PTZ_SL_CASE(8)
-#undef PTZ_SL_CASE
-    }
+    PTZ_DESC_FOR_KS(refs->KS, hipLaunchKernelGGL((k_desc_votes<K>), dim3(gx * gy), dim3(SL_WG), 0, st, R, Q, d_query_img, n_ref, M, w.tiles,
+                                                 w.n_slot, gx, gy, r2, d.max_dist2, partial));
   }
   const int per = SL_WG / WAVE;
   hipLaunchKernelGGL(k_desc_shortlist, dim3((n_query + per - 1) / per), dim3(SL_WG), 0, st, Q, d_query_img, n_query, n_ref, M, w.n_slot, s.max_refs,

@@ -1,6 +1,9 @@
-// ptz_host_batch.h -- what one call of an entry point holds on the device until it returns, and the check every *_device entry point
-// makes of the caller's buffers.  (The layout of the block is ptz_block_layout.h: up256 and the cursor.)
+// ptz_host_batch.h -- what one call of an entry point holds on the device until it returns, the owner of a pooled block that
+// outlives a call, and the check every *_device entry point makes of the caller's buffers.  (The layout of a block is
+// ptz_block_layout.h: up256 and the cursor.)
 #pragma once
+
+#include <utility>
 
 #include "ptz_common.h"
 #include "ptz_pool.h"
@@ -29,19 +32,25 @@ struct CallHeld {
     if (pooled_stream) ptzpool::stream_release(dev, st);
     for (hipEvent_t e : ev) ptzpool::event_release(dev, true, e);
   }
+  // The stream, if it is the pool's, and two events, unless the call holds them already: all a call without a block needs.
+  int open(int device)
+  {
+    dev = device;
+    if (pooled_stream && !st) PTZ_HIP_TRY(ptzpool::stream_acquire(dev, &st));
+    for (int k = 0; k < 2; ++k)
+      if (!ev[k]) PTZ_HIP_TRY(ptzpool::event_acquire(dev, true, &ev[k]));
+    return PTZ_OK;
+  }
   // A block of `bytes` -- blocks of an earlier acquire() go back first -- with a pinned one beside it if want_pinned (`pinned` stays
-  // null, and the error is cleared, where the host has none to give); the first time also the stream, if it is the pool's, and two
-  // events.  PTZ_ENOMEM: no device block (hipGetLastError() is left to the caller).  Other failures as PTZ_HIP_TRY answers them.
+  // null, and the error is cleared, where the host has none to give), then open().  PTZ_ENOMEM: no device block (hipGetLastError()
+  // is left to the caller).  Other failures as PTZ_HIP_TRY answers them.
   int acquire(int device, size_t bytes, bool want_pinned = false)
   {
     dev = device;
     release_blocks();
     if (ptzpool::dev_acquire(dev, bytes, (void**)&base) != hipSuccess) return PTZ_ENOMEM;
     if (want_pinned && ptzpool::pinned_acquire(bytes, &pinned) != hipSuccess) { pinned = nullptr; (void)hipGetLastError(); }
-    if (pooled_stream && !st) PTZ_HIP_TRY(ptzpool::stream_acquire(dev, &st));
-    for (int k = 0; k < 2; ++k)
-      if (!ev[k]) PTZ_HIP_TRY(ptzpool::event_acquire(dev, true, &ev[k]));
-    return PTZ_OK;
+    return open(device);
   }
   hipError_t third_event() { return ptzpool::event_acquire(dev, true, &ev[2]); }
   // milliseconds between ev[from] and ev[from + 1], both recorded and reached
@@ -59,6 +68,18 @@ struct CallHeld {
     ptzpool::pinned_release(pinned);
     base = nullptr; pinned = nullptr;
   }
+};
+
+// A pooled device block that outlives the call that fills it (a descriptor set, a match table, a chunk's matches): it goes back to
+// the pool with its owner.  The owner must outlive any CallHeld whose stream writes the block -- declare it first -- so that the
+// stream has been waited for when the block goes back.  Movable (a vector of parts), not copyable.
+struct PoolBlock {
+  int dev = 0;
+  char* p = nullptr;
+  PoolBlock() = default;
+  PoolBlock(PoolBlock&& o) noexcept : dev(o.dev), p(std::exchange(o.p, nullptr)) {}
+  ~PoolBlock() { ptzpool::dev_release(dev, p); }
+  hipError_t get(int device, size_t bytes) { dev = device; return ptzpool::dev_acquire(dev, bytes, (void**)&p); }
 };
 
 // The device that owns `p`, checked against the stream's: a launch goes to the device that owns the caller's buffers, on the caller's

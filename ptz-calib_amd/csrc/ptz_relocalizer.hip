@@ -38,21 +38,13 @@ __global__ void k_reloc_universe(int n_query, const int64_t* __restrict__ match_
   for (int64_t i = match_ptr[q] + threadIdx.x % WAVE; i < match_ptr[q + 1]; i += WAVE) mask[i] = 0;
 }
 
-struct Events {
+struct Events {  // the stamps around stages 3 .. 6 on the resident stream (the temporaries of stages 0 and 2 bring their own)
   int dev;
-  hipEvent_t e[8] = {};
+  hipEvent_t e[5] = {};
   explicit Events(int d) : dev(d) {}
   ~Events() { for (hipEvent_t x : e) ptzpool::event_release(dev, true, x); }
   hipError_t make() { for (hipEvent_t& x : e) { const hipError_t r = ptzpool::event_acquire(dev, true, &x); if (r != hipSuccess) return r; } return hipSuccess; }
   double ms(int a, int b) const { float t = 0; (void)hipEventElapsedTime(&t, e[a], e[b]); return t; }
-};
-
-struct DevBlock {  // a pooled block that goes back when the scope ends
-  int dev;
-  char* p = nullptr;
-  explicit DevBlock(int d) : dev(d) {}
-  ~DevBlock() { ptzpool::dev_release(dev, p); }
-  hipError_t take(size_t bytes) { return ptzpool::dev_acquire(dev, bytes ? bytes : 256, (void**)&p); }
 };
 
 }  // namespace
@@ -108,11 +100,12 @@ extern "C" int32_t ptz_relocalizer_create(const ptz_desc_set* ref_set, const dou
   if (const int32_t rc = ptz_reloc_ref_rotations(n_ref, ref_cams, R.data())) return rc;
   ptz_relocalizer* r = new ptz_relocalizer();
   r->device = device_id; r->n_ref = n_ref; r->refs = ref_set;
-  const size_t o_R = up256(sizeof(double) * 15 * n_ref), total = o_R + up256(sizeof(double) * 9 * n_ref);
-  hipError_t e = ptzpool::dev_acquire(device_id, total, (void**)&r->d_const);
+  BlockLayout b;
+  const size_t o_cams = b.take(sizeof(double) * 15 * n_ref), o_R = b.take(sizeof(double) * 9 * n_ref);
+  hipError_t e = ptzpool::dev_acquire(device_id, b.total(), (void**)&r->d_const);
   if (e == hipSuccess) e = ptzpool::stream_acquire(device_id, &r->st);
   if (e == hipSuccess) {
-    r->d_cams = (double*)r->d_const; r->d_R = (double*)(r->d_const + o_R);
+    r->d_cams = (double*)(r->d_const + o_cams); r->d_R = (double*)(r->d_const + o_R);
     e = hipMemcpyAsync(r->d_cams, ref_cams, sizeof(double) * 15 * n_ref, hipMemcpyHostToDevice, r->st);
   }
   if (e == hipSuccess) e = hipMemcpyAsync(r->d_R, R.data(), sizeof(double) * 9 * n_ref, hipMemcpyHostToDevice, r->st);
@@ -164,7 +157,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     if (query_wh[2 * q] <= 0 || query_wh[2 * q + 1] <= 0) return PTZ_EINVAL;
   if (o.factor_type < PTZ_KRT_F || o.factor_type > PTZ_KRT_FxfyDist) return PTZ_EUNSUPPORTED;
   if (o.match.device_id != r->device || (o.lm.device_id != 0 && o.lm.device_id != r->device)) return PTZ_EINVAL;
-  if (sl && (sl->max_refs < 1 || sl->n_probes < 1 || sl->min_votes < 0 || r->refs->n_img != r->n_ref || n_query > query_set->n_img)) return PTZ_EINVAL;
+  if (sl && (shortlist_options_check(*sl) || r->refs->n_img != r->n_ref || n_query > query_set->n_img)) return PTZ_EINVAL;
   for (double& t : res->stage_ms) t = 0;
   if (sl_res) sl_res->shortlist_ms = 0;
   if (n_query == 0) return PTZ_OK;
@@ -186,17 +179,18 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     BlockLayout b;
     const size_t o_sl = b.take(sizeof(int32_t) * R * nq), o_ns = b.take(sizeof(int32_t) * nq), o_votes = b.take(sizeof(int32_t) * nq * n_ref),
                  o_ws = b.take((size_t)ws);
-    DevBlock t(r->device);
-    if (t.take(b.total()) != hipSuccess) return PTZ_ENOMEM;
     std::vector<int32_t> list(R * nq), n_short(nq);
-    PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
-    if (const int32_t rc = ptz_desc_shortlist_device(r->refs, query_set, n_query, nullptr, &o.match, sl, (int32_t*)(t.p + o_sl), (int32_t*)(t.p + o_ns),
-                                                     (int32_t*)(t.p + o_votes), t.p + o_ws, ws, st))
+    CallHeld t(st);
+    if (const int32_t rc = t.acquire(r->device, b.total())) return rc;
+    char* const p = t.base;
+    PTZ_HIP_TRY(hipEventRecord(t.ev[0], st));
+    if (const int32_t rc = ptz_desc_shortlist_device(r->refs, query_set, n_query, nullptr, &o.match, sl, (int32_t*)(p + o_sl), (int32_t*)(p + o_ns),
+                                                     (int32_t*)(p + o_votes), p + o_ws, ws, st))
       return rc;
-    PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
-    PTZ_HIP_TRY(hipMemcpyAsync(list.data(), t.p + o_sl, sizeof(int32_t) * R * nq, hipMemcpyDeviceToHost, st));
-    PTZ_HIP_TRY(hipMemcpyAsync(n_short.data(), t.p + o_ns, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
-    if (sl_res && sl_res->votes) PTZ_HIP_TRY(hipMemcpyAsync(sl_res->votes, t.p + o_votes, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipEventRecord(t.ev[1], st));
+    PTZ_HIP_TRY(hipMemcpyAsync(list.data(), p + o_sl, sizeof(int32_t) * R * nq, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(n_short.data(), p + o_ns, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+    if (sl_res && sl_res->votes) PTZ_HIP_TRY(hipMemcpyAsync(sl_res->votes, p + o_votes, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
     PTZ_HIP_TRY(stream_wait(st));
     PTZ_HIP_TRY(hipGetLastError());
     for (size_t q = 0; q < nq; ++q) {
@@ -213,7 +207,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     if (sl_res) {
       if (sl_res->shortlist) memcpy(sl_res->shortlist, list.data(), sizeof(int32_t) * R * nq);
       if (sl_res->n_short) memcpy(sl_res->n_short, n_short.data(), sizeof(int32_t) * nq);
-      sl_res->shortlist_ms = ev.ms(0, 1);
+      sl_res->shortlist_ms = t.elapsed_ms();
     }
   }
   else {
@@ -247,24 +241,25 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     BlockLayout b;
     const size_t o_H = b.take(sizeof(double) * 9 * npair), o_f = b.take(sizeof(int32_t) * npair), o_p = b.take(sizeof(int64_t) * ((size_t)npair + 1)),
                  o_a = b.take(sizeof(float) * 2 * nmx), o_b = b.take(sizeof(float) * 2 * nmx);
-    DevBlock t(r->device);
-    if (t.take(b.total()) != hipSuccess) return PTZ_ENOMEM;
-    PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
-    if (const int32_t rc = ptz_match_gate_run_device(r->gate, npair, d_ptr, d_ua, d_ub, o.ransac_thresh, o.min_inliers, (double*)(t.p + o_H),
-                                                     (int32_t*)(t.p + o_f), nullptr, (int64_t*)(t.p + o_p), (float*)(t.p + o_a),
-                                                     (float*)(t.p + o_b), nullptr, st))
+    CallHeld t(st);
+    if (const int32_t rc = t.acquire(r->device, b.total())) return rc;
+    char* const p = t.base;
+    PTZ_HIP_TRY(hipEventRecord(t.ev[0], st));
+    if (const int32_t rc = ptz_match_gate_run_device(r->gate, npair, d_ptr, d_ua, d_ub, o.ransac_thresh, o.min_inliers, (double*)(p + o_H),
+                                                     (int32_t*)(p + o_f), nullptr, (int64_t*)(p + o_p), (float*)(p + o_a),
+                                                     (float*)(p + o_b), nullptr, st))
       return rc;
-    hipLaunchKernelGGL(k_reloc_found, dim3((npair + 255) / 256), dim3(256), 0, st, npair, (const int64_t*)(t.p + o_p), (int32_t*)(t.p + o_f));
+    hipLaunchKernelGGL(k_reloc_found, dim3((npair + 255) / 256), dim3(256), 0, st, npair, (const int64_t*)(p + o_p), (int32_t*)(p + o_f));
     PTZ_HIP_TRY(hipGetLastError());
-    PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
+    PTZ_HIP_TRY(hipEventRecord(t.ev[1], st));
     PTZ_HIP_TRY(stream_wait(st));  // the guided call runs on a stream of its own
     ptz_desc_matches* g = nullptr;
-    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), (const double*)(t.p + o_H),
-                                                              (const int32_t*)(t.p + o_f), o.guided_radius, &o.match, &g))
+    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), (const double*)(p + o_H),
+                                                              (const int32_t*)(p + o_f), o.guided_radius, &o.match, &g))
       return rc;
     ptz_desc_matches_destroy(m);
     m = g;
-    res->stage_ms[1] = ev.ms(0, 1) + ptz_desc_matches_device_ms(m);
+    res->stage_ms[1] = t.elapsed_ms() + ptz_desc_matches_device_ms(m);
     nm = ptz_desc_matches_n_matches(m);
     if (nm > INT32_MAX) return PTZ_ELIMIT;
     if (const int32_t rc = ptz_desc_matches_device_ptrs(m, &d_ptr, nullptr, nullptr, nullptr, &d_ua, &d_ub)) return rc;
@@ -294,13 +289,13 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_wh, query_wh, sizeof(int32_t) * 2 * nq, hipMemcpyHostToDevice, st));
 
   // 3. the assembly
-  PTZ_HIP_TRY(hipEventRecord(ev.e[2], st));
+  PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (const int32_t rc = ptz_reloc_assemble_device(n_query, npair, nm, n_ref, d_ptr, d_ua, d_ub, (const int32_t*)(d + o_pref), (const int64_t*)(d + o_qptr),
                                                    r->d_cams, r->d_R, (const int32_t*)(d + o_wh), o.factor_type, K, (int32_t*)(d + o_sel),
                                                    (int32_t*)(d + o_nsel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
                                                    (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
     return rc;
-  PTZ_HIP_TRY(hipEventRecord(ev.e[3], st));
+  PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
   std::vector<int64_t> optr(nq + 1), gptr(nq + 1, 0);
   PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d + o_optr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
   PTZ_HIP_TRY(stream_wait(st));  // the one word the host needs: the extent of the assembled arrays
@@ -325,7 +320,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     PTZ_HIP_TRY(hipGetLastError());
     PTZ_HIP_TRY(hipMemcpyAsync(gptr.data(), d + o_gptr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
   }
-  PTZ_HIP_TRY(hipEventRecord(ev.e[4], st));
+  PTZ_HIP_TRY(hipEventRecord(ev.e[2], st));
 
   // 5. the solve: on the gate's compacted CSR, or the trimming loop over the assembled arrays with the gate's set as its universe
   if (trimming) {
@@ -341,7 +336,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                     : ptz_krt_solve_batch_device(n_query, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
                                                                   o.max_reproj_error, &o.lm, d_sum, d_acc, st))
     return rc;
-  PTZ_HIP_TRY(hipEventRecord(ev.e[5], st));
+  PTZ_HIP_TRY(hipEventRecord(ev.e[3], st));
 
   // 6. the covariance over the matches a query kept
   if (cov) {
@@ -352,7 +347,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                                            (double*)(d + o_s0), (int32_t*)(d + o_cst), st))
       return rc;
   }
-  PTZ_HIP_TRY(hipEventRecord(ev.e[6], st));
+  PTZ_HIP_TRY(hipEventRecord(ev.e[4], st));
 
   // only per-query results reach the host
   std::vector<int32_t> sel(res->sel_ref ? (size_t)K * nq : 0);
@@ -375,7 +370,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     if (res->sel_ref)
       for (int s = 0; s < K; ++s) { const int32_t p = sel[q * K + s]; res->sel_ref[q * K + s] = p < 0 || p >= npair ? -1 : ia[p]; }
   }
-  res->stage_ms[2] = ev.ms(2, 3); res->stage_ms[3] = gated ? ev.ms(3, 4) : 0; res->stage_ms[4] = ev.ms(4, 5); res->stage_ms[5] = cov ? ev.ms(5, 6) : 0;
+  res->stage_ms[2] = ev.ms(0, 1); res->stage_ms[3] = gated ? ev.ms(1, 2) : 0; res->stage_ms[4] = ev.ms(2, 3); res->stage_ms[5] = cov ? ev.ms(3, 4) : 0;
   r->n_query = n_query; r->kept = kept;
   r->table = m;  // (kept for ptz_relocalizer_table)
   m = nullptr;

@@ -6,9 +6,8 @@ multiply-accumulates.  Online shape: 1000 queries x 2000 features against 200 re
 ptz_desc_match_pairs (minimum and median of 7 runs after a warm-up) beside two floors:
   matrix-core floor  the multiply-accumulates at the dense I8 rate (twice BF16, about 5 POPS);
   epilogue floor     the vector instructions of the top-2 update: VALU_PER_ELEMENT per output element, counted in the compiled
-                     D = 128 kernel's inner loop (75 vector instructions per step of 8 elements per lane: accumulator reads, the
-                     shift and subtract that form the key, compare / max / select / min, the address and fragment moves of the
-                     prefetch), at 256 CUs x 4 SIMDs x 16 lanes per clock and 2.4 GHz.
+                     D = 128 kernel's inner loop (69 vector instructions per step of 8 elements per lane: accumulator reads, the
+                     shift and subtract that form the key, compare / max / select / min, the addresses of the prefetch), at 256 CUs x 4 SIMDs x 16 lanes per clock and 2.4 GHz.
 and, for context, the one-thread time of the host restatement (tests/cpu_harness/desc_match_harness.cc) on a sample of the pairs.
 
 usage: probe_desc_match.py [--images 200] [--features 2000] [--queries 1000] [--runs 7] [--host_sample 0.01] [--host_only] [--no_host]
@@ -27,7 +26,8 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 I8_OPS_PER_S = 5.0e15          # dense I8, 2 ops per multiply-accumulate
-VALU_PER_ELEMENT = 75 / 8      # see above: counted by hand in the assembly of k_desc_top2<2, false>; recount when the kernel changes
+VALU_PER_ELEMENT = 69 / 8      # see above: counted in the assembly of k_desc_top2<2, false>, the inner loop's v_* other than the MFMAs
+                               # (profiles/NOTES_desc_sweep.md); recount when the kernel or ptz_desc_sweep.h changes
 VALU_LANE_OPS_PER_S = 256 * 4 * 16 * 2.4e9
 
 
