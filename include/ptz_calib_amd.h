@@ -256,6 +256,17 @@ int32_t ptz_debug_batch_initial_rays(ptz_ba_batch* b, double* ray);
  * Returns per-system status in fail[count] (1 = not positive definite). */
 int32_t ptz_chol_solve_batch(int32_t count, int32_t n, const double* A, const double* rhs, double* x, int32_t* fail,
                              int32_t device_id, double* device_ms);
+/* Diagnostic for the tests of the factorisation kernels: the same solve with the launch path chosen by the caller and one
+ * order per system.  A [count][ld][ld] and rhs / x [count][ld] hold system i in their leading n[i] rows and columns
+ * (ld >= max n; only the lower triangle of A is read).  path: 0 what ptz_chol_solve_batch would take, 1 the one-launch
+ * chain (count <= 32), 2 one launch per step, 3 right-looking panel + trailing update, 4 left-looking column update +
+ * panel (the path of a large bundle-adjustment batch).  flags bit 0: the device buffers the kernels write before they read
+ * (factored diagonal tiles, block and tile inverses, the solution) start as 0xFF bytes instead of whatever the allocation
+ * held.  active (may be NULL): systems with active[i] == 0 are skipped, x[i] and fail[i] stay as passed.  fail[i]: 1 = not
+ * positive definite.  PTZ_EINVAL, with nothing launched: count <= 0, an n[i] <= 0, ld < max n, path outside 0..4, path 1 with
+ * more than 32 systems. */
+int32_t ptz_debug_chol_solve(int32_t count, const int32_t* n, int32_t ld, const double* A, const double* rhs, double* x,
+                             int32_t* fail, const int32_t* active, int32_t path, int32_t flags, int32_t device_id);
 
 /* Measured FP64 matrix-core rate of the device (v_mfma_f64_16x16x4_f64 from registers, every wave slot busy): the
  * number the reduced-camera solve is priced against in the roofline reports. */

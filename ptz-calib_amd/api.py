@@ -42,7 +42,7 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_reloc_assemble_workspace_bytes", "ptz_reloc_assemble_device", "ptz_reloc_assemble", "ptz_reloc_options_default",
            "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table",
            "ptz_shortlist_options_default", "ptz_desc_shortlist", "ptz_desc_shortlist_workspace_bytes", "ptz_desc_shortlist_device",
-           "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs"]
+           "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs", "ptz_debug_chol_solve"]
 
 
 class PtzError(RuntimeError):
@@ -674,6 +674,33 @@ def chol_solve_batch(A, rhs, device_id=0):
     ms = C.c_double()
     _check(lib().ptz_chol_solve_batch(count, n, _p(A), _p(rhs), _p(x), _p(fail), device_id, C.byref(ms)), "ptz_chol_solve_batch")
     return x, fail, ms.value
+
+
+CHOL_AUTO, CHOL_CHAIN, CHOL_STEP, CHOL_RIGHT, CHOL_LEFT = 0, 1, 2, 3, 4
+
+
+def chol_solve_debug(A_list, rhs_list, path=0, poison=False, active=None, x0=None, fail0=None, device_id=0, ld=None):
+    """The dense solve on a chosen launch path (CHOL_*), systems of different order in one call (ptz_debug_chol_solve).
+    A_list: square arrays (lower triangle read), rhs_list: their right-hand sides.  poison: the buffers the kernels write
+    before they read start as 0xFF bytes.  active: per system, 0 = skipped (its x and fail are x0[i] / fail0[i], default 0).
+    Returns (list of x, fail [count] int32)."""
+    count = len(A_list)
+    n = np.array([np.shape(a)[0] for a in A_list], dtype=np.int32)
+    ld = int(n.max()) if ld is None and count else int(ld or 0)
+    A = np.zeros((count, max(ld, 1), max(ld, 1)))
+    rhs = np.zeros((count, max(ld, 1)))
+    x = np.zeros((count, max(ld, 1)))
+    fail = np.zeros(count, dtype=np.int32) if fail0 is None else np.array(fail0, dtype=np.int32)
+    for i in range(count):
+        k = min(int(n[i]), ld)
+        A[i, :k, :k] = np.asarray(A_list[i], dtype=np.float64)[:k, :k]
+        rhs[i, :k] = np.asarray(rhs_list[i], dtype=np.float64)[:k]
+        if x0 is not None:
+            x[i, :k] = np.asarray(x0[i], dtype=np.float64)[:k]
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    _check(lib().ptz_debug_chol_solve(count, _p(n), ld, _p(A), _p(rhs), _p(x), _p(fail), None if act is None else _p(act),
+                                      int(path), 1 if poison else 0, device_id), "ptz_debug_chol_solve")
+    return [x[i, :n[i]].copy() for i in range(count)], fail
 
 
 def find_homographies(match_ptr, src_uv, dst_uv, ransac_thresh=4.0, device_id=0, mask=True):

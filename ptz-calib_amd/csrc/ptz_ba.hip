@@ -836,6 +836,8 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
 
 namespace ptz {
 // defined here (needs ptz_ba_batch) but uses the kernels of ptz_chol.hip through chol_factor_solve pieces
+// (its left-looking loop stands a second time, without the profiling brackets, in ptz_debug_chol_solve, ptz_chol.hip, where the
+// kernel tests reach it: a change to either loop belongs in both)
 void chol_factor_solve_profiled(const CholBatch& cb, double* x, hipStream_t stream, void* prof, bool fused, int path_count)
 {
   // One-step look-ahead: after the triangular solve of block column k, the small update of block column k+1 stays on

@@ -19,6 +19,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "ptz_common.h"
 
@@ -2260,5 +2261,141 @@ extern "C" int32_t ptz_chol_solve_batch(int32_t count, int32_t n, const double* 
   if (dL2) (void)hipFree(dL2);
   if (dLi) (void)hipFree(dLi);
   if (dctl) (void)hipFree(dctl);
+  return lost ? PTZ_ENODEVICE : PTZ_OK;  // (a tile hand-over of the one-launch factorisation that did not arrive)
+}
+
+// ---- diagnostic entry: every factorisation family, chosen by the caller -----------------------------------
+// The same dense solve as ptz_chol_solve_batch with three things the tests of the kernels need and the product never asks for:
+// the launch path is the caller's (0: chol_factor_solve's own choice, 1: chol_chain_kernel, 2: chol_col_step_kernel per step,
+// 3: right-looking panel + syrk, 4: left-looking chol_update_col_h_kernel + panel), every system has its own order n[i] inside
+// one padded order np = chol_padded_order(max n), and the buffers the kernels write before they read can start from garbage.
+//
+// What has to start at zero, read off the kernels: chain_ctl (tickets, generation and flags of chol_chain_kernel: a flag counts
+// as raised when it holds the launch's generation) and A, which chol_clear zeroes in front of every assembly.  L, the second
+// matrix of paths 1 and 2, is handed over as the bundle adjustment hands it over, zeroed once at creation like chain_ctl: the
+// kernels write its strictly-lower tiles of the block columns that hold rows <= n and the back-substitution reads those and
+// the right-hand-side row's, so a dense system may well not need the zeros -- that is not tried here.  Ldiag, Dinv, Linv and
+// x are written by the factorisation / back-substitution before anything reads them; flags bit 0 fills them with 0xFF bytes
+// (NaNs) first so that a read of stale memory shows in the solution (the tests' poisoned runs return the unpoisoned bits).
+// An inactive system (active[i] == 0) is skipped by every kernel: x[i] and fail[i] come back as the caller passed them.
+namespace {
+struct DebugCholBuffers {
+  std::vector<void*> p;
+  hipStream_t stream = nullptr;
+  template <class T> hipError_t get(T** out, size_t bytes) { void* q = nullptr; const hipError_t e = hipMalloc(&q, bytes); if (e == hipSuccess) p.push_back(q); *out = (T*)q; return e; }
+  ~DebugCholBuffers() { if (stream) (void)hipStreamDestroy(stream); for (void* q : p) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int32_t ptz_debug_chol_solve(int32_t count, const int32_t* n, int32_t ld, const double* A, const double* rhs, double* x, int32_t* fail,
+                                        const int32_t* active, int32_t path, int32_t flags, int32_t device_id)
+{
+  using namespace ptz;
+  if (count <= 0 || !n || !A || !rhs || !x || !fail || path < 0 || path > 4) return PTZ_EINVAL;
+  int n_max = 0;
+  for (int i = 0; i < count; ++i) { if (n[i] <= 0) return PTZ_EINVAL; n_max = std::max(n_max, (int)n[i]); }
+  if (ld < n_max) return PTZ_EINVAL;
+  if (path == 1 && count > CHOL_CHAIN_SLOTS) return PTZ_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) return PTZ_ENODEVICE;
+  PTZ_DEVICE_GUARD(device_id);
+  clear_stale_error(__func__);
+  CholBatch cb;
+  cb.count = count;
+  cb.np = chol_padded_order(n_max);
+  const size_t np = cb.np, nt = np / CHOL_NB;
+  const size_t tile_bytes = sizeof(double) * (size_t)count * nt * CHOL_NB * CHOL_NB, dinv_bytes = sizeof(double) * (size_t)count * nt * 4 * 16 * 16;
+  const size_t mat_bytes = sizeof(double) * (size_t)count * np * np, x_bytes = sizeof(double) * (size_t)count * np;
+  DebugCholBuffers buf;
+  double *dx = nullptr;
+  int *dn = nullptr, *dact = nullptr;
+  PTZ_HIP_TRY(buf.get(&cb.A, mat_bytes));
+  PTZ_HIP_TRY(buf.get(&cb.Ldiag, tile_bytes));
+  PTZ_HIP_TRY(buf.get(&cb.Dinv, dinv_bytes));
+  PTZ_HIP_TRY(buf.get(&cb.Linv, tile_bytes));
+  PTZ_HIP_TRY(buf.get(&dx, x_bytes));
+  PTZ_HIP_TRY(buf.get(&dn, sizeof(int) * count));
+  PTZ_HIP_TRY(buf.get(&cb.fail, sizeof(int) * count));
+  cb.n = dn;
+  // the second matrix marks the one-launch / one-launch-per-step paths (chol_factor_solve); path 0 has it where
+  // ptz_chol_solve_batch has it
+  if (path == 1 || path == 2 || (path == 0 && count < 8)) {
+    PTZ_HIP_TRY(buf.get(&cb.L, mat_bytes));
+    PTZ_HIP_TRY(hipMemset(cb.L, 0, mat_bytes));
+    PTZ_HIP_TRY(buf.get(&cb.chain_ctl, sizeof(int) * chol_chain_ctl_ints((int)np)));
+    PTZ_HIP_TRY(hipMemset(cb.chain_ctl, 0, sizeof(int) * chol_chain_ctl_ints((int)np)));
+  }
+  if (flags & 1) {
+    PTZ_HIP_TRY(hipMemset(cb.Ldiag, 0xFF, tile_bytes));
+    PTZ_HIP_TRY(hipMemset(cb.Dinv, 0xFF, dinv_bytes));
+    PTZ_HIP_TRY(hipMemset(cb.Linv, 0xFF, tile_bytes));
+    PTZ_HIP_TRY(hipMemset(dx, 0xFF, x_bytes));
+  }
+  PTZ_HIP_TRY(hipMemcpy(dn, n, sizeof(int) * count, hipMemcpyHostToDevice));
+  PTZ_HIP_TRY(hipMemcpy(cb.fail, fail, sizeof(int) * count, hipMemcpyHostToDevice));
+  if (active) {
+    PTZ_HIP_TRY(buf.get(&dact, sizeof(int) * count));
+    PTZ_HIP_TRY(hipMemcpy(dact, active, sizeof(int) * count, hipMemcpyHostToDevice));
+    cb.active = dact;
+    for (int s = 0; s < count; ++s)  // what a skipped system's row of x must still hold afterwards
+      if (!active[s]) PTZ_HIP_TRY(hipMemcpy(dx + (size_t)s * np, x + (size_t)s * ld, sizeof(double) * n[s], hipMemcpyHostToDevice));
+  }
+  PTZ_HIP_TRY(hipStreamCreate(&buf.stream));
+  hipStream_t stream = buf.stream;
+  chol_clear(cb, stream);
+  for (int s = 0; s < count; ++s) {
+    if (active && !active[s]) continue;
+    const size_t ns = (size_t)n[s];
+    PTZ_HIP_TRY(hipMemcpy2DAsync(cb.A + (size_t)s * np * np, sizeof(double) * np, A + (size_t)s * ld * ld, sizeof(double) * ld,
+                                 sizeof(double) * ns, ns, hipMemcpyHostToDevice, stream));
+    PTZ_HIP_TRY(hipMemcpyAsync(cb.A + (size_t)s * np * np + ns * np, rhs + (size_t)s * ld, sizeof(double) * ns, hipMemcpyHostToDevice, stream));
+  }
+  const int ntile = (int)nt;
+  switch (path) {
+    case 0:
+      chol_factor_solve(cb, dx, stream);
+      break;
+    case 1:
+      chol_chain_launch(cb, stream);
+      chol_backsolve_launch(cb, dx, stream);
+      break;
+    case 2:
+      chol_diag_launch(cb, -1, stream);
+      for (int st = 0; st + 1 < chol_step_count(cb); ++st) chol_col_step_launch(cb, st, stream);
+      chol_backsolve_launch(cb, dx, stream);
+      break;
+    case 3:
+      for (int k = 0; k < ntile; ++k) {
+        chol_panel_launch(cb, k, stream, /*diag_done=*/k > 0);
+        chol_syrk_launch(cb, k, stream, 0, /*fuse_diag=*/true);
+      }
+      chol_tile_inverse_launch(cb, stream);
+      chol_backsolve_launch(cb, dx, stream);
+      break;
+    default:
+      // The left-looking loop of chol_factor_solve_profiled (ptz_ba.hip, the path of every large bundle-adjustment batch)
+      // without its profiling brackets: a change to either loop belongs in both.
+      for (int k = 0; k < ntile; ++k) {
+        if (k > 0) chol_update_col_launch(cb, k, stream, /*fuse_diag=*/true);
+        chol_panel_launch(cb, k, stream, /*diag_done=*/k > 0);
+      }
+      chol_tile_inverse_launch(cb, stream);
+      chol_backsolve_launch(cb, dx, stream);
+      break;
+  }
+  PTZ_HIP_TRY(hipStreamSynchronize(stream));
+  PTZ_HIP_TRY(hipGetLastError());
+  for (int s = 0; s < count; ++s)
+    PTZ_HIP_TRY(hipMemcpy(x + (size_t)s * ld, dx + (size_t)s * np, sizeof(double) * n[s], hipMemcpyDeviceToHost));
+  bool lost = false;
+  {
+    std::vector<int> hf(count);
+    PTZ_HIP_TRY(hipMemcpy(hf.data(), cb.fail, sizeof(int) * count, hipMemcpyDeviceToHost));
+    for (int s = 0; s < count; ++s) {
+      if (active && !active[s]) continue;
+      lost |= (hf[s] & 2) != 0;
+      fail[s] = hf[s] & 1;
+    }
+  }
   return lost ? PTZ_ENODEVICE : PTZ_OK;  // (a tile hand-over of the one-launch factorisation that did not arrive)
 }
