@@ -1004,6 +1004,69 @@ int32_t ptz_relocalizer_run_shortlisted(ptz_relocalizer* r, const ptz_desc_set* 
                                         ptz_shortlist_result* sl_result);
 int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr);
 
+/* ---- relocalization from a prior camera: overlap shortlist and pair homographies ------------------------------------------------
+ * For a query whose camera is roughly known (the last frame's, or pan / tilt / zoom telemetry) both expensive questions of the
+ * online half have answers before a feature is matched.  The contract is csrc/ptz_reloc_prior.h, doubles with + - * / only:
+ *   H          of pair (reference r, query q): K_q R_q R_r^T K_r^-1, with K^-1 written out; the query contributes its image centre
+ *              (0.5 w, 0.5 h), the prior's fx, and fy = fx for PTZ_KRT_F / PTZ_KRT_FDist, the prior's fy otherwise.  Distortion
+ *              does not enter: the matcher's radius absorbs it.  This is the H ptz_desc_match_pairs_guided takes (A = reference).
+ *   overlap    0 .. 128: of an 8 x 8 lattice of cell centres of the reference frame [0, 2cx) x [0, 2cy), the points H puts inside
+ *              the query frame, plus the same count of the query's lattice in the reference frame.
+ *   shortlist  references ranked by (overlap descending, index ascending), one below max(min_overlap, 1) never ranks, the first
+ *              min(max_refs, ranked) taken and written in ASCENDING index.
+ * ref_cams [15 n_ref], ref_R [9 n_ref] and prior_cams [15 n_query], prior_R [9 n_query]: the rotations are ptz_reloc_ref_rotations
+ * of the respective cameras (one host function for both).  query_wh [2 n_query].  Outputs: shortlist [max_refs n_query] (-1 in unused
+ * slots), n_short [n_query], overlap [n_query n_ref], H_slot [9 max_refs n_query] (H of each listed slot, zeros in unused ones).
+ * A query's output depends on its own prior, its image size, the references and the options only.
+ * ptz_reloc_prior_pairs (host arrays: upload, run, download; overlap, H_slot, device_ms may be NULL).  PTZ_EINVAL, before any device
+ * work: negative extents, n_ref < 1 with queries, a missing array, an image size that is not positive, a prior camera with a
+ * non-finite entry or a focal that is not positive, a radius that is not finite and positive, max_refs < 1, min_overlap outside
+ * 0 .. 128; PTZ_EUNSUPPORTED: factor_type; PTZ_ELIMIT: more than 2^31 - 1 slots or scores; n_query = 0 is PTZ_OK.  opt = NULL: defaults.
+ * ptz_reloc_prior_pairs_device: every array a DEVICE pointer on the device that owns d_shortlist, all of them required; enqueued
+ * on `hip_stream`, returns without synchronising.  The cameras are not validated there (they live on the device). */
+typedef struct ptz_prior_options {
+  double radius_px;    /* 40: the guided matcher's radius under the predicted H (ptz_relocalizer_run_tracked) */
+  int32_t max_refs;    /* 8: R, the most references a query keeps */
+  int32_t min_overlap; /* 8, of 128 */
+  int32_t reserved_;
+} ptz_prior_options;
+void ptz_prior_options_default(ptz_prior_options* o);
+int32_t ptz_reloc_prior_pairs(int32_t n_ref, const double* ref_cams, const double* ref_R, int32_t n_query, const double* prior_cams,
+                              const double* prior_R, const int32_t* query_wh, int32_t factor_type, const ptz_prior_options* opt,
+                              int32_t device_id, int32_t* shortlist, int32_t* n_short, int32_t* overlap /* or NULL */,
+                              double* H_slot /* or NULL */, double* device_ms /* or NULL */);
+int32_t ptz_reloc_prior_pairs_device(int32_t n_ref, const double* d_ref_cams, const double* d_ref_R, int32_t n_query,
+                                     const double* d_prior_cams, const double* d_prior_R, const int32_t* d_query_wh, int32_t factor_type,
+                                     const ptz_prior_options* opt, int32_t* d_shortlist, int32_t* d_n_short, int32_t* d_overlap,
+                                     double* d_H_slot, void* hip_stream);
+
+/* ptz_relocalizer_run with a prior camera per query, prior_cams [15 n_query] on the host: no dense pass, no vote pass and no
+ * per-pair RANSAC.  Stage 0 is ptz_reloc_prior_pairs_device of the priors against the resident references (the prior rotations
+ * computed on the host); the host downloads the lists and builds the pair list as the shortlisted run does, query-major, a query's
+ * references ascending; the H of each pair is gathered on the device and ptz_desc_match_pairs_guided_device runs with it, found =
+ * NULL and prior_opt->radius_px IN PLACE of stages 1 and 2 (options->guided_radius is ignored); stage 3 is the assembly; then the
+ * solve's initial camera takes the prior's focal, rotation and distortion (reloc_prior_camera); stages 4 - 6 are unchanged.
+ * THE GATE ON THE ASSEMBLED QUERY (stage 4) IS FORCED ON, whatever options->inlier_matches says: within a radius of tens of pixels a
+ * feature whose true partner is absent often has exactly one admissible candidate, which passes the ratio test (second = INT32_MAX)
+ * and the cross check.  options->match.max_dist2, if set, comes on top.  stage_ms[0] is 0, stage_ms[1] the guided matcher's time.
+ * prior_result (or NULL), every pointer nullable: shortlist [prior_opt->max_refs n_query], n_short, overlap [n_query n_ref], prior_ms
+ * the device time of stage 0.  A query with n_short = 0 goes on as one with n_sel = 0; a lost query is one that is not accepted --
+ * the caller's signal to fall back to ptz_relocalizer_run / _run_shortlisted.  To make it one signal, accepted[q] is also 0 for a query
+ * the gate kept nothing of (the solve on no matches converges where it stands and would say 1).  With a radius of tens of pixels
+ * min_inliers = 6 is weak evidence: a wrong prior's lone candidates agree with SOME homography in a dozen matches by chance; callers
+ * that rely on the signal raise options->min_inliers to a fraction of what a true overlap yields (tens).  ptz_relocalizer_pairs / _table / _matches work as after
+ * any run.  Known limits: gate_max_pair_matches (at most 4096) bounds an assembled query; H ignores distortion; an overlap list is
+ * only as good as the prior. */
+typedef struct ptz_prior_result {
+  int32_t* shortlist;
+  int32_t* n_short;
+  int32_t* overlap;
+  double prior_ms;
+} ptz_prior_result;
+int32_t ptz_relocalizer_run_tracked(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                    const double* prior_cams, const ptz_reloc_options* options, const ptz_prior_options* prior_opt,
+                                    ptz_reloc_result* result, ptz_prior_result* prior_result);
+
 #ifdef __cplusplus
 }
 #endif

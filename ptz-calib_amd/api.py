@@ -42,7 +42,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_reloc_assemble_workspace_bytes", "ptz_reloc_assemble_device", "ptz_reloc_assemble", "ptz_reloc_options_default",
            "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table",
            "ptz_shortlist_options_default", "ptz_desc_shortlist", "ptz_desc_shortlist_workspace_bytes", "ptz_desc_shortlist_device",
-           "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs", "ptz_debug_chol_solve"]
+           "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs", "ptz_debug_chol_solve", "ptz_prior_options_default",
+           "ptz_reloc_prior_pairs", "ptz_reloc_prior_pairs_device", "ptz_relocalizer_run_tracked"]
 
 
 class PtzError(RuntimeError):
@@ -1433,6 +1434,60 @@ def reloc_assemble_device(n_query, n_pair, n_match, n_ref, d_match_ptr, d_uv_ref
                                            C.c_void_p(stream) if stream else None), "ptz_reloc_assemble_device")
 
 
+# ---- relocalization from a prior camera (csrc/ptz_reloc_prior.h) --------------------------------------------------------------------
+class PriorOptions(C.Structure):
+    _fields_ = [("radius_px", C.c_double), ("max_refs", C.c_int32), ("min_overlap", C.c_int32), ("reserved_", C.c_int32)]
+
+
+def prior_options(**kw) -> PriorOptions:
+    o = PriorOptions()
+    lib().ptz_prior_options_default.restype = None
+    lib().ptz_prior_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown prior option {k}")
+        setattr(o, k, float(v) if k == "radius_px" else int(v))
+    return o
+
+
+def reloc_prior_pairs(ref_cams, prior_cams, query_wh, factor_type=0, ref_R=None, prior_R=None, device_id=0, **options):
+    """ptz_reloc_prior_pairs: the references worth matching for queries whose cameras are roughly known, and the homography of every
+    listed pair (b ~ H a, a in the reference image: what match_descriptors_guided takes).  ref_cams [n_ref, 15], prior_cams
+    [n_query, 15], query_wh [n_query, 2]; ref_R / prior_R: reloc_ref_rotations of the respective cameras unless given.
+    options: max_refs (8), min_overlap (8, of 128), radius_px (not used here).  Returns dict(shortlist [n_query, max_refs] with -1 in
+    unused slots, n_short [n_query], overlap [n_query, n_ref], H_slot [n_query, max_refs, 9], device_ms)."""
+    cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+    pri = np.ascontiguousarray(prior_cams, dtype=np.float64).reshape(-1, 15)
+    wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
+    Rr = reloc_ref_rotations(cams) if ref_R is None else np.ascontiguousarray(ref_R, dtype=np.float64).reshape(-1, 9)
+    Rq = reloc_ref_rotations(pri) if prior_R is None else np.ascontiguousarray(prior_R, dtype=np.float64).reshape(-1, 9)
+    if len(wh) != len(pri) or len(Rr) != len(cams) or len(Rq) != len(pri):
+        raise ValueError("query_wh: one size per query, ref_R / prior_R: one matrix per camera")
+    o = prior_options(**options)
+    n, R = len(pri), max(int(o.max_refs), 1)
+    sl = np.full((n, R), -1, dtype=np.int32)
+    ns = np.zeros(n, dtype=np.int32)
+    ov = np.zeros((n, len(cams)), dtype=np.int32)
+    Hs = np.zeros((n, R, 9))
+    ms = C.c_double()
+    _check(lib().ptz_reloc_prior_pairs(len(cams), _p(cams) if len(cams) else None, _p(Rr) if len(cams) else None, n, _p(pri) if n else None,
+                                       _p(Rq) if n else None, _p(wh) if n else None, int(factor_type), C.byref(o), int(device_id),
+                                       _p(sl) if n else None, _p(ns) if n else None, _p(ov) if ov.size else None, _p(Hs) if n else None,
+                                       C.byref(ms)), "ptz_reloc_prior_pairs")
+    return dict(shortlist=sl, n_short=ns, overlap=ov, H_slot=Hs, device_ms=ms.value)
+
+
+def reloc_prior_pairs_device(n_ref, d_ref_cams, d_ref_R, n_query, d_prior_cams, d_prior_R, d_query_wh, d_shortlist, d_n_short, d_overlap,
+                             d_H_slot, factor_type=0, stream=None, **options):
+    """ptz_reloc_prior_pairs_device: every d_* is a device buffer (torch tensor or integer address), all required.  Enqueues on
+    `stream` and returns without synchronising."""
+    o = prior_options(**options)
+    _check(lib().ptz_reloc_prior_pairs_device(int(n_ref), _dptr(d_ref_cams), _dptr(d_ref_R), int(n_query), _dptr(d_prior_cams), _dptr(d_prior_R),
+                                              _dptr(d_query_wh), int(factor_type), C.byref(o), _dptr(d_shortlist), _dptr(d_n_short),
+                                              _dptr(d_overlap), _dptr(d_H_slot), C.c_void_p(stream) if stream else None),
+           "ptz_reloc_prior_pairs_device")
+
+
 # ---- the resident serving loop (ptz_relocalizer_*) ---------------------------------------------------------------------------------
 class RelocOptions(C.Structure):
     _fields_ = [("match", DescOptions), ("guided_radius", C.c_double), ("ransac_thresh", C.c_double), ("min_inliers", C.c_int32),
@@ -1450,6 +1505,10 @@ class ShortlistResult(C.Structure):
     _fields_ = [("shortlist", C.c_void_p), ("n_short", C.c_void_p), ("votes", C.c_void_p), ("shortlist_ms", C.c_double)]
 
 
+class PriorResult(C.Structure):
+    _fields_ = [("shortlist", C.c_void_p), ("n_short", C.c_void_p), ("overlap", C.c_void_p), ("prior_ms", C.c_double)]
+
+
 class Relocalizer:
     """ptz_relocalizer: relocalization from features with the references resident on the device.  ref_set: a DescSet with key points
     (kept alive by this object), ref_cams [n_ref, 15] (image m of the set is camera m)."""
@@ -1465,14 +1524,20 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
         None), cov / sigma0 / cov_status (or None), stage_ms [6].
         shortlist: None (every reference of every query), or a dict of shortlist_options fields (max_refs, n_probes, min_votes; {} for
         the defaults): ptz_relocalizer_run_shortlisted -- only the references the vote pass keeps are matched, and the result gains
-        shortlist [n, R], n_short [n], votes [n, n_ref] and shortlist_ms."""
+        shortlist [n, R], n_short [n], votes [n, n_ref] and shortlist_ms.
+        prior: None, or a dict with cams [n, 15] (a prior camera per query) and optionally radius_px (40), max_refs (8), min_overlap
+        (8): ptz_relocalizer_run_tracked -- the references that overlap the prior are matched under the predicted homography alone
+        (no dense pass; guided_radius is ignored), the solve starts from the prior, and the gate on the assembled query is always on.
+        The result gains shortlist [n, R], n_short [n], overlap [n, n_ref] and prior_ms.  Exclusive with shortlist."""
+        if prior is not None and shortlist is not None:
+            raise ValueError("prior= and shortlist= are two ways to pick a query's references: give one")
         wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
         n, K = len(wh), int(max_refs)
         o = RelocOptions()
@@ -1498,7 +1563,20 @@ class Relocalizer:
         r.summaries, r.trim_report = C.addressof(summ), C.addressof(rep)
         r.cov, r.sigma0, r.cov_status = vp(cov), vp(s0), vp(cst)
         extra = {}
-        if shortlist is None:
+        if prior is not None:
+            po = dict(prior)
+            pc = np.ascontiguousarray(po.pop("cams"), dtype=np.float64).reshape(-1, 15)
+            if len(pc) != n:
+                raise ValueError("prior['cams']: one camera per query")
+            po = prior_options(**po)
+            pr = PriorResult()
+            sl = np.full((n, max(int(po.max_refs), 1)), -1, dtype=np.int32)
+            ns, ov = np.zeros(n, dtype=np.int32), np.zeros((n, len(self.ref_cams)), dtype=np.int32)
+            pr.shortlist, pr.n_short, pr.overlap = vp(sl), vp(ns), vp(ov)
+            _check(lib().ptz_relocalizer_run_tracked(self.handle, query_set.handle, n, _p(wh), _p(pc) if n else None, C.byref(o), C.byref(po),
+                                                     C.byref(r), C.byref(pr)), "ptz_relocalizer_run_tracked")
+            extra = dict(shortlist=sl, n_short=ns, overlap=ov, prior_ms=pr.prior_ms)
+        elif shortlist is None:
             _check(lib().ptz_relocalizer_run(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)), "ptz_relocalizer_run")
         else:
             so = shortlist_options(**shortlist)

@@ -10,6 +10,13 @@
 // --shortlist R (not in the reference; with --shortlist_probes, --shortlist_min_votes; implies --on_device) matches every test image
 // against the R reference images its probe features vote for instead of all of them (ptz_relocalizer_run_shortlisted); every record
 // gains n_shortlist.
+// --prior_params <json> (not in the reference; implies --on_device and --inlier_matches) relocalizes every test image that has a camera
+// in that file from it (ptz_relocalizer_run_tracked: overlap list, guided matching under the predicted homography, no dense pass), in
+// one run; the rest go through the path the other flags select.  --sequence takes the test images in name order, one run per frame: a
+// frame after a registered one is tracked with that frame's camera as its prior, the first frame and any frame after a lost one run
+// untracked (--shortlist if given, else all pairs), and a tracked frame that is lost is run again untracked -- one frame per run and
+// therefore latency-bound.  --prior_radius, --prior_refs: the matcher's radius (40 px) and the list length (8).  Every record gains
+// "tracked" and n_shortlist.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -97,6 +104,12 @@ int main(int argc, char** argv)
                                 "features vote for instead of all of them (implies --on_device); every record gains n_shortlist", false);
   parser.Add("shortlist_probes", '\0', "With --shortlist: features of a test image that vote (default 256)", false);
   parser.Add("shortlist_min_votes", '\0', "With --shortlist: votes a reference image needs to be listed (default 1)", false);
+  parser.Add("prior_params", '\0', "With --match_descriptors: prior cameras of test images (a parameters file keyed by image name); an image "
+                                   "with an entry is relocalized from it by guided matching alone (implies --on_device, --inlier_matches)", false);
+  parser.AddFlag("sequence", "With --match_descriptors: the test images are frames in name order; a frame after a registered one is relocalized "
+                             "from that frame's camera (implies --on_device, --inlier_matches)");
+  parser.Add("prior_radius", '\0', "With --prior_params / --sequence: the guided matcher's radius in pixels (default 40)", false);
+  parser.Add("prior_refs", '\0', "With --prior_params / --sequence: reference images a prior lists at most (default 8)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -110,9 +123,22 @@ int main(int argc, char** argv)
   }
   const int multi_ref = parser.Exist("multi_ref") ? atoi(parser.Get("multi_ref").c_str()) : 0;
   const bool shortlisting = parser.Exist("shortlist");
-  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting;
+  const bool prior_file = parser.Exist("prior_params"), sequence = parser.Exist("sequence"), tracking = prior_file || sequence;
+  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking;
   if (on_device && !parser.Exist("match_descriptors")) {
-    fprintf(stderr, "--on_device, --multi_ref and --shortlist need --match_descriptors\n");
+    fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params and --sequence need --match_descriptors\n");
+    return 1;
+  }
+  ptz_prior_options po;
+  ptz_prior_options_default(&po);
+  if (!tracking && (parser.Exist("prior_radius") || parser.Exist("prior_refs"))) {
+    fprintf(stderr, "--prior_radius and --prior_refs need --prior_params or --sequence\n");
+    return 1;
+  }
+  if (parser.Exist("prior_radius")) po.radius_px = atof(parser.Get("prior_radius").c_str());
+  if (parser.Exist("prior_refs")) po.max_refs = atoi(parser.Get("prior_refs").c_str());
+  if (!(po.radius_px > 0.0) || !std::isfinite(po.radius_px) || po.max_refs < 1) {
+    fprintf(stderr, "--prior_radius must be a positive number of pixels, --prior_refs at least 1\n");
     return 1;
   }
   ptz_shortlist_options sl;
@@ -242,6 +268,7 @@ int main(int argc, char** argv)
   struct Trimmed { double rms = 0; int n_matches = 0, n_removed = 0, rounds = 0; };
   std::vector<Trimmed> trimmed(test_fnames.size());
   std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0), n_shortlist(test_fnames.size(), 0);
+  std::vector<int> tracked(test_fnames.size(), 0);
   if (on_device && !test_fnames.empty()) {
     // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
     // guided pass, the assembly, the gate, the solve or the trimming loop, the covariance -- in the order of the code below
@@ -263,7 +290,7 @@ int main(int argc, char** argv)
     }
     ro.ransac_thresh = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
     ro.min_inliers = min_inliers;
-    ro.inlier_matches = parser.Exist("inlier_matches") ? 1 : 0;
+    ro.inlier_matches = (parser.Exist("inlier_matches") || tracking) ? 1 : 0;
     ro.trim = trimming ? 1 : 0;
     ro.trim_options = trim;
     ro.uncertainty = uncertainty ? 1 : 0;
@@ -271,101 +298,161 @@ int main(int argc, char** argv)
     ro.factor_type = parser.Exist("dist") ? PTZ_KRT_FDist : PTZ_KRT_F;
     ro.max_reproj_error = 100.0;
     ro.lm.max_num_iterations = 200;
-    const int32_t nq = static_cast<int32_t>(test_fnames.size()), n_ref = static_cast<int32_t>(ref_fnames.size()), K = ro.max_refs;
+    const int32_t n_ref = static_cast<int32_t>(ref_fnames.size()), K = ro.max_refs;
     const int32_t nf = ptz_krt_free_dim(ro.factor_type);
-    ptz_desc_set *ref_set = nullptr, *test_set = nullptr;
+    const bool gated = ro.inlier_matches != 0;
+    ptz_desc_set* ref_set = nullptr;
     ptz_relocalizer* rl = nullptr;
     std::vector<double> ref_cams;
     for (const Camera& c : ref_cameras) {
       const std::vector<double> v = c.ToVector();
       ref_cams.insert(ref_cams.end(), v.begin(), v.end());
     }
-    std::vector<int32_t> wh;
-    for (const Size& s : test_sizes) { wh.push_back(s.width); wh.push_back(s.height); }
-    std::vector<double> cam(15 * static_cast<size_t>(nq)), cov(static_cast<size_t>(nf) * nf * nq, 0.0), sigma0(nq, 0.0);
-    std::vector<int32_t> accepted(nq, 0), n_sel(nq, 0), n_matches(nq, 0), n_inliers(nq, 0), status(nq, -1), sel_ref(static_cast<size_t>(K) * nq, -1);
-    std::vector<ptz_lm_summary> summaries(nq);
-    std::vector<ptz_krt_trim_report> reports(nq);
-    ptz_reloc_result rr;
-    rr.cam = cam.data(); rr.accepted = accepted.data(); rr.summaries = summaries.data(); rr.sel_ref = sel_ref.data(); rr.n_sel = n_sel.data();
-    rr.n_matches = n_matches.data(); rr.n_inliers = n_inliers.data(); rr.trim_report = reports.data(); rr.cov = cov.data();
-    rr.sigma0 = sigma0.data(); rr.cov_status = status.data();
-    bool ok = n_ref > 0 && static_cast<size_t>(n_ref) == ref_cameras.size() && BuildDescSet(parser.Get("ref_features"), ref_fnames, ref_features, &ref_set) &&
-              BuildDescSet(parser.Get("test_features"), test_fnames, test_features, &test_set);
+    bool ok = n_ref > 0 && static_cast<size_t>(n_ref) == ref_cameras.size() && BuildDescSet(parser.Get("ref_features"), ref_fnames, ref_features, &ref_set);
     int32_t rc = PTZ_OK;
     if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
-    std::vector<int32_t> n_short(nq, 0);
-    ptz_shortlist_result sr;
-    sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
-    if (ok && rc == PTZ_OK)
-      rc = shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
-                        : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
-    for (int32_t q = 0; q < nq; ++q) n_shortlist[q] = n_short[q];
-    if (ok && rc == PTZ_OK && parser.Exist("save_matches")) {
-      // the table comes to the host once, for the file alone: blocks in the pairs' order, a pair without matches has none
-      const ptz_desc_matches* t = ptz_relocalizer_table(rl);
-      const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(t));
-      // (the run's own pair list: every reference of every test image, or the shortlisted ones)
-      int32_t n_pair = 0;
-      rc = ptz_relocalizer_pairs(rl, &n_pair, nullptr, nullptr);
-      std::vector<int32_t> pair_ref(std::max<int32_t>(n_pair, 1));
-      std::vector<int64_t> query_ptr(static_cast<size_t>(nq) + 1, 0);
-      if (rc == PTZ_OK) rc = ptz_relocalizer_pairs(rl, nullptr, pair_ref.data(), query_ptr.data());
-      std::vector<int64_t> mptr(static_cast<size_t>(n_pair) + 1, 0);
-      std::vector<int32_t> qa(std::max<size_t>(n, 1)), tb(std::max<size_t>(n, 1));
-      if (rc == PTZ_OK) rc = ptz_desc_matches_download(t, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
-      size_t pq = 0;  // the test image of pair p
-      for (size_t p = 0; rc == PTZ_OK && p + 1 < mptr.size(); ++p) {
-        while (static_cast<int64_t>(p) >= query_ptr[pq + 1]) ++pq;
-        if (mptr[p + 1] == mptr[p]) continue;
-        std::vector<DMatch> ms;
-        for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) {
-          DMatch m;
-          m.queryIdx = qa[static_cast<size_t>(k)];
-          m.trainIdx = tb[static_cast<size_t>(k)];
-          ms.push_back(m);
-        }
-        pairs_matches.push_back(ms);
-        img_pairs_name.push_back({ref_fnames[pair_ref[p]], test_fnames[pq]});
+
+    // one run over the test images idx (in that order): tracked from priors [15 per image], or by the path the other flags select
+    const auto run_block = [&](const std::vector<size_t>& idx, const double* priors) {
+      const int32_t nq = static_cast<int32_t>(idx.size());
+      if (!ok || rc != PTZ_OK || nq == 0) return;
+      std::vector<std::string> names;
+      std::vector<ImageFeatures> feats;
+      std::vector<int32_t> wh;
+      for (const size_t i : idx) {
+        names.push_back(test_fnames[i]);
+        feats.push_back(test_features[i]);
+        wh.push_back(test_sizes[i].width); wh.push_back(test_sizes[i].height);
       }
-      if (rc == PTZ_OK && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
-        fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
-        ok = false;
+      ptz_desc_set* test_set = nullptr;
+      ok = BuildDescSet(parser.Get("test_features"), names, feats, &test_set);
+      if (!ok) return;
+      std::vector<double> cam(15 * static_cast<size_t>(nq)), cov(static_cast<size_t>(nf) * nf * nq, 0.0), sigma0(nq, 0.0);
+      std::vector<int32_t> accepted(nq, 0), n_sel(nq, 0), n_matches(nq, 0), n_inliers(nq, 0), status(nq, -1), sel_ref(static_cast<size_t>(K) * nq, -1);
+      std::vector<ptz_lm_summary> summaries(nq);
+      std::vector<ptz_krt_trim_report> reports(nq);
+      ptz_reloc_result rr;
+      rr.cam = cam.data(); rr.accepted = accepted.data(); rr.summaries = summaries.data(); rr.sel_ref = sel_ref.data(); rr.n_sel = n_sel.data();
+      rr.n_matches = n_matches.data(); rr.n_inliers = n_inliers.data(); rr.trim_report = reports.data(); rr.cov = cov.data();
+      rr.sigma0 = sigma0.data(); rr.cov_status = status.data();
+      std::vector<int32_t> n_short(nq, priors || shortlisting ? 0 : n_ref);
+      ptz_shortlist_result sr;
+      sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
+      ptz_prior_result pr;
+      pr.shortlist = nullptr; pr.n_short = n_short.data(); pr.overlap = nullptr; pr.prior_ms = 0;
+      rc = priors ? ptz_relocalizer_run_tracked(rl, test_set, nq, wh.data(), priors, &ro, &po, &rr, &pr)
+           : shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
+                          : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
+      for (int32_t q = 0; q < nq; ++q) n_shortlist[idx[q]] = n_short[q];
+      if (rc == PTZ_OK && parser.Exist("save_matches")) {
+        // the table comes to the host once, for the file alone: blocks in the pairs' order, a pair without matches has none
+        const ptz_desc_matches* t = ptz_relocalizer_table(rl);
+        const size_t n = static_cast<size_t>(ptz_desc_matches_n_matches(t));
+        // (the run's own pair list: every reference of every test image, or the listed ones)
+        int32_t n_pair = 0;
+        rc = ptz_relocalizer_pairs(rl, &n_pair, nullptr, nullptr);
+        std::vector<int32_t> pair_ref(std::max<int32_t>(n_pair, 1));
+        std::vector<int64_t> query_ptr(static_cast<size_t>(nq) + 1, 0);
+        if (rc == PTZ_OK) rc = ptz_relocalizer_pairs(rl, nullptr, pair_ref.data(), query_ptr.data());
+        std::vector<int64_t> mptr(static_cast<size_t>(n_pair) + 1, 0);
+        std::vector<int32_t> qa(std::max<size_t>(n, 1)), tb(std::max<size_t>(n, 1));
+        if (rc == PTZ_OK) rc = ptz_desc_matches_download(t, mptr.data(), qa.data(), tb.data(), nullptr, nullptr, nullptr);
+        size_t pq = 0;  // the test image of pair p
+        for (size_t p = 0; rc == PTZ_OK && p + 1 < mptr.size(); ++p) {
+          while (static_cast<int64_t>(p) >= query_ptr[pq + 1]) ++pq;
+          if (mptr[p + 1] == mptr[p]) continue;
+          std::vector<DMatch> ms;
+          for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) {
+            DMatch m;
+            m.queryIdx = qa[static_cast<size_t>(k)];
+            m.trainIdx = tb[static_cast<size_t>(k)];
+            ms.push_back(m);
+          }
+          pairs_matches.push_back(ms);
+          img_pairs_name.push_back({ref_fnames[pair_ref[p]], names[pq]});
+        }
+      }
+      ptz_desc_set_destroy(test_set);
+      if (rc != PTZ_OK) return;
+      for (int32_t q = 0; q < nq; ++q) {
+        const size_t i = idx[q];
+        tracked[i] = priors ? 1 : 0;
+        multi_n_refs[i] = n_sel[q];
+        multi_n_matches[i] = n_matches[q];
+        // a tracked frame must also have MOST of its guided matches on one homography: under a true prior nearly all are, while the lone
+        // wrong candidates a wrong prior admits agree with some model in a dozen matches by chance (min_inliers alone lets those pass)
+        const bool consistent = !priors || 2 * static_cast<int64_t>(n_inliers[q]) >= n_matches[q];
+        if (n_sel[q] > 0 && accepted[q] && (!gated || n_inliers[q] > 0) && consistent) {
+          test_cameras[i].FromVector(std::vector<double>(cam.begin() + 15 * q, cam.begin() + 15 * (q + 1)));
+          success_ids.insert(static_cast<long>(i));
+          fprintf(stderr, "Running ptz-reloc success: %s\n", test_fnames[i].c_str());
+        }
+        else fprintf(stderr, "Running ptz-reloc failed: %s\n", test_fnames[i].c_str());
+        if (trimming) {
+          Trimmed& t = trimmed[i];
+          t.rms = reports[q].rms_last;
+          t.n_matches = n_matches[q];
+          t.n_removed = t.n_matches - reports[q].n_kept;
+          t.rounds = reports[q].rounds;
+        }
+        sigmas[i] = Sigma();
+        if (uncertainty && status[q] == PTZ_COV_OK) {
+          Sigma& sg = sigmas[i];
+          const double* c = cov.data() + static_cast<size_t>(nf) * nf * q;
+          sg.ok = true;
+          sg.f = std::sqrt(c[0]);
+          for (int k = 0; k < 3; ++k) sg.rot_deg[k] = std::sqrt(c[(1 + k) * nf + 1 + k]) * 180.0 / M_PI;
+          sg.s0 = sigma0[q];
+        }
+      }
+    };
+
+    std::vector<size_t> all(test_fnames.size());
+    for (size_t i = 0; i < all.size(); ++i) all[i] = i;
+    if (sequence) {
+      // frame by frame: the camera of a registered frame is the next frame's prior; a lost tracked frame is run again untracked
+      std::vector<double> prev;
+      for (const size_t t : all) {
+        const size_t mark = pairs_matches.size();
+        if (!prev.empty()) {
+          run_block({t}, prev.data());
+          if (ok && rc == PTZ_OK && !success_ids.count(static_cast<long>(t))) {
+            pairs_matches.resize(mark);
+            img_pairs_name.resize(mark);
+            prev.clear();
+          }
+        }
+        if (prev.empty()) run_block({t}, nullptr);
+        prev = success_ids.count(static_cast<long>(t)) ? test_cameras[t].ToVector() : std::vector<double>();
       }
     }
+    else if (prior_file) {
+      // one tracked run over the test images the file has a camera for, one run of the other flags' path over the rest
+      std::vector<size_t> with, without;
+      std::vector<double> priors;
+      for (const size_t t : all) {
+        std::vector<Camera> one;
+        if (ReadCamFromJson(parser.Get("prior_params"), {test_fnames[t]}, one)) {
+          const std::vector<double> v = one[0].ToVector();
+          priors.insert(priors.end(), v.begin(), v.end());
+          with.push_back(t);
+        }
+        else without.push_back(t);
+      }
+      run_block(with, priors.data());
+      run_block(without, nullptr);
+    }
+    else run_block(all, nullptr);
+    if (ok && rc == PTZ_OK && parser.Exist("save_matches") && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
+      fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
+      ok = false;
+    }
     ptz_relocalizer_destroy(rl);
-    ptz_desc_set_destroy(test_set);
     ptz_desc_set_destroy(ref_set);
     if (!ok) return -1;
     if (rc != PTZ_OK) {
       fprintf(stderr, "ptz_relocalizer_run failed with status %d (no usable HIP device?)\n", rc);
       return -1;
-    }
-    const bool gated = ro.inlier_matches != 0;
-    for (int32_t q = 0; q < nq; ++q) {
-      multi_n_refs[q] = n_sel[q];
-      multi_n_matches[q] = n_matches[q];
-      if (n_sel[q] > 0 && accepted[q] && (!gated || n_inliers[q] > 0)) {
-        test_cameras[q].FromVector(std::vector<double>(cam.begin() + 15 * q, cam.begin() + 15 * (q + 1)));
-        success_ids.insert(static_cast<long>(q));
-        fprintf(stderr, "Running ptz-reloc success: %s\n", test_fnames[q].c_str());
-      }
-      else fprintf(stderr, "Running ptz-reloc failed: %s\n", test_fnames[q].c_str());
-      if (trimming) {
-        Trimmed& t = trimmed[q];
-        t.rms = reports[q].rms_last;
-        t.n_matches = n_matches[q];
-        t.n_removed = t.n_matches - reports[q].n_kept;
-        t.rounds = reports[q].rounds;
-      }
-      if (uncertainty && status[q] == PTZ_COV_OK) {
-        Sigma& s = sigmas[q];
-        const double* c = cov.data() + static_cast<size_t>(nf) * nf * q;
-        s.ok = true;
-        s.f = std::sqrt(c[0]);
-        for (int k = 0; k < 3; ++k) s.rot_deg[k] = std::sqrt(c[(1 + k) * nf + 1 + k]) * 180.0 / M_PI;
-        s.s0 = sigma0[q];
-      }
     }
   }
   if (!query_image.empty()) {
@@ -463,7 +550,7 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty || trimming || multi_ref > 0 || shortlisting) {
+  if (uncertainty || trimming || multi_ref > 0 || shortlisting || tracking) {
     // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
@@ -487,7 +574,8 @@ int main(int argc, char** argv)
         j["n_refs"] = Json::Int(multi_n_refs[i]);
         if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
       }
-      if (shortlisting) j["n_shortlist"] = Json::Int(n_shortlist[i]);
+      if (shortlisting || tracking) j["n_shortlist"] = Json::Int(n_shortlist[i]);
+      if (tracking) j["tracked"] = Json::Int(tracked[i]);
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

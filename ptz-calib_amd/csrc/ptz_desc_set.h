@@ -51,4 +51,26 @@ inline int32_t shortlist_options_check(const ptz_shortlist_options& s)
   return s.max_refs < 1 || s.n_probes < 1 || s.min_votes < 0 ? PTZ_EINVAL : PTZ_OK;
 }
 
+inline int32_t prior_options_check(const ptz_prior_options& p)
+{
+  return !(std::isfinite(p.radius_px) && p.radius_px > 0) || p.max_refs < 1 || p.min_overlap < 0 || p.min_overlap > 128 ? PTZ_EINVAL : PTZ_OK;
+}
+
+// every entry of every prior camera finite, the focals positive
+inline int32_t prior_cams_check(int32_t n_query, const double* prior_cams)
+{
+  for (size_t q = 0; q < (size_t)(n_query > 0 ? n_query : 0); ++q) {
+    const double* c = prior_cams + 15 * q;
+    for (int k = 0; k < 15; ++k)
+      if (!std::isfinite(c[k])) return PTZ_EINVAL;
+    if (!(c[0] > 0) || !(c[1] > 0)) return PTZ_EINVAL;
+  }
+  return PTZ_OK;
+}
+
+// what ptz_relocalizer_run_tracked adds around the library's entry points (ptz_reloc_prior.hip): the H of every pair of the host's
+// list from the slots (pair p of query q is slot p - query_ptr[q]), and the prior's part of the solve's initial camera
+void reloc_prior_enqueue_gather(int n_pair, int n_query, int R, const int64_t* d_query_ptr, const double* d_H_slot, double* d_H, hipStream_t st);
+void reloc_prior_enqueue_cams(int n_query, const double* d_prior_cams, int factor_type, double* d_cam_cur, hipStream_t st);
+
 }  // namespace ptz

@@ -48,4 +48,28 @@ PTZ_HD bool sl_takes(const int32_t* votes, int32_t n_ref, int32_t r, int32_t R, 
   return before < R;
 }
 
+#if defined(__HIPCC__)
+// One wave writes a query's list: the references sl_takes takes on v [n_ref] go to out [R] in ascending index (a ballot prefix per
+// group of 64), -1 to the unused slots; each(slot, r) runs in the lane that owns a taken reference.  Returns the count, one value in
+// the wave (at most R: keys are unique).  The ranking of k_desc_shortlist (votes) and of k_reloc_prior (overlap scores).
+template <class Each>
+__device__ __forceinline__ int sl_wave_list(const int32_t* v, int n_ref, int R, int min_votes, int lane, int32_t* out, Each each)
+{
+  int taken = 0;
+  for (int r0 = 0; r0 < n_ref; r0 += 64) {
+    const int r = r0 + lane;
+    const bool take = r < n_ref && sl_takes(v, n_ref, r, R, min_votes);
+    const unsigned long long mask = __ballot(take);
+    if (take) {
+      const int s = taken + __popcll(mask & ((1ull << lane) - 1ull));
+      out[s] = r;
+      each(s, r);
+    }
+    taken += __popcll(mask);
+  }
+  for (int s = taken + lane; s < R; s += 64) out[s] = -1;
+  return taken;
+}
+#endif
+
 }  // namespace ptz

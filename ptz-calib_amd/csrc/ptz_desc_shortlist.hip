@@ -118,16 +118,7 @@ __global__ __launch_bounds__(SL_WG) void k_desc_shortlist(SlSide Q, const int32_
   }
   __syncthreads();  // the wave ranks on what its other lanes wrote
   if (!has) return;
-  int32_t* out = shortlist + (int64_t)q * R;
-  int taken = 0;
-  for (int r0 = 0; r0 < n_ref; r0 += WAVE) {
-    const int r = r0 + lane;
-    const bool take = r < n_ref && sl_takes(v, n_ref, r, R, min_votes);
-    const unsigned long long mask = __ballot(take);
-    if (take) out[taken + __popcll(mask & ((1ull << lane) - 1ull))] = r;
-    taken += __popcll(mask);
-  }
-  for (int s = taken + lane; s < R; s += WAVE) out[s] = -1;
+  const int taken = sl_wave_list(v, n_ref, R, min_votes, lane, shortlist + (int64_t)q * R, [](int, int) {});
   if (lane == 0) n_short[q] = taken;
 }
 

@@ -2,6 +2,9 @@
 // device (their descriptor set is the caller's, their cameras and rotation matrices are uploaded once); a run takes a set of query
 // images through
 //   0. (ptz_relocalizer_run_shortlisted) the vote pass that picks a query's references, read by the host   ptz_desc_shortlist_device
+//      (ptz_relocalizer_run_tracked) the overlap lists and pair homographies of the prior cameras            ptz_reloc_prior_pairs_device
+//      -- then the guided matcher under those homographies stands IN PLACE of stages 1 and 2, the prior enters the solve's initial
+//      camera after stage 3, and stage 4 is forced on (the lone-candidate finding of ptz_reloc_prior.h)
 //   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
@@ -10,9 +13,10 @@
 //   6. optionally the covariance                                 ptz_krt_covariance_batch_device
 // with every array between them on the device.  Nothing here computes: the stages are the library's own entry points, composed as
 // run_ptz_reloc and MatchDescriptors compose their host forms, so with max_refs = 1 a query's outputs are the bits of that path.
-// The two kernels of this file turn the gate's kept offsets into what the host code derives from its mask: a pair's `found` after
-// the min_inliers rule, and a mask that is zero for a query that does not pass.
+// The kernels of this file turn the gate's kept offsets into what the host code derives from its mask: a pair's `found` after
+// the min_inliers rule, a mask that is zero for a query that does not pass and, in a tracked run, accepted = 0 for such a query.
 #include <cmath>
+#include <optional>
 #include <vector>
 
 #include "ptz_common.h"
@@ -36,6 +40,14 @@ __global__ void k_reloc_universe(int n_query, const int64_t* __restrict__ match_
   const int q = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   if (q >= n_query || gate_ptr[q + 1] > gate_ptr[q]) return;
   for (int64_t i = match_ptr[q] + threadIdx.x % WAVE; i < match_ptr[q + 1]; i += WAVE) mask[i] = 0;
+}
+
+// a tracked run: a query the gate kept nothing of is LOST, whatever the solve on no matches answers (an empty query converges where it
+// stands): its accepted is 0, the caller's signal to fall back
+__global__ void k_reloc_lost(int n_query, const int64_t* __restrict__ gate_ptr, int32_t* __restrict__ accepted)
+{
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n_query && gate_ptr[q + 1] <= gate_ptr[q]) accepted[q] = 0;
 }
 
 struct Events {  // the stamps around stages 3 .. 6 on the resident stream (the temporaries of stages 0 and 2 bring their own)
@@ -142,9 +154,18 @@ static int32_t reloc_gate_for(ptz_relocalizer* r, int32_t pairs, int64_t matches
   return ptz_match_gate_create(r->gate_pairs, r->gate_matches, r->gate_pm, r->device, &r->gate);
 }
 
-// both runs: sl = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references
+// the prior cameras of a tracked run and what it reports of its stage 0
+struct RelocPrior {
+  const double* cams;
+  ptz_prior_options opt;
+  ptz_prior_result* res;
+};
+
+// all three runs: sl = pr = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references,
+// by votes (sl) or by the overlap with its prior camera (pr)
 static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
-                         const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res)
+                         const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res,
+                         const RelocPrior* pr = nullptr)
 {
   using namespace ptz;
   if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
@@ -158,10 +179,16 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   if (o.factor_type < PTZ_KRT_F || o.factor_type > PTZ_KRT_FxfyDist) return PTZ_EUNSUPPORTED;
   if (o.match.device_id != r->device || (o.lm.device_id != 0 && o.lm.device_id != r->device)) return PTZ_EINVAL;
   if (sl && (shortlist_options_check(*sl) || r->refs->n_img != r->n_ref || n_query > query_set->n_img)) return PTZ_EINVAL;
+  if (pr && (prior_options_check(pr->opt) || r->refs->n_img != r->n_ref || n_query > query_set->n_img || (n_query > 0 && !pr->cams) ||
+             prior_cams_check(n_query, pr->cams)))
+    return PTZ_EINVAL;
+  if (pr) o.inlier_matches = 1;  // a lone admissible candidate passes the ratio test: the tracked run always gates the assembled query
   for (double& t : res->stage_ms) t = 0;
   if (sl_res) sl_res->shortlist_ms = 0;
+  if (pr && pr->res) pr->res->prior_ms = 0;
   if (n_query == 0) return PTZ_OK;
-  const int32_t n_ref = r->n_ref, K = o.max_refs, per_query = sl ? (sl->max_refs < n_ref ? sl->max_refs : n_ref) : n_ref;
+  const int32_t n_ref = r->n_ref, K = o.max_refs, listed = sl ? sl->max_refs : (pr ? pr->opt.max_refs : n_ref),
+                per_query = listed < n_ref ? listed : n_ref;
   if ((int64_t)n_query * per_query > INT32_MAX || (int64_t)n_query * o.max_refs > INT32_MAX) return PTZ_ELIMIT;
   clear_stale_error(who);
   PTZ_DEVICE_GUARD(r->device);
@@ -172,7 +199,66 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   // the pairs test image by test image, the references in ascending order: FindBestMatch's first-wins tie picks the lowest reference
   std::vector<int32_t> ia, ib;
   std::vector<int64_t> qptr(nq + 1, 0);
-  if (sl) {
+  // a downloaded stage 0 -> the pair list, query-major, a query's references in the list's (ascending) order
+  const auto pairs_of = [&](const std::vector<int32_t>& list, const std::vector<int32_t>& n_short, size_t R) -> int32_t {
+    for (size_t q = 0; q < nq; ++q) {
+      const int32_t n = n_short[q];
+      if (n < 0 || n > per_query) return PTZ_ENODEVICE;  // (a kernel that did not run)
+      for (int32_t k = 0; k < n; ++k) {
+        const int32_t ref = list[q * R + k];
+        if (ref < 0 || ref >= n_ref) return PTZ_ENODEVICE;
+        ia.push_back(ref);
+        ib.push_back((int32_t)q);
+      }
+      qptr[q + 1] = (int64_t)ia.size();
+    }
+    return PTZ_OK;
+  };
+  std::optional<CallHeld> prior_held;  // a tracked run's stage 0 block: the pairs' H until the matcher has run, the priors until stage 3 has
+  const double *d_prior_H = nullptr, *d_prior_cams = nullptr;
+  if (pr) {
+    // 0. the overlap lists and the H of every slot from the prior cameras; the host reads the lists and keeps their order
+    const size_t R = (size_t)pr->opt.max_refs;
+    std::vector<double> pR(9 * nq);
+    if (const int32_t rc = ptz_reloc_ref_rotations(n_query, pr->cams, pR.data())) return rc;
+    BlockLayout b;
+    const size_t o_pc = b.take(sizeof(double) * 15 * nq), o_pR = b.take(sizeof(double) * 9 * nq), o_wh = b.take(sizeof(int32_t) * 2 * nq),
+                 o_sl = b.take(sizeof(int32_t) * R * nq), o_ns = b.take(sizeof(int32_t) * nq), o_ov = b.take(sizeof(int32_t) * nq * n_ref),
+                 o_Hs = b.take(sizeof(double) * 9 * R * nq), o_qp = b.take(sizeof(int64_t) * (nq + 1)),
+                 o_H = b.take(sizeof(double) * 9 * (size_t)per_query * nq);
+    std::vector<int32_t> list(R * nq), n_short(nq);
+    CallHeld& t = prior_held.emplace(st);
+    if (const int32_t rc = t.acquire(r->device, b.total())) return rc;
+    char* const p = t.base;
+    PTZ_HIP_TRY(hipMemcpyAsync(p + o_pc, pr->cams, sizeof(double) * 15 * nq, hipMemcpyHostToDevice, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(p + o_pR, pR.data(), sizeof(double) * 9 * nq, hipMemcpyHostToDevice, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(p + o_wh, query_wh, sizeof(int32_t) * 2 * nq, hipMemcpyHostToDevice, st));
+    PTZ_HIP_TRY(hipEventRecord(t.ev[0], st));
+    if (const int32_t rc = ptz_reloc_prior_pairs_device(n_ref, r->d_cams, r->d_R, n_query, (const double*)(p + o_pc), (const double*)(p + o_pR),
+                                                        (const int32_t*)(p + o_wh), o.factor_type, &pr->opt, (int32_t*)(p + o_sl),
+                                                        (int32_t*)(p + o_ns), (int32_t*)(p + o_ov), (double*)(p + o_Hs), st))
+      return rc;
+    PTZ_HIP_TRY(hipEventRecord(t.ev[1], st));
+    PTZ_HIP_TRY(hipMemcpyAsync(list.data(), p + o_sl, sizeof(int32_t) * R * nq, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(hipMemcpyAsync(n_short.data(), p + o_ns, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+    if (pr->res && pr->res->overlap) PTZ_HIP_TRY(hipMemcpyAsync(pr->res->overlap, p + o_ov, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
+    PTZ_HIP_TRY(stream_wait(st));
+    PTZ_HIP_TRY(hipGetLastError());
+    if (const int32_t rc = pairs_of(list, n_short, R)) return rc;
+    if (pr->res) {
+      if (pr->res->shortlist) memcpy(pr->res->shortlist, list.data(), sizeof(int32_t) * R * nq);
+      if (pr->res->n_short) memcpy(pr->res->n_short, n_short.data(), sizeof(int32_t) * nq);
+      pr->res->prior_ms = t.elapsed_ms();
+    }
+    // the H of every pair of the list, gathered where the matcher reads it; the matcher runs on a stream of its own
+    PTZ_HIP_TRY(hipMemcpyAsync(p + o_qp, qptr.data(), sizeof(int64_t) * (nq + 1), hipMemcpyHostToDevice, st));
+    reloc_prior_enqueue_gather((int)ia.size(), n_query, (int)R, (const int64_t*)(p + o_qp), (const double*)(p + o_Hs), (double*)(p + o_H), st);
+    PTZ_HIP_TRY(hipGetLastError());
+    PTZ_HIP_TRY(stream_wait(st));
+    d_prior_H = (const double*)(p + o_H);
+    d_prior_cams = (const double*)(p + o_pc);
+  }
+  else if (sl) {
     // 0. the vote pass over the resident references; the host reads the lists and keeps their order
     const size_t R = (size_t)sl->max_refs;
     const int64_t ws = ptz_desc_shortlist_workspace_bytes(r->refs, query_set, n_query, sl);
@@ -193,17 +279,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     if (sl_res && sl_res->votes) PTZ_HIP_TRY(hipMemcpyAsync(sl_res->votes, p + o_votes, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
     PTZ_HIP_TRY(stream_wait(st));
     PTZ_HIP_TRY(hipGetLastError());
-    for (size_t q = 0; q < nq; ++q) {
-      const int32_t n = n_short[q];
-      if (n < 0 || n > per_query) return PTZ_ENODEVICE;  // (a kernel that did not run)
-      for (int32_t k = 0; k < n; ++k) {
-        const int32_t ref = list[q * R + k];
-        if (ref < 0 || ref >= n_ref) return PTZ_ENODEVICE;
-        ia.push_back(ref);
-        ib.push_back((int32_t)q);
-      }
-      qptr[q + 1] = (int64_t)ia.size();
-    }
+    if (const int32_t rc = pairs_of(list, n_short, R)) return rc;
     if (sl_res) {
       if (sl_res->shortlist) memcpy(sl_res->shortlist, list.data(), sizeof(int32_t) * R * nq);
       if (sl_res->n_short) memcpy(sl_res->n_short, n_short.data(), sizeof(int32_t) * nq);
@@ -220,13 +296,21 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   }
   const int32_t npair = (int32_t)ia.size();
 
-  // 1. pass 1 over all pairs
+  // 1. pass 1 over all pairs; a tracked run: the guided matcher under the predicted H, every pair found, in place of stages 1 and 2
   ptz_desc_matches_destroy(r->table);
   r->table = nullptr;
   ptz_desc_matches* m = nullptr;
-  if (const int32_t rc = ptz_desc_match_pairs(r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
   struct Held { ptz_desc_matches*& m; ~Held() { ptz_desc_matches_destroy(m); } } held{m};
-  res->stage_ms[0] = ptz_desc_matches_device_ms(m);
+  if (pr) {
+    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), d_prior_H, nullptr, pr->opt.radius_px,
+                                                              &o.match, &m))
+      return rc;
+    res->stage_ms[1] = ptz_desc_matches_device_ms(m);
+  }
+  else {
+    if (const int32_t rc = ptz_desc_match_pairs(r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
+    res->stage_ms[0] = ptz_desc_matches_device_ms(m);
+  }
   int64_t nm = ptz_desc_matches_n_matches(m);
   if (nm > INT32_MAX) return PTZ_ELIMIT;
   const int64_t* d_ptr = nullptr;
@@ -235,7 +319,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   if (nm > 0 && (!d_ua || !d_ub)) return PTZ_EINVAL;  // sets without key points
 
   // 2. the gate on all pairs, then the guided pass with its device H / found, as MatchDescriptors composes them
-  if (o.guided_radius > 0.0 && npair > 0) {
+  if (!pr && o.guided_radius > 0.0 && npair > 0) {
     if (const int32_t rc = reloc_gate_for(r, npair, nm, o.gate_max_pair_matches)) return rc;
     const size_t nmx = (size_t)(nm > 0 ? nm : 1);
     BlockLayout b;
@@ -295,6 +379,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                                    (int32_t*)(d + o_nsel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
                                                    (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
     return rc;
+  if (pr) {  // the solve starts from the prior's focal, rotation and distortion (one small launch, inside stage 3's stamp)
+    reloc_prior_enqueue_cams(n_query, d_prior_cams, o.factor_type, (double*)(d + o_ccur), st);
+    PTZ_HIP_TRY(hipGetLastError());
+  }
   PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
   std::vector<int64_t> optr(nq + 1), gptr(nq + 1, 0);
   PTZ_HIP_TRY(hipMemcpyAsync(optr.data(), d + o_optr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
@@ -336,6 +424,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                     : ptz_krt_solve_batch_device(n_query, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
                                                                   o.max_reproj_error, &o.lm, d_sum, d_acc, st))
     return rc;
+  if (pr) {
+    hipLaunchKernelGGL(k_reloc_lost, dim3((n_query + 255) / 256), dim3(256), 0, st, n_query, (const int64_t*)(d + o_gptr), d_acc);
+    PTZ_HIP_TRY(hipGetLastError());
+  }
   PTZ_HIP_TRY(hipEventRecord(ev.e[3], st));
 
   // 6. the covariance over the matches a query kept
@@ -394,6 +486,16 @@ extern "C" int32_t ptz_relocalizer_run_shortlisted(ptz_relocalizer* r, const ptz
   ptz_shortlist_options_default(&s);
   if (sl_opt) s = *sl_opt;
   return reloc_run(__func__, r, query_set, n_query, query_wh, options, &s, res, sl_res);
+}
+
+extern "C" int32_t ptz_relocalizer_run_tracked(ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
+                                               const double* prior_cams, const ptz_reloc_options* options, const ptz_prior_options* prior_opt,
+                                               ptz_reloc_result* res, ptz_prior_result* prior_res)
+{
+  RelocPrior p = {prior_cams, {}, prior_res};
+  ptz_prior_options_default(&p.opt);
+  if (prior_opt) p.opt = *prior_opt;
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, &p);
 }
 
 extern "C" int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr)

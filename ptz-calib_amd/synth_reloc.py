@@ -55,11 +55,13 @@ def _project(cam, R, X, width, height):
 
 
 def make_reloc_scene(rig, n_query: int = 24, n_feat: int = 600, visible_share: float = 0.5, noise_px: float = 0.5,
-                     factor_type: int = 0, seed: int = 0, f_range=(1500.0, 4000.0), width: int = 1920, height: int = 1080) -> RelocScene:
+                     factor_type: int = 0, seed: int = 0, f_range=(1500.0, 4000.0), width: int = 1920, height: int = 1080,
+                     query_cams=None) -> RelocScene:
     """rig: the references' cameras [n_ref, 15] (one projection centre).  Every query looks near one of the references (pan within
     +-6 degrees, tilt within +-4 of it) with f ~ U(f_range) and, for factor_type & 1, k1 ~ U(-0.05, 0.05); it observes n_feat world
     rays, uniform over its frame.  A reference that sees a ray (8 px inside its frame) gets the feature with probability
-    visible_share; both pixels carry Gaussian noise of noise_px.  Features of an image are in ascending ray order."""
+    visible_share; both pixels carry Gaussian noise of noise_px.  Features of an image are in ascending ray order.
+    query_cams [n_query, 15]: the queries' cameras (focal, rotation vector, k1) instead of drawn ones -- make_reloc_sequence."""
     rng = np.random.default_rng(seed)
     rig = np.asarray(rig, dtype=np.float64)
     n_ref = rig.shape[0]
@@ -70,10 +72,13 @@ def make_reloc_scene(rig, n_query: int = 24, n_feat: int = 600, visible_share: f
     q_ptr, q_kp, q_track = [0], [], []
     obs = []  # per query: list over refs of (track ids seen, pixels)
     for q in range(n_query):
-        near = int(rng.integers(0, n_ref))
-        R = _rot_x(math.radians(rng.uniform(-4, 4))) @ _rot_y(math.radians(rng.uniform(-6, 6))) @ Rref[near]
-        f = rng.uniform(*f_range)
-        k1 = rng.uniform(-0.05, 0.05) if (factor_type & 1) else 0.0
+        if query_cams is None:
+            near = int(rng.integers(0, n_ref))
+            R = _rot_x(math.radians(rng.uniform(-4, 4))) @ _rot_y(math.radians(rng.uniform(-6, 6))) @ Rref[near]
+            f = rng.uniform(*f_range)
+            k1 = rng.uniform(-0.05, 0.05) if (factor_type & 1) else 0.0
+        else:
+            R, f, k1 = rodrigues(np.asarray(query_cams[q], dtype=np.float64)[4:7]), float(query_cams[q][0]), float(query_cams[q][10])
         cam = np.zeros(15)
         cam[0] = cam[1] = f
         cam[2], cam[3] = cx, cy
@@ -131,14 +136,25 @@ def make_reloc_scene(rig, n_query: int = 24, n_feat: int = 600, visible_share: f
                       query_kp=query_kp, query_track=query_track, width=width, height=height)
 
 
-def make_reloc_descriptors(scene: RelocScene, D: int = 128, noise: int = 12, n_distractors: int = 50, seed: int = 0):
+def make_reloc_descriptors(scene: RelocScene, D: int = 128, noise: int = 12, n_distractors: int = 50, seed: int = 0,
+                           repeat_share: float = 0, repeat_group: int = 4, repeat_noise: int = 6):
     """Descriptors as synth.make_descriptors draws them: one uniform random descriptor per world ray, every feature a copy with
     uniform integer noise in [-noise, noise], clipped; n_distractors unmatched random features are appended to every reference and
     every query image, so the scene's feature indices stay valid.
+    repeat_share > 0: texture that repeats -- of every query's rays that share (at random) is put in groups of repeat_group whose
+    base descriptors are one descriptor, each member with a perturbation of its own in [-repeat_noise, repeat_noise].  With
+    repeat_share = 0 no further random number is drawn.
     Returns ((feat_ptr, desc, kp) of the references, (feat_ptr, desc, kp) of the queries)."""
     rng = np.random.default_rng(seed)
     n_track = int(max(scene.ref_track.max(initial=-1), scene.query_track.max(initial=-1))) + 1
     base = rng.integers(0, 256, (n_track, D), dtype=np.int64)
+    if repeat_share > 0:
+        for q in range(len(scene.query_ptr_feat) - 1):
+            tracks = scene.query_track[int(scene.query_ptr_feat[q]):int(scene.query_ptr_feat[q + 1])]
+            n_rep = int(repeat_share * len(tracks)) // repeat_group * repeat_group
+            groups = tracks[rng.permutation(len(tracks))[:n_rep]].reshape(-1, repeat_group)
+            if len(groups):
+                base[groups] = np.clip(base[groups[:, 0]][:, None, :] + rng.integers(-repeat_noise, repeat_noise + 1, (len(groups), repeat_group, D)), 0, 255)
     out = []
     for ptr, kp, track in ((scene.ref_ptr, scene.ref_kp, scene.ref_track), (scene.query_ptr_feat, scene.query_kp, scene.query_track)):
         obs = np.clip(base[track] + rng.integers(-noise, noise + 1, (len(track), D)), 0, 255).astype(np.uint8)
@@ -152,3 +168,34 @@ def make_reloc_descriptors(scene: RelocScene, D: int = 128, noise: int = 12, n_d
         out.append((feat_ptr, np.concatenate(descs) if descs else np.zeros((0, D), np.uint8),
                     np.concatenate(kps).astype(np.float32) if kps else np.zeros((0, 2), np.float32)))
     return out[0], out[1]
+
+
+def perturb_cameras(cam, angle_deg: float, f_rel: float, seed: int = 0) -> np.ndarray:
+    """Prior cameras from true ones [n, 15]: every camera turned by angle_deg about an axis drawn uniformly on the sphere, its
+    focal lengths scaled by 1 + f_rel or 1 - f_rel (a fair coin); everything else is copied."""
+    rng = np.random.default_rng(seed)
+    out = np.array(cam, dtype=np.float64).reshape(-1, 15).copy()
+    for c in out:
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        c[4:7] = rodrigues_inv(rodrigues(axis * math.radians(angle_deg)) @ rodrigues(c[4:7]))
+        c[0:2] *= 1.0 + (f_rel if rng.random() < 0.5 else -f_rel)
+    return out
+
+
+def make_reloc_sequence(rig, n_frames: int = 12, step_deg: float = 0.4, zoom_rate: float = 0.01, cut_at=None, cut_deg: float = 45.0,
+                        start_pan_deg: float = -45.0, start_f: float = 2200.0, **scene) -> RelocScene:
+    """A broadcast sweep over the rig: frame t pans step_deg on from frame t - 1 and zooms in by zoom_rate (f_t = f_(t-1) (1 + zoom_rate)),
+    starting at pan start_pan_deg (tilt 0) and focal start_f; at frame cut_at, if given, the pan jumps by a further cut_deg -- a cut
+    to another camera position of the same rig.  The frames observe world rays as make_reloc_scene's queries do (its keyword
+    arguments pass through); cam_gt holds the frames' cameras in order."""
+    cams = np.zeros((n_frames, 15))
+    pan, f = start_pan_deg, start_f
+    for t in range(n_frames):
+        if t > 0:
+            pan, f = pan + step_deg, f * (1.0 + zoom_rate)
+        if cut_at is not None and t == cut_at:
+            pan += cut_deg
+        cams[t, 0] = cams[t, 1] = f
+        cams[t, 4:7] = rodrigues_inv(_rot_y(math.radians(pan)))
+    return make_reloc_scene(rig, n_query=n_frames, query_cams=cams, **scene)
