@@ -832,6 +832,18 @@ int32_t ptz_desc_match_pairs_guided(const ptz_desc_set* set_a, const ptz_desc_se
 int32_t ptz_desc_match_pairs_guided_device(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair, const int32_t* img_a,
                                            const int32_t* img_b, const double* d_H, const int32_t* d_found /* or NULL */,
                                            double radius_px, const ptz_desc_options* opt, ptz_desc_matches** out);
+/* The grid-binned guided matcher: a second implementation of the contract above (csrc/ptz_desc_grid.h), the signatures, the error
+ * lists and the output arrays of its namesakes, bit for bit.  Per (pair, direction) the searched positions are sorted into the cells
+ * of a 32 x 32 grid over their bounding box (cell size at least radius_px (1 + 2^-10)), a query tests the candidates of the cells its
+ * reach touches -- a superset of the admissible ones, by the monotonicity of the one cell function -- with the predicate above, and
+ * a wave computes the descriptor distance of each hit together.  Off by default everywhere: ptz_reloc_options.guided_grid,
+ * DescMatchOptions::guided_grid and --guided_grid select it. */
+int32_t ptz_desc_match_pairs_guided_grid(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair, const int32_t* img_a,
+                                         const int32_t* img_b, const double* H, const int32_t* found, double radius_px,
+                                         const ptz_desc_options* opt, ptz_desc_matches** out);
+int32_t ptz_desc_match_pairs_guided_grid_device(const ptz_desc_set* set_a, const ptz_desc_set* set_b, int32_t n_pair,
+                                                const int32_t* img_a, const int32_t* img_b, const double* d_H, const int32_t* d_found,
+                                                double radius_px, const ptz_desc_options* opt, ptz_desc_matches** out);
 /* tests only: the full matrix d2 [n_a, n_b] (host) of one pair, from the matcher's own matrix-core tile code */
 int32_t ptz_debug_desc_dist2(const ptz_desc_set* set_a, int32_t img_a, const ptz_desc_set* set_b, int32_t img_b, int32_t* out);
 
@@ -896,6 +908,8 @@ int32_t ptz_reloc_assemble(int32_t n_query, int32_t n_pair, int32_t n_ref, const
  * [max_refs n_query] (reference image of each slot, -1 unused), n_sel, n_matches (assembled), n_inliers (kept by the gate;
  * n_matches without it), trim_report (trim != 0), cov [NF NF n_query] / sigma0 / cov_status (uncertainty), and stage_ms [6]: device
  * time of the stages above (2: the gate's launches plus the guided matcher's).  A query with n_sel = 0 is solved on no matches.
+ * guided_grid = 1 runs every guided pass (stage 2, and the matcher of ptz_relocalizer_run_tracked) through
+ * ptz_desc_match_pairs_guided_grid_device: the same matches, hence the same outputs; any value but 0 and 1 is PTZ_EINVAL.
  * gate_max_pair_matches (2048, at most 4096): the pair size the gates' bound tables are built for; a pair (stage 2) or a query
  * (stage 4) with more matches does not pass.  The gate object is kept and grows with the runs.
  * ptz_relocalizer_matches downloads the last run's assembled matches (tests): match_ptr [n_query + 1], uv_ref / uv_cur
@@ -918,7 +932,7 @@ typedef struct ptz_reloc_options {
   int32_t factor_type;           /* PTZ_KRT_F */
   double max_reproj_error;       /* 100 */
   int32_t gate_max_pair_matches; /* 2048 */
-  int32_t reserved_;
+  int32_t guided_grid;           /* 0: the guided matcher's scan kernel; 1: its grid kernel (the same matches); else PTZ_EINVAL */
   ptz_lm_options lm;
 } ptz_reloc_options;
 void ptz_reloc_options_default(ptz_reloc_options* o);

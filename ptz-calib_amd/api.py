@@ -38,7 +38,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_krt_solve_batch_trimmed_device", "ptz_desc_options_default", "ptz_desc_set_create", "ptz_desc_set_destroy",
            "ptz_desc_match_pairs", "ptz_desc_matches_n_matches", "ptz_desc_matches_n_pairs", "ptz_desc_matches_device_ms",
            "ptz_desc_matches_n_chunks", "ptz_desc_matches_download", "ptz_desc_matches_device_ptrs", "ptz_desc_matches_destroy",
-           "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device", "ptz_reloc_ref_rotations",
+           "ptz_debug_desc_dist2", "ptz_desc_match_pairs_guided", "ptz_desc_match_pairs_guided_device",
+           "ptz_desc_match_pairs_guided_grid", "ptz_desc_match_pairs_guided_grid_device", "ptz_reloc_ref_rotations",
            "ptz_reloc_assemble_workspace_bytes", "ptz_reloc_assemble_device", "ptz_reloc_assemble", "ptz_reloc_options_default",
            "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table",
            "ptz_shortlist_options_default", "ptz_desc_shortlist", "ptz_desc_shortlist_workspace_bytes", "ptz_desc_shortlist_device",
@@ -1266,11 +1267,12 @@ def match_descriptors(set_a, set_b, img_a, img_b, resident=False, **options):
         m.close()
 
 
-def match_descriptors_guided(set_a, set_b, img_a, img_b, H, found=None, radius_px=4.0, resident=False, **options):
+def match_descriptors_guided(set_a, set_b, img_a, img_b, H, found=None, radius_px=4.0, resident=False, grid=False, **options):
     """ptz_desc_match_pairs_guided: match_descriptors over the candidates pair p's homography H[p] (b ~ H a, [n_pair, 9] or
     [n_pair, 3, 3]) admits within radius_px, the error measured in B's image; found [n_pair] or None (all 1): a pair whose found is
     not 1 has no matches.  H and found may also be DEVICE buffers (torch tensors or integer addresses) on the sets' device (what MatchGate.run_device leaves,
-    its stream synchronised): ptz_desc_match_pairs_guided_device.  Both sets need key points.  Returns what match_descriptors does."""
+    its stream synchronised): ptz_desc_match_pairs_guided_device.  Both sets need key points.  Returns what match_descriptors does.
+    grid=True: the grid-binned kernel (ptz_desc_match_pairs_guided_grid[_device]) -- the same arrays, bit for bit."""
     ia = np.ascontiguousarray(img_a, dtype=np.int32)
     ib = np.ascontiguousarray(img_b, dtype=np.int32)
     if ia.shape != ib.shape or ia.ndim != 1:
@@ -1281,17 +1283,17 @@ def match_descriptors_guided(set_a, set_b, img_a, img_b, H, found=None, radius_p
     if isinstance(H, int) or hasattr(H, "data_ptr"):
         if found is not None and not (isinstance(found, int) or hasattr(found, "data_ptr")):
             raise ValueError("a device H goes with a device found (or None)")
-        _check(lib().ptz_desc_match_pairs_guided_device(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _dptr(H), _dptr(found),
-                                                        C.c_double(radius_px), C.byref(o), C.byref(h)),
-               "ptz_desc_match_pairs_guided_device")
+        name = "ptz_desc_match_pairs_guided_grid_device" if grid else "ptz_desc_match_pairs_guided_device"
+        _check(getattr(lib(), name)(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _dptr(H), _dptr(found), C.c_double(radius_px),
+                                    C.byref(o), C.byref(h)), name)
     else:
         Hh = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
         fh = None if found is None else np.ascontiguousarray(found, dtype=np.int32)
         if len(Hh) != len(ia) or (fh is not None and fh.shape != ia.shape):
             raise ValueError("H: one 3 x 3 matrix per pair, found: one flag per pair")
-        _check(lib().ptz_desc_match_pairs_guided(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _p(Hh) if len(ia) else None,
-                                                 _p(fh) if fh is not None and len(ia) else None, C.c_double(radius_px), C.byref(o),
-                                                 C.byref(h)), "ptz_desc_match_pairs_guided")
+        name = "ptz_desc_match_pairs_guided_grid" if grid else "ptz_desc_match_pairs_guided"
+        _check(getattr(lib(), name)(set_a.handle, set_b.handle, len(ia), _p(ia), _p(ib), _p(Hh) if len(ia) else None,
+                                    _p(fh) if fh is not None and len(ia) else None, C.c_double(radius_px), C.byref(o), C.byref(h)), name)
     m = DescMatches(h)
     if resident:
         return m
@@ -1493,7 +1495,7 @@ class RelocOptions(C.Structure):
     _fields_ = [("match", DescOptions), ("guided_radius", C.c_double), ("ransac_thresh", C.c_double), ("min_inliers", C.c_int32),
                 ("inlier_matches", C.c_int32), ("trim", C.c_int32), ("uncertainty", C.c_int32), ("trim_options", KrtTrimOptions),
                 ("max_refs", C.c_int32), ("factor_type", C.c_int32), ("max_reproj_error", C.c_double), ("gate_max_pair_matches", C.c_int32),
-                ("reserved_", C.c_int32), ("lm", LmOptions)]
+                ("guided_grid", C.c_int32), ("lm", LmOptions)]
 
 
 class RelocResult(C.Structure):
@@ -1524,7 +1526,7 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
@@ -1535,7 +1537,8 @@ class Relocalizer:
         prior: None, or a dict with cams [n, 15] (a prior camera per query) and optionally radius_px (40), max_refs (8), min_overlap
         (8): ptz_relocalizer_run_tracked -- the references that overlap the prior are matched under the predicted homography alone
         (no dense pass; guided_radius is ignored), the solve starts from the prior, and the gate on the assembled query is always on.
-        The result gains shortlist [n, R], n_short [n], overlap [n, n_ref] and prior_ms.  Exclusive with shortlist."""
+        The result gains shortlist [n, R], n_short [n], overlap [n, n_ref] and prior_ms.  Exclusive with shortlist.
+        guided_grid: every guided pass of the run (guided_radius > 0, prior=) goes through the grid-binned kernel: the same outputs."""
         if prior is not None and shortlist is not None:
             raise ValueError("prior= and shortlist= are two ways to pick a query's references: give one")
         wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
@@ -1551,6 +1554,7 @@ class Relocalizer:
         o.guided_radius, o.ransac_thresh, o.min_inliers, o.inlier_matches = float(guided_radius), float(ransac_thresh), int(min_inliers), int(bool(inlier_matches))
         o.trim, o.uncertainty, o.max_refs, o.factor_type = int(trim is not None), int(bool(uncertainty)), K, int(factor_type)
         o.max_reproj_error, o.gate_max_pair_matches = float(max_reproj_error), int(gate_max_pair_matches)
+        o.guided_grid = int(guided_grid)
         nf = krt_free_dim(factor_type)
         cam, acc = np.zeros((n, 15)), np.zeros(n, dtype=np.int32)
         summ, rep = (LmSummary * max(n, 1))(), (KrtTrimReport * max(n, 1))()

@@ -195,6 +195,7 @@ int main(int argc, char** argv)
   parser.Add("save_matches", '\0', "With --match_descriptors: also write the matches to this file, in the format of pairs_matches.txt", false);
   parser.Add("match_guided", '\0', "With --match_descriptors: match every pair again within this many pixels of its RANSAC homography "
                                    "and keep these matches instead; a pair without a verified model keeps none (off unless given)", false);
+  parser.AddFlag("guided_grid", "With --match_guided: run the guided pass through the grid-binned kernel (the same matches, the same output)");
   parser.ParseCheck(argc, argv);
   TrimArgs trim;
   if (parser.Exist("trim_px")) {
@@ -242,6 +243,7 @@ int main(int argc, char** argv)
     if (parser.Exist("match_guided")) {
       mo.guided_radius = atof(parser.Get("match_guided").c_str());
       mo.min_inliers = min_inliers;
+      mo.guided_grid = parser.Exist("guided_grid");
       if (!(mo.guided_radius > 0.0) || !std::isfinite(mo.guided_radius)) {
         fprintf(stderr, "--match_guided must be a positive number of pixels\n");
         return 1;

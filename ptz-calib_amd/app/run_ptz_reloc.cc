@@ -110,6 +110,8 @@ int main(int argc, char** argv)
                              "from that frame's camera (implies --on_device, --inlier_matches)");
   parser.Add("prior_radius", '\0', "With --prior_params / --sequence: the guided matcher's radius in pixels (default 40)", false);
   parser.Add("prior_refs", '\0', "With --prior_params / --sequence: reference images a prior lists at most (default 8)", false);
+  parser.AddFlag("guided_grid", "With --match_guided, --prior_params or --sequence: run the guided matcher through the grid-binned kernel "
+                                "(the same matches, the same output)");
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -201,6 +203,7 @@ int main(int argc, char** argv)
     if (parser.Exist("match_guided")) {
       mo.guided_radius = atof(parser.Get("match_guided").c_str());
       mo.min_inliers = min_inliers;
+      mo.guided_grid = parser.Exist("guided_grid");
       if (!(mo.guided_radius > 0.0) || !std::isfinite(mo.guided_radius)) {
         fprintf(stderr, "--match_guided must be a positive number of pixels\n");
         return 1;
@@ -288,6 +291,7 @@ int main(int argc, char** argv)
         return 1;
       }
     }
+    ro.guided_grid = parser.Exist("guided_grid") ? 1 : 0;
     ro.ransac_thresh = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
     ro.min_inliers = min_inliers;
     ro.inlier_matches = (parser.Exist("inlier_matches") || tracking) ? 1 : 0;

@@ -8,6 +8,9 @@
 //   guided    ptz_desc_match_pairs_guided: the same running top-2 over the candidates within a radius of where the pair's
 //             homography puts the feature (the header's predicate) -- a radius search over positions staged in LDS, one query per
 //             lane, the exact d2 from the packed rows only on a hit; the state, and everything behind it, is the dense pass's.
+//   grid      ptz_desc_match_pairs_guided_grid: the guided contract again (ptz_desc_grid.h), selectable and off by default -- the
+//             searched positions sorted into the cells of a grid in LDS, a query testing only the cells its reach touches, the
+//             d2 of a hit computed by the wave; the same state bit for bit.
 //   join      the acceptance rule per feature of A -> a keep byte; counting, scan and scatter are ptz_gate_compact.h's kernels
 //             (min_matches as `need`); a gather writes indices, distances and the pixels of the resident key points.
 #include <cmath>
@@ -15,6 +18,7 @@
 #include <vector>
 
 #include "ptz_common.h"
+#include "ptz_desc_grid.h"
 #include "ptz_desc_match.h"
 #include "ptz_desc_set.h"
 #include "ptz_desc_sweep.h"
@@ -212,6 +216,215 @@ __global__ __launch_bounds__(DESC_WG) void k_desc_top2_guided(const DescPair* __
   }
 }
 
+// The guided pass over a grid (ptz_desc_grid.h): the contract, the launch grid and the empty states of k_desc_top2_guided, but a
+// query tests only the candidates of the cells its reach touches, and the distance of a hit is computed by the wave.
+//   index   per slab of at most kDescGridSlab searched positions (direction 0: B's key points, direction 1: A's warped points, NaN
+//           where the warp is not ok): every thread keeps its DESC_GRID_PER positions in registers, the workgroup reduces the
+//           bounding box of the finite ones, counts them per cell with LDS integer adds, scans the counts in place and scatters
+//           (x, y, feature) into cell order; after the scatter cur[c] is the END of cell c, so the cells cx0 .. cx1 of a grid row are
+//           the run [cur[row G + cx0 - 1], cur[row G + cx1]).  With one slab (the common case) the index is built once per workgroup.
+//   search  one query per lane.  A lane walks its runs up to its next admissible candidate (the header's predicate) and stops; the
+//           wave ballots the pending hits and takes them DESC_GRID_HITS(L) at a time, L = 16, 32 or 64 lanes per hit: the lanes of a
+//           group read the owner's query row and candidate by lane broadcast, load the words lane, lane + L, ... of the two packed
+//           rows, form desc_dot_i8x4 and sum over the group (integers: any order is exact); the owner applies
+//           desc_top2_take_keyed(qn + sn - 2 dot, j).  The update is order-free, so a lane's state simply runs on through the slabs.
+// Every lane of a wave takes part in every ballot and shuffle (a lane without a query, or out of candidates, has nothing pending),
+// and every wave reaches every barrier: nothing between two barriers depends on a thread's own query.
+constexpr int DESC_GRID_PER = kDescGridSlab / DESC_WG;  // positions of a slab per thread
+constexpr int DESC_GRID_CELLS = kDescGridG * kDescGridG;
+constexpr unsigned DESC_GRID_ROWS_FULL = 4096;  // rows of the launch grid from which one workgroup per row takes all its query tiles
+static_assert(kDescGridSlab % DESC_WG == 0 && DESC_GRID_CELLS % DESC_WG == 0, "a slab and the cells divide among the threads");
+
+template <int L>  // lanes per hit
+__global__ __launch_bounds__(DESC_WG) void k_desc_top2_guided_grid(const DescPair* __restrict__ pairs, int dirs, int DPW,
+                                                                   const uint32_t* __restrict__ desc_a, const int32_t* __restrict__ norm_a,
+                                                                   const uint32_t* __restrict__ desc_b, const int32_t* __restrict__ norm_b,
+                                                                   const float2* __restrict__ kp_a, const float2* __restrict__ kp_b,
+                                                                   const double* __restrict__ Hs, const int32_t* __restrict__ found, float r2f,
+                                                                   double reach, DescTop2* __restrict__ state)
+{
+  constexpr int HITS = WAVE / L;                  // hits of one wave step
+  constexpr int CPT = DESC_GRID_CELLS / DESC_WG;  // cells per thread in the scan
+  __shared__ float2 pos[kDescGridSlab];           // the slab's finite positions in cell order
+  __shared__ int32_t feat[kDescGridSlab];         // their features
+  __shared__ int32_t cur[DESC_GRID_CELLS];        // counts -> starts -> ends
+  __shared__ float box[4][DESC_WG / WAVE];
+  __shared__ int32_t wsum[DESC_WG / WAVE];
+  const int p = blockIdx.x / dirs, dir = blockIdx.x % dirs;
+  const DescPair P = pairs[p];
+  const int nq = dir ? P.n_b : P.n_a, ns = dir ? P.n_a : P.n_b;
+  DescTop2* out = state + P.soff + (dir ? P.n_a : 0);
+  // one value per workgroup, before any barrier
+  if ((found && found[p] != 1) || ns == 0) {
+    for (int64_t q = (int64_t)blockIdx.y * DESC_WG + threadIdx.x; q < nq; q += (int64_t)gridDim.y * DESC_WG) out[q] = desc_top2_empty();
+    return;
+  }
+  double H[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) H[k] = Hs[9 * (int64_t)p + k];
+  const uint32_t* qd = dir ? desc_b + P.row_b * DPW : desc_a + P.row_a * DPW;
+  const int32_t* qn = dir ? norm_b + P.row_b : norm_a + P.row_a;
+  const uint32_t* sdp = dir ? desc_a + P.row_a * DPW : desc_b + P.row_b * DPW;
+  const int32_t* sn = dir ? norm_a + P.row_a : norm_b + P.row_b;
+  const float2* ka = kp_a + P.kp_a;
+  const float2* kb = kp_b + P.kp_b;
+  const float qnan = __int_as_float(0x7fc00000), finf = __int_as_float(0x7f800000);
+  const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, sub = lane / L, wl = lane % L;
+  const bool one_slab = ns <= kDescGridSlab;
+  DescGridFrame F;
+  bool built = false;
+
+  for (int64_t tile = blockIdx.y; tile * DESC_WG < nq; tile += gridDim.y) {
+    const int64_t q = tile * DESC_WG + threadIdx.x;
+    bool ask = q < nq;  // (a lane without a query, or whose warp is not ok, builds the index and answers the ballots with the others)
+    float qx = 0.f, qy = 0.f;
+    if (ask) {
+      if (dir == 0) {
+        const float2 a = ka[q];
+        const DescWarp w = desc_guide_warp(H, a.x, a.y);
+        ask = w.ok; qx = w.x; qy = w.y;
+      }
+      else {
+        const float2 b = kb[q];
+        qx = b.x; qy = b.y;
+      }
+      ask = ask && desc_grid_indexed(qx, qy);
+    }
+    const int32_t my_qn = q < nq ? qn[q] : 0;
+    DescTop2 T = desc_top2_empty();
+    for (int s0 = 0; s0 < ns; s0 += kDescGridSlab) {
+      if (!(one_slab && built)) {
+        const int cnt = min(kDescGridSlab, ns - s0);
+        // the slab's positions, DESC_GRID_PER per thread in registers; the bounding box of the finite ones
+        float px[DESC_GRID_PER], py[DESC_GRID_PER];
+        float x0 = finf, x1 = -finf, y0 = finf, y1 = -finf;
+#pragma unroll
+        for (int u = 0; u < DESC_GRID_PER; ++u) {
+          const int k = u * DESC_WG + threadIdx.x;
+          float2 v = make_float2(qnan, qnan);
+          if (k < cnt) {
+            if (dir == 0) v = kb[s0 + k];
+            else {
+              const float2 a = ka[s0 + k];
+              const DescWarp w = desc_guide_warp(H, a.x, a.y);
+              if (w.ok) v = make_float2(w.x, w.y);
+            }
+          }
+          if (!desc_grid_indexed(v.x, v.y)) v.x = qnan;  // px is NaN <=> the position is not indexed
+          px[u] = v.x; py[u] = v.y;
+          if (v.x == v.x) { x0 = fminf(x0, v.x); x1 = fmaxf(x1, v.x); y0 = fminf(y0, v.y); y1 = fmaxf(y1, v.y); }
+        }
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+          x0 = fminf(x0, __shfl_xor(x0, d)); x1 = fmaxf(x1, __shfl_xor(x1, d));
+          y0 = fminf(y0, __shfl_xor(y0, d)); y1 = fmaxf(y1, __shfl_xor(y1, d));
+        }
+        __syncthreads();  // the slab before this one has been searched
+        if (lane == 0) { box[0][wave] = x0; box[1][wave] = x1; box[2][wave] = y0; box[3][wave] = y1; }
+#pragma unroll
+        for (int u = 0; u < CPT; ++u) cur[u * DESC_WG + threadIdx.x] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < DESC_WG / WAVE; ++w) {
+          x0 = fminf(x0, box[0][w]); x1 = fmaxf(x1, box[1][w]); y0 = fminf(y0, box[2][w]); y1 = fmaxf(y1, box[3][w]);
+        }
+        F = desc_grid_frame(x0, x1, y0, y1, reach);
+        // counts per cell
+        int cell[DESC_GRID_PER];
+#pragma unroll
+        for (int u = 0; u < DESC_GRID_PER; ++u) {
+          cell[u] = -1;
+          if (px[u] == px[u]) {
+            cell[u] = desc_grid_cell(F, 1, (double)py[u]) * kDescGridG + desc_grid_cell(F, 0, (double)px[u]);
+            atomicAdd(&cur[cell[u]], 1);
+          }
+        }
+        __syncthreads();
+        // exclusive scan in place: thread t owns the cells CPT t .. CPT t + CPT - 1
+        int c[CPT], sum = 0;
+#pragma unroll
+        for (int u = 0; u < CPT; ++u) { c[u] = cur[CPT * threadIdx.x + u]; sum += c[u]; }
+        int incl = sum;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+          const int o = __shfl_up(incl, d);
+          if (lane >= d) incl += o;
+        }
+        if (lane == WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        int at = incl - sum;
+        for (int w = 0; w < wave; ++w) at += wsum[w];
+#pragma unroll
+        for (int u = 0; u < CPT; ++u) { cur[CPT * threadIdx.x + u] = at; at += c[u]; }
+        __syncthreads();
+        // scatter: a cell's cursor ends at the cell's end
+#pragma unroll
+        for (int u = 0; u < DESC_GRID_PER; ++u)
+          if (cell[u] >= 0) {
+            const int at = atomicAdd(&cur[cell[u]], 1);
+            pos[at] = make_float2(px[u], py[u]);
+            feat[at] = s0 + u * DESC_WG + threadIdx.x;
+          }
+        __syncthreads();
+        built = true;
+      }
+      // ---- search: lane state = (grid row gy, position k in its run, the run's end e) --------------------------------------------
+      DescGridRange R = {0, 0, 1, 0};  // (cy0 > cy1: no row)
+      if (ask && !F.empty) R = desc_grid_range(F, qx, qy, reach);
+      int gy = R.cy0, k = 0, e = 0;
+      bool fresh = true;  // the run of row gy has not been opened
+      for (;;) {
+        // up to this lane's next hit
+        int32_t hit_j = -1;
+        while (gy <= R.cy1) {
+          if (fresh) {
+            const int c0 = gy * kDescGridG + R.cx0;
+            k = c0 > 0 ? cur[c0 - 1] : 0;
+            e = cur[gy * kDescGridG + R.cx1];
+            fresh = false;
+          }
+          while (k < e) {
+            const float2 v = pos[k];
+            const int at = k++;
+            if (desc_guide_err2(qx, qy, v.x, v.y) <= r2f) { hit_j = feat[at]; break; }
+          }
+          if (hit_j >= 0) break;
+          ++gy;
+          fresh = true;
+        }
+        uint64_t pending = __ballot(hit_j >= 0);
+        if (pending == 0) break;  // one value per wave
+        while (pending) {
+          // the owners of this step's groups
+          int own = -1, mine = -1;  // the owner of this lane's group; the group that works for this lane
+#pragma unroll
+          for (int h = 0; h < HITS; ++h)
+            if (pending) {
+              const int o = __builtin_ctzll(pending);
+              pending &= pending - 1;
+              if (sub == h) own = o;
+              if (lane == o) mine = h;
+            }
+          const int src = own >= 0 ? own : 0;
+          const int64_t oq = __shfl((int)q, src);  // (q < nq <= INT32_MAX for an owner)
+          const int32_t oj = __shfl(hit_j, src);
+          int32_t dot = 0;
+          if (own >= 0) {
+            const uint32_t* x = qd + oq * DPW;
+            const uint32_t* y = sdp + (int64_t)oj * DPW;
+            for (int w = wl; w < DPW; w += L) dot += desc_dot_i8x4(x[w], y[w]);
+          }
+#pragma unroll
+          for (int d = 1; d < L; d <<= 1) dot += __shfl_xor(dot, d);
+          const int32_t got = __shfl(dot, (mine >= 0 ? mine : 0) * L);
+          if (mine >= 0) desc_top2_take_keyed(T, my_qn + sn[hit_j] - 2 * got, hit_j);
+        }
+      }
+    }
+    if (q < nq) out[q] = T;
+  }
+}
+
 // the keep byte of every feature of A
 __global__ __launch_bounds__(256) void k_desc_join(const DescPair* __restrict__ pairs, const DescTop2* __restrict__ state, DescRule rule,
                                                    uint8_t* __restrict__ keep)
@@ -386,7 +599,21 @@ struct DescGuide {
   const int32_t* found;
   bool on_device;
   double radius_px;
+  bool grid;  // k_desc_top2_guided_grid in place of k_desc_top2_guided: the same arrays
 };
+
+// lanes per hit from the words of a packed row: a row of 16 or 32 words leaves room for four or two hits in one wave step
+void launch_guided_grid(int DPW, dim3 grid, hipStream_t st, const DescPair* pairs, int dirs, const uint32_t* da, const int32_t* na,
+                        const uint32_t* db, const int32_t* nb, const float2* ka, const float2* kb, const double* H, const int32_t* found,
+                        float r2f, double reach, DescTop2* state)
+{
+  if (DPW <= 16)
+    hipLaunchKernelGGL(k_desc_top2_guided_grid<16>, grid, dim3(DESC_WG), 0, st, pairs, dirs, DPW, da, na, db, nb, ka, kb, H, found, r2f, reach, state);
+  else if (DPW <= 32)
+    hipLaunchKernelGGL(k_desc_top2_guided_grid<32>, grid, dim3(DESC_WG), 0, st, pairs, dirs, DPW, da, na, db, nb, ka, kb, H, found, r2f, reach, state);
+  else
+    hipLaunchKernelGGL(k_desc_top2_guided_grid<64>, grid, dim3(DESC_WG), 0, st, pairs, dirs, DPW, da, na, db, nb, ka, kb, H, found, r2f, reach, state);
+}
 
 // the chunk loop of both matchers; guide = nullptr: the dense pass
 int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
@@ -404,6 +631,8 @@ int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_se
     if (!(std::isfinite(guide->radius_px) && guide->radius_px > 0)) return PTZ_EINVAL;
   }
   const float r2f = guide ? (float)(guide->radius_px * guide->radius_px) : 0.f;
+  // (an r2f that is not finite admits every pair whose error is not NaN, infinite positions included: no grid serves that)
+  const bool grid = guide && guide->grid && std::isfinite(r2f);
   clear_stale_error(who);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= A->device) return PTZ_ENODEVICE;
@@ -498,7 +727,15 @@ int32_t desc_match_run(const char* who, const ptz_desc_set* A, const ptz_desc_se
     aptr[npc] = c.n_a;
     PTZ_HIP_TRY(hipMemcpyAsync(d_aptr, aptr.data(), sizeof(int64_t) * (npc + 1), hipMemcpyHostToDevice, h.st));
     PTZ_HIP_TRY(hipEventRecord(h.ev[0], h.st));
-    if (guide)
+    if (grid) {
+      // the index of a (pair, direction) is built by every workgroup of its column: few of them once the rows fill the device
+      const unsigned rows = (unsigned)npc * dirs, gy = std::min(tiles_y(c.most_q, DESC_WG), std::max(1u, DESC_GRID_ROWS_FULL / rows));
+      launch_guided_grid(16 * A->KS, dim3(rows, gy), h.st, (const DescPair*)(d_tab + c.p0), dirs, (const uint32_t*)A->d_desc,
+                         (const int32_t*)A->d_norm, (const uint32_t*)B->d_desc, (const int32_t*)B->d_norm, (const float2*)A->d_kp,
+                         (const float2*)B->d_kp, g_H + 9 * (size_t)c.p0, g_found ? g_found + c.p0 : nullptr, r2f,
+                         desc_grid_reach(guide->radius_px), d_state);
+    }
+    else if (guide)
       hipLaunchKernelGGL(k_desc_top2_guided, dim3((unsigned)npc * dirs, tiles_y(c.most_q, DESC_WG)), dim3(DESC_WG), 0, h.st,
                          (const DescPair*)(d_tab + c.p0), dirs, 16 * A->KS, (const uint32_t*)A->d_desc, (const int32_t*)A->d_norm,
                          (const uint32_t*)B->d_desc, (const int32_t*)B->d_norm, (const float2*)A->d_kp, (const float2*)B->d_kp,
@@ -582,7 +819,15 @@ extern "C" int32_t ptz_desc_match_pairs_guided(const ptz_desc_set* A, const ptz_
                                                const int32_t* img_b, const double* H, const int32_t* found, double radius_px,
                                                const ptz_desc_options* opt, ptz_desc_matches** out)
 {
-  const ptz::DescGuide g = {H, found, false, radius_px};
+  const ptz::DescGuide g = {H, found, false, radius_px, false};
+  return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
+}
+
+extern "C" int32_t ptz_desc_match_pairs_guided_grid(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair, const int32_t* img_a,
+                                                    const int32_t* img_b, const double* H, const int32_t* found, double radius_px,
+                                                    const ptz_desc_options* opt, ptz_desc_matches** out)
+{
+  const ptz::DescGuide g = {H, found, false, radius_px, true};
   return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
 }
 
@@ -590,7 +835,16 @@ extern "C" int32_t ptz_desc_match_pairs_guided_device(const ptz_desc_set* A, con
                                                       const int32_t* img_b, const double* d_H, const int32_t* d_found, double radius_px,
                                                       const ptz_desc_options* opt, ptz_desc_matches** out)
 {
-  const ptz::DescGuide g = {d_H, d_found, true, radius_px};
+  const ptz::DescGuide g = {d_H, d_found, true, radius_px, false};
+  return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
+}
+
+extern "C" int32_t ptz_desc_match_pairs_guided_grid_device(const ptz_desc_set* A, const ptz_desc_set* B, int32_t n_pair,
+                                                           const int32_t* img_a, const int32_t* img_b, const double* d_H,
+                                                           const int32_t* d_found, double radius_px, const ptz_desc_options* opt,
+                                                           ptz_desc_matches** out)
+{
+  const ptz::DescGuide g = {d_H, d_found, true, radius_px, true};
   return ptz::desc_match_run(__func__, A, B, n_pair, img_a, img_b, &g, opt, out);
 }
 

@@ -172,7 +172,8 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   ptz_reloc_options o;
   if (options) o = *options; else ptz_reloc_options_default(&o);
   if (o.max_refs < 1 || o.min_inliers < 0 || !(o.guided_radius >= 0.0) || !std::isfinite(o.guided_radius) ||
-      !(std::isfinite(o.ransac_thresh) && o.ransac_thresh > 0) || o.gate_max_pair_matches < 0 || o.gate_max_pair_matches > 4096)
+      !(std::isfinite(o.ransac_thresh) && o.ransac_thresh > 0) || o.gate_max_pair_matches < 0 || o.gate_max_pair_matches > 4096 ||
+      (o.guided_grid != 0 && o.guided_grid != 1))
     return PTZ_EINVAL;
   for (int q = 0; q < n_query; ++q)
     if (query_wh[2 * q] <= 0 || query_wh[2 * q + 1] <= 0) return PTZ_EINVAL;
@@ -300,11 +301,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   ptz_desc_matches_destroy(r->table);
   r->table = nullptr;
   ptz_desc_matches* m = nullptr;
+  const auto guided = o.guided_grid ? ptz_desc_match_pairs_guided_grid_device : ptz_desc_match_pairs_guided_device;  // the same arrays
   struct Held { ptz_desc_matches*& m; ~Held() { ptz_desc_matches_destroy(m); } } held{m};
   if (pr) {
-    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), d_prior_H, nullptr, pr->opt.radius_px,
-                                                              &o.match, &m))
-      return rc;
+    if (const int32_t rc = guided(r->refs, query_set, npair, ia.data(), ib.data(), d_prior_H, nullptr, pr->opt.radius_px, &o.match, &m)) return rc;
     res->stage_ms[1] = ptz_desc_matches_device_ms(m);
   }
   else {
@@ -338,8 +338,8 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     PTZ_HIP_TRY(hipEventRecord(t.ev[1], st));
     PTZ_HIP_TRY(stream_wait(st));  // the guided call runs on a stream of its own
     ptz_desc_matches* g = nullptr;
-    if (const int32_t rc = ptz_desc_match_pairs_guided_device(r->refs, query_set, npair, ia.data(), ib.data(), (const double*)(p + o_H),
-                                                              (const int32_t*)(p + o_f), o.guided_radius, &o.match, &g))
+    if (const int32_t rc = guided(r->refs, query_set, npair, ia.data(), ib.data(), (const double*)(p + o_H), (const int32_t*)(p + o_f),
+                                  o.guided_radius, &o.match, &g))
       return rc;
     ptz_desc_matches_destroy(m);
     m = g;

@@ -271,7 +271,8 @@ bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& 
         for (int64_t k = mptr[p]; k < mptr[p + 1]; ++k) ones += found[p] == 1 && mask[static_cast<size_t>(k)] != 0;
         found[p] = found[p] == 1 && ones >= need ? 1 : 0;
       }
-      rc = ptz_desc_match_pairs_guided(set_a, set_b, n_pair, ia.data(), ib.data(), H.data(), found.data(), options.guided_radius, &o, &res);
+      rc = (options.guided_grid ? ptz_desc_match_pairs_guided_grid : ptz_desc_match_pairs_guided)(
+          set_a, set_b, n_pair, ia.data(), ib.data(), H.data(), found.data(), options.guided_radius, &o, &res);
     }
   }
   std::vector<int32_t> qa, tb;

@@ -45,6 +45,7 @@ struct DescMatchOptions {
   double guided_radius = 0.0;  // pixels; 0: off
   double ransac_thresh = 4.0;
   int min_inliers = 6;         // kDefaultMinInliers
+  bool guided_grid = false;    // the guided pass through ptz_desc_match_pairs_guided_grid: the same matches
 };
 bool MatchDescriptors(const std::string& dir_a, const std::vector<std::string>& fnames_a, const std::string& dir_b,
                       const std::vector<std::string>& fnames_b, const std::vector<std::pair<long, long>>& pairs, const DescMatchOptions& options,
