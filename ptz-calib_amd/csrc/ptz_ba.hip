@@ -192,8 +192,6 @@ struct ptz_ba_batch {
 };
 
 namespace {
-
-// dynamic LDS of k_schur: T table, scratch, staged entries, pair offsets, reduction strip
 // Elimination order of a reduced camera system at tile granularity.
 //
 // bisect_tiles: the tiles `ids` (natural numbers, ascending) with adjacency adj(a, e); looks for a separator made of a prefix
@@ -299,6 +297,29 @@ inline int level_schedule(int nt, const unsigned char* m, int* sched)
   std::vector<int> fill(steps, 0);
   for (int t = 0; t < nt; ++t) sched[level[t] * CHOL_STEP_COLS + fill[level[t]]++] = t;
   return steps;
+}
+
+// The tile mask `mask` in the elimination order `perm` (nullptr: the natural order), closed under the fill of the right-looking
+// factorisation, into the zeroed `m`; and the steps: from the filled structure when an order was planned, one block column after
+// the other otherwise.  Returns the number of steps.
+inline int fill_and_schedule(int nt, const unsigned char* mask, const int* perm, unsigned char* m, int* sched)
+{
+  for (int a = 0; a < nt; ++a)
+    for (int e = 0; e <= a; ++e) {
+      if (!mask[a * nt + e]) continue;
+      const int pa = perm ? perm[a] : a, pe = perm ? perm[e] : e;
+      m[std::max(pa, pe) * nt + std::min(pa, pe)] = 1;
+    }
+  for (int k = 0; k < nt; ++k)
+    for (int x = k + 1; x < nt; ++x) {
+      if (!m[x * nt + k]) continue;
+      for (int y = k + 1; y <= x; ++y)
+        if (m[y * nt + k]) m[x * nt + y] = 1;
+    }
+  if (perm) return level_schedule(nt, m, sched);
+  for (int i = 0; i < nt * CHOL_STEP_COLS; ++i) sched[i] = -1;
+  for (int t = 0; t < nt; ++t) sched[CHOL_STEP_COLS * t] = t;
+  return nt;
 }
 
 // threads of a k_schur workgroup = the most runs a camera's entries are cut into (ptz_ba_kernels.h schur_threads<TYPE>())
@@ -426,17 +447,63 @@ struct StagedUpload {
     }                                                                                                               \
   } while (0)
 
-// k_pairs' dynamic LDS beyond 64 KiB (very wide rigs): the attribute is set ONCE per device (hipFuncSetAttribute under a lock on every
-// batch creation was a measurable share of a view batch's 0.4 ms of enqueueing in the 64-rig lock step)
-static void pairs_lds_cap(int device)
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// run-time switches: read where they are used, on every create (tests change them between two creates of one process)
+inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
+inline int env_int(const char* name, int dflt, int lo) { const char* e = getenv(name); return e ? std::max(lo, atoi(e)) : dflt; }
+
+// fn(first, step) on nt threads, the caller's among them
+template <typename F> void run_strided(int nt, F&& fn)
+{
+  if (nt <= 1) { fn(0, 1); return; }
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; ++t) th.emplace_back(fn, t, nt);
+  fn(0, nt);
+  for (auto& x : th) x.join();
+}
+
+// FNV-1a, the hash of the structure diagnostics
+constexpr uint64_t FNV_BASIS = 1469598103934665603ull;
+inline void fnv_mix(uint64_t& h, const void* ptr, size_t bytes) { for (size_t i = 0; i < bytes; ++i) { h ^= ((const unsigned char*)ptr)[i]; h *= 1099511628211ull; } }
+
+// A batch under construction (and the one-shot solves' batch): every way out destroys it, a half-built one included --
+// ptz_ba_batch_destroy and the pool's releases take null members
+struct BatchDeleter { void operator()(ptz_ba_batch* b) const { ptz_ba_batch_destroy(b); } };
+using BatchOwner = std::unique_ptr<ptz_ba_batch, BatchDeleter>;
+// (the creation path's early return; no clean-up hides in it, the owner does that)
+#define PTZ_TRY(x) do { if (const int32_t rc_ = (x)) return rc_; } while (0)
+
+// rays per workgroup of the ray-centric kernels: one rig's ~13 k rays on 1024-ray workgroups keep 14 compute units busy,
+// so a few scenes use small workgroups; large batches amortise the LDS camera tables over many rays (results do not
+// depend on it: per-ray sums are reduced per wave of 64 rays)
+inline int ray_block_for(int slots)
+{
+  if (const char* e = getenv("PTZ_BA_RAY_BLOCK")) return std::min(RAY_BLOCK, std::max(64, (atoi(e) / 64) * 64));
+  return slots <= 4 ? 128 : (slots <= 32 ? 256 : RAY_BLOCK);
+}
+
+// The cap on dynamic LDS is a property of the kernel, not of a batch: each set of kernels has its caps raised ONCE per device, so
+// that batches of different sizes can live side by side (a per-batch value would let a small batch created later lower the cap
+// under a large one), and because hipFuncSetAttribute under a lock on every batch creation was a measurable share of a view
+// batch's 0.4 ms of enqueueing in the 64-rig lock step.  A set whose `raise` returns false stays undone: the next create tries again.
+enum CapSet { CAPS_PAIRS, CAPS_VIEW_SORT, CAPS_PASS, CAP_SETS };
+static bool once_per_device(CapSet set, int device, bool (*raise)())
 {
   static std::mutex mu;
-  static bool done[64] = {};
+  static std::vector<char> done[CAP_SETS];
   std::lock_guard<std::mutex> lk(mu);
-  if (done[device & 63]) return;
+  if ((int)done[set].size() <= device) done[set].resize(device + 1, 0);
+  if (!done[set][device] && raise()) done[set][device] = 1;
+  return done[set][device] != 0;
+}
+
+// k_pairs' dynamic LDS beyond 64 KiB (very wide rigs)
+static bool raise_pairs_caps()
+{
   (void)hipFuncSetAttribute((const void*)k_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
   (void)hipFuncSetAttribute((const void*)k_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-  done[device & 63] = true;
+  return true;
 }
 
 template <int TYPE> void enqueue_linearize(ptz_ba_batch* b)
@@ -998,23 +1065,9 @@ int32_t ptz_ba_plan_tile_order(int32_t nt, int32_t first_dense, const uint8_t* m
   const bool planned = plan_dissection(nt, first_dense, mask, perm, &la, &lb);
   if (!planned) { for (int t = 0; t < nt; ++t) perm[t] = t; la = lb = 0; }
   lanes[0] = la; lanes[1] = lb;
-  if (sched && n_steps) {  // as ptz_ba_batch_create does: permuted mask, fill, levels
+  if (sched && n_steps) {  // the function batches run: permuted mask, fill, levels
     std::vector<unsigned char> m((size_t)nt * nt, 0);
-    for (int a = 0; a < nt; ++a)
-      for (int e = 0; e <= a; ++e)
-        if (mask[a * nt + e]) m[std::max(perm[a], perm[e]) * nt + std::min(perm[a], perm[e])] = 1;
-    for (int k = 0; k < nt; ++k)
-      for (int x = k + 1; x < nt; ++x) {
-        if (!m[x * nt + k]) continue;
-        for (int y = k + 1; y <= x; ++y)
-          if (m[y * nt + k]) m[x * nt + y] = 1;
-      }
-    if (planned) n_steps[0] = level_schedule(nt, m.data(), sched);
-    else {
-      for (int i = 0; i < nt * CHOL_STEP_COLS; ++i) sched[i] = -1;
-      for (int t = 0; t < nt; ++t) sched[CHOL_STEP_COLS * t] = t;
-      n_steps[0] = nt;
-    }
+    n_steps[0] = fill_and_schedule(nt, mask, planned ? perm : nullptr, m.data(), sched);
   }
   return planned ? 1 : 0;
 }
@@ -1079,7 +1132,27 @@ struct ObsDest {
   int* rayptr; double* w;                                      // + ray_off (+ scene index for the pointer array)
   int* camptr; int* campair; int* camrun;                      // + cam_off + scene index
   int* wpos;                                                   // + obs_off
-};  // (member order = the order of the initialiser in ptz_ba_batch_create)
+};  // (member order = the order of the initialiser in build_scene_wave)
+
+// The batch-wide host arrays of the observation side and where every scene's part of them begins
+struct HostObs {
+  std::vector<size_t> obs_base, ray_base, cam_base;  // [n + 1]
+  RawVec<float2> uv, camuv;
+  RawVec<int> cam, ray, camobs, camray, wpos;
+  std::vector<int> rayptr, camptr, campair, camrun;
+  std::vector<double> w;
+  void set_bases(int n, const ptz_ba_problem* p)
+  {
+    obs_base.assign(n + 1, 0); ray_base.assign(n + 1, 0); cam_base.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) { obs_base[i + 1] = obs_base[i] + (size_t)p[i].n_obs; ray_base[i + 1] = ray_base[i] + p[i].n_ray; cam_base[i + 1] = cam_base[i] + p[i].n_cam; }
+  }
+  void resize_all(int n)  // (uninitialised where RawVec: every element is written by the builder threads)
+  {
+    const size_t to = obs_base[n], tr = ray_base[n], tc = cam_base[n];
+    uv.resize(to); camuv.resize(to); cam.resize(to); ray.resize(to); camobs.resize(to); camray.resize(to); wpos.resize(to);
+    rayptr.resize(tr + n); w.resize(tr); camptr.resize(tc + n); campair.resize(tc + n); camrun.resize(tc + n);
+  }
+};
 
 // Scratch vectors of build_pairs, handed from call to call (a batch builds its scenes on short-lived worker threads, several
 // batches at a time in the lock-step PTZ-IBA): a vector that keeps its capacity costs no allocation and, above all, no page
@@ -1304,6 +1377,24 @@ void build_pairs(const ptz_ba_problem& p_in, int obase, int ray_off, const ObsDe
   out.n_pair = npair;
   out.n_ent = n_ent;
 }
+
+// Scenes [first, first + count) on up to n_threads host threads: the observation-side arrays and the ray order are written in
+// place, the pair lists of scene first + k go to wave[k]
+void build_scene_wave(const ptz_ba_problem* problems, int first, int count, int n_threads, HostObs& h, int* ray_perm, std::vector<PairBuild>& wave,
+                      bool pairs_on_device)
+{
+  wave.assign(count, PairBuild());
+  run_strided(std::min(n_threads, count), [&](int t0, int step) {
+    for (int k = t0; k < count; k += step) {
+      const int s = first + k;
+      const size_t ob = h.obs_base[s], rb = h.ray_base[s], cb = h.cam_base[s];
+      const ObsDest od = {h.uv.data() + ob, h.cam.data() + ob, h.ray.data() + ob, h.camobs.data() + ob, h.camray.data() + ob, h.camuv.data() + ob,
+                          h.rayptr.data() + rb + s, h.w.data() + rb, h.camptr.data() + cb + s, h.campair.data() + cb + s,
+                          h.camrun.data() + cb + s, h.wpos.data() + ob};
+      build_pairs(problems[s], (int)ob, (int)rb, od, wave[k], ray_perm + rb, schur_threads_of(problems[s].factor_type), pairs_on_device);
+    }
+  });
+}
 }  // namespace
 
 static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_rig_view* views, int32_t view_type, const ptz_lm_options* opt,
@@ -1326,43 +1417,56 @@ int32_t ptz_ba_batch_create_views(int32_t n, const ptz_rig_view* views, int32_t 
   return create_impl(n, nullptr, views, factor_type, opt, out);
 }
 
-// views == nullptr: the n packed problems.  Else: the packed problems of n views of resident rigs, built on the device
-// (ptz_view_kernels.h) -- the structure arrays then have the extents of the WHOLE rigs (nothing is read back to size them),
-// each scene's real counts live in its SceneDev.
-static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_rig_view* views, int32_t view_type, const ptz_lm_options* opt,
-                           ptz_ba_batch** out)
-{
-  *out = nullptr;
-  const bool vm = views != nullptr;
+// ---- the stages of create_impl, in the order it runs them --------------------------------------------------------------------
+namespace {
+// What the stages hand to one another; lives as long as create_impl runs
+struct CreateCtx {
+  int n = 0;
+  const ptz_ba_problem* problems = nullptr;  // the packed problems, or the stand-ins of the views (vprob)
+  const ptz_rig_view* views = nullptr;       // nullptr: packed problems
   std::vector<ptz_ba_problem> vprob;
-  if (vm) {  // stand-ins that carry the sizes the layout is made for
-    vprob.resize(n);
-    for (int i = 0; i < n; ++i) {
-      memset(&vprob[i], 0, sizeof(ptz_ba_problem));
-      vprob[i].n_cam = views[i].n_cam; vprob[i].n_ray = views[i].rig->n_track; vprob[i].n_obs = views[i].rig->n_view;
-      vprob[i].factor_type = view_type;
-    }
-    problems = vprob.data();
-  }
-  const bool dbg_t = getenv("PTZ_BA_DEBUG_TIMING") != nullptr;
-  auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tc0 = now_ms();
-  double tc1 = 0, tc2 = 0, tc3 = 0, ts_obs = 0, ts_ent = 0;
   ptz_lm_options o;
-  if (opt) o = *opt; else ptz_lm_options_default(&o);
-  if (o.max_num_iterations <= 0) return PTZ_EINVAL;  // CheckValid, ptzray_optimizer.cc:521
-  const int type = problems[0].factor_type;
-  if (type != PTZ_BA_PTZRay && type != PTZ_BA_PTZRayDist && type != PTZ_BA_PTZRayFxfyDist && type != PTZ_BA_PTZRayDistDisp) return PTZ_EUNSUPPORTED;
-  const bool disp = type == PTZ_BA_PTZRayDistDisp;
-  int has3d = 0;
-  std::vector<int> cam_hist;
-  int pre_max_cam_obs = 0, pre_max_cam = 0;  // (decides whether the pair lists are built on the device, before anything is built)
-  // ---- validate + sizes (host only; no device touched before this passes)
-  for (int i = 0; vm && i < n; ++i) {
-    for (int c = 0; c < views[i].n_cam; ++c) pre_max_cam_obs = std::max(pre_max_cam_obs, views[i].rig->img_obs[views[i].cam_image[c]]);
-    pre_max_cam = std::max(pre_max_cam, views[i].n_cam);
+  // sizes decided up front
+  int type = 0, NC = 0, CBS = 0, CDS = 0, has3d = 0, pre_max_cam = 0, pre_max_cam_obs = 0, n_threads = 1;  // n_threads: of the scene waves
+  size_t pairs_lds = 0;
+  bool disp = false, gpu_pairs = false, pairs_check = false;  // pair lists by k_pairs; and by the host as well, compared word for word
+  // the host structure
+  HostObs h;
+  std::vector<int> h_pci, h_pcj, h_pptr, h_pbrow, h_prun, h_o3cam, h_grpptr, h_grpmem;
+  RawVec<unsigned> h_ent;
+  std::vector<uint2> h_runs; std::vector<double> h_o3xyz; std::vector<float2> h_o3uv;
+  std::vector<unsigned char> h_grpcls, h_camflag, h_adj;  // h_adj, views: tile adjacency of every scene's reduced system, marked on the device
+  bool any_shared = false, dbg_t = false;
+  double ts_ent = 0;
+};
+
+// validate + sizes (host only; no device touched before this passes)
+int32_t create_validate(int32_t n, const ptz_ba_problem* problems, const ptz_rig_view* views, int32_t view_type, const ptz_lm_options* opt, CreateCtx& c)
+{
+  c.n = n; c.views = views;
+  if (views) {  // stand-ins that carry the sizes the layout is made for
+    c.vprob.resize(n);
+    for (int i = 0; i < n; ++i) {
+      memset(&c.vprob[i], 0, sizeof(ptz_ba_problem));
+      c.vprob[i].n_cam = views[i].n_cam; c.vprob[i].n_ray = views[i].rig->n_track; c.vprob[i].n_obs = views[i].rig->n_view;
+      c.vprob[i].factor_type = view_type;
+    }
+    problems = c.vprob.data();
   }
-  for (int i = 0; !vm && i < n; ++i) {
+  c.problems = problems;
+  c.dbg_t = getenv("PTZ_BA_DEBUG_TIMING") != nullptr;
+  if (opt) c.o = *opt; else ptz_lm_options_default(&c.o);
+  if (c.o.max_num_iterations <= 0) return PTZ_EINVAL;  // CheckValid, ptzray_optimizer.cc:521
+  const int type = c.type = problems[0].factor_type;
+  if (type != PTZ_BA_PTZRay && type != PTZ_BA_PTZRayDist && type != PTZ_BA_PTZRayFxfyDist && type != PTZ_BA_PTZRayDistDisp) return PTZ_EUNSUPPORTED;
+  c.disp = type == PTZ_BA_PTZRayDistDisp;
+  std::vector<int> cam_hist;
+  // (pre_max_cam, pre_max_cam_obs decide whether the pair lists are built on the device, before anything is built)
+  for (int i = 0; views && i < n; ++i) {
+    for (int k = 0; k < views[i].n_cam; ++k) c.pre_max_cam_obs = std::max(c.pre_max_cam_obs, views[i].rig->img_obs[views[i].cam_image[k]]);
+    c.pre_max_cam = std::max(c.pre_max_cam, views[i].n_cam);
+  }
+  for (int i = 0; !views && i < n; ++i) {
     const ptz_ba_problem& p = problems[i];
     if (p.factor_type != type) return PTZ_EINVAL;
     if (p.n_cam <= 0 || p.n_ray <= 0 || p.n_obs <= 0) return PTZ_EINVAL;  // num_cams_ == 0 -> false (:517)
@@ -1370,836 +1474,727 @@ static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_
     if (p.n_obs3d < 0 || (p.n_obs3d > 0 && (!p.obs3d_uv || !p.obs3d_xyz || !p.obs3d_cam))) return PTZ_EINVAL;
     for (int a = 0; a < p.n_obs3d; ++a)
       if (p.obs3d_cam[a] < 0 || p.obs3d_cam[a] >= p.n_cam) return PTZ_EINVAL;
-    if (p.n_obs3d > 0) has3d = 1;
+    if (p.n_obs3d > 0) c.has3d = 1;
     cam_hist.assign(p.n_cam, 0);
     for (int64_t a = 0; a < p.n_obs; ++a) {
       if (p.obs_cam[a] < 0 || p.obs_cam[a] >= p.n_cam || p.obs_ray[a] < 0 || p.obs_ray[a] >= p.n_ray) return PTZ_EINVAL;
       if (a > 0 && p.obs_ray[a] < p.obs_ray[a - 1]) return PTZ_EINVAL;
       ++cam_hist[p.obs_cam[a]];
     }
-    for (int c = 0; c < p.n_cam; ++c) pre_max_cam_obs = std::max(pre_max_cam_obs, cam_hist[c]);
-    pre_max_cam = std::max(pre_max_cam, p.n_cam);
+    for (int k = 0; k < p.n_cam; ++k) c.pre_max_cam_obs = std::max(c.pre_max_cam_obs, cam_hist[k]);
+    c.pre_max_cam = std::max(c.pre_max_cam, p.n_cam);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= o.device_id) return PTZ_ENODEVICE;
-  PTZ_DEVICE_GUARD(o.device_id);
-
   // fy becomes a live column with annotation residuals; PTZRayFxfyDist has it anyway
-  const int NC = type == PTZ_BA_PTZRayFxfyDist ? 6 : ((type == PTZ_BA_PTZRay) ? 4 : (disp ? 8 : 5)) + has3d;
-  const int CBS = disp ? CAMBLK_DISP + 1 : CAMBLK + 1, CDS = disp ? CAMBLK_DISP + 1 : CANDBLK + 1;  // Dims<TYPE>::CBS / CDS
-  ptz_ba_batch* b = new ptz_ba_batch();
-  b->has3d = has3d;
-  b->n_scene = n; b->type = type; b->nc = NC; b->opt = o; b->device = o.device_id;
-  if (ptzpool::stream_acquire(b->device, &b->io) != hipSuccess) { delete b; return PTZ_ENODEVICE; }
-  // rays per workgroup of the ray-centric kernels: one rig's ~13 k rays on 1024-ray workgroups keep 14 compute units busy,
-  // so a few scenes use small workgroups; large batches amortise the LDS camera tables over many rays (results do not
-  // depend on it: per-ray sums are reduced per wave of 64 rays)
-  b->ray_block = n <= 4 ? 128 : (n <= 32 ? 256 : RAY_BLOCK);
-  if (const char* e = getenv("PTZ_BA_RAY_BLOCK")) b->ray_block = std::min(RAY_BLOCK, std::max(64, (atoi(e) / 64) * 64));
-  RawVec<float2> h_uv, h_camuv;
-  RawVec<int> h_cam, h_ray, h_camobs, h_camray, h_wpos;
-  std::vector<int> h_rayptr, h_camptr, h_pci, h_pcj, h_pptr;
-  RawVec<unsigned> h_ent;
-  std::vector<int> h_pbrow;
-  std::vector<int> h_campair, h_camrun, h_prun;
-  std::vector<uint2> h_runs;
-  std::vector<double> h_w, h_o3xyz;
-  std::vector<float2> h_o3uv;
-  std::vector<int> h_o3cam;
-  std::vector<int> h_grpptr, h_grpmem;
-  std::vector<unsigned char> h_grpcls;
-  if (!vm) {
-    size_t to = 0, tr = 0, tc = 0;
-    for (int i = 0; i < n; ++i) { to += (size_t)problems[i].n_obs; tr += (size_t)problems[i].n_ray; tc += (size_t)problems[i].n_cam; }
-    h_uv.reserve(to); h_cam.reserve(to); h_ray.reserve(to); h_camobs.reserve(to); h_wpos.reserve(to); h_camray.reserve(to);
-    h_rayptr.reserve(tr + n); h_w.reserve(tr); h_camptr.reserve(tc + n); h_campair.reserve(tc + n);
-    h_ent.reserve(to * 4);
-  }
-  std::vector<unsigned char> h_camflag;
-  int total_grp = 0;
-  bool any_shared = false;
-  int64_t tot_obs = 0, tot_ent = 0;
-  for (int i = 0; i < n; ++i) {
-    tot_obs += problems[i].n_obs;
-  }
-  if (tot_obs > 0x7fffffff) { delete b; return PTZ_EINVAL; }
-  if (!vm) { h_uv.reserve(tot_obs); h_cam.reserve(tot_obs); h_ray.reserve(tot_obs); h_camobs.reserve(tot_obs); }
-  // the pair lists of the scenes are built a wave at a time on up to 8 host threads (PTZ_BA_HOST_THREADS)
-  std::vector<int> obs_base(n, 0), ray_base(n, 0), cam_base(n, 0);
-  for (int i = 1; i < n; ++i) {
-    obs_base[i] = obs_base[i - 1] + (int)problems[i - 1].n_obs;
-    ray_base[i] = ray_base[i - 1] + problems[i - 1].n_ray;
-    cam_base[i] = cam_base[i - 1] + problems[i - 1].n_cam;
-  }
-  if (!vm) {
-    const size_t tr = (size_t)ray_base[n - 1] + problems[n - 1].n_ray, tc = (size_t)cam_base[n - 1] + problems[n - 1].n_cam;
-    h_uv.resize(tot_obs); h_camuv.resize(tot_obs); h_cam.resize(tot_obs); h_ray.resize(tot_obs); h_camobs.resize(tot_obs); h_camray.resize(tot_obs);
-    h_rayptr.resize(tr + n); h_w.resize(tr); h_camptr.resize(tc + n); h_campair.resize(tc + n); h_camrun.resize(tc + n); h_wpos.resize(tot_obs);
-    b->ray_perm.resize((size_t)ray_base[n - 1] + problems[n - 1].n_ray);
-  }
-  else h_camptr.assign((size_t)cam_base[n - 1] + problems[n - 1].n_cam + n, 0);  // (read by the per-camera flags below: no camera has residuals as far as they are concerned)
-  b->views_mode = vm;
-  int n_threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (const char* e = getenv("PTZ_BA_HOST_THREADS")) n_threads = std::max(1, atoi(e));
-  const int wave_scenes = 4 * n_threads;
-  // Pair lists on the device (k_pairs) unless the round-2 kernels are asked for, the per-camera bitmaps do not fit in LDS, or
-  // PTZ_BA_GPU_STRUCT=0 (the host builder: 2.1 of its 3.6 ms per 170-view problem are these lists)
-  bool gpu_pairs = !getenv("PTZ_BA_SCHUR_W") || atoi(getenv("PTZ_BA_SCHUR_W")) == 0;
-  const size_t pairs_lds = sizeof(unsigned) * ((size_t)pre_max_cam * ((pre_max_cam_obs + 31) / 32) + 5 * (size_t)pre_max_cam + 8);
-  if (pairs_lds > 150 * 1024 || pre_max_cam_obs > 65535) gpu_pairs = false;
-  if (const char* e = getenv("PTZ_BA_GPU_STRUCT")) gpu_pairs = gpu_pairs && atoi(e) != 0;
-  if (vm && (pairs_lds > 150 * 1024 || pre_max_cam_obs > 65535)) { delete b; return PTZ_ELIMIT; }  // (a view is built on the device or not at all)
-  if (vm) gpu_pairs = true;
+  c.NC = type == PTZ_BA_PTZRayFxfyDist ? 6 : ((type == PTZ_BA_PTZRay) ? 4 : (c.disp ? 8 : 5)) + c.has3d;
+  c.CBS = c.disp ? CAMBLK_DISP + 1 : CAMBLK + 1; c.CDS = c.disp ? CAMBLK_DISP + 1 : CANDBLK + 1;  // Dims<TYPE>::CBS / CDS
+  return PTZ_OK;
+}
+
+// Pair lists on the device (k_pairs) unless the round-2 kernels are asked for, the per-camera bitmaps do not fit in LDS, or
+// PTZ_BA_GPU_STRUCT=0 (the host builder: 2.1 of its 3.6 ms per 170-view problem are these lists)
+int32_t choose_pair_builder(CreateCtx& c)
+{
+  c.pairs_lds = sizeof(unsigned) * ((size_t)c.pre_max_cam * ((c.pre_max_cam_obs + 31) / 32) + 5 * (size_t)c.pre_max_cam + 8);
+  const bool too_wide = c.pairs_lds > 150 * 1024 || c.pre_max_cam_obs > 65535;
+  if (c.views && too_wide) return PTZ_ELIMIT;  // (a view is built on the device or not at all)
+  c.gpu_pairs = c.views || (!env_flag("PTZ_BA_SCHUR_W", false) && !too_wide && env_flag("PTZ_BA_GPU_STRUCT", true));
   // PTZ_BA_GPU_STRUCT_CHECK=1 (tests): the host builds its lists as well and the device's must equal them word for word
-  const bool pairs_check = gpu_pairs && getenv("PTZ_BA_GPU_STRUCT_CHECK") != nullptr;
+  c.pairs_check = c.gpu_pairs && getenv("PTZ_BA_GPU_STRUCT_CHECK") != nullptr;
+  return PTZ_OK;
+}
+
+// A view's scene: extents of the WHOLE rig (the real counts are the device's to find, and nothing is read back to size an array):
+// pairs of the candidates, the rig's entries, at most max(runs per workgroup, pairs of a camera) runs per camera
+int32_t bound_view_scene(ptz_ba_batch* b, const CreateCtx& c, int i, SceneDev& s)
+{
+  const ptz_rig_view& v = c.views[i];
+  const int64_t pair_bound = (int64_t)v.n_cam * (v.n_cam - 1) / 2;
+  const int64_t run_bound = (int64_t)v.n_cam * std::max(schur_threads_of(c.type), v.n_cam);
+  if ((int64_t)b->total_ent + v.rig->ent_bound > 0x7fffffff || (int64_t)b->total_pair + pair_bound > 0x7fffffff ||
+      (int64_t)b->total_run + run_bound > 0x7fffffff) return PTZ_ELIMIT;
+  s.run_off = b->total_run; s.n_pair = 0;
+  b->total_run += (int)run_bound; b->total_pair += (int)pair_bound; b->total_ent += (int)v.rig->ent_bound;
+  for (int k = 0; k < v.n_cam; ++k) {
+    b->max_cam_obs = std::max(b->max_cam_obs, v.rig->img_obs[v.cam_image[k]]);
+    b->max_cam_ent = std::max(b->max_cam_ent, v.rig->img_ent[v.cam_image[k]]);
+  }
+  b->max_cam_pair = std::max(b->max_cam_pair, v.n_cam - 1);
+  b->max_cam_run = std::max(b->max_cam_run, std::max(schur_threads_of(c.type), v.n_cam - 1));
+  return PTZ_OK;
+}
+
+// One wave of scenes on the host threads; their entry lists go into the batch-wide array in one resize and a parallel copy
+int32_t build_wave_entries(ptz_ba_batch* b, CreateCtx& c, int first, int wn, std::vector<PairBuild>& wave)
+{
+  build_scene_wave(c.problems, first, wn, c.n_threads, c.h, b->ray_perm.data(), wave, c.gpu_pairs && !c.pairs_check);
+  std::vector<size_t> ent_at(wn);
+  size_t at = c.h_ent.size();
+  bool wave_ok = true;
+  for (int k = 0; k < wn; ++k) { ent_at[k] = at; at += wave[k].ent.size(); wave_ok &= wave[k].err == PTZ_OK; }
+  if (!wave_ok || at > 0x7fffffff) return PTZ_EINVAL;
+  c.h_ent.resize(at);
+  run_strided(std::min(c.n_threads, wn), [&](int t0, int step) {
+    for (int k = t0; k < wn; k += step) {
+      if (!wave[k].ent.empty()) memcpy(c.h_ent.data() + ent_at[k], wave[k].ent.data(), sizeof(unsigned) * wave[k].ent.size());
+      std::vector<unsigned>().swap(wave[k].ent);
+    }
+  });
+  return PTZ_OK;
+}
+
+// A packed scene: its pair lists appended to the batch's, entry positions made batch-wide
+int32_t append_scene_pairs(ptz_ba_batch* b, CreateCtx& c, const PairBuild& pb, SceneDev& s)
+{
+  if (pb.err != PTZ_OK || (int64_t)b->total_ent + pb.n_ent > 0x7fffffff) return PTZ_EINVAL;
+  c.h_pci.insert(c.h_pci.end(), pb.pci.begin(), pb.pci.end());
+  c.h_pcj.insert(c.h_pcj.end(), pb.pcj.begin(), pb.pcj.end());
+  c.h_pbrow.insert(c.h_pbrow.end(), pb.pbrow.begin(), pb.pbrow.end());
+  for (int v : pb.pptr) c.h_pptr.push_back(b->total_ent + v);
+  for (const uint2& r : pb.runs) c.h_runs.push_back(make_uint2(r.x + (unsigned)b->total_ent, r.y));
+  c.h_prun.insert(c.h_prun.end(), pb.prun.begin(), pb.prun.end());
+  s.run_off = b->total_run; s.n_pair = pb.n_pair;
+  b->total_run += (int)pb.runs.size(); b->total_ent += (int)pb.n_ent; b->total_pair += pb.n_pair;
+  b->max_cam_run = std::max(b->max_cam_run, pb.max_cam_run); b->max_cam_obs = std::max(b->max_cam_obs, pb.max_cam_obs);
+  b->max_cam_ent = std::max(b->max_cam_ent, pb.max_cam_ent); b->max_cam_pair = std::max(b->max_cam_pair, pb.max_cam_pair);
+  return PTZ_OK;
+}
+
+// Shared intrinsics groups of scene i (ids are arbitrary integers; members in ascending camera order; groups in order of their
+// first member); a camera alone in its group needs nothing.  And the cameras' flags: which of a group counts, which carries the
+// displacement block.  `total_grp`: the groups of the scenes before this one.
+void scene_groups(ptz_ba_batch* b, CreateCtx& c, int i, SceneDev& s, int total_grp)
+{
+  const ptz_ba_problem& p = c.problems[i];
+  s.grp_off = total_grp; s.n_grp = 0;
+  std::vector<int> first(p.n_cam);
+  for (int k = 0; k < p.n_cam; ++k) {
+    first[k] = k;
+    if (p.ic_of_cam)
+      for (int m = 0; m < k; ++m)
+        if (p.ic_of_cam[m] == p.ic_of_cam[k]) { first[k] = m; break; }
+  }
+  for (int k = 0; k < p.n_cam; ++k) b->first_of_group.push_back(b->total_cam + first[k]);
+  std::vector<char> counted(p.n_cam, 0);  // group (by first member) already has its counting camera
+  bool disp_counted = false;
+  const int* camptr_s = c.h.camptr.data() + c.h.cam_base[i] + i;  // filled by build_pairs for this scene (views: no camera has residuals as far as the flags are concerned)
+  for (int k = 0; k < p.n_cam; ++k) {
+    const bool has_res = camptr_s[k + 1] > camptr_s[k];
+    unsigned char flag = 0;
+    if (has_res && !counted[first[k]]) { flag = 1; counted[first[k]] = 1; }
+    if (c.disp && has_res && !disp_counted) { flag |= 2; disp_counted = true; }
+    c.h_camflag.push_back(flag);
+  }
+  c.h_grpptr.push_back((int)c.h_grpmem.size());
+  for (int k = 0; k < p.n_cam; ++k) {
+    if (first[k] != k) continue;
+    int members = 0;
+    for (int m = k; m < p.n_cam; ++m) members += first[m] == k;
+    if (members < 2) continue;
+    for (int m = k; m < p.n_cam; ++m) if (first[m] == k) c.h_grpmem.push_back(m);
+    c.h_grpptr.push_back((int)c.h_grpmem.size());
+    c.h_grpcls.push_back(0);
+    ++s.n_grp;
+    c.any_shared = true;
+  }
+  if (c.disp) {  // the displacement block is one parameter of the whole problem: a group of all cameras, over the d slots
+    for (int m = 0; m < p.n_cam; ++m) c.h_grpmem.push_back(m);
+    c.h_grpptr.push_back((int)c.h_grpmem.size());
+    c.h_grpcls.push_back(1);
+    ++s.n_grp;
+    c.any_shared = true;
+  }
+  b->max_grp = std::max(b->max_grp, s.n_grp);
+}
+
+// The scenes' places in the batch-wide arrays (SceneDev), the 2D-3D arrays, and per scene: the rig's bounds (views) or the host-built
+// observation and pair lists (packed problems: built a wave of scenes at a time on up to 16 host threads, PTZ_BA_HOST_THREADS --
+// the observation-side arrays are written in place, the pair lists appended here), then its intrinsics groups
+int32_t create_layout(ptz_ba_batch* b, CreateCtx& c)
+{
+  const int n = c.n, NC = c.NC, has3d = c.has3d;
+  const bool vm = c.views != nullptr;
+  c.h.set_bases(n, c.problems);
+  if (c.h.obs_base[n] > 0x7fffffff) return PTZ_EINVAL;
+  if (!vm) { c.h.resize_all(n); b->ray_perm.resize(c.h.ray_base[n]); }
+  else c.h.camptr.assign(c.h.cam_base[n] + n, 0);  // (read by the per-camera flags: see scene_groups)
+  c.n_threads = env_int("PTZ_BA_HOST_THREADS", (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())), 1);
+  const int wave_scenes = 4 * c.n_threads;
+  PTZ_TRY(choose_pair_builder(c));
   std::vector<PairBuild> wave;
-  int wave_first = 0;
+  int wave_first = 0, total_grp = 0;
   for (int i = 0; i < n; ++i) {
-    const ptz_ba_problem& p = problems[i];
+    const ptz_ba_problem& p = c.problems[i];
     SceneDev s;
     s.n_cam = p.n_cam; s.n_ray = p.n_ray; s.n_obs = (int)p.n_obs;
     s.cam_off = b->total_cam; s.ray_off = b->total_ray; s.obs_off = b->total_obs;
     s.pair_off = b->total_pair; s.ent_off = b->total_ent; s.part_off = b->total_chunk;
-    s.n_chunk = (p.n_ray + b->ray_block - 1) / b->ray_block;
-    s.n_wave = (p.n_ray + 63) / 64;
-    s.n = NC * p.n_cam + 6 * has3d;
-    s.idx = i;
+    s.n_chunk = (p.n_ray + b->ray_block - 1) / b->ray_block; s.n_wave = (p.n_ray + 63) / 64;
+    s.n = NC * p.n_cam + 6 * has3d; s.idx = i;
     s.o3_off = b->total_o3; s.n_o3 = p.n_obs3d;
     for (int a = 0; a < p.n_obs3d; ++a) {
-      h_o3uv.push_back(make_float2(p.obs3d_uv[2 * a], p.obs3d_uv[2 * a + 1]));
-      h_o3cam.push_back(p.obs3d_cam[a]);
-      for (int k = 0; k < 3; ++k) h_o3xyz.push_back(p.obs3d_xyz[3 * a + k]);
+      c.h_o3uv.push_back(make_float2(p.obs3d_uv[2 * a], p.obs3d_uv[2 * a + 1]));
+      c.h_o3cam.push_back(p.obs3d_cam[a]);
+      for (int k = 0; k < 3; ++k) c.h_o3xyz.push_back(p.obs3d_xyz[3 * a + k]);
     }
     b->total_o3 += p.n_obs3d;
-    // observations, ray ranges, camera-major lists, camera-pair entry lists: built ahead of this loop, a wave of scenes at a
-    // time on several threads (build_pairs); the observation-side arrays are written in place, the pair lists appended here
-    const double tsb = now_ms();
-    if (vm) {
-      // extents of the WHOLE rig (the real counts are the device's to find, and nothing is read back to size an array): pairs of
-      // the candidates, the rig's entries, at most max(runs per workgroup, pairs of a camera) runs per camera
-      const ptz_rig* rg = views[i].rig;
-      const int64_t pair_bound = (int64_t)p.n_cam * (p.n_cam - 1) / 2;
-      const int64_t run_bound = (int64_t)p.n_cam * std::max(schur_threads_of(type), p.n_cam);
-      if ((int64_t)b->total_ent + rg->ent_bound > 0x7fffffff || (int64_t)b->total_pair + pair_bound > 0x7fffffff ||
-          (int64_t)b->total_run + run_bound > 0x7fffffff) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
-      s.run_off = b->total_run;
-      s.n_pair = 0;
-      b->total_run += (int)run_bound;
-      b->total_pair += (int)pair_bound;
-      b->total_ent += (int)rg->ent_bound;
-      for (int c = 0; c < p.n_cam; ++c) {
-        b->max_cam_obs = std::max(b->max_cam_obs, rg->img_obs[views[i].cam_image[c]]);
-        b->max_cam_ent = std::max(b->max_cam_ent, rg->img_ent[views[i].cam_image[c]]);
-      }
-      b->max_cam_pair = std::max(b->max_cam_pair, p.n_cam - 1);
-      b->max_cam_run = std::max(b->max_cam_run, std::max(schur_threads_of(type), p.n_cam - 1));
-    }
+    if (vm) PTZ_TRY(bound_view_scene(b, c, i, s));
     else {
+      const double tsb = now_ms();
       if (i >= wave_first + (int)wave.size()) {
         wave_first = i;
-        const int wn = std::min(n - i, wave_scenes);
-        wave.assign(wn, PairBuild());
-        auto work = [&](int t0, int step) {
-          for (int k = t0; k < wn; k += step) {
-            const int sidx = wave_first + k;
-            const ObsDest od = {h_uv.data() + obs_base[sidx], h_cam.data() + obs_base[sidx], h_ray.data() + obs_base[sidx],
-                                h_camobs.data() + obs_base[sidx], h_camray.data() + obs_base[sidx], h_camuv.data() + obs_base[sidx],
-                                h_rayptr.data() + ray_base[sidx] + sidx, h_w.data() + ray_base[sidx],
-                                h_camptr.data() + cam_base[sidx] + sidx, h_campair.data() + cam_base[sidx] + sidx,
-                                h_camrun.data() + cam_base[sidx] + sidx, h_wpos.data() + obs_base[sidx]};
-            build_pairs(problems[sidx], obs_base[sidx], ray_base[sidx], od, wave[k], b->ray_perm.data() + ray_base[sidx], schur_threads_of(type), gpu_pairs && !pairs_check);
-          }
-        };
-        const int nt = std::min(n_threads, wn);
-        auto run = [&](auto&& fn) {
-          if (nt <= 1) { fn(0, 1); return; }
-          std::vector<std::thread> th;
-          for (int t = 1; t < nt; ++t) th.emplace_back(fn, t, nt);
-          fn(0, nt);
-          for (auto& x : th) x.join();
-        };
-        run(work);
-        // the entry lists of the wave go into the batch-wide array in one resize and a parallel copy
-        std::vector<size_t> ent_at(wn);
-        size_t at = h_ent.size();
-        bool wave_ok = true;
-        for (int k = 0; k < wn; ++k) { ent_at[k] = at; at += wave[k].ent.size(); wave_ok &= wave[k].err == PTZ_OK; }
-        if (!wave_ok || at > 0x7fffffff) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }
-        h_ent.resize(at);
-        run([&](int t0, int step) {
-          for (int k = t0; k < wn; k += step) {
-            if (!wave[k].ent.empty()) memcpy(h_ent.data() + ent_at[k], wave[k].ent.data(), sizeof(unsigned) * wave[k].ent.size());
-            std::vector<unsigned>().swap(wave[k].ent);
-          }
-        });
+        PTZ_TRY(build_wave_entries(b, c, i, std::min(n - i, wave_scenes), wave));
       }
-      PairBuild& pb = wave[i - wave_first];
-      if (pb.err != PTZ_OK || (int64_t)b->total_ent + pb.n_ent > 0x7fffffff) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }
-      h_pci.insert(h_pci.end(), pb.pci.begin(), pb.pci.end());
-      h_pcj.insert(h_pcj.end(), pb.pcj.begin(), pb.pcj.end());
-      h_pbrow.insert(h_pbrow.end(), pb.pbrow.begin(), pb.pbrow.end());
-      for (int v : pb.pptr) h_pptr.push_back(b->total_ent + v);
-      for (const uint2& r : pb.runs) h_runs.push_back(make_uint2(r.x + (unsigned)b->total_ent, r.y));
-      h_prun.insert(h_prun.end(), pb.prun.begin(), pb.prun.end());
-      s.run_off = b->total_run;
-      b->total_run += (int)pb.runs.size();
-      b->max_cam_run = std::max(b->max_cam_run, pb.max_cam_run);
-      b->max_cam_obs = std::max(b->max_cam_obs, pb.max_cam_obs);
-      b->max_cam_ent = std::max(b->max_cam_ent, pb.max_cam_ent);
-      b->max_cam_pair = std::max(b->max_cam_pair, pb.max_cam_pair);
-      s.n_pair = pb.n_pair;
-      b->total_ent += (int)pb.n_ent;
-      b->total_pair += pb.n_pair;
-      ts_ent += now_ms() - tsb;
-      pb = PairBuild();  // release this scene's lists
+      PTZ_TRY(append_scene_pairs(b, c, wave[i - wave_first], s));
+      c.ts_ent += now_ms() - tsb;
+      wave[i - wave_first] = PairBuild();  // release this scene's lists
     }
-    // shared intrinsics groups (ids are arbitrary integers; members in ascending camera order; groups in order of their
-    // first member); a camera alone in its group needs nothing
-    {
-      s.grp_off = total_grp;
-      s.n_grp = 0;
-      std::vector<int> first(p.n_cam);
-      for (int c = 0; c < p.n_cam; ++c) {
-        first[c] = c;
-        if (p.ic_of_cam)
-          for (int m = 0; m < c; ++m)
-            if (p.ic_of_cam[m] == p.ic_of_cam[c]) { first[c] = m; break; }
-      }
-      for (int c = 0; c < p.n_cam; ++c) b->first_of_group.push_back(b->total_cam + first[c]);
-      std::vector<char> counted(p.n_cam, 0);  // group (by first member) already has its counting camera
-      bool disp_counted = false;
-      for (int c = 0; c < p.n_cam; ++c) {
-        const int* camptr_s = h_camptr.data() + cam_base[i] + i;  // filled by build_pairs for this scene
-        const bool has_res = camptr_s[c + 1] > camptr_s[c];
-        unsigned char flag = 0;
-        if (has_res && !counted[first[c]]) { flag = 1; counted[first[c]] = 1; }
-        if (disp && has_res && !disp_counted) { flag |= 2; disp_counted = true; }
-        h_camflag.push_back(flag);
-      }
-      h_grpptr.push_back((int)h_grpmem.size());
-      for (int c = 0; c < p.n_cam; ++c) {
-        if (first[c] != c) continue;
-        int members = 0;
-        for (int m = c; m < p.n_cam; ++m) members += first[m] == c;
-        if (members < 2) continue;
-        for (int m = c; m < p.n_cam; ++m) if (first[m] == c) h_grpmem.push_back(m);
-        h_grpptr.push_back((int)h_grpmem.size());
-        h_grpcls.push_back(0);
-        ++s.n_grp;
-        any_shared = true;
-      }
-      if (disp) {  // the displacement block is one parameter of the whole problem: a group of all cameras, over the d slots
-        for (int m = 0; m < p.n_cam; ++m) h_grpmem.push_back(m);
-        h_grpptr.push_back((int)h_grpmem.size());
-        h_grpcls.push_back(1);
-        ++s.n_grp;
-        any_shared = true;
-      }
-      total_grp += s.n_grp;
-      b->max_grp = std::max(b->max_grp, s.n_grp);
-    }
+    scene_groups(b, c, i, s, total_grp);
+    total_grp += s.n_grp;
     b->total_cam += p.n_cam; b->total_ray += p.n_ray; b->total_obs += (int)p.n_obs; b->total_chunk += s.n_wave + 1;
     b->max_cam = std::max(b->max_cam, p.n_cam); b->max_ray = std::max(b->max_ray, p.n_ray);
     b->max_chunk = std::max(b->max_chunk, s.n_chunk); b->max_pair = std::max(b->max_pair, s.n_pair);
     b->max_n = std::max(b->max_n, s.n);
     b->scenes.push_back(s);
   }
-  (void)tot_ent;
+  return PTZ_OK;
+}
 
-  tc1 = now_ms();
+// ---- k_pairs' arguments, shared by the view stage (arrays at the rigs' bounds, nothing read back to size them) and the
+// device-pairs stage (arrays sized exactly, from the totals it reads back)
+void pairs_inputs(const ptz_ba_batch* b, PairsDev& pa)
+{
+  const Dev& d = b->d;
+  memset(&pa, 0, sizeof(pa));
+  pa.scene = d.scene; pa.obs_cam = d.obs_cam; pa.obs_ray = d.obs_ray; pa.ray_ptr = d.ray_ptr; pa.cam_ptr = d.cam_ptr; pa.cam_obs = d.cam_obs;
+  pa.wpos = d.wpos;
+  pa.max_runs = schur_threads_of(b->type);
+}
+// the pair, entry and run arrays, from the batch's totals as they stand
+int32_t alloc_pair_arrays(ptz_ba_batch* b, PairsDev& pa)
+{
+  const size_t n = (size_t)b->n_scene, pairs = (size_t)b->total_pair, cams = (size_t)b->total_cam;
+  PTZ_TRY(b->alloc(&pa.pci, pairs)); PTZ_TRY(b->alloc(&pa.pcj, pairs)); PTZ_TRY(b->alloc(&pa.pbrow, pairs));
+  PTZ_TRY(b->alloc(&pa.pptr, pairs + n)); PTZ_TRY(b->alloc(&pa.prun, pairs + n));
+  PTZ_TRY(b->alloc(&pa.campair, cams + n)); PTZ_TRY(b->alloc(&pa.camrun, cams + n));
+  PTZ_TRY(b->alloc(&pa.runs, (size_t)b->total_run));
+  return b->alloc(&pa.ent, (size_t)b->total_ent);
+}
+void publish_pairs(const PairsDev& pa, Dev& d)
+{
+  d.pair_ci = pa.pci; d.pair_cj = pa.pcj; d.pair_brow = pa.pbrow; d.pair_ptr = pa.pptr; d.pair_run = pa.prun;
+  d.cam_pair = pa.campair; d.cam_run = pa.camrun; d.run_rec = pa.runs; d.ent = pa.ent;
+}
+// a scene's six totals as k_pair_scan leaves them: pairs, entries, runs, and the most pairs, entries, runs of one camera
+void widen_pair_maxima(ptz_ba_batch* b, const int* t)
+{
+  b->max_pair = std::max(b->max_pair, t[0]);
+  b->max_cam_pair = std::max(b->max_cam_pair, t[3]); b->max_cam_ent = std::max(b->max_cam_ent, t[4]); b->max_cam_run = std::max(b->max_cam_run, t[5]);
+}
+
+// ---- views: what the device is given of them
+struct ViewInputs {
+  std::vector<ViewDev> hv; std::vector<int> map, camimg, chunkoff;
+  size_t trk_total = 0, chunk_total = 0;  // chunk_total: [chunks of 256 rays][cameras] counters of the views (k_view_hist), bounds from the rigs' track counts
+  int max_trk = 0; bool block_sort = false;  // block_sort: one launch sorts a view's tracks (k_view_sort); else the batch-wide sort
+};
+int32_t view_inputs(const ptz_ba_batch* b, const CreateCtx& c, ViewInputs& vi)
+{
+  const int n = c.n;
+  vi.hv.resize(n);
+  int64_t view_key_top = 0;  // largest (longest candidate track bound) * cameras + cameras of the views: what the sort keys must hold
+  for (int i = 0; i < n; ++i) {
+    const ptz_rig* rg = c.views[i].rig;
+    if (rg->device != b->device) return PTZ_EINVAL;
+    ViewDev& v = vi.hv[i];
+    v.trk_ptr = rg->d_trk_ptr; v.trk_img = rg->d_trk_img; v.trk_uv = rg->d_trk_uv;
+    v.n_track = rg->n_track; v.n_img = rg->n_img; v.n_cam = c.views[i].n_cam;
+    v.map_off = (int)vi.map.size(); v.trk_off = (int)vi.trk_total;
+    v.n_ray = 0; v.n_obs = 0; v.max_len = 0;
+    vi.map.insert(vi.map.end(), (size_t)rg->n_img, -1);
+    for (int k = 0; k < v.n_cam; ++k) { vi.map[v.map_off + c.views[i].cam_image[k]] = k; vi.camimg.push_back(c.views[i].cam_image[k]); }
+    vi.trk_total += (size_t)rg->n_track;
+    vi.max_trk = std::max(vi.max_trk, rg->n_track);
+    // the sort key of the internal ray order holds (longest - length) * cameras + first camera in 22 bits, the track in 24.  What
+    // k_view_keys puts there is below (the view's longest candidate track) * cameras, and a candidate track is no longer than the
+    // rig's longest track or the number of candidate images -- NOT the rig's mean length: one long track in a wide view would
+    // otherwise spill into the bits of the view number, and the batch-wide sort would silently be a different order.
+    // That bound belongs to the BATCH-WIDE sort (k_view_keys, taken when a rig has more than 16 384 tracks or on request);
+    // the one-launch sort (k_view_sort) keeps a 32-bit key of its own per view, whose padding value 2 << bits(top) must fit: top < 2^29.
+    view_key_top = std::max(view_key_top, (int64_t)std::min(rg->max_track_len, v.n_cam) * v.n_cam + v.n_cam);
+    if (rg->n_track >= (1 << 24)) return PTZ_ELIMIT;
+  }
+  vi.block_sort = vi.max_trk <= 16384 && env_flag("PTZ_BA_VIEW_BLOCK_SORT", true);
+  if (view_key_top >= (vi.block_sort ? ((int64_t)1 << 29) : ((int64_t)1 << 22))) return PTZ_ELIMIT;
+  vi.chunkoff.resize(n);
+  for (int i = 0; i < n; ++i) {
+    vi.chunkoff[i] = (int)vi.chunk_total;
+    vi.chunk_total += (size_t)((c.views[i].rig->n_track + 255) / 256) * c.views[i].n_cam;
+    if (vi.chunk_total > 0x7fffffffu) return PTZ_ELIMIT;
+  }
+  return PTZ_OK;
+}
+
+// the views' internal ray order: one launch (a workgroup per view sorts its tracks) when every view fits, else the batch-wide sort
+int32_t enqueue_view_sort(ptz_ba_batch* b, const ViewInputs& vi, const ViewBuild& vb, unsigned long long* key_out, int* val_out)
+{
+  const int n = b->n_scene;
+  hipStream_t st = b->io;
+  if (vi.block_sort) {
+    (void)once_per_device(CAPS_VIEW_SORT, b->device, [] { (void)hipFuncSetAttribute((const void*)k_view_sort<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); return true; });
+    if (vi.max_trk <= 4096) hipLaunchKernelGGL(k_view_sort<4>, dim3(n), dim3(1024), sizeof(rocprim::block_radix_sort<unsigned, 1024, 4, int>::storage_type), st, vb, val_out);
+    else hipLaunchKernelGGL(k_view_sort<16>, dim3(n), dim3(1024), sizeof(rocprim::block_radix_sort<unsigned, 1024, 16, int>::storage_type), st, vb, val_out);
+    return PTZ_OK;
+  }
+  hipLaunchKernelGGL(k_view_keys, dim3((vi.max_trk + 255) / 256, n), dim3(256), 0, st, vb);
+  unsigned end_bit = 47;
+  while ((1u << (end_bit - 47)) < (unsigned)n) ++end_bit;
+  size_t tmp_bytes = 0;
+  // (the low 24 bits of a key are the track number and the keys are generated in (view, track) order: a STABLE sort on the bits
+  //  above them gives the same order in four digit passes instead of seven)
+  const unsigned begin_bit = 24;
+  if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, vb.key_in, key_out, vb.val_in, val_out, vi.trk_total, begin_bit, end_bit, st) != hipSuccess) return PTZ_ENODEVICE;
+  char* tmp = nullptr;
+  PTZ_TRY(b->alloc(&tmp, tmp_bytes + 256));
+  if (rocprim::radix_sort_pairs((void*)tmp, tmp_bytes, vb.key_in, key_out, vb.val_in, val_out, vi.trk_total, begin_bit, end_bit, st) != hipSuccess) return PTZ_ENODEVICE;
+  return PTZ_OK;
+}
+
+// The packed problems of the views, on the device (ptz_view_kernels.h): observations in the library's order, ray and camera lists,
+// camera pairs (k_pairs as for any batch); one read-back at the end (counts, pair totals, the error word, tile adjacency), nothing
+// in between.  `tc1`: when the stage began (PTZ_BA_DEBUG_TIMING).
+int32_t create_view_structure(ptz_ba_batch* b, CreateCtx& c, double tc1)
+{
+  const int n = c.n;
   Dev& d = b->d;
-  memset(&d, 0, sizeof(d));
-  d.n_scene = n;
-  int rc = PTZ_OK;
-#define TRY(x) do { rc = (x); if (rc) { ptz_ba_batch_destroy(b); return rc; } } while (0)
-  std::vector<unsigned char> h_adj;  // views: tile adjacency of every scene's reduced system, marked on the device
-  if (vm) {
-    // ---- the packed problems of the views, on the device (ptz_view_kernels.h): observations in the library's order, ray and camera
-    // lists, camera pairs; one read-back at the end (counts, tile adjacency), nothing in between
-    const int nt_e = chol_padded_order(b->max_n) / CHOL_NB;
-    std::vector<ViewDev> hv(n);
-    std::vector<int> h_map, h_camimg;
-    size_t trk_total = 0;
-    int max_trk = 0;
-    int64_t view_key_top = 0;  // largest (longest candidate track bound) * cameras + cameras of the views: what the sort keys must hold
-    for (int i = 0; i < n; ++i) {
-      const ptz_rig* rg = views[i].rig;
-      if (rg->device != b->device) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }
-      ViewDev& v = hv[i];
-      v.trk_ptr = rg->d_trk_ptr; v.trk_img = rg->d_trk_img; v.trk_uv = rg->d_trk_uv;
-      v.n_track = rg->n_track; v.n_img = rg->n_img; v.n_cam = views[i].n_cam;
-      v.map_off = (int)h_map.size(); v.trk_off = (int)trk_total;
-      v.n_ray = 0; v.n_obs = 0; v.max_len = 0;
-      h_map.insert(h_map.end(), (size_t)rg->n_img, -1);
-      for (int c = 0; c < v.n_cam; ++c) { h_map[v.map_off + views[i].cam_image[c]] = c; h_camimg.push_back(views[i].cam_image[c]); }
-      trk_total += (size_t)rg->n_track;
-      max_trk = std::max(max_trk, rg->n_track);
-      // the sort key of the internal ray order holds (longest - length) * cameras + first camera in 22 bits, the track in 24.  What
-      // k_view_keys puts there is below (the view's longest candidate track) * cameras, and a candidate track is no longer than the
-      // rig's longest track or the number of candidate images -- NOT the rig's mean length: one long track in a wide view would
-      // otherwise spill into the bits of the view number, and the batch-wide sort would silently be a different order.
-      // That bound belongs to the BATCH-WIDE sort (k_view_keys, taken below when a rig has more than 16 384 tracks or on request);
-      // the one-launch sort (k_view_sort) keeps a 32-bit key of its own per view, whose padding value 2 << bits(top) must fit: top < 2^29.
-      view_key_top = std::max(view_key_top, (int64_t)std::min(rg->max_track_len, v.n_cam) * v.n_cam + v.n_cam);
-      if (rg->n_track >= (1 << 24)) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
-    }
-    const bool block_sort = max_trk <= 16384 && !(getenv("PTZ_BA_VIEW_BLOCK_SORT") && atoi(getenv("PTZ_BA_VIEW_BLOCK_SORT")) == 0);
-    if (view_key_top >= (block_sort ? ((int64_t)1 << 29) : ((int64_t)1 << 22))) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
-    const ViewDev* dviews_c = nullptr;
-    const int *d_map = nullptr, *d_camimg = nullptr, *d_chunkoff = nullptr;
-    std::vector<int> h_chunkoff(n);
-    size_t chunk_total = 0;  // [chunks of 256 rays][cameras] counters of the views (k_view_hist), bounds from the rigs' track counts
-    for (int i = 0; i < n; ++i) {
-      h_chunkoff[i] = (int)chunk_total;
-      chunk_total += (size_t)((views[i].rig->n_track + 255) / 256) * views[i].n_cam;
-      if (chunk_total > 0x7fffffffu) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
-    }
-    {
-      StagedUpload up;
-      up.add(b->scenes, &d.scene);
-      up.add(hv, &dviews_c);
-      up.add(h_map, &d_map);
-      up.add(h_camimg, &d_camimg);
-      up.add(h_chunkoff, &d_chunkoff);
-      TRY(up.commit(b, /*wait=*/false));
-    }
-    ViewBuild vb;
-    memset(&vb, 0, sizeof(vb));
-    vb.views = const_cast<ViewDev*>(dviews_c);
-    vb.cam_of_image = d_map; vb.cam_image = d_camimg;
-    vb.scene = const_cast<SceneDev*>(d.scene);
-    vb.chunk_off = d_chunkoff;
-    if (b->max_cam <= VIEW_LDS_CAMS) TRY(b->alloc(&vb.chunk_cnt, chunk_total));  // (unused by the wide path)
-    unsigned long long *key_out = nullptr;
-    int* val_out = nullptr;
-    TRY(b->alloc(&vb.t_len, trk_total)); TRY(b->alloc(&vb.t_first, trk_total)); TRY(b->alloc(&vb.t_ext, trk_total));
-    TRY(b->alloc(&vb.key_in, trk_total)); TRY(b->alloc(&vb.val_in, trk_total)); TRY(b->alloc(&key_out, trk_total)); TRY(b->alloc(&val_out, trk_total));
-    TRY(b->alloc(&vb.ray_trk, (size_t)b->total_ray)); TRY(b->alloc(&vb.ray_len, (size_t)b->total_ray)); TRY(b->alloc(&vb.cam_cnt, (size_t)b->total_cam));
-    TRY(b->alloc(&vb.obs_uv, (size_t)b->total_obs)); TRY(b->alloc(&vb.obs_cam, (size_t)b->total_obs)); TRY(b->alloc(&vb.obs_ray, (size_t)b->total_obs));
-    TRY(b->alloc(&vb.ray_ptr, (size_t)b->total_ray + n)); TRY(b->alloc(&vb.cam_ptr, (size_t)b->total_cam + n));
-    TRY(b->alloc(&vb.cam_obs, (size_t)b->total_obs)); TRY(b->alloc(&vb.wpos, (size_t)b->total_obs)); TRY(b->alloc(&vb.cam_ray, (size_t)b->total_obs));
-    TRY(b->alloc(&vb.cam_uv, (size_t)b->total_obs)); TRY(b->alloc(&vb.ray_w, (size_t)b->total_ray)); TRY(b->alloc(&vb.ray_perm, (size_t)b->total_ray));
-    d.obs_uv = vb.obs_uv; d.obs_cam = vb.obs_cam; d.obs_ray = vb.obs_ray; d.ray_ptr = vb.ray_ptr; d.cam_ptr = vb.cam_ptr; d.cam_obs = vb.cam_obs;
-    d.wpos = vb.wpos; d.cam_ray = vb.cam_ray; d.cam_uv = vb.cam_uv; d.ray_w = vb.ray_w; b->d_ray_perm = vb.ray_perm;
-    hipStream_t st = b->io;
-    const dim3 gtrk((max_trk + 255) / 256, n);
-    const double tv0 = now_ms();
-    hipLaunchKernelGGL(k_view_tracks, gtrk, dim3(256), 0, st, vb);
-    hipLaunchKernelGGL(k_view_scan, dim3(n), dim3(1024), 0, st, vb);
-    // the views' internal ray order: one launch (a workgroup per view sorts its tracks) when every view fits, else the batch-wide sort
-    if (block_sort) {
-      {
-        static std::mutex sort_mu;
-        static bool sort_cap[64] = {};
-        std::lock_guard<std::mutex> lk(sort_mu);
-        const int dv = b->device & 63;
-        if (!sort_cap[dv]) { (void)hipFuncSetAttribute((const void*)k_view_sort<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); sort_cap[dv] = true; }
-      }
-      if (max_trk <= 4096) hipLaunchKernelGGL(k_view_sort<4>, dim3(n), dim3(1024), sizeof(rocprim::block_radix_sort<unsigned, 1024, 4, int>::storage_type), st, vb, val_out);
-      else hipLaunchKernelGGL(k_view_sort<16>, dim3(n), dim3(1024), sizeof(rocprim::block_radix_sort<unsigned, 1024, 16, int>::storage_type), st, vb, val_out);
-    }
-    else {
-      hipLaunchKernelGGL(k_view_keys, gtrk, dim3(256), 0, st, vb);
-      unsigned end_bit = 47;
-      while ((1u << (end_bit - 47)) < (unsigned)n) ++end_bit;
-      size_t tmp_bytes = 0;
-      void* tmp = nullptr;
-      // (the low 24 bits of a key are the track number and the keys are generated in (view, track) order: a STABLE sort on the bits
-      //  above them gives the same order in four digit passes instead of seven)
-      const unsigned begin_bit = 24;
-      if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, vb.key_in, key_out, vb.val_in, val_out, trk_total, begin_bit, end_bit, st) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-      char* tmpc = nullptr;
-      TRY(b->alloc(&tmpc, tmp_bytes + 256));
-      tmp = tmpc;
-      if (rocprim::radix_sort_pairs(tmp, tmp_bytes, vb.key_in, key_out, vb.val_in, val_out, trk_total, begin_bit, end_bit, st) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    }
-    const double tva = now_ms();
-    hipLaunchKernelGGL(k_view_rays, gtrk, dim3(256), 0, st, vb, (const int*)val_out);
-    hipLaunchKernelGGL(k_view_rayscan, dim3(n), dim3(1024), 0, st, vb, b->ray_block);
-    // (PTZ_BA_DEBUG_VIEW_WIDE=1: the path of views wider than VIEW_LDS_CAMS for any view -- tests: the same lists)
-    const bool view_wide = b->max_cam > VIEW_LDS_CAMS || (getenv("PTZ_BA_DEBUG_VIEW_WIDE") && atoi(getenv("PTZ_BA_DEBUG_VIEW_WIDE")) != 0);
-    if (!view_wide) {  // camera-major lists by counting: chunk histograms, running sums, placement
-      hipLaunchKernelGGL(k_view_hist, gtrk, dim3(256), sizeof(int) * (size_t)b->max_cam, st, vb);
-      hipLaunchKernelGGL(k_view_chunkscan, dim3(n), dim3(1024), 0, st, vb);
-      hipLaunchKernelGGL(k_view_place, gtrk, dim3(256), sizeof(unsigned long long) * 4 * (size_t)b->max_cam, st, vb);
-    }
-    else {
-      hipLaunchKernelGGL(k_view_obs, gtrk, dim3(256), 0, st, vb);
-      hipLaunchKernelGGL(k_view_camscan, dim3(n), dim3(1024), 0, st, vb);
-      hipLaunchKernelGGL(k_view_camlists_wide, dim3(b->max_cam, n), dim3(256), 0, st, vb);
-    }
-    const double tvb = now_ms();
-    // camera pairs, entry lists, runs: k_pairs as for any batch, into arrays of the bounds' extents (no sizing read-back)
-    PairsDev pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.scene = d.scene; pa.obs_cam = d.obs_cam; pa.obs_ray = d.obs_ray; pa.ray_ptr = d.ray_ptr; pa.cam_ptr = d.cam_ptr; pa.cam_obs = d.cam_obs;
-    pa.wpos = d.wpos;
-    pa.max_runs = schur_threads_of(type);
-    int *d_cnt = nullptr, *d_off3 = nullptr, *d_tot = nullptr, *d_err = nullptr;
-    unsigned char* d_adj = nullptr;
-    TRY(b->alloc(&d_cnt, (size_t)3 * b->total_cam));
-    TRY(b->alloc(&d_off3, (size_t)3 * b->total_cam));
-    TRY(b->alloc(&d_tot, (size_t)6 * n + 1));
-    d_err = d_tot + 6 * n;
-    TRY(b->alloc(&d_adj, (size_t)n * nt_e * nt_e));
-    pa.cam_cnt = d_cnt; pa.cam_off3 = d_off3; pa.scene_tot = d_tot; pa.err = d_err;
-    TRY(b->alloc(&pa.pci, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pcj, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pbrow, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pptr, (size_t)b->total_pair + n));
-    TRY(b->alloc(&pa.prun, (size_t)b->total_pair + n));
-    TRY(b->alloc(&pa.campair, (size_t)b->total_cam + n));
-    TRY(b->alloc(&pa.camrun, (size_t)b->total_cam + n));
-    TRY(b->alloc(&pa.runs, (size_t)b->total_run));
-    TRY(b->alloc(&pa.ent, (size_t)b->total_ent));
-    pairs_lds_cap(b->device);
-    const double tvc = now_ms();
-    if (hipMemsetAsync(d_err, 0, sizeof(int), st) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    hipLaunchKernelGGL(k_pairs<false>, dim3(b->max_cam, n), dim3(256), pairs_lds, st, pa);
-    hipLaunchKernelGGL(k_pair_scan, dim3((n + 63) / 64), dim3(64), 0, st, d.scene, n, (const int*)d_cnt, d_off3, d_tot);
-    hipLaunchKernelGGL(k_view_pairs_patch, dim3((n + 63) / 64), dim3(64), 0, st, vb.scene, n, (const int*)d_tot);
-    hipLaunchKernelGGL(k_pairs<true>, dim3(b->max_cam, n), dim3(256), pairs_lds, st, pa);
-    hipLaunchKernelGGL(k_view_adjacency, dim3(n), dim3(256), 0, st, d.scene, (const int*)pa.pci, (const int*)pa.pcj, NC, nt_e, d_adj);
-    d.pair_ci = pa.pci; d.pair_cj = pa.pcj; d.pair_brow = pa.pbrow; d.pair_ptr = pa.pptr; d.pair_run = pa.prun;
-    d.cam_pair = pa.campair; d.cam_run = pa.camrun; d.run_rec = pa.runs; d.ent = pa.ent;
-    // the one read-back: the views' counts, the pair totals, the error word, the tile adjacency
-    const double tvd = now_ms();
-    std::vector<int> h_tot((size_t)6 * n + 1);
-    h_adj.resize((size_t)n * nt_e * nt_e);
-    {
-      hipError_t e = hipMemcpyAsync(hv.data(), dviews_c, sizeof(ViewDev) * n, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(h_tot.data(), d_tot, sizeof(int) * (6 * n + 1), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(h_adj.data(), d_adj, h_adj.size(), hipMemcpyDeviceToHost, st);
-      const double tv1 = now_ms();
-      if (e == hipSuccess) e = stream_wait(st);
-      if (dbg_t) fprintf(stderr, "[ptz_ba_create] views: allocations + upload %.3f ms, build enqueued in %.3f ms, waited %.3f ms for it | tracks..sort %.3f, rays..place %.3f, pair arrays %.3f, memset + pairs launches %.3f, copies back %.3f\n", tv0 - tc1, tv1 - tv0, now_ms() - tv1,
-                         tva - tv0, tvb - tva, tvc - tvb, tvd - tvc, tv1 - tvd);
-      b->release_staged();
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e != hipSuccess) { (void)hipGetLastError(); ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    }
-    if (h_tot[(size_t)6 * n]) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }  // an image twice in one track (tracks.cc:77)
-    b->max_pair = 0; b->max_cam_pair = 0; b->max_cam_ent = 0; b->max_cam_run = 0;
-    for (int i = 0; i < n; ++i) {
-      if (hv[i].n_obs <= 0 || hv[i].n_ray <= 0) { ptz_ba_batch_destroy(b); return PTZ_ENOOBS; }  // no candidate observation: not a problem (:517); its own code, so that callers can tell it from a malformed view
-      SceneDev& sd = b->scenes[i];
-      const int* t = h_tot.data() + 6 * (size_t)i;
-      sd.n_ray = hv[i].n_ray; sd.n_obs = hv[i].n_obs;
-      sd.n_wave = (sd.n_ray + 63) / 64; sd.n_chunk = (sd.n_ray + b->ray_block - 1) / b->ray_block;
-      sd.n_pair = t[0];
-      b->max_pair = std::max(b->max_pair, t[0]);
-      b->max_cam_pair = std::max(b->max_cam_pair, t[3]);
-      b->max_cam_ent = std::max(b->max_cam_ent, t[4]);
-      b->max_cam_run = std::max(b->max_cam_run, t[5]);
-    }
-    gpu_pairs = false;  // (done)
+  const int nt_e = chol_padded_order(b->max_n) / CHOL_NB;
+  ViewInputs vi;
+  PTZ_TRY(view_inputs(b, c, vi));
+  const ViewDev* dviews_c = nullptr;
+  const int *d_map = nullptr, *d_camimg = nullptr, *d_chunkoff = nullptr;
+  StagedUpload up;
+  up.add(b->scenes, &d.scene); up.add(vi.hv, &dviews_c);
+  up.add(vi.map, &d_map); up.add(vi.camimg, &d_camimg); up.add(vi.chunkoff, &d_chunkoff);
+  PTZ_TRY(up.commit(b, /*wait=*/false));
+  ViewBuild vb;
+  memset(&vb, 0, sizeof(vb));
+  vb.views = const_cast<ViewDev*>(dviews_c); vb.scene = const_cast<SceneDev*>(d.scene);
+  vb.cam_of_image = d_map; vb.cam_image = d_camimg; vb.chunk_off = d_chunkoff;
+  if (b->max_cam <= VIEW_LDS_CAMS) PTZ_TRY(b->alloc(&vb.chunk_cnt, vi.chunk_total));  // (unused by the wide path)
+  unsigned long long* key_out = nullptr;  // the batch-wide sort's outputs; val_out: the tracks of every view in ray order
+  int* val_out = nullptr;
+  const size_t trk = vi.trk_total, rays = (size_t)b->total_ray, cams = (size_t)b->total_cam, obs = (size_t)b->total_obs;
+  PTZ_TRY(b->alloc(&vb.t_len, trk)); PTZ_TRY(b->alloc(&vb.t_first, trk)); PTZ_TRY(b->alloc(&vb.t_ext, trk));
+  PTZ_TRY(b->alloc(&vb.key_in, trk)); PTZ_TRY(b->alloc(&vb.val_in, trk)); PTZ_TRY(b->alloc(&key_out, trk)); PTZ_TRY(b->alloc(&val_out, trk));
+  PTZ_TRY(b->alloc(&vb.ray_trk, rays)); PTZ_TRY(b->alloc(&vb.ray_len, rays)); PTZ_TRY(b->alloc(&vb.cam_cnt, cams));
+  PTZ_TRY(b->alloc(&vb.obs_uv, obs)); PTZ_TRY(b->alloc(&vb.obs_cam, obs)); PTZ_TRY(b->alloc(&vb.obs_ray, obs));
+  PTZ_TRY(b->alloc(&vb.ray_ptr, rays + n)); PTZ_TRY(b->alloc(&vb.cam_ptr, cams + n));
+  PTZ_TRY(b->alloc(&vb.cam_obs, obs)); PTZ_TRY(b->alloc(&vb.wpos, obs)); PTZ_TRY(b->alloc(&vb.cam_ray, obs));
+  PTZ_TRY(b->alloc(&vb.cam_uv, obs)); PTZ_TRY(b->alloc(&vb.ray_w, rays)); PTZ_TRY(b->alloc(&vb.ray_perm, rays));
+  d.obs_uv = vb.obs_uv; d.obs_cam = vb.obs_cam; d.obs_ray = vb.obs_ray; d.ray_ptr = vb.ray_ptr; d.cam_ptr = vb.cam_ptr; d.cam_obs = vb.cam_obs;
+  d.wpos = vb.wpos; d.cam_ray = vb.cam_ray; d.cam_uv = vb.cam_uv; d.ray_w = vb.ray_w; b->d_ray_perm = vb.ray_perm;
+  hipStream_t st = b->io;
+  const dim3 gtrk((vi.max_trk + 255) / 256, n);
+  const double tv0 = now_ms();
+  hipLaunchKernelGGL(k_view_tracks, gtrk, dim3(256), 0, st, vb);
+  hipLaunchKernelGGL(k_view_scan, dim3(n), dim3(1024), 0, st, vb);
+  PTZ_TRY(enqueue_view_sort(b, vi, vb, key_out, val_out));
+  const double tva = now_ms();
+  hipLaunchKernelGGL(k_view_rays, gtrk, dim3(256), 0, st, vb, (const int*)val_out);
+  hipLaunchKernelGGL(k_view_rayscan, dim3(n), dim3(1024), 0, st, vb, b->ray_block);
+  // (PTZ_BA_DEBUG_VIEW_WIDE=1: the path of views wider than VIEW_LDS_CAMS for any view -- tests: the same lists)
+  const bool view_wide = b->max_cam > VIEW_LDS_CAMS || env_flag("PTZ_BA_DEBUG_VIEW_WIDE", false);
+  if (!view_wide) {  // camera-major lists by counting: chunk histograms, running sums, placement
+    hipLaunchKernelGGL(k_view_hist, gtrk, dim3(256), sizeof(int) * (size_t)b->max_cam, st, vb);
+    hipLaunchKernelGGL(k_view_chunkscan, dim3(n), dim3(1024), 0, st, vb);
+    hipLaunchKernelGGL(k_view_place, gtrk, dim3(256), sizeof(unsigned long long) * 4 * (size_t)b->max_cam, st, vb);
   }
   else {
-    StagedUpload up;
-    up.add(b->scenes, &d.scene);
-    up.add(h_uv, &d.obs_uv);
-    up.add(h_cam, &d.obs_cam);
-    up.add(h_ray, &d.obs_ray);
-    up.add(h_rayptr, &d.ray_ptr);
-    up.add(h_camptr, &d.cam_ptr);
-    up.add(h_camobs, &d.cam_obs);
-    up.add(h_wpos, &d.wpos);
-    up.add(h_camray, &d.cam_ray);
-    up.add(h_camuv, &d.cam_uv);
-    up.add(h_pci, &d.pair_ci);
-    up.add(h_pcj, &d.pair_cj);
-    up.add(h_pbrow, &d.pair_brow);
-    up.add(h_pptr, &d.pair_ptr);
-    up.add(h_campair, &d.cam_pair);
-    up.add(h_camrun, &d.cam_run);
-    up.add(h_runs, &d.run_rec);
-    up.add(h_prun, &d.pair_run);
-    up.add(h_ent, &d.ent);
-    up.add(h_w, &d.ray_w);
-    up.add(h_o3uv, &d.o3_uv);
-    up.add(h_o3xyz, &d.o3_xyz);
-    up.add(h_o3cam, &d.o3_cam);
-    up.add(b->ray_perm, &b->d_ray_perm);
-    TRY(up.commit(b));
+    hipLaunchKernelGGL(k_view_obs, gtrk, dim3(256), 0, st, vb);
+    hipLaunchKernelGGL(k_view_camscan, dim3(n), dim3(1024), 0, st, vb);
+    hipLaunchKernelGGL(k_view_camlists_wide, dim3(b->max_cam, n), dim3(256), 0, st, vb);
   }
-  if (gpu_pairs) {
-    // camera pairs, entry lists and runs on the device (k_pairs): count, scan, read the totals back (the arrays are sized
-    // exactly), write; then the pairs' cameras come back for the tile structure below
-    PairsDev pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.scene = d.scene; pa.obs_cam = d.obs_cam; pa.obs_ray = d.obs_ray; pa.ray_ptr = d.ray_ptr; pa.cam_ptr = d.cam_ptr; pa.cam_obs = d.cam_obs;
-    pa.wpos = d.wpos;
-    pa.max_runs = schur_threads_of(type);
-    int *d_cnt = nullptr, *d_off3 = nullptr, *d_tot = nullptr, *d_err = nullptr;
-    TRY(b->alloc(&d_cnt, (size_t)3 * b->total_cam));
-    TRY(b->alloc(&d_off3, (size_t)3 * b->total_cam));
-    TRY(b->alloc(&d_tot, (size_t)6 * n));
-    TRY(b->alloc(&d_err, 1));
-    pa.cam_cnt = d_cnt; pa.cam_off3 = d_off3; pa.scene_tot = d_tot; pa.err = d_err;
-    pairs_lds_cap(b->device);  // dynamic LDS beyond 64 KiB for very wide rigs
-    if (hipMemsetAsync(d_err, 0, sizeof(int), b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    hipLaunchKernelGGL(k_pairs<false>, dim3(b->max_cam, n), dim3(256), pairs_lds, b->io, pa);
-    hipLaunchKernelGGL(k_pair_scan, dim3((n + 63) / 64), dim3(64), 0, b->io, d.scene, n, (const int*)d_cnt, d_off3, d_tot);
-    std::vector<int> h_tot((size_t)6 * n + 1);
-    {
-      hipError_t e = hipMemcpyAsync(h_tot.data(), d_tot, sizeof(int) * 6 * n, hipMemcpyDeviceToHost, b->io);
-      if (e == hipSuccess) e = hipMemcpyAsync(h_tot.data() + 6 * n, d_err, sizeof(int), hipMemcpyDeviceToHost, b->io);
-      if (e == hipSuccess) e = stream_wait(b->io);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e != hipSuccess) { (void)hipGetLastError(); ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    }
-    if (h_tot[(size_t)6 * n]) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }  // an image twice in one track (tracks.cc:77)
-    const int chk_pair = b->total_pair, chk_run = b->total_run, chk_mcp = b->max_cam_pair, chk_mce = b->max_cam_ent, chk_mcr = b->max_cam_run;
-    const std::vector<SceneDev> chk_scenes = pairs_check ? b->scenes : std::vector<SceneDev>();
-    if (pairs_check) { b->max_cam_pair = 0; b->max_cam_ent = 0; b->max_cam_run = 0; }
-    b->total_pair = 0; b->total_run = 0; b->max_pair = 0;
-    for (int i = 0; i < n; ++i) {
-      SceneDev& sd = b->scenes[i];
-      const int* t = h_tot.data() + 6 * (size_t)i;
-      int64_t ne = 0;  // (the host's count of the scene's entries, from the track lengths)
-      ne = (i + 1 < n ? b->scenes[i + 1].ent_off : b->total_ent) - sd.ent_off;
-      if (t[1] != ne || (int64_t)b->total_pair + t[0] > 0x7fffffff || (int64_t)b->total_run + t[2] > 0x7fffffff) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }
-      sd.n_pair = t[0];
-      sd.pair_off = b->total_pair;
-      sd.run_off = b->total_run;
-      b->total_pair += t[0];
-      b->total_run += t[2];
-      b->max_pair = std::max(b->max_pair, t[0]);
-      b->max_cam_pair = std::max(b->max_cam_pair, t[3]);
-      b->max_cam_ent = std::max(b->max_cam_ent, t[4]);
-      b->max_cam_run = std::max(b->max_cam_run, t[5]);
-    }
-    if (copy_on(b->io, const_cast<SceneDev*>(d.scene), b->scenes.data(), sizeof(SceneDev) * n, hipMemcpyHostToDevice) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    TRY(b->alloc(&pa.pci, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pcj, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pbrow, (size_t)b->total_pair));
-    TRY(b->alloc(&pa.pptr, (size_t)b->total_pair + n));
-    TRY(b->alloc(&pa.prun, (size_t)b->total_pair + n));
-    TRY(b->alloc(&pa.campair, (size_t)b->total_cam + n));
-    TRY(b->alloc(&pa.camrun, (size_t)b->total_cam + n));
-    TRY(b->alloc(&pa.runs, (size_t)b->total_run));
-    TRY(b->alloc(&pa.ent, (size_t)b->total_ent));
-    hipLaunchKernelGGL(k_pairs<true>, dim3(b->max_cam, n), dim3(256), pairs_lds, b->io, pa);
-    d.pair_ci = pa.pci; d.pair_cj = pa.pcj; d.pair_brow = pa.pbrow; d.pair_ptr = pa.pptr; d.pair_run = pa.prun;
-    d.cam_pair = pa.campair; d.cam_run = pa.camrun; d.run_rec = pa.runs; d.ent = pa.ent;
-    if (pairs_check) {
-      long bad = 0;
-      if (chk_pair != b->total_pair || chk_run != b->total_run || chk_mcp != b->max_cam_pair || chk_mce != b->max_cam_ent || chk_mcr != b->max_cam_run) ++bad;
-      for (int i = 0; i < n && !bad; ++i)
-        if (chk_scenes[i].n_pair != b->scenes[i].n_pair || chk_scenes[i].pair_off != b->scenes[i].pair_off || chk_scenes[i].run_off != b->scenes[i].run_off) ++bad;
-      auto cmp = [&](const void* dev, const void* host, size_t bytes, const char* name) {
-        std::vector<unsigned char> tmp(bytes + 1);
-        if (bytes && (hipMemcpyAsync(tmp.data(), dev, bytes, hipMemcpyDeviceToHost, b->io) != hipSuccess || stream_wait(b->io) != hipSuccess)) { ++bad; return; }
-        if (bytes && memcmp(tmp.data(), host, bytes) != 0) { ++bad; fprintf(stderr, "[ptz_ba_create] device-built %s differs from the host builder's\n", name); }
-      };
-      if (!bad) {
-        cmp(pa.pci, h_pci.data(), sizeof(int) * h_pci.size(), "pair_ci");
-        cmp(pa.pcj, h_pcj.data(), sizeof(int) * h_pcj.size(), "pair_cj");
-        cmp(pa.pbrow, h_pbrow.data(), sizeof(int) * h_pbrow.size(), "pair_brow");
-        cmp(pa.pptr, h_pptr.data(), sizeof(int) * h_pptr.size(), "pair_ptr");
-        cmp(pa.prun, h_prun.data(), sizeof(int) * h_prun.size(), "pair_run");
-        cmp(pa.campair, h_campair.data(), sizeof(int) * h_campair.size(), "cam_pair");
-        cmp(pa.camrun, h_camrun.data(), sizeof(int) * h_camrun.size(), "cam_run");
-        cmp(pa.runs, h_runs.data(), sizeof(uint2) * h_runs.size(), "run_rec");
-        cmp(pa.ent, h_ent.data(), sizeof(unsigned) * h_ent.size(), "ent");
-      }
-      else fprintf(stderr, "[ptz_ba_create] device-built pair totals differ from the host builder's\n");
-      if (bad) { ptz_ba_batch_destroy(b); return PTZ_EINVAL; }
-    }
-    h_pci.resize(b->total_pair);
-    h_pcj.resize(b->total_pair);
-    {
-      hipError_t e = b->total_pair ? hipMemcpyAsync(h_pci.data(), pa.pci, sizeof(int) * b->total_pair, hipMemcpyDeviceToHost, b->io) : hipSuccess;
-      if (e == hipSuccess && b->total_pair) e = hipMemcpyAsync(h_pcj.data(), pa.pcj, sizeof(int) * b->total_pair, hipMemcpyDeviceToHost, b->io);
-      if (e == hipSuccess) e = stream_wait(b->io);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e != hipSuccess) { (void)hipGetLastError(); ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    }
+  const double tvb = now_ms();
+  // camera pairs, entry lists, runs: into arrays of the bounds' extents (no sizing read-back)
+  PairsDev pa;
+  pairs_inputs(b, pa);
+  int *d_cnt = nullptr, *d_off3 = nullptr, *d_tot = nullptr;
+  unsigned char* d_adj = nullptr;
+  PTZ_TRY(b->alloc(&d_cnt, (size_t)3 * b->total_cam)); PTZ_TRY(b->alloc(&d_off3, (size_t)3 * b->total_cam));
+  PTZ_TRY(b->alloc(&d_tot, (size_t)6 * n + 1));
+  int* d_err = d_tot + 6 * n;
+  PTZ_TRY(b->alloc(&d_adj, (size_t)n * nt_e * nt_e));
+  pa.cam_cnt = d_cnt; pa.cam_off3 = d_off3; pa.scene_tot = d_tot; pa.err = d_err;
+  PTZ_TRY(alloc_pair_arrays(b, pa));
+  (void)once_per_device(CAPS_PAIRS, b->device, raise_pairs_caps);
+  const double tvc = now_ms();
+  if (hipMemsetAsync(d_err, 0, sizeof(int), st) != hipSuccess) return PTZ_ENODEVICE;
+  hipLaunchKernelGGL(k_pairs<false>, dim3(b->max_cam, n), dim3(256), c.pairs_lds, st, pa);
+  hipLaunchKernelGGL(k_pair_scan, dim3((n + 63) / 64), dim3(64), 0, st, d.scene, n, (const int*)d_cnt, d_off3, d_tot);
+  hipLaunchKernelGGL(k_view_pairs_patch, dim3((n + 63) / 64), dim3(64), 0, st, vb.scene, n, (const int*)d_tot);
+  hipLaunchKernelGGL(k_pairs<true>, dim3(b->max_cam, n), dim3(256), c.pairs_lds, st, pa);
+  hipLaunchKernelGGL(k_view_adjacency, dim3(n), dim3(256), 0, st, d.scene, (const int*)pa.pci, (const int*)pa.pcj, c.NC, nt_e, d_adj);
+  publish_pairs(pa, d);
+  // the one read-back: the views' counts, the pair totals, the error word, the tile adjacency
+  const double tvd = now_ms();
+  std::vector<int> h_tot((size_t)6 * n + 1);
+  c.h_adj.resize((size_t)n * nt_e * nt_e);
+  hipError_t e = hipMemcpyAsync(vi.hv.data(), dviews_c, sizeof(ViewDev) * n, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_tot.data(), d_tot, sizeof(int) * (6 * n + 1), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(c.h_adj.data(), d_adj, c.h_adj.size(), hipMemcpyDeviceToHost, st);
+  const double tv1 = now_ms();
+  if (e == hipSuccess) e = stream_wait(st);
+  if (c.dbg_t) fprintf(stderr, "[ptz_ba_create] views: allocations + upload %.3f ms, build enqueued in %.3f ms, waited %.3f ms for it | tracks..sort %.3f, rays..place %.3f, pair arrays %.3f, memset + pairs launches %.3f, copies back %.3f\n", tv0 - tc1, tv1 - tv0, now_ms() - tv1,
+                       tva - tv0, tvb - tva, tvc - tvb, tvd - tvc, tv1 - tvd);
+  b->release_staged();
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) { (void)hipGetLastError(); return PTZ_ENODEVICE; }
+  if (h_tot[(size_t)6 * n]) return PTZ_EINVAL;  // an image twice in one track (tracks.cc:77)
+  b->max_pair = 0; b->max_cam_pair = 0; b->max_cam_ent = 0; b->max_cam_run = 0;
+  for (int i = 0; i < n; ++i) {
+    if (vi.hv[i].n_obs <= 0 || vi.hv[i].n_ray <= 0) return PTZ_ENOOBS;  // no candidate observation: not a problem (:517); its own code, so that callers can tell it from a malformed view
+    SceneDev& sd = b->scenes[i];
+    const int* t = h_tot.data() + 6 * (size_t)i;
+    sd.n_ray = vi.hv[i].n_ray; sd.n_obs = vi.hv[i].n_obs;
+    sd.n_wave = (sd.n_ray + 63) / 64; sd.n_chunk = (sd.n_ray + b->ray_block - 1) / b->ray_block; sd.n_pair = t[0];
+    widen_pair_maxima(b, t);
   }
+  return PTZ_OK;
+}
+
+// packed problems: the host structure, in one staged upload
+int32_t create_upload_structure(ptz_ba_batch* b, CreateCtx& c)
+{
+  Dev& d = b->d;
+  StagedUpload up;
+  up.add(b->scenes, &d.scene);
+  up.add(c.h.uv, &d.obs_uv); up.add(c.h.cam, &d.obs_cam); up.add(c.h.ray, &d.obs_ray);
+  up.add(c.h.rayptr, &d.ray_ptr); up.add(c.h.camptr, &d.cam_ptr);
+  up.add(c.h.camobs, &d.cam_obs); up.add(c.h.wpos, &d.wpos); up.add(c.h.camray, &d.cam_ray); up.add(c.h.camuv, &d.cam_uv);
+  up.add(c.h_pci, &d.pair_ci); up.add(c.h_pcj, &d.pair_cj); up.add(c.h_pbrow, &d.pair_brow); up.add(c.h_pptr, &d.pair_ptr);
+  up.add(c.h.campair, &d.cam_pair); up.add(c.h.camrun, &d.cam_run);
+  up.add(c.h_runs, &d.run_rec); up.add(c.h_prun, &d.pair_run); up.add(c.h_ent, &d.ent); up.add(c.h.w, &d.ray_w);
+  up.add(c.h_o3uv, &d.o3_uv); up.add(c.h_o3xyz, &d.o3_xyz); up.add(c.h_o3cam, &d.o3_cam); up.add(b->ray_perm, &b->d_ray_perm);
+  return up.commit(b);
+}
+
+// PTZ_BA_GPU_STRUCT_CHECK: what the host builder found, kept aside before the device's totals replace it
+struct HostPairTotals { int pair, run, max_cam_pair, max_cam_ent, max_cam_run; std::vector<SceneDev> scenes; };
+int32_t check_pairs_against_host(ptz_ba_batch* b, const CreateCtx& c, const PairsDev& pa, const HostPairTotals& chk)
+{
+  const int n = c.n;
+  long bad = 0;
+  if (chk.pair != b->total_pair || chk.run != b->total_run || chk.max_cam_pair != b->max_cam_pair || chk.max_cam_ent != b->max_cam_ent || chk.max_cam_run != b->max_cam_run) ++bad;
+  for (int i = 0; i < n && !bad; ++i)
+    if (chk.scenes[i].n_pair != b->scenes[i].n_pair || chk.scenes[i].pair_off != b->scenes[i].pair_off || chk.scenes[i].run_off != b->scenes[i].run_off) ++bad;
+  auto cmp = [&](const void* dev, const void* host, size_t bytes, const char* name) {
+    std::vector<unsigned char> tmp(bytes + 1);
+    if (bytes && (hipMemcpyAsync(tmp.data(), dev, bytes, hipMemcpyDeviceToHost, b->io) != hipSuccess || stream_wait(b->io) != hipSuccess)) { ++bad; return; }
+    if (bytes && memcmp(tmp.data(), host, bytes) != 0) { ++bad; fprintf(stderr, "[ptz_ba_create] device-built %s differs from the host builder's\n", name); }
+  };
+  if (!bad) {
+    cmp(pa.pci, c.h_pci.data(), sizeof(int) * c.h_pci.size(), "pair_ci"); cmp(pa.pcj, c.h_pcj.data(), sizeof(int) * c.h_pcj.size(), "pair_cj");
+    cmp(pa.pbrow, c.h_pbrow.data(), sizeof(int) * c.h_pbrow.size(), "pair_brow"); cmp(pa.pptr, c.h_pptr.data(), sizeof(int) * c.h_pptr.size(), "pair_ptr");
+    cmp(pa.prun, c.h_prun.data(), sizeof(int) * c.h_prun.size(), "pair_run");
+    cmp(pa.campair, c.h.campair.data(), sizeof(int) * c.h.campair.size(), "cam_pair"); cmp(pa.camrun, c.h.camrun.data(), sizeof(int) * c.h.camrun.size(), "cam_run");
+    cmp(pa.runs, c.h_runs.data(), sizeof(uint2) * c.h_runs.size(), "run_rec"); cmp(pa.ent, c.h_ent.data(), sizeof(unsigned) * c.h_ent.size(), "ent");
+  }
+  else fprintf(stderr, "[ptz_ba_create] device-built pair totals differ from the host builder's\n");
+  return bad ? PTZ_EINVAL : PTZ_OK;
+}
+
+// packed problems: camera pairs, entry lists and runs on the device (k_pairs) -- count, scan, read the totals back (the arrays are
+// sized exactly), write; then the pairs' cameras come back for the tile structure
+int32_t create_device_pairs(ptz_ba_batch* b, CreateCtx& c)
+{
+  const int n = c.n;
+  Dev& d = b->d;
+  PairsDev pa;
+  pairs_inputs(b, pa);
+  int *d_cnt = nullptr, *d_off3 = nullptr, *d_tot = nullptr, *d_err = nullptr;
+  PTZ_TRY(b->alloc(&d_cnt, (size_t)3 * b->total_cam)); PTZ_TRY(b->alloc(&d_off3, (size_t)3 * b->total_cam));
+  PTZ_TRY(b->alloc(&d_tot, (size_t)6 * n)); PTZ_TRY(b->alloc(&d_err, 1));
+  pa.cam_cnt = d_cnt; pa.cam_off3 = d_off3; pa.scene_tot = d_tot; pa.err = d_err;
+  (void)once_per_device(CAPS_PAIRS, b->device, raise_pairs_caps);
+  if (hipMemsetAsync(d_err, 0, sizeof(int), b->io) != hipSuccess) return PTZ_ENODEVICE;
+  hipLaunchKernelGGL(k_pairs<false>, dim3(b->max_cam, n), dim3(256), c.pairs_lds, b->io, pa);
+  hipLaunchKernelGGL(k_pair_scan, dim3((n + 63) / 64), dim3(64), 0, b->io, d.scene, n, (const int*)d_cnt, d_off3, d_tot);
+  std::vector<int> h_tot((size_t)6 * n + 1);
+  hipError_t e = hipMemcpyAsync(h_tot.data(), d_tot, sizeof(int) * 6 * n, hipMemcpyDeviceToHost, b->io);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_tot.data() + 6 * n, d_err, sizeof(int), hipMemcpyDeviceToHost, b->io);
+  if (e == hipSuccess) e = stream_wait(b->io);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) { (void)hipGetLastError(); return PTZ_ENODEVICE; }
+  if (h_tot[(size_t)6 * n]) return PTZ_EINVAL;  // an image twice in one track (tracks.cc:77)
+  const HostPairTotals chk = {b->total_pair, b->total_run, b->max_cam_pair, b->max_cam_ent, b->max_cam_run,
+                              c.pairs_check ? b->scenes : std::vector<SceneDev>()};
+  if (c.pairs_check) { b->max_cam_pair = 0; b->max_cam_ent = 0; b->max_cam_run = 0; }
+  b->total_pair = 0; b->total_run = 0; b->max_pair = 0;
+  for (int i = 0; i < n; ++i) {
+    SceneDev& sd = b->scenes[i];
+    const int* t = h_tot.data() + 6 * (size_t)i;
+    const int64_t ne = (i + 1 < n ? b->scenes[i + 1].ent_off : b->total_ent) - sd.ent_off;  // (the host's count of the scene's entries, from the track lengths)
+    if (t[1] != ne || (int64_t)b->total_pair + t[0] > 0x7fffffff || (int64_t)b->total_run + t[2] > 0x7fffffff) return PTZ_EINVAL;
+    sd.n_pair = t[0]; sd.pair_off = b->total_pair; sd.run_off = b->total_run;
+    b->total_pair += t[0]; b->total_run += t[2];
+    widen_pair_maxima(b, t);
+  }
+  if (copy_on(b->io, const_cast<SceneDev*>(d.scene), b->scenes.data(), sizeof(SceneDev) * n, hipMemcpyHostToDevice) != hipSuccess) return PTZ_ENODEVICE;
+  PTZ_TRY(alloc_pair_arrays(b, pa));
+  hipLaunchKernelGGL(k_pairs<true>, dim3(b->max_cam, n), dim3(256), c.pairs_lds, b->io, pa);
+  publish_pairs(pa, d);
+  if (c.pairs_check) PTZ_TRY(check_pairs_against_host(b, c, pa, chk));
+  c.h_pci.resize(b->total_pair); c.h_pcj.resize(b->total_pair);
+  e = b->total_pair ? hipMemcpyAsync(c.h_pci.data(), pa.pci, sizeof(int) * b->total_pair, hipMemcpyDeviceToHost, b->io) : hipSuccess;
+  if (e == hipSuccess && b->total_pair) e = hipMemcpyAsync(c.h_pcj.data(), pa.pcj, sizeof(int) * b->total_pair, hipMemcpyDeviceToHost, b->io);
+  if (e == hipSuccess) e = stream_wait(b->io);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) { (void)hipGetLastError(); return PTZ_ENODEVICE; }
+  return PTZ_OK;
+}
+
+// solver state -- parameters, linearisation, LM control -- and the reduced camera systems (the zero fills go on `io`, behind the structure)
+int32_t alloc_solver_state(ptz_ba_batch* b, const CreateCtx& c)
+{
+  const int n = c.n, NC = c.NC, CBS = c.CBS, CDS = c.CDS, type = c.type;
+  const bool disp = c.disp;
+  Dev& d = b->d;
   d.tlw_stride = (size_t)n * 6;
-  TRY(b->alloc(&d.tlw_x, 2 * d.tlw_stride));
-  TRY(b->alloc(&b->tlw0, d.tlw_stride));
+  const size_t cams = (size_t)b->total_cam, rays = (size_t)b->total_ray, o3 = (size_t)b->total_o3;
+  // T_l_w and the 2D-3D term
+  PTZ_TRY(b->alloc(&d.tlw_x, 2 * d.tlw_stride)); PTZ_TRY(b->alloc(&b->tlw0, d.tlw_stride));
   d.tlwblk_stride = (size_t)n * TLWBLK;
-  TRY(b->alloc(&d.tlwblk, 2 * d.tlwblk_stride));
-  TRY(b->alloc(&d.tlwcand, (size_t)n * TLWBLK));
-  TRY(b->alloc(&d.scale_t, (size_t)n * 6));
-  TRY(b->alloc(&d.diag_t, (size_t)n * 6));
-  TRY(b->alloc(&d.Ut, (size_t)n * 36));
-  TRY(b->alloc(&d.gt, (size_t)n * 6));
-  TRY(b->alloc(&d.dt, (size_t)n * 6));
-  TRY(b->alloc(&d.Jc3, (size_t)b->total_o3 * 2 * NC));
-  TRY(b->alloc(&d.Jt3, (size_t)b->total_o3 * 12));
-  TRY(b->alloc(&d.r3, (size_t)b->total_o3 * 2));
-  if (hipMemsetAsync(b->tlw0, 0, sizeof(double) * d.tlw_stride, b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-  d.cam_stride = (size_t)b->total_cam * 15;
-  d.ray_stride = (size_t)b->total_ray * 3;
-  TRY(b->alloc(&d.cam_x, 2 * d.cam_stride));
-  TRY(b->alloc(&d.ray_x, 2 * d.ray_stride));
-  TRY(b->alloc(&b->cam0, d.cam_stride));
+  PTZ_TRY(b->alloc(&d.tlwblk, 2 * d.tlwblk_stride)); PTZ_TRY(b->alloc(&d.tlwcand, (size_t)n * TLWBLK));
+  PTZ_TRY(b->alloc(&d.scale_t, (size_t)n * 6)); PTZ_TRY(b->alloc(&d.diag_t, (size_t)n * 6)); PTZ_TRY(b->alloc(&d.Ut, (size_t)n * 36));
+  PTZ_TRY(b->alloc(&d.gt, (size_t)n * 6)); PTZ_TRY(b->alloc(&d.dt, (size_t)n * 6));
+  PTZ_TRY(b->alloc(&d.Jc3, o3 * 2 * NC)); PTZ_TRY(b->alloc(&d.Jt3, o3 * 12)); PTZ_TRY(b->alloc(&d.r3, o3 * 2));
+  if (hipMemsetAsync(b->tlw0, 0, sizeof(double) * d.tlw_stride, b->io) != hipSuccess) return PTZ_ENODEVICE;
+  // parameters: both halves of the double-buffered state, and the initial one
+  d.cam_stride = cams * 15; d.ray_stride = rays * 3;
+  PTZ_TRY(b->alloc(&d.cam_x, 2 * d.cam_stride)); PTZ_TRY(b->alloc(&d.ray_x, 2 * d.ray_stride)); PTZ_TRY(b->alloc(&b->cam0, d.cam_stride));
   if (disp) {
-    d.dsp_stride = (size_t)b->total_cam * 3;
-    TRY(b->alloc(&d.dsp_x, 2 * d.dsp_stride));
-    TRY(b->alloc(&b->dsp0, d.dsp_stride));
-    if (hipMemsetAsync(b->dsp0, 0, sizeof(double) * d.dsp_stride, b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }  // :655
+    d.dsp_stride = cams * 3;
+    PTZ_TRY(b->alloc(&d.dsp_x, 2 * d.dsp_stride)); PTZ_TRY(b->alloc(&b->dsp0, d.dsp_stride));
+    if (hipMemsetAsync(b->dsp0, 0, sizeof(double) * d.dsp_stride, b->io) != hipSuccess) return PTZ_ENODEVICE;  // :655
   }
-  TRY(b->alloc(&b->ray0, d.ray_stride));
-  d.camblk_stride = ((size_t)b->total_cam * CBS + 2 + 1) & ~(size_t)1;
-  TRY(b->alloc(&d.camblk, 2 * d.camblk_stride));
-  TRY(b->alloc(&d.candblk, (size_t)b->total_cam * CDS + 2));
-  TRY(b->alloc(&d.scale_c, (size_t)b->total_cam * NC));
-  TRY(b->alloc(&d.scale_r, (size_t)b->total_ray * 3));
-  TRY(b->alloc(&d.U, (size_t)2 * b->total_cam * NC * NC));
-  TRY(b->alloc(&d.gc, (size_t)2 * b->total_cam * NC));
-  TRY(b->alloc(&d.costc, (size_t)2 * b->total_cam));
+  PTZ_TRY(b->alloc(&b->ray0, d.ray_stride));
+  // camera side of the linearisation
+  d.camblk_stride = (cams * CBS + 2 + 1) & ~(size_t)1;
+  PTZ_TRY(b->alloc(&d.camblk, 2 * d.camblk_stride)); PTZ_TRY(b->alloc(&d.candblk, cams * CDS + 2));
+  PTZ_TRY(b->alloc(&d.scale_c, cams * NC)); PTZ_TRY(b->alloc(&d.scale_r, rays * 3));
+  PTZ_TRY(b->alloc(&d.U, 2 * cams * NC * NC)); PTZ_TRY(b->alloc(&d.gc, 2 * cams * NC)); PTZ_TRY(b->alloc(&d.costc, 2 * cams));
   d.lin_cams = b->total_cam;
-  TRY(b->alloc(&d.diag_c, (size_t)2 * b->total_cam * NC));
-  TRY(b->alloc(&d.dc, (size_t)b->total_cam * NC));
-  TRY(b->alloc(&d.dct, (size_t)b->total_cam * (NC | 1) + 4));
-  // (two halves each: k_eval leaves the ray-side linearisation of its candidate in the half that LmState.cur does not select)
-  d.V_stride = (size_t)b->total_ray * 6; d.gr_stride = (size_t)b->total_ray * 3;
-  d.rayrec_stride = (size_t)b->total_ray * 8; d.plin_stride = (size_t)b->total_chunk * 2;
-  TRY(b->alloc(&d.V, 2 * d.V_stride));
-  TRY(b->alloc(&d.gr, 2 * d.gr_stride));
-  TRY(b->alloc(&d.diag_r, (size_t)b->total_ray * 3));
-  TRY(b->alloc(&d.E, (size_t)b->total_ray * EZS));  // the rays' records, as EZS / 2 planes of 16-byte pieces (e_piece)
-  d.e_stride = (size_t)b->total_ray;
-  d.shared = any_shared ? 1 : 0;
-  if (any_shared) {
-    TRY(upload(b, h_grpptr, &d.grp_ptr));
-    TRY(upload(b, h_grpmem, &d.grp_mem));
-    TRY(upload(b, h_camflag, &d.cam_flag));
-    if (disp) TRY(upload(b, h_grpcls, &d.grp_cls));
-    TRY(b->alloc(&d.gfold, (size_t)b->total_cam * NC));
+  PTZ_TRY(b->alloc(&d.diag_c, 2 * cams * NC)); PTZ_TRY(b->alloc(&d.dc, cams * NC)); PTZ_TRY(b->alloc(&d.dct, cams * (NC | 1) + 4));
+  // ray side (two halves each: k_eval leaves the ray-side linearisation of its candidate in the half that LmState.cur does not select)
+  d.V_stride = rays * 6; d.gr_stride = rays * 3; d.rayrec_stride = rays * 8; d.plin_stride = (size_t)b->total_chunk * 2;
+  PTZ_TRY(b->alloc(&d.V, 2 * d.V_stride)); PTZ_TRY(b->alloc(&d.gr, 2 * d.gr_stride)); PTZ_TRY(b->alloc(&d.diag_r, rays * 3));
+  PTZ_TRY(b->alloc(&d.E, rays * EZS));  // the rays' records, as EZS / 2 planes of 16-byte pieces (e_piece)
+  d.e_stride = rays;
+  d.shared = c.any_shared ? 1 : 0;
+  if (c.any_shared) {
+    PTZ_TRY(upload(b, c.h_grpptr, &d.grp_ptr));
+    PTZ_TRY(upload(b, c.h_grpmem, &d.grp_mem));
+    PTZ_TRY(upload(b, c.h_camflag, &d.cam_flag));
+    if (disp) PTZ_TRY(upload(b, c.h_grpcls, &d.grp_cls));
+    PTZ_TRY(b->alloc(&d.gfold, (size_t)b->total_cam * NC));
   }
   // W = Jc^T Jr rows are not materialised by the solver (k_schur rebuilds them from the rays); ptz_ba_batch_linearize allocates
   // them when a caller asks for them, PTZ_BA_SCHUR_W=1 brings round 2's kernels back for A/B measurements
-  if (const char* e = getenv("PTZ_BA_SCHUR_W")) b->schur_w = atoi(e) != 0;
-  if (b->schur_w) TRY(b->alloc(&d.W, (size_t)b->total_obs * (disp ? 24 : type == PTZ_BA_PTZRayFxfyDist ? 18 : 16)));  // room for the widest row stride
-  TRY(b->alloc(&d.rayrec, 2 * d.rayrec_stride));
-  TRY(b->alloc(&d.partial, (size_t)b->total_chunk * 4));
-  TRY(b->alloc(&d.partial_lin, 2 * d.plin_stride));
+  b->schur_w = env_flag("PTZ_BA_SCHUR_W", false);
+  if (b->schur_w) PTZ_TRY(b->alloc(&d.W, (size_t)b->total_obs * (disp ? 24 : type == PTZ_BA_PTZRayFxfyDist ? 18 : 16)));  // room for the widest row stride
+  PTZ_TRY(b->alloc(&d.rayrec, 2 * d.rayrec_stride)); PTZ_TRY(b->alloc(&d.partial, (size_t)b->total_chunk * 4)); PTZ_TRY(b->alloc(&d.partial_lin, 2 * d.plin_stride));
   d.ray_block = b->ray_block;
-  TRY(b->alloc(&d.camstep, (size_t)b->total_cam * 2));
-  TRY(b->alloc(&d.cam_gmax, (size_t)2 * b->total_cam));
-  TRY(b->alloc(&d.tail_cnt, (size_t)2 * n));
-  TRY(b->alloc(&d.lm, (size_t)n));
-  TRY(b->alloc(&d.active, (size_t)n));
-  TRY(b->alloc(&d.ray_fail, (size_t)n));
+  // LM control
+  PTZ_TRY(b->alloc(&d.camstep, cams * 2)); PTZ_TRY(b->alloc(&d.cam_gmax, 2 * cams)); PTZ_TRY(b->alloc(&d.tail_cnt, (size_t)2 * n));
+  PTZ_TRY(b->alloc(&d.lm, (size_t)n)); PTZ_TRY(b->alloc(&d.active, (size_t)n)); PTZ_TRY(b->alloc(&d.ray_fail, (size_t)n));
   // reduced camera systems
-  d.chol.count = n;
-  d.chol.np = chol_padded_order(b->max_n);
-  // the systems' orders and (below) their tile structure, elimination order, step schedule and back-substitution lists: ONE upload
-  StagedUpload up2;
+  d.chol.count = n; d.chol.np = chol_padded_order(b->max_n);
+  PTZ_TRY(b->alloc(&d.chol.A, (size_t)n * d.chol.np * d.chol.np));
+  // the one-launch-per-column factorisation (a few scenes, or the last few active scenes of a large batch) publishes its
+  // finished L tiles in a second matrix, indexed by launch slot: up to CHOL_CHAIN_SLOTS slots per scene group
+  const int groups = std::max(1, std::min(b->n_group_hint(n), n));
+  const size_t slots = (size_t)std::min(n, CHOL_CHAIN_SLOTS) * groups;
+  PTZ_TRY(b->alloc(&d.chol.L, slots * d.chol.np * d.chol.np));
+  if (hipMemsetAsync(d.chol.L, 0, sizeof(double) * slots * d.chol.np * d.chol.np, b->io) != hipSuccess) return PTZ_ENODEVICE;
+  PTZ_TRY(b->alloc(&b->d_act, (size_t)n));
+  const size_t ctl_ints = chol_chain_ctl_ints(d.chol.np) * groups;
+  PTZ_TRY(b->alloc(&d.chol.chain_ctl, ctl_ints));
+  if (hipMemsetAsync(d.chol.chain_ctl, 0, sizeof(int) * ctl_ints, b->io) != hipSuccess) return PTZ_ENODEVICE;
+  const size_t diag_tiles = (size_t)n * (d.chol.np / CHOL_NB);
+  PTZ_TRY(b->alloc(&d.chol.Ldiag, diag_tiles * CHOL_NB * CHOL_NB)); PTZ_TRY(b->alloc(&d.chol.Dinv, diag_tiles * 4 * 16 * 16));
+  PTZ_TRY(b->alloc(&d.chol.Linv, diag_tiles * CHOL_NB * CHOL_NB)); PTZ_TRY(b->alloc(&d.chol.fail, (size_t)n));
+  d.chol.active = d.active;
+  return b->alloc(&d.yc, (size_t)n * d.chol.np);
+}
+
+// Tile mask of scene i's reduced camera system, before any reordering: cameras that share a track couple their tiles, the T_l_w
+// block and the rhs row couple to everything.  Views: marked on the device by the same rule (k_view_adjacency).  Returns the first
+// dense tile row.
+int scene_tile_mask(const ptz_ba_batch* b, const CreateCtx& c, int i, int nt, unsigned char* m0)
+{
+  const SceneDev& sd = b->scenes[i];
+  const int NC = c.NC;
+  auto tile_lo = [&](int cam) { return (cam * NC) / CHOL_NB; };
+  auto tile_hi = [&](int cam) { return (cam * NC + NC - 1) / CHOL_NB; };
+  if (c.views) memcpy(m0, c.h_adj.data() + (size_t)i * nt * nt, (size_t)nt * nt);
+  else {
+    memset(m0, 0, (size_t)nt * nt);
+    for (int k = 0; k < sd.n_cam; ++k)
+      for (int a = tile_lo(k); a <= tile_hi(k); ++a)
+        for (int e = tile_lo(k); e <= a; ++e) m0[a * nt + e] = 1;
+    for (int p = 0; p < sd.n_pair; ++p) {
+      const int ci = c.h_pci[sd.pair_off + p], cj = c.h_pcj[sd.pair_off + p];
+      for (int a = tile_lo(ci); a <= tile_hi(ci); ++a)
+        for (int e = tile_lo(cj); e <= tile_hi(cj); ++e) {
+          if (a >= e) m0[a * nt + e] = 1; else m0[e * nt + a] = 1;
+        }
+    }
+  }
+  // shared intrinsics: the fold puts a dense row / column at every group's representative (its last camera)
+  if (c.any_shared) {
+    const int* gp = c.h_grpptr.data() + sd.grp_off + i;
+    for (int g = 0; g < sd.n_grp; ++g) {
+      const int rep = c.h_grpmem[gp[g + 1] - 1];
+      for (int a = tile_lo(rep); a <= tile_hi(rep); ++a) {
+        for (int e = 0; e <= a; ++e) m0[a * nt + e] = 1;
+        for (int r = a; r < nt; ++r) m0[r * nt + a] = 1;
+      }
+    }
+  }
+  // dense rows: the global block (if any) and the rhs row, index n_cam * NC .. n
+  const int first_dense = (sd.n_cam * NC) / CHOL_NB;
+  for (int a = first_dense; a < nt; ++a)
+    for (int e = 0; e <= a; ++e) m0[a * nt + e] = 1;
+  return first_dense;
+}
+
+// The systems' orders and their tile structure, elimination order, step schedule and back-substitution lists: ONE upload.
+// The tiles are eliminated in the order plan_dissection picks (arcs of a ring side by side, separators last) when that shortens
+// the dependent chain of the factorisation; Dev::tperm carries the order to the kernels, CholBatch::sched the steps.
+int32_t create_tile_plan(ptz_ba_batch* b, const CreateCtx& c)
+{
+  const int n = c.n;
+  Dev& d = b->d;
+  StagedUpload up;
   std::vector<int> hn(n);
   for (int i = 0; i < n; ++i) hn[i] = b->scenes[i].n;
-  up2.add(hn, &d.chol.n);
+  up.add(hn, &d.chol.n);
   std::vector<unsigned char> hm;
-  std::vector<int> h_tperm, h_sched, h_groups;
-  std::vector<BsItem> h_items;
-  TRY(b->alloc(&d.chol.A, (size_t)n * d.chol.np * d.chol.np));
-  {
-    // the one-launch-per-column factorisation (a few scenes, or the last few active scenes of a large batch) publishes its
-    // finished L tiles in a second matrix, indexed by launch slot: up to CHOL_CHAIN_SLOTS slots per scene group
-    const int groups = std::max(1, std::min(b->n_group_hint(n), n));
-    const size_t slots = (size_t)std::min(n, CHOL_CHAIN_SLOTS) * groups;
-    TRY(b->alloc(&d.chol.L, slots * d.chol.np * d.chol.np));
-    if (hipMemsetAsync(d.chol.L, 0, sizeof(double) * slots * d.chol.np * d.chol.np, b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-    TRY(b->alloc(&b->d_act, (size_t)n));
-    const size_t ctl_ints = chol_chain_ctl_ints(d.chol.np) * groups;
-    TRY(b->alloc(&d.chol.chain_ctl, ctl_ints));
-    if (hipMemsetAsync(d.chol.chain_ctl, 0, sizeof(int) * ctl_ints, b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-  }
-  TRY(b->alloc(&d.chol.Ldiag, (size_t)n * (d.chol.np / CHOL_NB) * CHOL_NB * CHOL_NB));
-  TRY(b->alloc(&d.chol.Dinv, (size_t)n * (d.chol.np / CHOL_NB) * 4 * 16 * 16));
-  TRY(b->alloc(&d.chol.Linv, (size_t)n * (d.chol.np / CHOL_NB) * CHOL_NB * CHOL_NB));
-  TRY(b->alloc(&d.chol.fail, (size_t)n));
-  d.chol.active = d.active;
-  TRY(b->alloc(&d.yc, (size_t)n * d.chol.np));
-  tc2 = now_ms();
-  // Tile-level structure of every reduced camera system: cameras that share a track couple their tiles, the T_l_w
-  // block and the rhs row couple to everything; closed under the fill of the right-looking factorisation.  The tiles are
-  // eliminated in the order plan_dissection picks (arcs of a ring side by side, separators last) when that shortens the
-  // dependent chain of the factorisation; Dev::tperm carries the order to the kernels, CholBatch::sched the steps.
+  std::vector<int> h_tperm, h_sched, h_groups; std::vector<BsItem> h_items;
   if (!getenv("PTZ_BA_DENSE_CHOL")) {
     const int nt = d.chol.np / CHOL_NB;
-    bool dissect = true;
-    bool nested = true;
+    bool dissect = true, nested = true;
     if (const char* e = getenv("PTZ_BA_ORDER")) { dissect = strcmp(e, "natural") != 0; nested = strcmp(e, "flat") != 0; }
     hm.assign((size_t)n * nt * nt, 0);
-    h_tperm.resize((size_t)n * nt); h_sched.assign((size_t)n * nt * CHOL_STEP_COLS, -1);
-    int max_steps = 0;
-    bool any_plan = false;
+    h_tperm.resize((size_t)n * nt); h_sched.resize((size_t)n * nt * CHOL_STEP_COLS);
+    int max_steps = 0; bool any_plan = false;
     std::vector<unsigned char> m0((size_t)nt * nt);
     for (int i = 0; i < n; ++i) {
-      const SceneDev& sd = b->scenes[i];
-      std::fill(m0.begin(), m0.end(), 0);
-      auto tile_lo = [&](int cam) { return (cam * NC) / CHOL_NB; };
-      auto tile_hi = [&](int cam) { return (cam * NC + NC - 1) / CHOL_NB; };
-      if (vm) memcpy(m0.data(), h_adj.data() + (size_t)i * nt * nt, (size_t)nt * nt);  // (marked on the device by the same rule: k_view_adjacency)
-      for (int c = 0; !vm && c < sd.n_cam; ++c)
-        for (int a = tile_lo(c); a <= tile_hi(c); ++a)
-          for (int e = tile_lo(c); e <= a; ++e) m0[a * nt + e] = 1;
-      for (int p = 0; !vm && p < sd.n_pair; ++p) {
-        const int ci = h_pci[sd.pair_off + p], cj = h_pcj[sd.pair_off + p];
-        for (int a = tile_lo(ci); a <= tile_hi(ci); ++a)
-          for (int e = tile_lo(cj); e <= tile_hi(cj); ++e) {
-            if (a >= e) m0[a * nt + e] = 1; else m0[e * nt + a] = 1;
-          }
-      }
-      // shared intrinsics: the fold puts a dense row / column at every group's representative (its last camera)
-      if (any_shared) {
-        const int* gp = h_grpptr.data() + sd.grp_off + i;
-        for (int g = 0; g < sd.n_grp; ++g) {
-          const int rep = h_grpmem[gp[g + 1] - 1];
-          for (int a = tile_lo(rep); a <= tile_hi(rep); ++a) {
-            for (int e = 0; e <= a; ++e) m0[a * nt + e] = 1;
-            for (int r = a; r < nt; ++r) m0[r * nt + a] = 1;
-          }
-        }
-      }
-      // dense rows: the global block (if any) and the rhs row, index n_cam * NC .. n
-      const int first_dense = (sd.n_cam * NC) / CHOL_NB;
-      for (int a = first_dense; a < nt; ++a)
-        for (int e = 0; e <= a; ++e) m0[a * nt + e] = 1;
+      const int first_dense = scene_tile_mask(b, c, i, nt, m0.data());
       int* perm = h_tperm.data() + (size_t)i * nt;
       int* sched = h_sched.data() + (size_t)i * nt * CHOL_STEP_COLS;
       int lane_a = 0, lane_b = 0;
-      const bool planned = dissect && sd.n_grp == 0 && plan_dissection(nt, first_dense, m0.data(), perm, &lane_a, &lane_b, nested);
+      const bool planned = dissect && b->scenes[i].n_grp == 0 && plan_dissection(nt, first_dense, m0.data(), perm, &lane_a, &lane_b, nested);
       if (!planned) for (int t = 0; t < nt; ++t) perm[t] = t;
       if (planned) any_plan = true;
-      unsigned char* m = hm.data() + (size_t)i * nt * nt;
-      for (int a = 0; a < nt; ++a)
-        for (int e = 0; e <= a; ++e) {
-          if (!m0[a * nt + e]) continue;
-          const int pa = perm[a], pe = perm[e];
-          m[std::max(pa, pe) * nt + std::min(pa, pe)] = 1;
-        }
-      for (int k = 0; k < nt; ++k)
-        for (int x = k + 1; x < nt; ++x) {
-          if (!m[x * nt + k]) continue;
-          for (int y = k + 1; y <= x; ++y)
-            if (m[y * nt + k]) m[x * nt + y] = 1;
-        }
-      // steps: from the filled structure when the order was planned, one block column after the other otherwise
-      int steps = 0;
-      if (planned) steps = level_schedule(nt, m, sched);
-      else for (int t = 0; t < nt; ++t, ++steps) sched[CHOL_STEP_COLS * steps] = t;
+      const int steps = fill_and_schedule(nt, m0.data(), planned ? perm : nullptr, hm.data() + (size_t)i * nt * nt, sched);
       max_steps = std::max(max_steps, steps);
       if ((int)b->sched_kmin.size() < steps) b->sched_kmin.resize(steps, nt);
       for (int st = 0; st < steps; ++st) b->sched_kmin[st] = std::min(b->sched_kmin[st], sched[CHOL_STEP_COLS * st]);  // (slot 0 of a step holds its smallest column)
-      if (dbg_t && i == 0) fprintf(stderr, "[ptz_ba_create] scene 0: %d tiles, elimination %s: lanes %d + %d, %d steps\n", nt, planned ? "dissected" : "natural", lane_a, lane_b, steps);
+      if (c.dbg_t && i == 0) fprintf(stderr, "[ptz_ba_create] scene 0: %d tiles, elimination %s: lanes %d + %d, %d steps\n", nt, planned ? "dissected" : "natural", lane_a, lane_b, steps);
     }
-    up2.add(hm, &d.chol.tmask);
+    up.add(hm, &d.chol.tmask);
     if (any_plan) {
-      up2.add(h_tperm, &d.tperm);  // (d.chol.xperm = d.tperm once the upload has placed it)
-      up2.add(h_sched, &d.chol.sched);
+      up.add(h_tperm, &d.tperm);  // (d.chol.xperm = d.tperm once the upload has placed it)
+      up.add(h_sched, &d.chol.sched);
       d.chol.n_steps = max_steps;
       d.chol.sched_kmin = b->sched_kmin.data();
     }
-    {  // the back-substitution's work list, per scene (the kernel would otherwise make it itself, every launch: ~6 us of one wave)
-      const int mg = chol_backsolve_max_groups(d.chol.np);
-      const char* e = getenv("PTZ_BA_BACKSOLVE_HOST_LIST");  // 0: the kernel makes the list itself (tests: the same list, the same bits)
-      // (mg <= 1024: chol_backsolve_kernel keeps the kinds of the host list's groups in a fixed array of that many)
-      if ((!e || atoi(e) != 0) && mg <= 1024 && sizeof(double) * ((size_t)d.chol.np + 1024) + sizeof(BsItem) * 4 * (size_t)mg <= 150 * 1024) {  // (the kernel's own list form applies)
-        h_items.resize((size_t)n * 4 * mg);
-        h_groups.resize(n);
-        // a few systems: the two arcs of a dissected system on a workgroup each (chol_backsolve_arcs); PTZ_BA_BACKSOLVE_SPLIT=0: one workgroup
-        const char* es = getenv("PTZ_BA_BACKSOLVE_SPLIT");
-        const bool want_split = any_plan && n <= 8 && nt <= 64 && !(es && atoi(es) == 0);
-        for (int i = 0; i < n; ++i) {
-          bool split = false;
-          h_groups[i] = chol_backsolve_plan(d.chol.np, b->scenes[i].n, hm.data() + (size_t)i * nt * nt,
-                                            any_plan ? h_sched.data() + (size_t)i * nt * CHOL_STEP_COLS : nullptr, max_steps, h_items.data() + (size_t)i * 4 * mg,
-                                            want_split, &split);
-          if (split) d.chol.bs_split = 1;
-        }
-        up2.add(h_items, &d.chol.bs_items);
-        up2.add(h_groups, &d.chol.bs_groups);
+    // the back-substitution's work list, per scene (the kernel would otherwise make it itself, every launch: ~6 us of one wave)
+    const int mg = chol_backsolve_max_groups(d.chol.np);
+    const char* e = getenv("PTZ_BA_BACKSOLVE_HOST_LIST");  // 0: the kernel makes the list itself (tests: the same list, the same bits)
+    // (mg <= 1024: chol_backsolve_kernel keeps the kinds of the host list's groups in a fixed array of that many)
+    if ((!e || atoi(e) != 0) && mg <= 1024 && sizeof(double) * ((size_t)d.chol.np + 1024) + sizeof(BsItem) * 4 * (size_t)mg <= 150 * 1024) {  // (the kernel's own list form applies)
+      h_items.resize((size_t)n * 4 * mg);
+      h_groups.resize(n);
+      // a few systems: the two arcs of a dissected system on a workgroup each (chol_backsolve_arcs); PTZ_BA_BACKSOLVE_SPLIT=0: one workgroup
+      const char* es = getenv("PTZ_BA_BACKSOLVE_SPLIT");
+      const bool want_split = any_plan && n <= 8 && nt <= 64 && !(es && atoi(es) == 0);
+      for (int i = 0; i < n; ++i) {
+        bool split = false;
+        h_groups[i] = chol_backsolve_plan(d.chol.np, b->scenes[i].n, hm.data() + (size_t)i * nt * nt,
+                                          any_plan ? h_sched.data() + (size_t)i * nt * CHOL_STEP_COLS : nullptr, max_steps, h_items.data() + (size_t)i * 4 * mg,
+                                          want_split, &split);
+        if (split) d.chol.bs_split = 1;
       }
+      up.add(h_items, &d.chol.bs_items);
+      up.add(h_groups, &d.chol.bs_groups);
     }
     // tiles outside the structure are never written again: zero everything once (the block may be a recycled one)
-    if (hipMemsetAsync(d.chol.A, 0, sizeof(double) * (size_t)n * d.chol.np * d.chol.np, b->io) != hipSuccess) { ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
+    if (hipMemsetAsync(d.chol.A, 0, sizeof(double) * (size_t)n * d.chol.np * d.chol.np, b->io) != hipSuccess) return PTZ_ENODEVICE;
   }
-  TRY(up2.commit(b, /*wait=*/false));  // (the wait for the zero fills at the end of this function ends it)
+  PTZ_TRY(up.commit(b, /*wait=*/false));  // (the hand-over event at the end of create ends it)
   d.chol.xperm = d.tperm;
-#undef TRY
+  return PTZ_OK;
+}
+
+// The solver's options, the knobs of the pass pipeline, the scene groups with their streams and control blocks, the launch shapes
+int32_t create_pipeline(ptz_ba_batch* b, const CreateCtx& c)
+{
+  const int n = c.n;
+  const ptz_lm_options& o = c.o;
+  Dev& d = b->d;
   d.cam_x0 = b->cam0; d.ray_x0 = b->ray0;
-  d.opt.max_num_iterations = o.max_num_iterations;
-  d.opt.max_consecutive_invalid = o.max_num_consecutive_invalid_steps;
-  d.opt.jacobi_scaling = o.jacobi_scaling;
-  d.opt.initial_radius = o.initial_trust_region_radius;
-  d.opt.max_radius = o.max_trust_region_radius;
-  d.opt.min_radius = o.min_trust_region_radius;
-  d.opt.min_relative_decrease = o.min_relative_decrease;
-  d.opt.min_lm_diagonal = o.min_lm_diagonal;
-  d.opt.max_lm_diagonal = o.max_lm_diagonal;
-  d.opt.function_tolerance = o.function_tolerance;
-  d.opt.gradient_tolerance = o.gradient_tolerance;
-  d.opt.parameter_tolerance = o.parameter_tolerance;
+  d.opt.max_num_iterations = o.max_num_iterations; d.opt.max_consecutive_invalid = o.max_num_consecutive_invalid_steps;
+  d.opt.jacobi_scaling = o.jacobi_scaling; d.opt.min_relative_decrease = o.min_relative_decrease;
+  d.opt.initial_radius = o.initial_trust_region_radius; d.opt.max_radius = o.max_trust_region_radius; d.opt.min_radius = o.min_trust_region_radius;
+  d.opt.min_lm_diagonal = o.min_lm_diagonal; d.opt.max_lm_diagonal = o.max_lm_diagonal;
+  d.opt.function_tolerance = o.function_tolerance; d.opt.gradient_tolerance = o.gradient_tolerance; d.opt.parameter_tolerance = o.parameter_tolerance;
   // Two independently pipelined groups for batches: the groups drift out of phase, so the latency-bound block-column chain of
   // one overlaps the throughput kernels of the other (measured on the 256-scene C2 batch: 35.0k -> 36.8k LM it/s; four groups
   // 36.2k, six slower than one).  Small batches stay in one group.
-  b->n_group = n >= 32 ? 2 : 1;
-  if (const char* e = getenv("PTZ_BA_STREAMS")) b->n_group = std::max(1, atoi(e));
-  b->lookahead = n >= 8;  // look-ahead pays for mid-size batches; a single scene is better off with fewer launches
-  if (const char* e = getenv("PTZ_BA_LOOKAHEAD")) b->lookahead = atoi(e) != 0;
+  b->n_group = b->n_group_hint(n);
+  b->lookahead = env_flag("PTZ_BA_LOOKAHEAD", n >= 8);  // look-ahead pays for mid-size batches; a single scene is better off with fewer launches
   // batches: left-looking column updates (half the tile traffic, no trailing-update launches); a few scenes: right-looking,
   // whose updates of one column step spread over many workgroups instead of looping inside one (measured: 256 scenes
   // 141.9 -> 137.8 ms, single scene 16.4 -> 19.4 ms with the left-looking form)
-  b->left_looking = n >= 8;
-  if (const char* e = getenv("PTZ_BA_CHOL_LEFT")) b->left_looking = atoi(e) != 0;
+  b->left_looking = env_flag("PTZ_BA_CHOL_LEFT", n >= 8);
   // (small batches -- the view batches of the incremental pipeline converge in two or three passes -- run two ahead: every pass
   //  enqueued beyond the last real one is a dozen empty launches; large batches, whose passes last milliseconds, keep three)
-  b->ahead = n <= 32 ? 2 : 3;
-  if (const char* e = getenv("PTZ_BA_AHEAD")) b->ahead = std::max(1, atoi(e));
+  b->ahead = env_int("PTZ_BA_AHEAD", n <= 32 ? 2 : 3, 1);
   // compacted (item, slot) launches deal their workgroups over the XCDs by the device's live count (ptz_xcd_map.h); 0: by the grid
-  b->d.xcd_live = 1;
-  if (const char* e = getenv("PTZ_BA_XCD_LIVE")) b->d.xcd_live = atoi(e) != 0;
-  b->d.chol.xcd_live = b->d.xcd_live;
-  if (const char* e = getenv("PTZ_BA_DEBUG_STALL")) b->d.debug_stall = std::max(0, atoi(e));
-  if (const char* e = getenv("PTZ_BA_DEBUG_CHAIN_SPIN")) b->d.chol.chain_spin_limit = std::max(0, atoi(e));  // tests: hand-overs that time out
-  if (const char* e = getenv("PTZ_BA_GRAPH")) b->use_graph = atoi(e) != 0;
+  d.xcd_live = d.chol.xcd_live = env_flag("PTZ_BA_XCD_LIVE", true);
+  d.debug_stall = env_int("PTZ_BA_DEBUG_STALL", d.debug_stall, 0);
+  d.chol.chain_spin_limit = env_int("PTZ_BA_DEBUG_CHAIN_SPIN", d.chol.chain_spin_limit, 0);  // tests: hand-overs that time out
+  b->use_graph = env_flag("PTZ_BA_GRAPH", b->use_graph);
   b->ctl_groups = std::max(1, std::min(b->n_group, n));
   if (b->alloc(&b->d_ctl, (size_t)4 * b->ctl_groups) != PTZ_OK ||
       ptzpool::pinned_acquire(sizeof(int) * 4 * b->ctl_groups, (void**)&b->h_ctl) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&b->h_ctl_dev, b->h_ctl, 0) != hipSuccess) {
-    ptz_ba_batch_destroy(b);
+      hipHostGetDevicePointer((void**)&b->h_ctl_dev, b->h_ctl, 0) != hipSuccess)
     return PTZ_ENODEVICE;
-  }
   make_groups(b);
   b->stream = b->streams.empty() ? nullptr : b->streams[0];
   if (b->stream == nullptr || ptzpool::event_acquire(b->device, true, &b->ev0) != hipSuccess ||
-      ptzpool::event_acquire(b->device, true, &b->ev1) != hipSuccess) {
-    ptz_ba_batch_destroy(b);
+      ptzpool::event_acquire(b->device, true, &b->ev1) != hipSuccess)
     return PTZ_ENODEVICE;
-  }
+  // ---- the launch-shape ladder (PassShape): the full size, then compacted shapes
+  const int NC = c.NC, CBS = c.CBS, CDS = c.CDS;
   // kernels that stage camera tables need > 64 KiB of dynamic LDS for large rigs
   // Rigs whose camera tables do not fit in LDS (the 160 KiB hold ~340 cameras) read them from global memory instead: the
   // reference has no cap on the number of views (ptzray_optimizer.cc:799-885)
-  b->gtab = sizeof(double) * ((size_t)b->max_cam * (CBS + CDS + (NC | 1)) + 16 + 18) + (size_t)OBS_PREFETCH_BYTES * 256 > 160 * 1024;
-  if (const char* e = getenv("PTZ_BA_GLOBAL_TABLES")) b->gtab = atoi(e) != 0;
-  b->compaction = true;
-  if (const char* e = getenv("PTZ_BA_COMPACT")) b->compaction = atoi(e) != 0;
-  b->exact_fit = true;
-  if (const char* e = getenv("PTZ_BA_EXACT_FIT")) b->exact_fit = atoi(e) != 0;
+  b->gtab = env_flag("PTZ_BA_GLOBAL_TABLES", sizeof(double) * ((size_t)b->max_cam * (CBS + CDS + (NC | 1)) + 16 + 18) + (size_t)OBS_PREFETCH_BYTES * 256 > 160 * 1024);
+  b->compaction = env_flag("PTZ_BA_COMPACT", true);
+  b->exact_fit = env_flag("PTZ_BA_EXACT_FIT", true);
   auto make_shape = [&](int slots, bool compact) {
     PassShape sh;
     sh.slots = slots; sh.compact = compact;
-    // rays per workgroup of the ray-centric kernels: one rig's ~13 k rays on 1024-ray workgroups keep 14 compute units busy,
-    // so a few scenes use small workgroups; large batches amortise the LDS camera tables over many rays (results do not
-    // depend on it: per-ray sums are reduced per wave of 64 rays)
-    sh.ray_block = slots <= 4 ? 128 : (slots <= 32 ? 256 : RAY_BLOCK);
-    if (const char* e = getenv("PTZ_BA_RAY_BLOCK")) sh.ray_block = std::min(RAY_BLOCK, std::max(64, (atoi(e) / 64) * 64));
+    sh.ray_block = ray_block_for(slots);
     sh.small_blocks = sh.ray_block <= 256;
     // one launch per factorisation (chol_chain_kernel) or per step (chol_col_step_kernel) for a few systems; up to CHOL_CHAIN_SLOTS when
     // the one-launch form takes them (chol_chain_fits)
-    sh.fused = slots <= 8 || chol_chain_fits(slots, b->d.chol.np);
-    if (const char* e = getenv("PTZ_BA_CHOL_FUSED")) sh.fused = atoi(e) != 0 && sh.fused;
+    sh.fused = (slots <= 8 || chol_chain_fits(slots, b->d.chol.np)) && env_flag("PTZ_BA_CHOL_FUSED", true);
     // a few scenes: LM control and the camera update ride in the tails / prologue of k_eval and k_lin_cam (three launches less per pass)
-    sh.fuse_ctl = slots <= 8 && sh.small_blocks && !b->gtab;
-    if (const char* e = getenv("PTZ_BA_FUSE_CTL")) sh.fuse_ctl = sh.fuse_ctl && atoi(e) != 0;
-    sh.eval_lanes = (sh.fuse_ctl && sh.ray_block <= 128) ? 4 : 1;
-    if (const char* e = getenv("PTZ_BA_EVAL_LANES")) sh.eval_lanes = (atoi(e) == 4 && sh.fuse_ctl && sh.ray_block <= 128) ? 4 : 1;  // (tests: the same bits either way)
+    sh.fuse_ctl = slots <= 8 && sh.small_blocks && !b->gtab && env_flag("PTZ_BA_FUSE_CTL", true);
+    sh.eval_lanes = (sh.fuse_ctl && sh.ray_block <= 128 && env_int("PTZ_BA_EVAL_LANES", 4, 1) == 4) ? 4 : 1;  // (tests: the same bits either way)
     sh.max_chunk = (b->max_ray + sh.ray_block - 1) / sh.ray_block;
     const size_t obs_lds = sh.small_blocks ? (size_t)OBS_PREFETCH_BYTES * sh.ray_block : 0;
     if (b->gtab) { sh.eval_smem = sizeof(double) * 16 + obs_lds + 16; sh.lin_smem = obs_lds + 16; }
@@ -2210,92 +2205,111 @@ static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_
     return sh;
   };
   b->shapes.clear();
-  b->shapes.push_back(make_shape(n, false));
+  b->shapes.push_back(make_shape(n, false));  // (its ray_block is the batch's: ray_block_for(n))
   // (two slots: the last rigs of a large batch get the one-launch factorisation, chol_chain_kernel; a batch of up to eight keeps
   //  its single shape -- a second one costs it a k_compact launch per pass)
   for (int sl = n > 8 ? 2 : 8; sl < n; sl *= 4) b->shapes.push_back(make_shape(sl, true));
-  b->ray_block = b->shapes[0].ray_block;
-  b->d.ray_block = b->ray_block;
-  const int eval_smem = (int)b->shapes[0].eval_smem, lin_smem = (int)b->shapes[0].lin_smem;
+  return PTZ_OK;
+}
+
+// Which Schur kernel, where its T table lives, and the limits of what LDS holds
+int32_t create_schur_limits(ptz_ba_batch* b, const CreateCtx& c)
+{
+  const int NC = c.NC, type = c.type;
   // k_schur keeps a camera's T_a rows in LDS (up to ~1700 observations of one view); beyond that the table goes to global
   // memory.  What remains is the 16-bit position inside the camera-pair entry records: 65535 observations per view.
-  if (b->max_cam_obs > 65535) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
+  if (b->max_cam_obs > 65535) return PTZ_ELIMIT;
   // (also when a view has more runs than a workgroup has threads -- more pairs than that: the several rounds k_schur then needs
   // cannot reuse the table's LDS space for their sums)
-  const int NW2d = NC - ((has3d && type != PTZ_BA_PTZRayFxfyDist) ? 1 : 0);  // Dims<TYPE>::NW
+  const int NW2d = NC - ((c.has3d && type != PTZ_BA_PTZRayFxfyDist) ? 1 : 0);  // Dims<TYPE>::NW
   b->d.schur_ent_cap = b->max_cam_ent;
   for (auto& dgp : b->dg) dgp.schur_ent_cap = b->max_cam_ent;
   // PTZRay: the factored rows of k_schur_f (8 doubles per observation instead of 15: three workgroups per compute unit, and
   // the LDS table holds views of ~2000 observations); PTZ_BA_SCHUR_F=0 keeps k_schur (A/B measurements)
-  b->schur_f = type == PTZ_BA_PTZRay && !b->schur_w;
-  if (const char* e = getenv("PTZ_BA_SCHUR_F")) b->schur_f = b->schur_f && atoi(e) != 0;
+  b->schur_f = type == PTZ_BA_PTZRay && !b->schur_w && env_flag("PTZ_BA_SCHUR_F", true);
   const int frow = b->schur_f ? SCHUR_F_ROW : 0;
   b->d.e_fold = b->schur_f ? 1 : 0;
   for (auto& dgp : b->dg) dgp.e_fold = b->d.e_fold;
   b->schur_tg = schur_lds_bytes(b->max_cam_obs, NC, b->d.chol.np, b->schur_w, schur_threads_of(type), NW2d, b->max_cam_ent, frow) > 160 * 1024 ||
                 (!b->schur_w && b->max_cam_run > schur_threads_of(type));
-  if (!b->schur_w && schur_lds_bytes(0, NC, b->d.chol.np, false, schur_threads_of(type), NW2d, b->max_cam_ent, frow) > 160 * 1024) {
-    ptz_ba_batch_destroy(b);  // a view with more pair entries than the LDS copy of its list holds (~60 000)
-    return PTZ_ELIMIT;
-  }
-  if (const char* e = getenv("PTZ_BA_SCHUR_GLOBAL_T")) b->schur_tg = atoi(e) != 0;
+  // a view with more pair entries than the LDS copy of its list holds (~60 000)
+  if (!b->schur_w && schur_lds_bytes(0, NC, b->d.chol.np, false, schur_threads_of(type), NW2d, b->max_cam_ent, frow) > 160 * 1024) return PTZ_ELIMIT;
+  b->schur_tg = env_flag("PTZ_BA_SCHUR_GLOBAL_T", b->schur_tg);
   if (b->schur_tg) {
-    const int rc2 = b->alloc(&b->d.Tbuf, (size_t)b->total_obs * ((NC * 3 + 3) | 1));
-    if (rc2) { ptz_ba_batch_destroy(b); return rc2; }
+    PTZ_TRY(b->alloc(&b->d.Tbuf, (size_t)b->total_obs * ((NC * 3 + 3) | 1)));
     for (auto& dgp : b->dg) dgp.Tbuf = b->d.Tbuf;
   }
-  if (eval_smem > 160 * 1024 || lin_smem > 160 * 1024) { ptz_ba_batch_destroy(b); return PTZ_ELIMIT; }
-  {
-    // The cap on dynamic LDS is a property of the kernel, not of a batch: raise it to the hardware limit once per device
-    // and instantiation, so that batches of different sizes can live side by side (a per-batch value would let a small
-    // batch created later lower the cap under a large one).
-    static std::mutex attr_mu;
-    static std::vector<char> attr_done;
-    std::lock_guard<std::mutex> lk(attr_mu);
-    if ((int)attr_done.size() <= o.device_id) attr_done.resize(o.device_id + 1, 0);
-    if (!attr_done[o.device_id]) {
-      bool attr_ok = true;
-      auto raise_cap = [&](const void* fn) {
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { attr_ok = false; return; }
-        const int cap = 160 * 1024 - (int)fa.sharedSizeBytes;  // the statically declared part counts against the same 160 KB
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) attr_ok = false;
-      };
-#define PTZ_SET_ATTR(T)                        \
-      raise_cap((const void*)k_schur<T, false>);      \
-      raise_cap((const void*)k_schur<T, true>);       \
-      raise_cap((const void*)k_schur_w<T, false>);    \
-      raise_cap((const void*)k_schur_w<T, true>);     \
-      raise_cap((const void*)k_eval<T, true, false>);       \
-      raise_cap((const void*)k_eval<T, false, false>);      \
-      raise_cap((const void*)k_lin_ray<T, true, false>);    \
-      raise_cap((const void*)k_lin_ray<T, false, false>);
-      raise_cap((const void*)k_eval<0, true, false, true>);
-      raise_cap((const void*)k_eval<0, true, false, true, 4>);
-      raise_cap((const void*)k_eval<1, true, false, true, 4>);
-      raise_cap((const void*)k_eval<2, true, false, true, 4>);
-      raise_cap((const void*)k_schur_f<0, false>);
-      raise_cap((const void*)k_schur_f<0, true>);
-      raise_cap((const void*)k_schur_f<4, false>);
-      raise_cap((const void*)k_schur_f<4, true>);
-      raise_cap((const void*)k_eval<1, true, false, true>);
-      raise_cap((const void*)k_eval<2, true, false, true>);
-      PTZ_SET_ATTR(0) PTZ_SET_ATTR(1) PTZ_SET_ATTR(2) PTZ_SET_ATTR(3) PTZ_SET_ATTR(4) PTZ_SET_ATTR(5) PTZ_SET_ATTR(6) PTZ_SET_ATTR(7)
+  if (b->shapes[0].eval_smem > 160 * 1024 || b->shapes[0].lin_smem > 160 * 1024) return PTZ_ELIMIT;
+  return PTZ_OK;
+}
+
+// dynamic LDS caps of the pass kernels, at the hardware limit
+bool raise_pass_caps()
+{
+  bool attr_ok = true;
+  auto raise_cap = [&](const void* fn) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, fn) != hipSuccess) { attr_ok = false; return; }
+    const int cap = 160 * 1024 - (int)fa.sharedSizeBytes;  // the statically declared part counts against the same 160 KB
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) attr_ok = false;
+  };
+#define PTZ_SET_ATTR(T)                                                                                     \
+  raise_cap((const void*)k_schur<T, false>); raise_cap((const void*)k_schur<T, true>);                      \
+  raise_cap((const void*)k_schur_w<T, false>); raise_cap((const void*)k_schur_w<T, true>);                  \
+  raise_cap((const void*)k_eval<T, true, false>); raise_cap((const void*)k_eval<T, false, false>);          \
+  raise_cap((const void*)k_lin_ray<T, true, false>); raise_cap((const void*)k_lin_ray<T, false, false>);
+  raise_cap((const void*)k_eval<0, true, false, true>); raise_cap((const void*)k_eval<1, true, false, true>); raise_cap((const void*)k_eval<2, true, false, true>);
+  raise_cap((const void*)k_eval<0, true, false, true, 4>); raise_cap((const void*)k_eval<1, true, false, true, 4>); raise_cap((const void*)k_eval<2, true, false, true, 4>);
+  raise_cap((const void*)k_schur_f<0, false>); raise_cap((const void*)k_schur_f<0, true>);
+  raise_cap((const void*)k_schur_f<4, false>); raise_cap((const void*)k_schur_f<4, true>);
+  PTZ_SET_ATTR(0) PTZ_SET_ATTR(1) PTZ_SET_ATTR(2) PTZ_SET_ATTR(3) PTZ_SET_ATTR(4) PTZ_SET_ATTR(5) PTZ_SET_ATTR(6) PTZ_SET_ATTR(7)
 #undef PTZ_SET_ATTR
-      if (!attr_ok) { (void)hipGetLastError(); ptz_ba_batch_destroy(b); return PTZ_ENODEVICE; }
-      attr_done[o.device_id] = 1;
-    }
+  return attr_ok;
+}
+}  // namespace
+
+// views == nullptr: the n packed problems.  Else: the packed problems of n views of resident rigs, built on the device
+// (ptz_view_kernels.h) -- the structure arrays then have the extents of the WHOLE rigs (nothing is read back to size them),
+// each scene's real counts live in its SceneDev.
+static int32_t create_impl(int32_t n, const ptz_ba_problem* problems, const ptz_rig_view* views, int32_t view_type, const ptz_lm_options* opt,
+                           ptz_ba_batch** out)
+{
+  *out = nullptr;
+  const double tc0 = now_ms();
+  CreateCtx c;
+  PTZ_TRY(create_validate(n, problems, views, view_type, opt, c));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c.o.device_id) return PTZ_ENODEVICE;
+  PTZ_DEVICE_GUARD(c.o.device_id);
+  BatchOwner owner(new ptz_ba_batch());  // from here on every return destroys what has been built
+  ptz_ba_batch* b = owner.get();
+  b->has3d = c.has3d; b->views_mode = views != nullptr;
+  b->n_scene = n; b->type = c.type; b->nc = c.NC; b->opt = c.o; b->device = c.o.device_id;
+  if (ptzpool::stream_acquire(b->device, &b->io) != hipSuccess) return PTZ_ENODEVICE;
+  b->ray_block = ray_block_for(n);
+  PTZ_TRY(create_layout(b, c));
+  const double tc1 = now_ms();
+  memset(&b->d, 0, sizeof(b->d)); b->d.n_scene = n;
+  if (views) PTZ_TRY(create_view_structure(b, c, tc1));
+  else {
+    PTZ_TRY(create_upload_structure(b, c));
+    if (c.gpu_pairs) PTZ_TRY(create_device_pairs(b, c));
   }
+  PTZ_TRY(alloc_solver_state(b, c));
+  const double tc2 = now_ms();
+  PTZ_TRY(create_tile_plan(b, c));
+  PTZ_TRY(create_pipeline(b, c));
+  PTZ_TRY(create_schur_limits(b, c));
+  if (!once_per_device(CAPS_PASS, b->device, raise_pass_caps)) { (void)hipGetLastError(); return PTZ_ENODEVICE; }
   // The zero fills and the staged upload are still in flight on `io`: the batch's first stream waits for them ON THE DEVICE (every
   // later entry point works on that stream or behind it), the host does not -- it goes on to the caller's set_state / solve while
   // the device finishes the structure.  (The staging blocks are released behind the next host-side wait: solve, destroy.)
   if (ptzpool::event_acquire(b->device, false, &b->create_ev) != hipSuccess || hipEventRecord(b->create_ev, b->io) != hipSuccess ||
       hipStreamWaitEvent(b->stream, b->create_ev, 0) != hipSuccess) {
-    (void)hipGetLastError(); ptz_ba_batch_destroy(b); return PTZ_ENODEVICE;
+    (void)hipGetLastError(); return PTZ_ENODEVICE;
   }
-  tc3 = now_ms();
-  if (dbg_t) fprintf(stderr, "[ptz_ba_create] host structure %.2f ms (observations %.2f, pair entries %.2f), uploads + allocations %.2f ms, mask + rest %.2f ms\n", tc1 - tc0, ts_obs, ts_ent, tc2 - tc1, tc3 - tc2);
-  *out = b;
+  if (c.dbg_t) fprintf(stderr, "[ptz_ba_create] host structure %.2f ms (pair entries %.2f), uploads + allocations %.2f ms, mask + rest %.2f ms\n", tc1 - tc0, c.ts_ent, tc2 - tc1, now_ms() - tc2);
+  *out = owner.release();
   return PTZ_OK;
 }
 
@@ -2491,12 +2505,10 @@ int32_t ptz_ba_covariance(const ptz_ba_problem* p, const double* cam, const doub
   if (ba_cov_dim(p->factor_type) < 0 || p->n_obs3d > 0 || p->ic_of_cam) return PTZ_EUNSUPPORTED;
   if (gauge_cam < 0 || gauge_cam >= p->n_cam) return PTZ_EINVAL;
   ptz_ba_batch* b = nullptr;
-  int rc = ptz_ba_batch_create(1, p, opt, &b);
-  if (rc) return rc;
-  rc = ptz_ba_batch_set_state(b, cam, ray, nullptr);
-  if (!rc) rc = ptz_ba_batch_covariance(b, &gauge_cam, pixel_sigma, cov, sigma0, status, nullptr);
-  ptz_ba_batch_destroy(b);
-  return rc;
+  PTZ_TRY(ptz_ba_batch_create(1, p, opt, &b));
+  BatchOwner owner(b);
+  PTZ_TRY(ptz_ba_batch_set_state(b, cam, ray, nullptr));
+  return ptz_ba_batch_covariance(b, &gauge_cam, pixel_sigma, cov, sigma0, status, nullptr);
 }
 
 int32_t ptz_ba_geo_cov_dim(int32_t factor_type)
@@ -2536,12 +2548,10 @@ int32_t ptz_ba_covariance_georef(const ptz_ba_problem* p, const double* cam, con
   if (ba_geo_cov_dim(p->factor_type) < 0 || p->ic_of_cam) return PTZ_EUNSUPPORTED;
   if (gauge_cam < 0 || gauge_cam >= p->n_cam) return PTZ_EINVAL;
   ptz_ba_batch* b = nullptr;
-  int rc = ptz_ba_batch_create(1, p, opt, &b);
-  if (rc) return rc;
-  rc = ptz_ba_batch_set_state(b, cam, ray, tlw);
-  if (!rc) rc = ptz_ba_batch_covariance_georef(b, &gauge_cam, pixel_sigma, annotation_sigma, cov, cov_centre, sigma0, status, nullptr);
-  ptz_ba_batch_destroy(b);
-  return rc;
+  PTZ_TRY(ptz_ba_batch_create(1, p, opt, &b));
+  BatchOwner owner(b);
+  PTZ_TRY(ptz_ba_batch_set_state(b, cam, ray, tlw));
+  return ptz_ba_batch_covariance_georef(b, &gauge_cam, pixel_sigma, annotation_sigma, cov, cov_centre, sigma0, status, nullptr);
 }
 
 namespace {
@@ -2830,8 +2840,8 @@ int32_t ptz_debug_batch_structure_hash(ptz_ba_batch* b, uint64_t* hash)
   if (!b || !hash) return PTZ_EINVAL;
   PTZ_DEVICE_GUARD(b->device);
   const Dev& d = b->d;
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* ptr, size_t bytes) { const unsigned char* c = (const unsigned char*)ptr; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } };
+  uint64_t h = FNV_BASIS;
+  auto mix = [&](const void* ptr, size_t bytes) { fnv_mix(h, ptr, bytes); };
   std::vector<unsigned char> buf;
   auto fetch = [&](const void* dev, size_t bytes) -> const unsigned char* {
     buf.resize(bytes + 8);
@@ -2886,25 +2896,39 @@ int32_t ptz_debug_batch_structure_hash(ptz_ba_batch* b, uint64_t* hash)
 
 void ptz_trim_cache(void) { ptzpool::trim(); }
 
+// a batch for one solve: create, set the state (and the displacement block), solve, read the result back over the caller's arrays
+static int32_t solve_in_place(int32_t n, const ptz_ba_problem* problems, const ptz_lm_options* opt, double* cam, double* ray, double* tlw,
+                              double* disp, ptz_lm_summary* summaries)
+{
+  ptz_ba_batch* b = nullptr;
+  PTZ_TRY(ptz_ba_batch_create(n, problems, opt, &b));
+  BatchOwner owner(b);
+  PTZ_TRY(ptz_ba_batch_set_state(b, cam, ray, tlw));
+  if (disp) PTZ_TRY(ptz_ba_batch_set_disp(b, disp));
+  PTZ_TRY(ptz_ba_batch_solve(b, summaries));
+  PTZ_TRY(ptz_ba_batch_get_state(b, cam, ray, tlw));
+  return disp ? ptz_ba_batch_get_disp(b, disp) : PTZ_OK;
+}
+
 int32_t ptz_ba_solve(const ptz_ba_problem* p, double* cam, double* ray, double* tlw, const ptz_lm_options* opt, ptz_lm_summary* summary)
 {
   if (!p || !cam || !ray) return PTZ_EINVAL;
   const bool dbg = getenv("PTZ_BA_DEBUG_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
+  const double t0 = now_ms();
   ptz_ba_batch* b = nullptr;
   int rc = ptz_ba_batch_create(1, p, opt, &b);
   if (rc) return rc;
-  const double t1 = now();
+  BatchOwner owner(b);
+  const double t1 = now_ms();
   rc = ptz_ba_batch_set_state(b, cam, ray, tlw);
-  const double t2 = now();
+  const double t2 = now_ms();
   if (!rc) rc = ptz_ba_batch_solve(b, summary);
-  const double t3 = now();
+  const double t3 = now_ms();
   if (!rc) rc = ptz_ba_batch_get_state(b, cam, ray, tlw);
-  const double t4 = now();
-  ptz_ba_batch_destroy(b);
+  const double t4 = now_ms();
+  owner.reset();
   if (dbg) fprintf(stderr, "[ptz_ba_solve] n_cam %d n_obs %lld: create %.2f set_state %.2f solve %.2f get_state %.2f destroy %.2f ms\n", p->n_cam,
-                   (long long)p->n_obs, t1 - t0, t2 - t1, t3 - t2, t4 - t3, now() - t4);
+                   (long long)p->n_obs, t1 - t0, t2 - t1, t3 - t2, t4 - t3, now_ms() - t4);
   return rc;
 }
 
@@ -2913,16 +2937,7 @@ int32_t ptz_ba_solve_disp(const ptz_ba_problem* p, double* cam, double* ray, dou
 {
   if (!p || !cam || !ray) return PTZ_EINVAL;
   if (p->factor_type != PTZ_BA_PTZRayDistDisp) return PTZ_EUNSUPPORTED;
-  ptz_ba_batch* b = nullptr;
-  int rc = ptz_ba_batch_create(1, p, opt, &b);
-  if (rc) return rc;
-  rc = ptz_ba_batch_set_state(b, cam, ray, tlw);
-  if (!rc && disp) rc = ptz_ba_batch_set_disp(b, disp);
-  if (!rc) rc = ptz_ba_batch_solve(b, summary);
-  if (!rc) rc = ptz_ba_batch_get_state(b, cam, ray, tlw);
-  if (!rc && disp) rc = ptz_ba_batch_get_disp(b, disp);
-  ptz_ba_batch_destroy(b);
-  return rc;
+  return solve_in_place(1, p, opt, cam, ray, tlw, disp, summary);
 }
 
 // Many scenes over several devices of one node, from one process: scenes are dealt longest-first to the least loaded device
@@ -2968,15 +2983,9 @@ int32_t ptz_ba_solve_sharded(int32_t n, const ptz_ba_problem* problems, double* 
     }
     ptz_lm_options o = base;
     o.device_id = device_ids[dv];
-    ptz_ba_batch* b = nullptr;
-    int rc = ptz_ba_batch_create((int32_t)ids.size(), probs.data(), &o, &b);
     std::vector<ptz_lm_summary> summ(ids.size());
-    if (!rc) rc = ptz_ba_batch_set_state(b, c.data(), r.data(), tlw ? t.data() : nullptr);
-    if (!rc) rc = ptz_ba_batch_solve(b, summ.data());
-    if (!rc) rc = ptz_ba_batch_get_state(b, c.data(), r.data(), tlw ? t.data() : nullptr);
-    if (b) ptz_ba_batch_destroy(b);
-    rcs[dv] = rc;
-    if (rc) return;
+    rcs[dv] = solve_in_place((int32_t)ids.size(), probs.data(), &o, c.data(), r.data(), tlw ? t.data() : nullptr, nullptr, summ.data());
+    if (rcs[dv]) return;
     size_t co = 0, ro = 0;
     for (size_t k = 0; k < ids.size(); ++k) {
       const int i = ids[k];
@@ -3001,36 +3010,23 @@ int32_t ptz_ba_solve_sharded(int32_t n, const ptz_ba_problem* problems, double* 
 int32_t ptz_debug_host_structure(int32_t n, const ptz_ba_problem* problems, int32_t n_threads, int32_t reps, double* ms_per_rep, uint64_t* hash_out)
 {
   if (n <= 0 || !problems || n_threads <= 0 || reps <= 0 || !ms_per_rep) return PTZ_EINVAL;
-  std::vector<size_t> ob(n + 1, 0), rb(n + 1, 0), cb(n + 1, 0);
-  for (int i = 0; i < n; ++i) { ob[i + 1] = ob[i] + (size_t)problems[i].n_obs; rb[i + 1] = rb[i] + problems[i].n_ray; cb[i + 1] = cb[i] + problems[i].n_cam; }
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < reps; ++rep) {
-    RawVec<float2> uv(ob[n]), camuv(ob[n]);
-    RawVec<int> cam(ob[n]), ray(ob[n]), camobs(ob[n]), camray(ob[n]), wpos(ob[n]);
-    std::vector<int> rayptr(rb[n] + n), camptr(cb[n] + n), campair(cb[n] + n), camrun(cb[n] + n), perm(rb[n]);
-    std::vector<double> w(rb[n]);
-    std::vector<PairBuild> wave(n);
-    auto work = [&](int t, int step) {
-      for (int k = t; k < n; k += step) {
-        const ObsDest od = {uv.data() + ob[k], cam.data() + ob[k], ray.data() + ob[k], camobs.data() + ob[k], camray.data() + ob[k], camuv.data() + ob[k],
-                            rayptr.data() + rb[k] + k, w.data() + rb[k], camptr.data() + cb[k] + k, campair.data() + cb[k] + k,
-                            camrun.data() + cb[k] + k, wpos.data() + ob[k]};
-        build_pairs(problems[k], (int)ob[k], (int)rb[k], od, wave[k], perm.data() + rb[k], schur_threads_of(problems[k].factor_type));
-      }
-    };
-    const int nt = std::min(n_threads, n);
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(work, t, nt);
-    work(0, nt);
-    for (auto& x : th) x.join();
+    HostObs a;
+    a.set_bases(n, problems);
+    a.resize_all(n);
+    std::vector<int> perm(a.ray_base[n]);
+    std::vector<PairBuild> wave;
+    build_scene_wave(problems, 0, n, n_threads, a, perm.data(), wave, /*pairs_on_device=*/false);
     for (int k = 0; k < n; ++k) if (wave[k].err != PTZ_OK) return wave[k].err;
     if (hash_out && rep == 0) {  // FNV-1a over everything the stage produces, in a fixed order
-      uint64_t h = 1469598103934665603ull;
-      auto mix = [&](const void* ptr, size_t bytes) { const unsigned char* c = (const unsigned char*)ptr; for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; } };
-      mix(uv.data(), sizeof(float2) * ob[n]); mix(camuv.data(), sizeof(float2) * ob[n]); mix(cam.data(), 4 * ob[n]); mix(ray.data(), 4 * ob[n]);
-      mix(camobs.data(), 4 * ob[n]); mix(camray.data(), 4 * ob[n]); mix(wpos.data(), 4 * ob[n]);
-      mix(rayptr.data(), 4 * rayptr.size()); mix(camptr.data(), 4 * camptr.size()); mix(campair.data(), 4 * campair.size()); mix(camrun.data(), 4 * camrun.size());
-      mix(perm.data(), 4 * perm.size()); mix(w.data(), 8 * w.size());
+      uint64_t h = FNV_BASIS;
+      auto mix = [&](const void* ptr, size_t bytes) { fnv_mix(h, ptr, bytes); };
+      const size_t to = a.obs_base[n];
+      mix(a.uv.data(), sizeof(float2) * to); mix(a.camuv.data(), sizeof(float2) * to); mix(a.cam.data(), 4 * to); mix(a.ray.data(), 4 * to);
+      mix(a.camobs.data(), 4 * to); mix(a.camray.data(), 4 * to); mix(a.wpos.data(), 4 * to);
+      mix(a.rayptr.data(), 4 * a.rayptr.size()); mix(a.camptr.data(), 4 * a.camptr.size()); mix(a.campair.data(), 4 * a.campair.size()); mix(a.camrun.data(), 4 * a.camrun.size());
+      mix(perm.data(), 4 * perm.size()); mix(a.w.data(), 8 * a.w.size());
       for (int k = 0; k < n; ++k) {
         const PairBuild& pb = wave[k];
         mix(pb.pci.data(), 4 * pb.pci.size()); mix(pb.pcj.data(), 4 * pb.pcj.size()); mix(pb.pptr.data(), 4 * pb.pptr.size()); mix(pb.pbrow.data(), 4 * pb.pbrow.size());
