@@ -1081,6 +1081,70 @@ int32_t ptz_relocalizer_run_tracked(ptz_relocalizer* r, const ptz_desc_set* quer
                                     const double* prior_cams, const ptz_reloc_options* options, const ptz_prior_options* prior_opt,
                                     ptz_reloc_result* result, ptz_prior_result* prior_result);
 
+/* ---- landmark map: relocalize against one ray and one descriptor per track --------------------------------------------------------
+ * The references overlap, so a world point sits in the resident set once per view that saw it.  A landmark map holds it ONCE: per
+ * track of the reference images a unit ray from the shared projection centre and an aggregated descriptor.  The contract is
+ * csrc/ptz_landmark.h (integers, and + - * / sqrt in double rounded one by one; the references' rotations from
+ * ptz_reloc_ref_rotations).
+ * Map build.  ref_set: the references' resident set WITH key points, image m = camera m of ref_cams [15 n_ref]; tracks as CSR:
+ * trk_ptr [n_track + 1], trk_img / trk_feat [trk_ptr[n_track]] (the feature's index inside its image); min_views >= 1.  Per track,
+ * over its views in CSR order: a view is valid iff image and feature are in range and, for factor_type & 1, its undistorted pixel
+ * lies inside its view's frame; ray_v = R_r^T n / |R_r^T n|; L = s / |s| with s the left-to-right sum of ray_v over the valid views;
+ * the track is a landmark iff it has at least min_views valid views and L is finite; descriptor byte k = (2 S_k + n) / (2 n), S_k
+ * the int32 sum of byte k over the n valid views; home = the reference of the valid view with the largest (R_r L)_z, the first in
+ * CSR order on a tie.  Landmarks are compacted in ascending track order.
+ * ptz_landmark_map_download, every pointer nullable: lm_track / lm_home / lm_views [n_lm], lm_ray [3 n_lm], lm_desc [n_lm D].
+ * ptz_landmark_map_desc_set: the map's descriptors as a ptz_desc_set of ONE image of n_lm features (placeholder key points), the
+ * map's until it is destroyed: what ptz_desc_match_pairs takes as set_a with img_a = 0.
+ * PTZ_EINVAL, before any device work: NULL set / cameras / trk_ptr / out, n_ref < 1 or not the set's image count, n_track < 0,
+ * offsets that do not start at 0 or decrease, views without trk_img / trk_feat, min_views < 1, a set with features but without key
+ * points, device_id not the set's; PTZ_EUNSUPPORTED: factor_type; PTZ_ELIMIT: more than 8192 references (the anchor vote's LDS
+ * counters).  Out-of-range images and features are not errors: such a view is not valid.
+ * Assembly.  Pair q is (map, query q): match_ptr [n_query + 1], idx_a (landmark index) and uv_b (query pixel) in the layout of
+ * ptz_desc_matches_device_ptrs.  A match votes for lm_home[idx_a]; the anchor of a query is the reference with the most votes, the
+ * lowest index on a tie; without a vote anchor_ref = -1, the range is empty and the cameras are those of reference 0.  cam_ref is
+ * the virtual anchor [fa, fa, S, S, rvec_a, t_a, 0 x 5] of ptz_reloc_assemble (K > 1), cam_cur its cam_cur.  Each match is
+ * transferred as m = R_a L, kept iff m_z > 0, m finite and the pixel (float)(fa m_x / m_z + S), .. lies in [0, 2S)^2.  Outputs in
+ * the layout of ptz_reloc_assemble: anchor_ref [n_query], out_ptr [n_query + 1], out_uv_ref / out_uv_cur [n_match, 2], out_src
+ * [n_match] of which the first out_ptr[n_query] entries are written, cam_ref / cam_cur [15 n_query].  A query's output depends on
+ * its own matches and the map only.  ref_cams / ref_R: those the map was built with (ref_R from ptz_reloc_ref_rotations).
+ * ptz_landmark_assemble (host arrays).  PTZ_EINVAL, before any device work: NULL map, n_query < 0, offsets that do not start at 0
+ * or decrease, idx_a outside [0, n_lm), missing arrays, an image size that is not positive; PTZ_EUNSUPPORTED: factor_type;
+ * PTZ_ELIMIT: more than 2^31 - 1 matches; n_query = 0 is PTZ_OK.
+ * ptz_landmark_assemble_device: DEVICE pointers on the map's device, enqueued on `hip_stream`, no synchronisation inside.  Nothing
+ * on the device is validated: a malformed range is an empty one, a match whose landmark is out of range neither votes nor is
+ * kept.  d_workspace: 256-byte aligned, at least ptz_landmark_assemble_workspace_bytes(n_query, n_match) bytes, the caller's until
+ * the stream has run the call; whatever it holds before is never read.
+ * ptz_relocalizer_run_landmarks: stage 1 is ptz_desc_match_pairs over the n_query (map, query) pairs, stage 3 the landmark
+ * assembly, stages 4 - 6 exactly ptz_relocalizer_run's; options->max_refs is ignored: sel_ref is [n_query], sel_ref[q] the anchor
+ * (-1 without one), n_sel 0 or 1.  The map must come from the relocalizer's references, device and D: the count of references, the
+ * device and D are checked (PTZ_EINVAL); that the map was built from the SAME cameras is not -- the assembly reads the
+ * relocalizer's cameras, and a map built from others with the same count gives wrong pixels silently.  guided_radius > 0 is
+ * PTZ_EUNSUPPORTED: there is no pair homography between a map and an image.  ptz_relocalizer_table / _matches / _pairs work as
+ * after any run (pair_ref is the map's image, 0). */
+typedef struct ptz_landmark_map ptz_landmark_map;
+int32_t ptz_landmark_map_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t n_track, const int64_t* trk_ptr,
+                                const int32_t* trk_img, const int32_t* trk_feat, int32_t factor_type, int32_t min_views, int32_t device_id,
+                                ptz_landmark_map** out);
+void ptz_landmark_map_destroy(ptz_landmark_map* m);
+int32_t ptz_landmark_map_n_landmarks(const ptz_landmark_map* m);
+double ptz_landmark_map_build_ms(const ptz_landmark_map* m); /* the build's launches, between events on the call's stream */
+int32_t ptz_landmark_map_download(const ptz_landmark_map* m, int32_t* lm_track, double* lm_ray, int32_t* lm_home, int32_t* lm_views,
+                                  uint8_t* lm_desc);
+const ptz_desc_set* ptz_landmark_map_desc_set(const ptz_landmark_map* m);
+int64_t ptz_landmark_assemble_workspace_bytes(int32_t n_query, int64_t n_match);
+int32_t ptz_landmark_assemble(const ptz_landmark_map* map, int32_t n_query, const int64_t* match_ptr, const int32_t* idx_a, const float* uv_b,
+                              const double* ref_cams, const double* ref_R, const int32_t* query_wh, int32_t factor_type, int32_t* anchor_ref,
+                              int64_t* out_ptr, float* out_uv_ref, float* out_uv_cur, int32_t* out_src, double* cam_ref, double* cam_cur,
+                              double* device_ms /* or NULL */);
+int32_t ptz_landmark_assemble_device(const ptz_landmark_map* map, int32_t n_query, int64_t n_match, const int64_t* d_match_ptr,
+                                     const int32_t* d_idx_a, const float* d_uv_b, const double* d_ref_cams, const double* d_ref_R,
+                                     const int32_t* d_query_wh, int32_t factor_type, int32_t* d_anchor_ref, int64_t* d_out_ptr,
+                                     float* d_out_uv_ref, float* d_out_uv_cur, int32_t* d_out_src, double* d_cam_ref, double* d_cam_cur,
+                                     void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
+                                      const int32_t* query_wh, const ptz_reloc_options* options, ptz_reloc_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,10 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_relocalizer_create", "ptz_relocalizer_destroy", "ptz_relocalizer_run", "ptz_relocalizer_n_matches", "ptz_relocalizer_matches", "ptz_relocalizer_table",
            "ptz_shortlist_options_default", "ptz_desc_shortlist", "ptz_desc_shortlist_workspace_bytes", "ptz_desc_shortlist_device",
            "ptz_relocalizer_run_shortlisted", "ptz_relocalizer_pairs", "ptz_debug_chol_solve", "ptz_prior_options_default",
-           "ptz_reloc_prior_pairs", "ptz_reloc_prior_pairs_device", "ptz_relocalizer_run_tracked"]
+           "ptz_reloc_prior_pairs", "ptz_reloc_prior_pairs_device", "ptz_relocalizer_run_tracked", "ptz_landmark_map_create",
+           "ptz_landmark_map_destroy", "ptz_landmark_map_n_landmarks", "ptz_landmark_map_build_ms", "ptz_landmark_map_download",
+           "ptz_landmark_map_desc_set", "ptz_landmark_assemble_workspace_bytes", "ptz_landmark_assemble", "ptz_landmark_assemble_device",
+           "ptz_relocalizer_run_landmarks"]
 
 
 class PtzError(RuntimeError):
@@ -1490,6 +1493,110 @@ def reloc_prior_pairs_device(n_ref, d_ref_cams, d_ref_R, n_query, d_prior_cams, 
            "ptz_reloc_prior_pairs_device")
 
 
+# ---- landmark map (csrc/ptz_landmark.h) ---------------------------------------------------------------------------------------------
+class _BorrowedDescSet:
+    """The map's descriptor set as match_descriptors takes it: one image of n_lm features, owned by the map."""
+
+    def __init__(self, handle, D, device_id):
+        self.handle, self.D, self.device_id, self.n_img, self.has_kp = handle, D, device_id, 1, True
+
+
+class LandmarkMap:
+    """ptz_landmark_map: one unit ray and one aggregated descriptor per track of the reference images.  ref_set: the references'
+    DescSet with key points (image m is camera m of ref_cams [n_ref, 15]); tracks as CSR: trk_ptr [n_track + 1], trk_img / trk_feat
+    (the feature's index inside its image).  A track becomes a landmark with at least min_views valid views and a finite ray."""
+
+    def __init__(self, ref_set, ref_cams, trk_ptr, trk_img, trk_feat, factor_type=0, min_views=1, device_id=None):
+        self.ref_cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+        ptr = np.ascontiguousarray(trk_ptr, dtype=np.int64)
+        img = np.ascontiguousarray(trk_img, dtype=np.int32)
+        feat = np.ascontiguousarray(trk_feat, dtype=np.int32)
+        if len(ptr) < 1 or len(img) != len(feat) or (len(ptr) > 1 and int(ptr[-1]) != len(img)):
+            raise ValueError("trk_ptr, trk_img and trk_feat disagree on the number of views")
+        self.device_id = ref_set.device_id if device_id is None else int(device_id)
+        self.D, self.factor_type = ref_set.D, int(factor_type)
+        self.handle = C.c_void_p()
+        L = lib()
+        L.ptz_landmark_map_destroy.restype = None
+        L.ptz_landmark_map_build_ms.restype = C.c_double
+        L.ptz_landmark_map_desc_set.restype = C.c_void_p
+        _check(L.ptz_landmark_map_create(ref_set.handle, _p(self.ref_cams), len(self.ref_cams), len(ptr) - 1, _p(ptr), _p(img) if len(img) else None,
+                                         _p(feat) if len(feat) else None, self.factor_type, int(min_views), self.device_id, C.byref(self.handle)),
+               "ptz_landmark_map_create")
+        self.n_landmarks = int(L.ptz_landmark_map_n_landmarks(self.handle))
+        self.build_ms = float(L.ptz_landmark_map_build_ms(self.handle))
+
+    def arrays(self):
+        """dict of numpy arrays: lm_track / lm_home / lm_views [n_lm], lm_ray [n_lm, 3], lm_desc [n_lm, D]."""
+        n = self.n_landmarks
+        trk, home, views = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        ray, desc = np.zeros((n, 3)), np.zeros((n, self.D), dtype=np.uint8)
+        _check(lib().ptz_landmark_map_download(self.handle, _p(trk), _p(ray), _p(home), _p(views), _p(desc)), "ptz_landmark_map_download")
+        return dict(lm_track=trk, lm_ray=ray, lm_home=home, lm_views=views, lm_desc=desc)
+
+    def desc_set(self):
+        """The map's descriptors as the set_a of match_descriptors (img_a = 0); the map's until it is closed."""
+        return _BorrowedDescSet(C.c_void_p(lib().ptz_landmark_map_desc_set(self.handle)), self.D, self.device_id)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_landmark_map_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def landmark_assemble_workspace_bytes(n_query, n_match) -> int:
+    lib().ptz_landmark_assemble_workspace_bytes.restype = C.c_int64
+    return int(lib().ptz_landmark_assemble_workspace_bytes(int(n_query), C.c_int64(int(n_match))))
+
+
+def landmark_assemble(lmap, match_ptr, idx_a, uv_b, query_wh, ref_R=None):
+    """ptz_landmark_assemble: from the match CSR of the (map, query) pairs -- match_ptr [n_query + 1], idx_a (landmark index), uv_b
+    (query pixel) -- to the solve's inputs.  Returns a dict: anchor_ref [n_query] (-1: no match votes), match_ptr [n_query + 1],
+    uv_ref / uv_cur [n_kept, 2], src [n_kept] (index in the input arrays), cam_ref / cam_init [n_query, 15], device_ms."""
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    ia = np.ascontiguousarray(idx_a, dtype=np.int32)
+    b = np.ascontiguousarray(uv_b, dtype=np.float32).reshape(-1, 2)
+    wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
+    R = reloc_ref_rotations(lmap.ref_cams) if ref_R is None else np.ascontiguousarray(ref_R, dtype=np.float64).reshape(-1, 9)
+    nq, nm = len(ptr) - 1, len(ia)
+    if len(wh) != nq or len(b) != nm or len(R) != len(lmap.ref_cams):
+        raise ValueError("query_wh: one size per query, uv_b: one pixel per match, ref_R: one matrix per reference")
+    anchor = np.full(nq, -1, dtype=np.int32)
+    optr = np.zeros(nq + 1, dtype=np.int64)
+    oa, ob = np.zeros((nm, 2), dtype=np.float32), np.zeros((nm, 2), dtype=np.float32)
+    osrc = np.zeros(nm, dtype=np.int32)
+    cref, ccur = np.zeros((nq, 15)), np.zeros((nq, 15))
+    ms = C.c_double()
+    _check(lib().ptz_landmark_assemble(lmap.handle, nq, _p(ptr), _p(ia) if nm else None, _p(b) if nm else None, _p(lmap.ref_cams), _p(R), _p(wh),
+                                       lmap.factor_type, _p(anchor), _p(optr), _p(oa) if nm else None, _p(ob) if nm else None,
+                                       _p(osrc) if nm else None, _p(cref), _p(ccur), C.byref(ms)), "ptz_landmark_assemble")
+    k = int(optr[-1])
+    return dict(anchor_ref=anchor, match_ptr=optr, uv_ref=oa[:k], uv_cur=ob[:k], src=osrc[:k], cam_ref=cref, cam_init=ccur, device_ms=ms.value)
+
+
+def landmark_assemble_device(lmap, n_query, n_match, d_match_ptr, d_idx_a, d_uv_b, d_ref_cams, d_ref_R, d_query_wh, d_anchor_ref, d_out_ptr,
+                             d_out_uv_ref, d_out_uv_cur, d_out_src, d_cam_ref, d_cam_cur, d_workspace, workspace_bytes, stream=None):
+    """ptz_landmark_assemble_device: every d_* is a device buffer (torch tensor or integer address); d_workspace needs
+    landmark_assemble_workspace_bytes(n_query, n_match) bytes.  Enqueues on `stream` and returns without synchronising."""
+    _check(lib().ptz_landmark_assemble_device(lmap.handle, int(n_query), C.c_int64(int(n_match)), _dptr(d_match_ptr), _dptr(d_idx_a), _dptr(d_uv_b),
+                                              _dptr(d_ref_cams), _dptr(d_ref_R), _dptr(d_query_wh), lmap.factor_type, _dptr(d_anchor_ref),
+                                              _dptr(d_out_ptr), _dptr(d_out_uv_ref), _dptr(d_out_uv_cur), _dptr(d_out_src), _dptr(d_cam_ref),
+                                              _dptr(d_cam_cur), _dptr(d_workspace), C.c_int64(int(workspace_bytes)),
+                                              C.c_void_p(stream) if stream else None), "ptz_landmark_assemble_device")
+
+
 # ---- the resident serving loop (ptz_relocalizer_*) ---------------------------------------------------------------------------------
 class RelocOptions(C.Structure):
     _fields_ = [("match", DescOptions), ("guided_radius", C.c_double), ("ransac_thresh", C.c_double), ("min_inliers", C.c_int32),
@@ -1526,7 +1633,7 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
@@ -1538,9 +1645,16 @@ class Relocalizer:
         (8): ptz_relocalizer_run_tracked -- the references that overlap the prior are matched under the predicted homography alone
         (no dense pass; guided_radius is ignored), the solve starts from the prior, and the gate on the assembled query is always on.
         The result gains shortlist [n, R], n_short [n], overlap [n, n_ref] and prior_ms.  Exclusive with shortlist.
-        guided_grid: every guided pass of the run (guided_radius > 0, prior=) goes through the grid-binned kernel: the same outputs."""
+        guided_grid: every guided pass of the run (guided_radius > 0, prior=) goes through the grid-binned kernel: the same outputs.
+        landmarks: None, or a LandmarkMap built from this relocalizer's references: ptz_relocalizer_run_landmarks -- every query is
+        matched against the map's one image, not against reference images; max_refs is ignored, sel_ref [n, 1] is the anchor and
+        n_sel is 0 or 1; guided_radius > 0 is PTZ_EUNSUPPORTED.  Exclusive with shortlist and prior."""
         if prior is not None and shortlist is not None:
             raise ValueError("prior= and shortlist= are two ways to pick a query's references: give one")
+        if landmarks is not None and (prior is not None or shortlist is not None):
+            raise ValueError("landmarks= matches against the map, not against reference images: exclusive with shortlist= and prior=")
+        if landmarks is not None:
+            max_refs = 1
         wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
         n, K = len(wh), int(max_refs)
         o = RelocOptions()
@@ -1580,6 +1694,9 @@ class Relocalizer:
             _check(lib().ptz_relocalizer_run_tracked(self.handle, query_set.handle, n, _p(wh), _p(pc) if n else None, C.byref(o), C.byref(po),
                                                      C.byref(r), C.byref(pr)), "ptz_relocalizer_run_tracked")
             extra = dict(shortlist=sl, n_short=ns, overlap=ov, prior_ms=pr.prior_ms)
+        elif landmarks is not None:
+            _check(lib().ptz_relocalizer_run_landmarks(self.handle, landmarks.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)),
+                   "ptz_relocalizer_run_landmarks")
         elif shortlist is None:
             _check(lib().ptz_relocalizer_run(self.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)), "ptz_relocalizer_run")
         else:

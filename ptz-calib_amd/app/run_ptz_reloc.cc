@@ -17,6 +17,11 @@
 // untracked (--shortlist if given, else all pairs), and a tracked frame that is lost is run again untracked -- one frame per run and
 // therefore latency-bound.  --prior_radius, --prior_refs: the matcher's radius (40 px) and the list length (8).  Every record gains
 // "tracked" and n_shortlist.
+// --landmarks (not in the reference; with --landmark_min_views; implies --on_device) relocalizes against a landmark MAP instead of
+// reference images: the reference images are matched among themselves (MatchDescriptors, --match_ratio and --match_min), the host
+// TracksBuilder turns the matches into tracks as PTZRayOptimizer does, ptz_landmark_map_create makes one ray and one descriptor per
+// track, and every test image goes through ptz_relocalizer_run_landmarks -- one (map, image) pair each.  Every record gains
+// n_landmarks and n_matches.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -30,6 +35,7 @@
 #include "../../include/ptz_calib_amd.h"
 #include "../host/data_io.h"
 #include "../host/json_mini.h"
+#include "../host/tracks.h"
 #include "args.h"
 
 using namespace ptzcalib;
@@ -112,6 +118,11 @@ int main(int argc, char** argv)
   parser.Add("prior_refs", '\0', "With --prior_params / --sequence: reference images a prior lists at most (default 8)", false);
   parser.AddFlag("guided_grid", "With --match_guided, --prior_params or --sequence: run the guided matcher through the grid-binned kernel "
                                 "(the same matches, the same output)");
+  parser.AddFlag("landmarks", "With --match_descriptors: relocalize every test image against a landmark map -- one ray and one descriptor per "
+                              "track of the reference images -- instead of reference images (implies --on_device); every record gains "
+                              "n_landmarks and n_matches");
+  parser.Add("landmark_min_views", '\0', "With --landmarks: reference images a track needs to become a landmark (default 2; the tracks come from "
+                                         "matches between reference images, so they have two views at least and 1 acts as 2)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -126,9 +137,24 @@ int main(int argc, char** argv)
   const int multi_ref = parser.Exist("multi_ref") ? atoi(parser.Get("multi_ref").c_str()) : 0;
   const bool shortlisting = parser.Exist("shortlist");
   const bool prior_file = parser.Exist("prior_params"), sequence = parser.Exist("sequence"), tracking = prior_file || sequence;
-  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking;
+  const bool landmarks = parser.Exist("landmarks");
+  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking || landmarks;
   if (on_device && !parser.Exist("match_descriptors")) {
-    fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params and --sequence need --match_descriptors\n");
+    fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params, --sequence and --landmarks need --match_descriptors\n");
+    return 1;
+  }
+  if (landmarks && (parser.Exist("match_guided") || shortlisting || parser.Exist("multi_ref") || tracking || parser.Exist("save_matches"))) {
+    fprintf(stderr, "--landmarks matches against the map, not against reference images: it does not go with --match_guided, --shortlist, "
+                    "--multi_ref, --prior_params, --sequence or --save_matches\n");
+    return 1;
+  }
+  if (!landmarks && parser.Exist("landmark_min_views")) {
+    fprintf(stderr, "--landmark_min_views needs --landmarks\n");
+    return 1;
+  }
+  const int landmark_min_views = parser.Exist("landmark_min_views") ? atoi(parser.Get("landmark_min_views").c_str()) : 2;
+  if (landmark_min_views < 1) {
+    fprintf(stderr, "--landmark_min_views must be at least 1\n");
     return 1;
   }
   ptz_prior_options po;
@@ -272,6 +298,7 @@ int main(int argc, char** argv)
   std::vector<Trimmed> trimmed(test_fnames.size());
   std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0), n_shortlist(test_fnames.size(), 0);
   std::vector<int> tracked(test_fnames.size(), 0);
+  int n_landmarks = 0;
   if (on_device && !test_fnames.empty()) {
     // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
     // guided pass, the assembly, the gate, the solve or the trimming loop, the covariance -- in the order of the code below
@@ -315,6 +342,41 @@ int main(int argc, char** argv)
     bool ok = n_ref > 0 && static_cast<size_t>(n_ref) == ref_cameras.size() && BuildDescSet(parser.Get("ref_features"), ref_fnames, ref_features, &ref_set);
     int32_t rc = PTZ_OK;
     if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
+    ptz_landmark_map* lmap = nullptr;
+    if (ok && rc == PTZ_OK && landmarks) {
+      // the references among themselves, every pair once; the tracks of those matches; one landmark per track
+      DescMatchOptions mo;
+      mo.ratio = ro.match.ratio;
+      mo.min_matches = ro.match.min_matches;
+      std::vector<std::pair<long, long>> pairs;
+      for (long r = 0; r < n_ref; ++r)
+        for (long s = r + 1; s < n_ref; ++s) pairs.push_back({r, s});
+      std::vector<std::vector<DMatch>> ref_matches;
+      std::vector<std::pair<std::string, std::string>> ref_pairs_name;
+      ok = MatchDescriptors(parser.Get("ref_features"), ref_fnames, parser.Get("ref_features"), ref_fnames, pairs, mo, false, ref_matches,
+                            ref_pairs_name);
+      if (!ok) fprintf(stderr, "Error matching the descriptors of the reference images among themselves. Exiting ...\n");
+      std::vector<MatchesInfo> infos(ref_matches.size());
+      for (size_t i = 0; ok && i < ref_matches.size(); ++i) {
+        infos[i].src_img_idx = FindImgIndex(ref_fnames, ref_pairs_name[i].first);
+        infos[i].dst_img_idx = FindImgIndex(ref_fnames, ref_pairs_name[i].second);
+        infos[i].matches = ref_matches[i];
+      }
+      if (ok) {
+        TracksBuilder builder;
+        builder.Build(infos);
+        builder.Filter(std::max(landmark_min_views, 2));  // (a track of the builder has two views at least)
+        std::vector<int> id, img, feat;
+        std::vector<int64_t> ptr;
+        builder.ExportFlat(id, ptr, img, feat);
+        if (ptr.empty()) ptr.push_back(0);
+        const std::vector<int32_t> timg(img.begin(), img.end()), tfeat(feat.begin(), feat.end());
+        rc = ptz_landmark_map_create(ref_set, ref_cams.data(), n_ref, static_cast<int32_t>(ptr.size() - 1), ptr.data(), timg.data(), tfeat.data(),
+                                     ro.factor_type, landmark_min_views, 0, &lmap);
+        if (rc == PTZ_OK) fprintf(stderr, "Landmark map: %d landmarks from %zu tracks of %d reference images\n", ptz_landmark_map_n_landmarks(lmap),
+                                  ptr.size() - 1, n_ref);
+      }
+    }
 
     // one run over the test images idx (in that order): tracked from priors [15 per image], or by the path the other flags select
     const auto run_block = [&](const std::vector<size_t>& idx, const double* priors) {
@@ -344,7 +406,8 @@ int main(int argc, char** argv)
       sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
       ptz_prior_result pr;
       pr.shortlist = nullptr; pr.n_short = n_short.data(); pr.overlap = nullptr; pr.prior_ms = 0;
-      rc = priors ? ptz_relocalizer_run_tracked(rl, test_set, nq, wh.data(), priors, &ro, &po, &rr, &pr)
+      rc = lmap   ? ptz_relocalizer_run_landmarks(rl, lmap, test_set, nq, wh.data(), &ro, &rr)
+           : priors ? ptz_relocalizer_run_tracked(rl, test_set, nq, wh.data(), priors, &ro, &po, &rr, &pr)
            : shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
                           : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
       for (int32_t q = 0; q < nq; ++q) n_shortlist[idx[q]] = n_short[q];
@@ -451,7 +514,9 @@ int main(int argc, char** argv)
       fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
       ok = false;
     }
+    n_landmarks = ptz_landmark_map_n_landmarks(lmap);
     ptz_relocalizer_destroy(rl);
+    ptz_landmark_map_destroy(lmap);
     ptz_desc_set_destroy(ref_set);
     if (!ok) return -1;
     if (rc != PTZ_OK) {
@@ -554,7 +619,7 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty || trimming || multi_ref > 0 || shortlisting || tracking) {
+  if (uncertainty || trimming || multi_ref > 0 || shortlisting || tracking || landmarks) {
     // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
@@ -576,6 +641,10 @@ int main(int argc, char** argv)
       Json& j = cams[rootname];
       if (multi_ref > 0) {
         j["n_refs"] = Json::Int(multi_n_refs[i]);
+        if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
+      }
+      if (landmarks) {
+        j["n_landmarks"] = Json::Int(n_landmarks);
         if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
       }
       if (shortlisting || tracking) j["n_shortlist"] = Json::Int(n_shortlist[i]);

@@ -5,6 +5,8 @@
 //      (ptz_relocalizer_run_tracked) the overlap lists and pair homographies of the prior cameras            ptz_reloc_prior_pairs_device
 //      -- then the guided matcher under those homographies stands IN PLACE of stages 1 and 2, the prior enters the solve's initial
 //      camera after stage 3, and stage 4 is forced on (the lone-candidate finding of ptz_reloc_prior.h)
+//      (ptz_relocalizer_run_landmarks) nothing: the run's pairs are (map, query q), one per query -- stage 1 matches every query
+//      against the landmark map's one image, stage 2 does not exist, and stage 3 is ptz_landmark_assemble_device
 //   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
@@ -22,6 +24,7 @@
 #include "ptz_common.h"
 #include "ptz_desc_set.h"
 #include "ptz_host_batch.h"
+#include "ptz_landmark_map.h"
 
 namespace ptz {
 namespace {
@@ -162,15 +165,16 @@ struct RelocPrior {
 };
 
 // all three runs: sl = pr = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references,
-// by votes (sl) or by the overlap with its prior camera (pr)
+// by votes (sl) or by the overlap with its prior camera (pr); lmap: the landmark run, whose one pair per query is (map, query)
 static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
                          const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res,
-                         const RelocPrior* pr = nullptr)
+                         const RelocPrior* pr = nullptr, const ptz_landmark_map* lmap = nullptr)
 {
   using namespace ptz;
   if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
   ptz_reloc_options o;
   if (options) o = *options; else ptz_reloc_options_default(&o);
+  if (lmap) o.max_refs = 1;  // one slot: the anchor
   if (o.max_refs < 1 || o.min_inliers < 0 || !(o.guided_radius >= 0.0) || !std::isfinite(o.guided_radius) ||
       !(std::isfinite(o.ransac_thresh) && o.ransac_thresh > 0) || o.gate_max_pair_matches < 0 || o.gate_max_pair_matches > 4096 ||
       (o.guided_grid != 0 && o.guided_grid != 1))
@@ -183,6 +187,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   if (pr && (prior_options_check(pr->opt) || r->refs->n_img != r->n_ref || n_query > query_set->n_img || (n_query > 0 && !pr->cams) ||
              prior_cams_check(n_query, pr->cams)))
     return PTZ_EINVAL;
+  if (lmap && (lmap->device != r->device || lmap->n_ref != r->n_ref || !lmap->set || lmap->D != query_set->D || query_set->device != r->device ||
+               n_query > query_set->n_img))
+    return PTZ_EINVAL;
+  if (lmap && o.guided_radius > 0.0) return PTZ_EUNSUPPORTED;  // no pair homography between a map and an image
   if (pr) o.inlier_matches = 1;  // a lone admissible candidate passes the ratio test: the tracked run always gates the assembled query
   for (double& t : res->stage_ms) t = 0;
   if (sl_res) sl_res->shortlist_ms = 0;
@@ -287,6 +295,11 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
       sl_res->shortlist_ms = t.elapsed_ms();
     }
   }
+  else if (lmap) {
+    ia.assign(nq, 0);  // the map's set is one image
+    ib.resize(nq);
+    for (int q = 0; q < n_query; ++q) { ib[q] = q; qptr[q + 1] = q + 1; }
+  }
   else {
     ia.resize((size_t)n_query * n_ref);
     ib.resize(ia.size());
@@ -308,14 +321,15 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     res->stage_ms[1] = ptz_desc_matches_device_ms(m);
   }
   else {
-    if (const int32_t rc = ptz_desc_match_pairs(r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
+    if (const int32_t rc = ptz_desc_match_pairs(lmap ? lmap->set : r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
     res->stage_ms[0] = ptz_desc_matches_device_ms(m);
   }
   int64_t nm = ptz_desc_matches_n_matches(m);
   if (nm > INT32_MAX) return PTZ_ELIMIT;
   const int64_t* d_ptr = nullptr;
+  const int32_t* d_ia = nullptr;
   const float *d_ua = nullptr, *d_ub = nullptr;
-  if (const int32_t rc = ptz_desc_matches_device_ptrs(m, &d_ptr, nullptr, nullptr, nullptr, &d_ua, &d_ub)) return rc;
+  if (const int32_t rc = ptz_desc_matches_device_ptrs(m, &d_ptr, &d_ia, nullptr, nullptr, &d_ua, &d_ub)) return rc;
   if (nm > 0 && (!d_ua || !d_ub)) return PTZ_EINVAL;  // sets without key points
 
   // 2. the gate on all pairs, then the guided pass with its device H / found, as MatchDescriptors composes them
@@ -353,7 +367,8 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   const bool gated = o.inlier_matches != 0, trimming = o.trim != 0, cov = o.uncertainty != 0;
   const int nf = ptz_krt_free_dim(o.factor_type);
   const size_t nmx = (size_t)(nm > 0 ? nm : 1);
-  const int64_t ws_asm = ptz_reloc_assemble_workspace_bytes(n_query, nm), ws_trim = trimming ? ptz_krt_trim_workspace_bytes(n_query, nm) : 0;
+  const int64_t ws_asm = lmap ? ptz_landmark_assemble_workspace_bytes(n_query, nm) : ptz_reloc_assemble_workspace_bytes(n_query, nm);
+  const int64_t ws_trim = trimming ? ptz_krt_trim_workspace_bytes(n_query, nm) : 0;
   BlockLayout b;
   const size_t o_pref = b.take(sizeof(int32_t) * npair), o_qptr = b.take(sizeof(int64_t) * (nq + 1)), o_wh = b.take(sizeof(int32_t) * 2 * nq),
                o_sel = b.take(sizeof(int32_t) * K * nq), o_nsel = b.take(sizeof(int32_t) * nq), o_optr = b.take(sizeof(int64_t) * (nq + 1)),
@@ -374,7 +389,13 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
 
   // 3. the assembly
   PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
-  if (const int32_t rc = ptz_reloc_assemble_device(n_query, npair, nm, n_ref, d_ptr, d_ua, d_ub, (const int32_t*)(d + o_pref), (const int64_t*)(d + o_qptr),
+  if (lmap) {  // the anchor takes slot 0 of sel (K = 1); n_sel is derived on the host
+    if (const int32_t rc = ptz_landmark_assemble_device(lmap, n_query, nm, d_ptr, d_ia, d_ub, r->d_cams, r->d_R, (const int32_t*)(d + o_wh), o.factor_type,
+                                                        (int32_t*)(d + o_sel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
+                                                        (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
+      return rc;
+  }
+  else if (const int32_t rc = ptz_reloc_assemble_device(n_query, npair, nm, n_ref, d_ptr, d_ua, d_ub, (const int32_t*)(d + o_pref), (const int64_t*)(d + o_qptr),
                                                    r->d_cams, r->d_R, (const int32_t*)(d + o_wh), o.factor_type, K, (int32_t*)(d + o_sel),
                                                    (int32_t*)(d + o_nsel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
                                                    (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
@@ -442,12 +463,12 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   PTZ_HIP_TRY(hipEventRecord(ev.e[4], st));
 
   // only per-query results reach the host
-  std::vector<int32_t> sel(res->sel_ref ? (size_t)K * nq : 0);
+  std::vector<int32_t> sel(res->sel_ref || (lmap && res->n_sel) ? (size_t)K * nq : 0);
   if (res->cam) PTZ_HIP_TRY(hipMemcpyAsync(res->cam, a_ccur, sizeof(double) * 15 * nq, hipMemcpyDeviceToHost, st));
   if (res->accepted) PTZ_HIP_TRY(hipMemcpyAsync(res->accepted, d_acc, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
   if (res->summaries) PTZ_HIP_TRY(hipMemcpyAsync(res->summaries, d_sum, sizeof(ptz_lm_summary) * nq, hipMemcpyDeviceToHost, st));
-  if (res->sel_ref) PTZ_HIP_TRY(hipMemcpyAsync(sel.data(), d + o_sel, sizeof(int32_t) * K * nq, hipMemcpyDeviceToHost, st));
-  if (res->n_sel) PTZ_HIP_TRY(hipMemcpyAsync(res->n_sel, d + o_nsel, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+  if (!sel.empty()) PTZ_HIP_TRY(hipMemcpyAsync(sel.data(), d + o_sel, sizeof(int32_t) * K * nq, hipMemcpyDeviceToHost, st));
+  if (res->n_sel && !lmap) PTZ_HIP_TRY(hipMemcpyAsync(res->n_sel, d + o_nsel, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
   if (res->trim_report && trimming) PTZ_HIP_TRY(hipMemcpyAsync(res->trim_report, d + o_rep, sizeof(ptz_krt_trim_report) * nq, hipMemcpyDeviceToHost, st));
   if (cov) {
     if (res->cov) PTZ_HIP_TRY(hipMemcpyAsync(res->cov, d + o_cov, sizeof(double) * nf * nf * nq, hipMemcpyDeviceToHost, st));
@@ -459,7 +480,12 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   for (size_t q = 0; q < nq; ++q) {
     if (res->n_matches) res->n_matches[q] = (int32_t)(optr[q + 1] - optr[q]);
     if (res->n_inliers) res->n_inliers[q] = (int32_t)(gated ? gptr[q + 1] - gptr[q] : optr[q + 1] - optr[q]);
-    if (res->sel_ref)
+    if (lmap) {  // sel holds reference images already
+      const int32_t a = sel.empty() ? -1 : sel[q];
+      if (res->sel_ref) res->sel_ref[q] = a >= 0 && a < n_ref ? a : -1;
+      if (res->n_sel) res->n_sel[q] = a >= 0 && a < n_ref ? 1 : 0;
+    }
+    else if (res->sel_ref)
       for (int s = 0; s < K; ++s) { const int32_t p = sel[q * K + s]; res->sel_ref[q * K + s] = p < 0 || p >= npair ? -1 : ia[p]; }
   }
   res->stage_ms[2] = ev.ms(0, 1); res->stage_ms[3] = gated ? ev.ms(1, 2) : 0; res->stage_ms[4] = ev.ms(2, 3); res->stage_ms[5] = cov ? ev.ms(3, 4) : 0;
@@ -496,6 +522,13 @@ extern "C" int32_t ptz_relocalizer_run_tracked(ptz_relocalizer* r, const ptz_des
   ptz_prior_options_default(&p.opt);
   if (prior_opt) p.opt = *prior_opt;
   return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, &p);
+}
+
+extern "C" int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
+                                                 const int32_t* query_wh, const ptz_reloc_options* options, ptz_reloc_result* res)
+{
+  if (!map) return PTZ_EINVAL;
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, nullptr, map);
 }
 
 extern "C" int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr)

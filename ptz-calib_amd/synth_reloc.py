@@ -170,6 +170,21 @@ def make_reloc_descriptors(scene: RelocScene, D: int = 128, noise: int = 12, n_d
     return out[0], out[1]
 
 
+def scene_tracks(scene: RelocScene, n_distractors: int = 0):
+    """The tracks of the references' features as CSR, from RelocScene.ref_track: one track per world ray some reference sees, in
+    ascending ray order, its views in ascending image order.  trk_feat is the feature's index inside its image -- the index it keeps
+    in the sets of make_reloc_descriptors(scene, n_distractors=...), whose distractor features come after an image's own and belong
+    to no track (n_distractors is taken for the signature's sake: it moves no index).
+    Returns (trk_ptr int64 [n_track + 1], trk_img int32, trk_feat int32, trk_ray int64 [n_track]: the world ray of each track)."""
+    del n_distractors
+    img = np.repeat(np.arange(scene.n_ref), np.diff(scene.ref_ptr)).astype(np.int64)
+    feat = np.arange(len(scene.ref_track), dtype=np.int64) - scene.ref_ptr[img]
+    order = np.lexsort((img, scene.ref_track))  # by ray, then by image
+    rays, counts = np.unique(scene.ref_track[order], return_counts=True)
+    trk_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return trk_ptr, img[order].astype(np.int32), feat[order].astype(np.int32), rays.astype(np.int64)
+
+
 def perturb_cameras(cam, angle_deg: float, f_rel: float, seed: int = 0) -> np.ndarray:
     """Prior cameras from true ones [n, 15]: every camera turned by angle_deg about an axis drawn uniformly on the sphere, its
     focal lengths scaled by 1 + f_rel or 1 - f_rel (a fair coin); everything else is copied."""
