@@ -1145,6 +1145,67 @@ int32_t ptz_landmark_assemble_device(const ptz_landmark_map* map, int32_t n_quer
 int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
                                       const int32_t* query_wh, const ptz_reloc_options* options, ptz_reloc_result* result);
 
+/* ---- landmark view: relocalize against the map from a prior camera -----------------------------------------------------------------
+ * A landmark is a unit ray L from the shared centre, so under a prior (K_q, R_q) its pixel in the query is K_q R_q L: no homography,
+ * no reference image, no reference-side distortion.  The contract is csrc/ptz_landmark_prior.h (+ - * / in double rounded one by
+ * one; prior_R [9 n_query] is ptz_reloc_ref_rotations of prior_cams [15 n_query]).
+ * Prediction: m = R_q L, rows summed left to right; ok = m_z > 0 and m finite; px = fx (m_x / m_z) + 0.5 w, py = fy (m_y / m_z) +
+ * 0.5 h, fx the prior's and fy = fx for F / FDist, the prior's fy otherwise.  The prior's distortion does not enter.
+ * Visibility: ok, -radius_px <= px < w + radius_px and -radius_px <= py < h + radius_px, on the doubles; position ((float)px,
+ * (float)py).  The VIEW of query q is its visible landmarks in ascending landmark index: vis_ptr [n_query + 1], vis_lm [n_vis],
+ * vis_uv [n_vis, 2].  It depends on the query's own prior, its image size and the map only.
+ * ptz_landmark_visible (host arrays) builds the view and gathers the packed descriptor rows of the visible landmarks into a
+ * ptz_desc_set of n_query images whose key points are vis_uv (ptz_landmark_view_desc_set, the view's until it is destroyed): the
+ * guided matcher over the pairs (view image q, query image q) under H = identity and radius_px gives the matches of (map, q), idx_a
+ * view-local (the landmark is vis_lm[vis_ptr[q] + idx_a]).  The host reads vis_ptr once, to size the set.
+ * PTZ_EINVAL, before any device work: NULL map / out, n_query < 0, missing arrays, an image size that is not positive, a prior
+ * with a non-finite entry or a focal that is not positive, a radius that is not finite and positive, max_view_bytes < 1;
+ * PTZ_EUNSUPPORTED: factor_type; PTZ_ELIMIT: a view whose set needs more than max_view_bytes or 2^31 - 1 rows -- the caller splits
+ * the batch; n_query = 0 is PTZ_OK with an empty view.  opt = NULL: defaults.
+ * ptz_landmark_view_download / _device_ptrs: every pointer nullable.  ptz_landmark_view_device_ms: the launches of both passes.
+ * ptz_landmark_visible_device: raw DEVICE pointers on the device that owns d_vis_ptr, enqueued on `hip_stream`, no synchronisation;
+ * d_ray [3 n_lm] are arbitrary rays, nothing is validated.  d_vis_ptr [n_query + 1] is always complete; of d_vis_lm / d_vis_uv at
+ * most `capacity` entries are written.  d_workspace: 256-byte aligned, at least ptz_landmark_visible_workspace_bytes(n_lm, n_query)
+ * bytes; whatever it holds before is never read.  PTZ_ELIMIT: n_query x ceil(n_lm / 1024) above 2^31 - 1.
+ * ptz_relocalizer_run_landmarks_tracked is ptz_relocalizer_run_landmarks with three differences: stage 0 builds the view from
+ * prior_cams (lp_opt->radius_px; the prior rotations computed on the host); stage 1 is the guided matcher
+ * (options->guided_grid selects the kernel) over the pairs (view image q, query q) under identity H, and its idx_a is lifted to
+ * landmark indices by a small kernel before ptz_landmark_assemble_device; the solve starts from reloc_prior_camera.  As in
+ * ptz_relocalizer_run_tracked THE GATE ON THE ASSEMBLED QUERY IS FORCED ON and accepted[q] is 0 for a query the gate kept nothing
+ * of.  options->guided_radius is ignored.  stage_ms[0] is the view's device time, stage_ms[1] the matcher's.  view_result (or
+ * NULL), pointers nullable: n_visible [n_query], view_ms.  ptz_relocalizer_table returns the matcher's table: idx_a is view-local,
+ * uv_a the predicted pixel.  ptz_relocalizer_view downloads the last such run's view (every pointer nullable; PTZ_EINVAL when the
+ * last run was no tracked landmark run).  Validation is that of the two runs it combines.  Known limits: the prior's distortion is
+ * ignored in the prediction; max_view_bytes; gate_max_pair_matches still bounds an assembled query; a view is only as good as the
+ * prior. */
+typedef struct ptz_landmark_prior_options {
+  double radius_px;       /* 40: the margin of the visibility rule and the guided matcher's radius */
+  int64_t max_view_bytes; /* 2 GiB: the most a view's gathered set may take on the device */
+} ptz_landmark_prior_options;
+void ptz_landmark_prior_options_default(ptz_landmark_prior_options* o);
+typedef struct ptz_landmark_view ptz_landmark_view;
+int32_t ptz_landmark_visible(const ptz_landmark_map* map, int32_t n_query, const double* prior_cams, const double* prior_R,
+                             const int32_t* query_wh, int32_t factor_type, const ptz_landmark_prior_options* opt, ptz_landmark_view** out);
+void ptz_landmark_view_destroy(ptz_landmark_view* v);
+int64_t ptz_landmark_view_n_visible(const ptz_landmark_view* v);
+int32_t ptz_landmark_view_download(const ptz_landmark_view* v, int64_t* vis_ptr, int32_t* vis_lm, float* vis_uv);
+const ptz_desc_set* ptz_landmark_view_desc_set(const ptz_landmark_view* v);
+int32_t ptz_landmark_view_device_ptrs(const ptz_landmark_view* v, const int64_t** d_vis_ptr, const int32_t** d_vis_lm, const float** d_vis_uv);
+double ptz_landmark_view_device_ms(const ptz_landmark_view* v);
+int64_t ptz_landmark_visible_workspace_bytes(int32_t n_lm, int32_t n_query);
+int32_t ptz_landmark_visible_device(int32_t n_lm, const double* d_ray, int32_t n_query, const double* d_prior_cams, const double* d_prior_R,
+                                    const int32_t* d_query_wh, int32_t factor_type, double radius_px, int64_t* d_vis_ptr, int32_t* d_vis_lm,
+                                    float* d_vis_uv, int64_t capacity, void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+typedef struct ptz_landmark_view_result {
+  int32_t* n_visible;
+  double view_ms;
+} ptz_landmark_view_result;
+int32_t ptz_relocalizer_run_landmarks_tracked(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
+                                              const int32_t* query_wh, const double* prior_cams, const ptz_reloc_options* options,
+                                              const ptz_landmark_prior_options* lp_opt, ptz_reloc_result* result,
+                                              ptz_landmark_view_result* view_result);
+int32_t ptz_relocalizer_view(const ptz_relocalizer* r, int64_t* n_visible, int64_t* vis_ptr, int32_t* vis_lm, float* vis_uv);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,10 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_reloc_prior_pairs", "ptz_reloc_prior_pairs_device", "ptz_relocalizer_run_tracked", "ptz_landmark_map_create",
            "ptz_landmark_map_destroy", "ptz_landmark_map_n_landmarks", "ptz_landmark_map_build_ms", "ptz_landmark_map_download",
            "ptz_landmark_map_desc_set", "ptz_landmark_assemble_workspace_bytes", "ptz_landmark_assemble", "ptz_landmark_assemble_device",
-           "ptz_relocalizer_run_landmarks"]
+           "ptz_relocalizer_run_landmarks", "ptz_landmark_prior_options_default", "ptz_landmark_visible", "ptz_landmark_view_destroy",
+           "ptz_landmark_view_n_visible", "ptz_landmark_view_download", "ptz_landmark_view_desc_set", "ptz_landmark_view_device_ptrs",
+           "ptz_landmark_view_device_ms", "ptz_landmark_visible_workspace_bytes", "ptz_landmark_visible_device",
+           "ptz_relocalizer_run_landmarks_tracked", "ptz_relocalizer_view"]
 
 
 class PtzError(RuntimeError):
@@ -1597,6 +1600,116 @@ def landmark_assemble_device(lmap, n_query, n_match, d_match_ptr, d_idx_a, d_uv_
                                               C.c_void_p(stream) if stream else None), "ptz_landmark_assemble_device")
 
 
+# ---- landmark view: the map from a prior camera (csrc/ptz_landmark_prior.h) ----------------------------------------------------------
+class LandmarkPriorOptions(C.Structure):
+    _fields_ = [("radius_px", C.c_double), ("max_view_bytes", C.c_int64)]
+
+
+def landmark_prior_options(**kw) -> LandmarkPriorOptions:
+    o = LandmarkPriorOptions()
+    lib().ptz_landmark_prior_options_default.restype = None
+    lib().ptz_landmark_prior_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown landmark prior option {k}")
+        setattr(o, k, float(v) if k == "radius_px" else int(v))
+    return o
+
+
+class _ViewDescSet(_BorrowedDescSet):
+    """A view's gathered descriptor set as match_descriptors_guided takes it: image q holds the landmarks query q sees."""
+
+    def __init__(self, handle, D, device_id, feat_ptr):
+        super().__init__(handle, D, device_id)
+        self.feat_ptr, self.n_img = feat_ptr, len(feat_ptr) - 1
+
+
+class LandmarkView:
+    """ptz_landmark_view: per query the landmarks of a map its prior camera sees (ascending landmark index) and their predicted
+    pixels, with their descriptors gathered into a set of n_query images.  Made by landmark_visible."""
+
+    def __init__(self, handle, n_query, D, device_id):
+        self.handle, self.n_query, self.D, self.device_id = handle, int(n_query), int(D), int(device_id)
+        L = lib()
+        L.ptz_landmark_view_n_visible.restype = C.c_int64
+        L.ptz_landmark_view_device_ms.restype = C.c_double
+        L.ptz_landmark_view_desc_set.restype = C.c_void_p
+        L.ptz_landmark_view_destroy.restype = None
+        self.n_visible = int(L.ptz_landmark_view_n_visible(handle))
+        self.device_ms = float(L.ptz_landmark_view_device_ms(handle))
+
+    def arrays(self):
+        """dict of numpy arrays: vis_ptr [n_query + 1], vis_lm [n_vis], vis_uv [n_vis, 2]."""
+        n = self.n_visible
+        ptr, lm, uv = np.zeros(self.n_query + 1, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros((n, 2), dtype=np.float32)
+        _check(lib().ptz_landmark_view_download(self.handle, _p(ptr), _p(lm) if n else None, _p(uv) if n else None), "ptz_landmark_view_download")
+        return dict(vis_ptr=ptr, vis_lm=lm, vis_uv=uv)
+
+    def desc_set(self):
+        """The gathered set as the set_a of match_descriptors_guided (img_a = q, H = identity); the view's until it is closed."""
+        return _ViewDescSet(C.c_void_p(lib().ptz_landmark_view_desc_set(self.handle)), self.D, self.device_id, self.arrays()["vis_ptr"])
+
+    def device_ptrs(self):
+        """Integer device addresses (vis_ptr, vis_lm, vis_uv), the view's until it is closed."""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(lib().ptz_landmark_view_device_ptrs(self.handle, *[C.byref(x) for x in p]), "ptz_landmark_view_device_ptrs")
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_landmark_view_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def landmark_visible(lmap, prior_cams, query_wh, factor_type=0, prior_R=None, **opt):
+    """ptz_landmark_visible: the LandmarkView of a prior camera per query -- prior_cams [n_query, 15], query_wh [n_query, 2]; prior_R:
+    reloc_ref_rotations of the priors unless given.  opt: radius_px (40), max_view_bytes (2 GiB)."""
+    pri = np.ascontiguousarray(prior_cams, dtype=np.float64).reshape(-1, 15)
+    wh = np.ascontiguousarray(query_wh, dtype=np.int32).reshape(-1, 2)
+    o = landmark_prior_options(**opt)
+    if len(wh) != len(pri):
+        raise ValueError("query_wh: one size per query")
+    n = len(pri)
+    if prior_R is None:
+        R = reloc_ref_rotations(pri)
+    else:
+        R = np.ascontiguousarray(prior_R, dtype=np.float64).reshape(-1, 9)
+    if len(R) != n:
+        raise ValueError("prior_R: one matrix per prior")
+    h = C.c_void_p()
+    _check(lib().ptz_landmark_visible(lmap.handle, n, _p(pri) if n else None, _p(R) if n else None, _p(wh) if n else None, int(factor_type),
+                                      C.byref(o), C.byref(h)), "ptz_landmark_visible")
+    return LandmarkView(h, n, lmap.D, lmap.device_id)
+
+
+def landmark_visible_workspace_bytes(n_lm, n_query) -> int:
+    lib().ptz_landmark_visible_workspace_bytes.restype = C.c_int64
+    return int(lib().ptz_landmark_visible_workspace_bytes(int(n_lm), int(n_query)))
+
+
+def landmark_visible_device(n_lm, d_ray, n_query, d_prior_cams, d_prior_R, d_query_wh, d_vis_ptr, d_vis_lm, d_vis_uv, capacity, d_workspace,
+                            workspace_bytes, factor_type=0, radius_px=40.0, stream=None):
+    """ptz_landmark_visible_device: every d_* is a device buffer (torch tensor or integer address); d_ray [n_lm, 3] are arbitrary
+    rays; d_vis_ptr [n_query + 1] is always complete, d_vis_lm / d_vis_uv take at most `capacity` entries; d_workspace needs
+    landmark_visible_workspace_bytes(n_lm, n_query) bytes.  Enqueues on `stream` and returns without synchronising."""
+    _check(lib().ptz_landmark_visible_device(int(n_lm), _dptr(d_ray), int(n_query), _dptr(d_prior_cams), _dptr(d_prior_R), _dptr(d_query_wh),
+                                             int(factor_type), C.c_double(float(radius_px)), _dptr(d_vis_ptr), _dptr(d_vis_lm), _dptr(d_vis_uv),
+                                             C.c_int64(int(capacity)), _dptr(d_workspace), C.c_int64(int(workspace_bytes)),
+                                             C.c_void_p(stream) if stream else None), "ptz_landmark_visible_device")
+
+
 # ---- the resident serving loop (ptz_relocalizer_*) ---------------------------------------------------------------------------------
 class RelocOptions(C.Structure):
     _fields_ = [("match", DescOptions), ("guided_radius", C.c_double), ("ransac_thresh", C.c_double), ("min_inliers", C.c_int32),
@@ -1618,6 +1731,10 @@ class PriorResult(C.Structure):
     _fields_ = [("shortlist", C.c_void_p), ("n_short", C.c_void_p), ("overlap", C.c_void_p), ("prior_ms", C.c_double)]
 
 
+class LandmarkViewResult(C.Structure):
+    _fields_ = [("n_visible", C.c_void_p), ("view_ms", C.c_double)]
+
+
 class Relocalizer:
     """ptz_relocalizer: relocalization from features with the references resident on the device.  ref_set: a DescSet with key points
     (kept alive by this object), ref_cams [n_ref, 15] (image m of the set is camera m)."""
@@ -1633,7 +1750,7 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, landmark_prior=None, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
@@ -1648,7 +1765,13 @@ class Relocalizer:
         guided_grid: every guided pass of the run (guided_radius > 0, prior=) goes through the grid-binned kernel: the same outputs.
         landmarks: None, or a LandmarkMap built from this relocalizer's references: ptz_relocalizer_run_landmarks -- every query is
         matched against the map's one image, not against reference images; max_refs is ignored, sel_ref [n, 1] is the anchor and
-        n_sel is 0 or 1; guided_radius > 0 is PTZ_EUNSUPPORTED.  Exclusive with shortlist and prior."""
+        n_sel is 0 or 1; guided_radius > 0 is PTZ_EUNSUPPORTED.  Exclusive with shortlist and prior.
+        landmark_prior (with landmarks): None, or a dict with cams [n, 15] (a prior camera per query) and optionally radius_px (40),
+        max_view_bytes: ptz_relocalizer_run_landmarks_tracked -- only the landmarks the prior sees are matched, by the guided matcher
+        around their predicted pixels (guided_grid selects the kernel; guided_radius is ignored), the solve starts from the prior and
+        the gate on the assembled query is always on.  The result gains n_visible [n] and view_ms; view() downloads the view."""
+        if landmark_prior is not None and landmarks is None:
+            raise ValueError("landmark_prior= predicts the landmarks of a map: it needs landmarks=")
         if prior is not None and shortlist is not None:
             raise ValueError("prior= and shortlist= are two ways to pick a query's references: give one")
         if landmarks is not None and (prior is not None or shortlist is not None):
@@ -1694,6 +1817,19 @@ class Relocalizer:
             _check(lib().ptz_relocalizer_run_tracked(self.handle, query_set.handle, n, _p(wh), _p(pc) if n else None, C.byref(o), C.byref(po),
                                                      C.byref(r), C.byref(pr)), "ptz_relocalizer_run_tracked")
             extra = dict(shortlist=sl, n_short=ns, overlap=ov, prior_ms=pr.prior_ms)
+        elif landmarks is not None and landmark_prior is not None:
+            po = dict(landmark_prior)
+            pc = np.ascontiguousarray(po.pop("cams"), dtype=np.float64).reshape(-1, 15)
+            if len(pc) != n:
+                raise ValueError("landmark_prior['cams']: one camera per query")
+            po = landmark_prior_options(**po)
+            vr = LandmarkViewResult()
+            nvis = np.zeros(n, dtype=np.int32)
+            vr.n_visible = vp(nvis)
+            _check(lib().ptz_relocalizer_run_landmarks_tracked(self.handle, landmarks.handle, query_set.handle, n, _p(wh), _p(pc) if n else None,
+                                                               C.byref(o), C.byref(po), C.byref(r), C.byref(vr)),
+                   "ptz_relocalizer_run_landmarks_tracked")
+            extra = dict(n_visible=nvis, view_ms=vr.view_ms)
         elif landmarks is not None:
             _check(lib().ptz_relocalizer_run_landmarks(self.handle, landmarks.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)),
                    "ptz_relocalizer_run_landmarks")
@@ -1735,6 +1871,14 @@ class Relocalizer:
         ua, ub = (np.zeros((n, 2), dtype=np.float32) for _ in range(2))
         _check(L.ptz_desc_matches_download(t, _p(ptr), _p(ia), _p(ib), _p(d2), _p(ua) if n else None, _p(ub) if n else None), "ptz_desc_matches_download")
         return dict(match_ptr=ptr, idx_a=ia, idx_b=ib, dist2=d2, uv_a=ua, uv_b=ub)
+
+    def view(self):
+        """The view of the last run, if it had landmark_prior=: dict of vis_ptr [n + 1], vis_lm [n_vis], vis_uv [n_vis, 2]."""
+        k = C.c_int64()
+        _check(lib().ptz_relocalizer_view(self.handle, C.byref(k), None, None, None), "ptz_relocalizer_view")
+        ptr, lm, uv = np.zeros(self._last_n + 1, dtype=np.int64), np.zeros(k.value, dtype=np.int32), np.zeros((k.value, 2), dtype=np.float32)
+        _check(lib().ptz_relocalizer_view(self.handle, None, _p(ptr), _p(lm) if k.value else None, _p(uv) if k.value else None), "ptz_relocalizer_view")
+        return dict(vis_ptr=ptr, vis_lm=lm, vis_uv=uv)
 
     def matches(self):
         """The last run's assembled matches (tests): dict of match_ptr, uv_ref, uv_cur, src."""

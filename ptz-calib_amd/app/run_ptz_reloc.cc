@@ -22,6 +22,10 @@
 // TracksBuilder turns the matches into tracks as PTZRayOptimizer does, ptz_landmark_map_create makes one ray and one descriptor per
 // track, and every test image goes through ptz_relocalizer_run_landmarks -- one (map, image) pair each.  Every record gains
 // n_landmarks and n_matches.
+// --landmark_prior_params <json> / --landmark_sequence (with --landmarks and --landmark_prior_radius; they imply --inlier_matches) are
+// --prior_params / --sequence against the map: a test image with a prior camera goes through ptz_relocalizer_run_landmarks_tracked -- only
+// the landmarks the prior sees are matched, around their predicted pixels -- and the untracked path is the dense landmark run.  Every
+// record gains "tracked" and n_visible.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -123,6 +127,12 @@ int main(int argc, char** argv)
                               "n_landmarks and n_matches");
   parser.Add("landmark_min_views", '\0', "With --landmarks: reference images a track needs to become a landmark (default 2; the tracks come from "
                                          "matches between reference images, so they have two views at least and 1 acts as 2)", false);
+  parser.Add("landmark_prior_params", '\0', "With --landmarks: prior cameras of test images (a parameters file keyed by image name); an image "
+                                            "with an entry is matched against the landmarks its prior sees only (implies --inlier_matches)", false);
+  parser.AddFlag("landmark_sequence", "With --landmarks: the test images are frames in name order; a frame after a registered one is relocalized "
+                                      "against the landmarks that frame's camera sees (implies --inlier_matches)");
+  parser.Add("landmark_prior_radius", '\0', "With --landmark_prior_params / --landmark_sequence: the margin of the predicted view and the guided "
+                                            "matcher's radius in pixels (default 40)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -138,6 +148,23 @@ int main(int argc, char** argv)
   const bool shortlisting = parser.Exist("shortlist");
   const bool prior_file = parser.Exist("prior_params"), sequence = parser.Exist("sequence"), tracking = prior_file || sequence;
   const bool landmarks = parser.Exist("landmarks");
+  const bool lm_prior_file = parser.Exist("landmark_prior_params"), lm_sequence = parser.Exist("landmark_sequence"),
+             lm_tracking = lm_prior_file || lm_sequence;
+  if (!landmarks && (lm_tracking || parser.Exist("landmark_prior_radius"))) {
+    fprintf(stderr, "--landmark_prior_params, --landmark_sequence and --landmark_prior_radius need --landmarks\n");
+    return 1;
+  }
+  if (!lm_tracking && parser.Exist("landmark_prior_radius")) {
+    fprintf(stderr, "--landmark_prior_radius needs --landmark_prior_params or --landmark_sequence\n");
+    return 1;
+  }
+  ptz_landmark_prior_options lpo;
+  ptz_landmark_prior_options_default(&lpo);
+  if (parser.Exist("landmark_prior_radius")) lpo.radius_px = atof(parser.Get("landmark_prior_radius").c_str());
+  if (!(lpo.radius_px > 0.0) || !std::isfinite(lpo.radius_px)) {
+    fprintf(stderr, "--landmark_prior_radius must be a positive number of pixels\n");
+    return 1;
+  }
   const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking || landmarks;
   if (on_device && !parser.Exist("match_descriptors")) {
     fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params, --sequence and --landmarks need --match_descriptors\n");
@@ -297,7 +324,7 @@ int main(int argc, char** argv)
   struct Trimmed { double rms = 0; int n_matches = 0, n_removed = 0, rounds = 0; };
   std::vector<Trimmed> trimmed(test_fnames.size());
   std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0), n_shortlist(test_fnames.size(), 0);
-  std::vector<int> tracked(test_fnames.size(), 0);
+  std::vector<int> tracked(test_fnames.size(), 0), n_visible(test_fnames.size(), 0);
   int n_landmarks = 0;
   if (on_device && !test_fnames.empty()) {
     // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
@@ -321,7 +348,7 @@ int main(int argc, char** argv)
     ro.guided_grid = parser.Exist("guided_grid") ? 1 : 0;
     ro.ransac_thresh = 4.0;  // LoadMatchesInfo's (data_io.cc:384)
     ro.min_inliers = min_inliers;
-    ro.inlier_matches = (parser.Exist("inlier_matches") || tracking) ? 1 : 0;
+    ro.inlier_matches = (parser.Exist("inlier_matches") || tracking || lm_tracking) ? 1 : 0;
     ro.trim = trimming ? 1 : 0;
     ro.trim_options = trim;
     ro.uncertainty = uncertainty ? 1 : 0;
@@ -406,7 +433,11 @@ int main(int argc, char** argv)
       sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
       ptz_prior_result pr;
       pr.shortlist = nullptr; pr.n_short = n_short.data(); pr.overlap = nullptr; pr.prior_ms = 0;
-      rc = lmap   ? ptz_relocalizer_run_landmarks(rl, lmap, test_set, nq, wh.data(), &ro, &rr)
+      std::vector<int32_t> n_vis(nq, 0);
+      ptz_landmark_view_result vr;
+      vr.n_visible = n_vis.data(); vr.view_ms = 0;
+      rc = lmap && priors ? ptz_relocalizer_run_landmarks_tracked(rl, lmap, test_set, nq, wh.data(), priors, &ro, &lpo, &rr, &vr)
+           : lmap ? ptz_relocalizer_run_landmarks(rl, lmap, test_set, nq, wh.data(), &ro, &rr)
            : priors ? ptz_relocalizer_run_tracked(rl, test_set, nq, wh.data(), priors, &ro, &po, &rr, &pr)
            : shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
                           : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
@@ -444,6 +475,7 @@ int main(int argc, char** argv)
       for (int32_t q = 0; q < nq; ++q) {
         const size_t i = idx[q];
         tracked[i] = priors ? 1 : 0;
+        n_visible[i] = n_vis[q];
         multi_n_refs[i] = n_sel[q];
         multi_n_matches[i] = n_matches[q];
         // a tracked frame must also have MOST of its guided matches on one homography: under a true prior nearly all are, while the lone
@@ -476,7 +508,7 @@ int main(int argc, char** argv)
 
     std::vector<size_t> all(test_fnames.size());
     for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-    if (sequence) {
+    if (sequence || lm_sequence) {
       // frame by frame: the camera of a registered frame is the next frame's prior; a lost tracked frame is run again untracked
       std::vector<double> prev;
       for (const size_t t : all) {
@@ -493,13 +525,14 @@ int main(int argc, char** argv)
         prev = success_ids.count(static_cast<long>(t)) ? test_cameras[t].ToVector() : std::vector<double>();
       }
     }
-    else if (prior_file) {
+    else if (prior_file || lm_prior_file) {
+      const std::string prior_path = parser.Get(lm_prior_file ? "landmark_prior_params" : "prior_params");
       // one tracked run over the test images the file has a camera for, one run of the other flags' path over the rest
       std::vector<size_t> with, without;
       std::vector<double> priors;
       for (const size_t t : all) {
         std::vector<Camera> one;
-        if (ReadCamFromJson(parser.Get("prior_params"), {test_fnames[t]}, one)) {
+        if (ReadCamFromJson(prior_path, {test_fnames[t]}, one)) {
           const std::vector<double> v = one[0].ToVector();
           priors.insert(priors.end(), v.begin(), v.end());
           with.push_back(t);
@@ -648,7 +681,8 @@ int main(int argc, char** argv)
         if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
       }
       if (shortlisting || tracking) j["n_shortlist"] = Json::Int(n_shortlist[i]);
-      if (tracking) j["tracked"] = Json::Int(tracked[i]);
+      if (tracking || lm_tracking) j["tracked"] = Json::Int(tracked[i]);
+      if (lm_tracking) j["n_visible"] = Json::Int(n_visible[i]);
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

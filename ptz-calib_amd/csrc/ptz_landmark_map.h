@@ -23,3 +23,21 @@ struct ptz_landmark_map {
   ptz_desc_set* set = nullptr;
   double build_ms = 0;
 };
+
+// A landmark view (ptz_landmark_visible, ptz_landmark_prior.hip): per query the landmarks its prior camera sees, and their packed
+// descriptor rows gathered into a ptz_desc_set of n_query images whose key points are the predicted pixels, so that the guided
+// matcher runs on it as on any set.  Everything stays on the device; only vis_ptr has a host copy (the one read that sizes the set).
+struct ptz_landmark_view {
+  int device = 0;
+  int32_t n_query = 0, n_lm = 0;
+  int64_t n_vis = 0;
+  ptz::PoolBlock blk;               // [prior_cams | H | vis_ptr]
+  const double* d_prior_cams = nullptr;  // [15 n_query]: the run's initial cameras take their focal, rotation and distortion
+  const double* d_H = nullptr;           // [9 n_query]: identities, the guided matcher's H of pair (view image q, query q)
+  const int64_t* d_vis_ptr = nullptr;    // [n_query + 1]
+  const int32_t* d_vis_lm = nullptr;     // [n_vis], in the set's block
+  const float* d_vis_uv = nullptr;       // [2 n_vis] = the set's key points
+  std::vector<int64_t> vis_ptr;
+  ptz_desc_set* set = nullptr;
+  double device_ms = 0;
+};

@@ -7,6 +7,10 @@
 //      camera after stage 3, and stage 4 is forced on (the lone-candidate finding of ptz_reloc_prior.h)
 //      (ptz_relocalizer_run_landmarks) nothing: the run's pairs are (map, query q), one per query -- stage 1 matches every query
 //      against the landmark map's one image, stage 2 does not exist, and stage 3 is ptz_landmark_assemble_device
+//      (ptz_relocalizer_run_landmarks_tracked) the landmark view of the prior cameras                        ptz_landmark_visible
+//      -- then the guided matcher over the pairs (view image q, query q) under identity H stands in place of stage 1, its idx_a is
+//      lifted from view-local to landmark indices in front of the landmark assembly, the prior enters the solve's initial camera,
+//      and stage 4 is forced on, as in the tracked run
 //   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
@@ -53,6 +57,20 @@ __global__ void k_reloc_lost(int n_query, const int64_t* __restrict__ gate_ptr, 
   if (q < n_query && gate_ptr[q + 1] <= gate_ptr[q]) accepted[q] = 0;
 }
 
+// a tracked landmark run: the matcher's idx_a is local to the view image of its pair (= its query); the assembly wants landmarks.
+// One wave per query; an index outside the view becomes -1, which neither votes nor is kept.
+__global__ void k_reloc_lift(int n_query, const int64_t* __restrict__ match_ptr, const int32_t* __restrict__ idx_a,
+                             const int64_t* __restrict__ vis_ptr, const int32_t* __restrict__ vis_lm, int32_t* __restrict__ lifted)
+{
+  const int q = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  if (q >= n_query) return;
+  const int64_t v0 = vis_ptr[q], nv = vis_ptr[q + 1] - v0;
+  for (int64_t i = match_ptr[q] + threadIdx.x % WAVE; i < match_ptr[q + 1]; i += WAVE) {
+    const int32_t a = idx_a[i];
+    lifted[i] = a >= 0 && a < nv ? vis_lm[v0 + a] : -1;
+  }
+}
+
 struct Events {  // the stamps around stages 3 .. 6 on the resident stream (the temporaries of stages 0 and 2 bring their own)
   int dev;
   hipEvent_t e[5] = {};
@@ -76,6 +94,7 @@ struct ptz_relocalizer {
   int32_t gate_pairs = 0, gate_pm = 0;
   int64_t gate_matches = 0;
   ptz_desc_matches* table = nullptr;  // the last run's match table of its pairs (the guided one, if that pass ran)
+  ptz_landmark_view* view = nullptr;  // the last run's landmark view, if it was a tracked landmark run
   std::vector<int32_t> pair_ref;      // the last run's pair list: the reference of each pair,
   std::vector<int64_t> query_ptr;     // and each query's range of it
   // the last run's block: the assembled matches stay until the next run
@@ -141,6 +160,7 @@ extern "C" void ptz_relocalizer_destroy(ptz_relocalizer* r)
   if (r->st) { (void)ptz::stream_wait(r->st); ptzpool::stream_release(r->device, r->st); }
   ptz_match_gate_destroy(r->gate);
   ptz_desc_matches_destroy(r->table);
+  ptz_landmark_view_destroy(r->view);
   ptzpool::dev_release(r->device, r->blk);
   ptzpool::dev_release(r->device, r->d_const);
   delete r;
@@ -164,17 +184,26 @@ struct RelocPrior {
   ptz_prior_result* res;
 };
 
-// all three runs: sl = pr = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references,
-// by votes (sl) or by the overlap with its prior camera (pr); lmap: the landmark run, whose one pair per query is (map, query)
+// the prior cameras of a tracked landmark run and what it reports of its stage 0
+struct RelocLmPrior {
+  const double* cams;
+  ptz_landmark_prior_options opt;
+  ptz_landmark_view_result* res;
+};
+
+// all the runs: sl = pr = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references,
+// by votes (sl) or by the overlap with its prior camera (pr); lmap: the landmark run, whose one pair per query is (map, query);
+// lp (with lmap): the tracked landmark run, whose pair is (the query's view of the map, query)
 static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
                          const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res,
-                         const RelocPrior* pr = nullptr, const ptz_landmark_map* lmap = nullptr)
+                         const RelocPrior* pr = nullptr, const ptz_landmark_map* lmap = nullptr, const RelocLmPrior* lp = nullptr)
 {
   using namespace ptz;
   if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
   ptz_reloc_options o;
   if (options) o = *options; else ptz_reloc_options_default(&o);
   if (lmap) o.max_refs = 1;  // one slot: the anchor
+  if (lp) o.guided_radius = 0.0;  // (ignored: the radius is lp's)
   if (o.max_refs < 1 || o.min_inliers < 0 || !(o.guided_radius >= 0.0) || !std::isfinite(o.guided_radius) ||
       !(std::isfinite(o.ransac_thresh) && o.ransac_thresh > 0) || o.gate_max_pair_matches < 0 || o.gate_max_pair_matches > 4096 ||
       (o.guided_grid != 0 && o.guided_grid != 1))
@@ -190,11 +219,17 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   if (lmap && (lmap->device != r->device || lmap->n_ref != r->n_ref || !lmap->set || lmap->D != query_set->D || query_set->device != r->device ||
                n_query > query_set->n_img))
     return PTZ_EINVAL;
+  if (lp && (!lmap || !(std::isfinite(lp->opt.radius_px) && lp->opt.radius_px > 0) || lp->opt.max_view_bytes < 1 || (n_query > 0 && !lp->cams) ||
+             prior_cams_check(n_query, lp->cams)))
+    return PTZ_EINVAL;
   if (lmap && o.guided_radius > 0.0) return PTZ_EUNSUPPORTED;  // no pair homography between a map and an image
-  if (pr) o.inlier_matches = 1;  // a lone admissible candidate passes the ratio test: the tracked run always gates the assembled query
+  if (pr || lp) o.inlier_matches = 1;  // a lone admissible candidate passes the ratio test: the tracked run always gates the assembled query
   for (double& t : res->stage_ms) t = 0;
   if (sl_res) sl_res->shortlist_ms = 0;
   if (pr && pr->res) pr->res->prior_ms = 0;
+  if (lp && lp->res) lp->res->view_ms = 0;
+  ptz_landmark_view_destroy(r->view);  // (whatever this run is, the last run's view goes)
+  r->view = nullptr;
   if (n_query == 0) return PTZ_OK;
   const int32_t n_ref = r->n_ref, K = o.max_refs, listed = sl ? sl->max_refs : (pr ? pr->opt.max_refs : n_ref),
                 per_query = listed < n_ref ? listed : n_ref;
@@ -299,6 +334,19 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     ia.assign(nq, 0);  // the map's set is one image
     ib.resize(nq);
     for (int q = 0; q < n_query; ++q) { ib[q] = q; qptr[q + 1] = q + 1; }
+    if (lp) {
+      // 0. the view of every query's prior: its visible landmarks and their descriptor rows as image q of a set of its own
+      std::vector<double> pR(9 * nq);
+      if (const int32_t rc = ptz_reloc_ref_rotations(n_query, lp->cams, pR.data())) return rc;
+      if (const int32_t rc = ptz_landmark_visible(lmap, n_query, lp->cams, pR.data(), query_wh, o.factor_type, &lp->opt, &r->view)) return rc;
+      for (int q = 0; q < n_query; ++q) ia[q] = q;
+      res->stage_ms[0] = r->view->device_ms;
+      if (lp->res) {
+        lp->res->view_ms = r->view->device_ms;
+        if (lp->res->n_visible)
+          for (size_t q = 0; q < nq; ++q) lp->res->n_visible[q] = (int32_t)(r->view->vis_ptr[q + 1] - r->view->vis_ptr[q]);
+      }
+    }
   }
   else {
     ia.resize((size_t)n_query * n_ref);
@@ -318,6 +366,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   struct Held { ptz_desc_matches*& m; ~Held() { ptz_desc_matches_destroy(m); } } held{m};
   if (pr) {
     if (const int32_t rc = guided(r->refs, query_set, npair, ia.data(), ib.data(), d_prior_H, nullptr, pr->opt.radius_px, &o.match, &m)) return rc;
+    res->stage_ms[1] = ptz_desc_matches_device_ms(m);
+  }
+  else if (lp) {
+    if (const int32_t rc = guided(r->view->set, query_set, npair, ia.data(), ib.data(), r->view->d_H, nullptr, lp->opt.radius_px, &o.match, &m)) return rc;
     res->stage_ms[1] = ptz_desc_matches_device_ms(m);
   }
   else {
@@ -378,7 +430,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                o_found = b.take(sizeof(int32_t) * nq), o_mask = b.take(nmx), o_gptr = b.take(sizeof(int64_t) * (nq + 1)),
                o_ga = b.take(sizeof(float) * 2 * nmx), o_gb = b.take(sizeof(float) * 2 * nmx), o_kept = b.take(nmx),
                o_rep = b.take(sizeof(ptz_krt_trim_report) * nq), o_wst = b.take((size_t)ws_trim), o_cov = b.take(sizeof(double) * nf * nf * nq),
-               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq);
+               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq), o_lift = b.take(lp ? sizeof(int32_t) * nmx : 0);
   ptzpool::dev_release(r->device, r->blk);
   r->blk = nullptr; r->n_query = 0; r->kept = 0;
   if (ptzpool::dev_acquire(r->device, b.total(), (void**)&r->blk) != hipSuccess) return PTZ_ENOMEM;
@@ -390,6 +442,12 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   // 3. the assembly
   PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (lmap) {  // the anchor takes slot 0 of sel (K = 1); n_sel is derived on the host
+    if (lp) {
+      hipLaunchKernelGGL(k_reloc_lift, dim3((n_query + 3) / 4), dim3(256), 0, st, n_query, d_ptr, d_ia, r->view->d_vis_ptr, r->view->d_vis_lm,
+                         (int32_t*)(d + o_lift));
+      PTZ_HIP_TRY(hipGetLastError());
+      d_ia = (const int32_t*)(d + o_lift);
+    }
     if (const int32_t rc = ptz_landmark_assemble_device(lmap, n_query, nm, d_ptr, d_ia, d_ub, r->d_cams, r->d_R, (const int32_t*)(d + o_wh), o.factor_type,
                                                         (int32_t*)(d + o_sel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
                                                         (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
@@ -400,8 +458,8 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                                    (int32_t*)(d + o_nsel), (int64_t*)(d + o_optr), (float*)(d + o_oa), (float*)(d + o_ob),
                                                    (int32_t*)(d + o_osrc), (double*)(d + o_cref), (double*)(d + o_ccur), d + o_ws, ws_asm, st))
     return rc;
-  if (pr) {  // the solve starts from the prior's focal, rotation and distortion (one small launch, inside stage 3's stamp)
-    reloc_prior_enqueue_cams(n_query, d_prior_cams, o.factor_type, (double*)(d + o_ccur), st);
+  if (pr || lp) {  // the solve starts from the prior's focal, rotation and distortion (one small launch, inside stage 3's stamp)
+    reloc_prior_enqueue_cams(n_query, pr ? d_prior_cams : r->view->d_prior_cams, o.factor_type, (double*)(d + o_ccur), st);
     PTZ_HIP_TRY(hipGetLastError());
   }
   PTZ_HIP_TRY(hipEventRecord(ev.e[1], st));
@@ -445,7 +503,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                                     : ptz_krt_solve_batch_device(n_query, a_ptr, a_ref, a_cur, nullptr, nullptr, nullptr, a_cref, a_ccur, o.factor_type,
                                                                   o.max_reproj_error, &o.lm, d_sum, d_acc, st))
     return rc;
-  if (pr) {
+  if (pr || lp) {
     hipLaunchKernelGGL(k_reloc_lost, dim3((n_query + 255) / 256), dim3(256), 0, st, n_query, (const int64_t*)(d + o_gptr), d_acc);
     PTZ_HIP_TRY(hipGetLastError());
   }
@@ -529,6 +587,25 @@ extern "C" int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_l
 {
   if (!map) return PTZ_EINVAL;
   return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, nullptr, map);
+}
+
+extern "C" int32_t ptz_relocalizer_run_landmarks_tracked(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set,
+                                                         int32_t n_query, const int32_t* query_wh, const double* prior_cams,
+                                                         const ptz_reloc_options* options, const ptz_landmark_prior_options* lp_opt,
+                                                         ptz_reloc_result* res, ptz_landmark_view_result* view_res)
+{
+  if (!map) return PTZ_EINVAL;
+  RelocLmPrior p = {prior_cams, {}, view_res};
+  ptz_landmark_prior_options_default(&p.opt);
+  if (lp_opt) p.opt = *lp_opt;
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, nullptr, map, &p);
+}
+
+extern "C" int32_t ptz_relocalizer_view(const ptz_relocalizer* r, int64_t* n_visible, int64_t* vis_ptr, int32_t* vis_lm, float* vis_uv)
+{
+  if (!r || !r->view || r->n_query <= 0 || r->view->n_query != r->n_query) return PTZ_EINVAL;  // (a run that failed leaves no view to read)
+  if (n_visible) *n_visible = ptz_landmark_view_n_visible(r->view);
+  return ptz_landmark_view_download(r->view, vis_ptr, vis_lm, vis_uv);
 }
 
 extern "C" int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pair, int32_t* pair_ref, int64_t* query_ptr)
