@@ -1175,7 +1175,7 @@ int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_landmark_map
  * of.  options->guided_radius is ignored.  stage_ms[0] is the view's device time, stage_ms[1] the matcher's.  view_result (or
  * NULL), pointers nullable: n_visible [n_query], view_ms.  ptz_relocalizer_table returns the matcher's table: idx_a is view-local,
  * uv_a the predicted pixel.  ptz_relocalizer_view downloads the last such run's view (every pointer nullable; PTZ_EINVAL when the
- * last run was no tracked landmark run).  Validation is that of the two runs it combines.  Known limits: the prior's distortion is
+ * last run was neither a tracked nor a shortlisted landmark run).  Validation is that of the two runs it combines.  Known limits: the prior's distortion is
  * ignored in the prediction; max_view_bytes; gate_max_pair_matches still bounds an assembled query; a view is only as good as the
  * prior. */
 typedef struct ptz_landmark_prior_options {
@@ -1205,6 +1205,60 @@ int32_t ptz_relocalizer_run_landmarks_tracked(ptz_relocalizer* r, const ptz_land
                                               const ptz_landmark_prior_options* lp_opt, ptz_reloc_result* result,
                                               ptz_landmark_view_result* view_result);
 int32_t ptz_relocalizer_view(const ptz_relocalizer* r, int64_t* n_visible, int64_t* vis_ptr, int32_t* vis_lm, float* vis_uv);
+
+/* ---- landmark shortlist: relocalize against the map through probe votes for its cells ----------------------------------------------
+ * Without a prior the landmark run matches every query feature against every landmark.  The map already holds a partition to vote
+ * over: a landmark's HOME is the reference whose optical axis is nearest its ray, a cell of the view sphere.  The contract is
+ * csrc/ptz_landmark_shortlist.h, all integer, on top of csrc/ptz_desc_shortlist.h:
+ *   home set   the landmarks grouped by home: image r of a ptz_desc_set of n_ref images holds the landmarks with home == r in
+ *              ascending landmark index (home_ptr [n_ref + 1], home_lm [n_lm]); a reference that is home of nothing is an empty
+ *              image.  ptz_landmark_map_home_set builds it from the map's host copies on the first request (NULL if that fails);
+ *              the map owns it.  ptz_landmark_map_home_groups downloads the grouping (pointers nullable).
+ *   votes      ptz_landmark_shortlist / _device / _workspace_bytes ARE ptz_desc_shortlist / _device / _workspace_bytes with the home
+ *              set as the reference set: the same kernels, arguments, errors and outputs (shortlist [max_refs n_query] of home
+ *              indices in ascending order, -1 in unused slots; n_short; votes [n_query n_ref]).
+ *   view       the view of query q is every landmark whose home is on q's list, in ascending landmark index (a tie in the matcher
+ *              resolves to the lowest landmark, as in the dense run); a home listed twice counts once.
+ *              ptz_landmark_view_from_homes (host lists [R n_query]; an entry outside [0, n_ref) other than -1 is PTZ_EINVAL) and
+ *              ptz_landmark_view_from_homes_device (a DEVICE list on the map's device, written on `hip_stream` or already complete;
+ *              such an entry is ignored) return a ptz_landmark_view of kind PTZ_LANDMARK_VIEW_HOMES: vis_ptr and vis_lm as for the
+ *              prior's view, a gathered set of n_query images whose key points -- and vis_uv -- are zeros, as the map's own set's.
+ *              Both wait for the stream: the host reads vis_ptr once, to size the set.  PTZ_ELIMIT: a set beyond max_view_bytes or
+ *              2^31 - 1 rows, more than 2^31 - 1 list slots or (query, tile) cells.  R >= 1; n_query = 0 is an empty view.
+ *   matches    ptz_desc_match_pairs over the pairs (view image q, query image q); idx_a is view-local, the landmark is
+ *              vis_lm[vis_ptr[q] + idx_a].  A list that names every non-empty home makes the view the whole map in order, and the
+ *              matches are those of the pairs (map, query q), array for array.
+ * ptz_relocalizer_run_landmarks_shortlisted is ptz_relocalizer_run_landmarks with a stage 0 in front: 0a the vote pass on the
+ * device (options->match's ratio and max_dist2, sl_opt; the lists are not downloaded for the run's own use), 0b the view from the
+ * device lists (at most the default max_view_bytes of ptz_landmark_prior_options); stage 1 is the DENSE matcher over (view q,
+ * query q) with its ratio test and cross check, its idx_a lifted to landmark indices in front of ptz_landmark_assemble_device; the
+ * rest is the landmark run's.  The gate is NOT forced on.  guided_radius > 0 is PTZ_EUNSUPPORTED.  A query with n_short = 0 has an
+ * empty view and no anchor (n_sel = 0).  stage_ms[0] is the matcher's; sl_result (or NULL, pointers nullable): shortlist
+ * [sl_opt->max_refs n_query], n_short, votes [n_query n_ref], shortlist_ms the vote pass; view_result (or NULL): n_visible, view_ms.
+ * ptz_relocalizer_view downloads the run's view, ptz_relocalizer_table its view-local table.  Validation is that of
+ * ptz_relocalizer_run_landmarks and ptz_desc_shortlist_device. */
+#define PTZ_LANDMARK_VIEW_PRIOR 0
+#define PTZ_LANDMARK_VIEW_HOMES 1
+const ptz_desc_set* ptz_landmark_map_home_set(const ptz_landmark_map* map);
+int32_t ptz_landmark_map_home_groups(const ptz_landmark_map* map, int64_t* home_ptr, int32_t* home_lm);
+int32_t ptz_landmark_shortlist(const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_img,
+                               const ptz_desc_options* desc_opt, const ptz_shortlist_options* sl_opt, int32_t* shortlist, int32_t* n_short,
+                               int32_t* votes /* or NULL */, double* device_ms /* or NULL */);
+int64_t ptz_landmark_shortlist_workspace_bytes(const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
+                                               const ptz_shortlist_options* sl_opt);
+int32_t ptz_landmark_shortlist_device(const ptz_landmark_map* map, const ptz_desc_set* query_set, int32_t n_query,
+                                      const int32_t* d_query_img /* or NULL */, const ptz_desc_options* desc_opt,
+                                      const ptz_shortlist_options* sl_opt, int32_t* d_shortlist, int32_t* d_n_short,
+                                      int32_t* d_votes /* or NULL */, void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+int32_t ptz_landmark_view_from_homes(const ptz_landmark_map* map, int32_t n_query, int32_t max_refs, const int32_t* shortlist,
+                                     int64_t max_view_bytes, ptz_landmark_view** out);
+int32_t ptz_landmark_view_from_homes_device(const ptz_landmark_map* map, int32_t n_query, int32_t max_refs, const int32_t* d_shortlist,
+                                            int64_t max_view_bytes, void* hip_stream, ptz_landmark_view** out);
+int32_t ptz_landmark_view_kind(const ptz_landmark_view* v);
+int32_t ptz_relocalizer_run_landmarks_shortlisted(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set,
+                                                  int32_t n_query, const int32_t* query_wh, const ptz_reloc_options* options,
+                                                  const ptz_shortlist_options* sl_opt, ptz_reloc_result* result,
+                                                  ptz_shortlist_result* sl_result, ptz_landmark_view_result* view_result);
 
 #ifdef __cplusplus
 }

@@ -50,7 +50,9 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_relocalizer_run_landmarks", "ptz_landmark_prior_options_default", "ptz_landmark_visible", "ptz_landmark_view_destroy",
            "ptz_landmark_view_n_visible", "ptz_landmark_view_download", "ptz_landmark_view_desc_set", "ptz_landmark_view_device_ptrs",
            "ptz_landmark_view_device_ms", "ptz_landmark_visible_workspace_bytes", "ptz_landmark_visible_device",
-           "ptz_relocalizer_run_landmarks_tracked", "ptz_relocalizer_view"]
+           "ptz_relocalizer_run_landmarks_tracked", "ptz_relocalizer_view", "ptz_landmark_map_home_set", "ptz_landmark_map_home_groups",
+           "ptz_landmark_shortlist", "ptz_landmark_shortlist_workspace_bytes", "ptz_landmark_shortlist_device", "ptz_landmark_view_from_homes",
+           "ptz_landmark_view_from_homes_device", "ptz_landmark_view_kind", "ptz_relocalizer_run_landmarks_shortlisted"]
 
 
 class PtzError(RuntimeError):
@@ -1541,6 +1543,21 @@ class LandmarkMap:
         """The map's descriptors as the set_a of match_descriptors (img_a = 0); the map's until it is closed."""
         return _BorrowedDescSet(C.c_void_p(lib().ptz_landmark_map_desc_set(self.handle)), self.D, self.device_id)
 
+    def home_set(self):
+        """The HOME SET (csrc/ptz_landmark_shortlist.h) as a set of n_ref images: image r holds the landmarks with home r in
+        ascending landmark index.  Built on the first request; the map's until it is closed."""
+        lib().ptz_landmark_map_home_set.restype = C.c_void_p
+        h = lib().ptz_landmark_map_home_set(self.handle)
+        if not h:
+            raise PtzError(-3, "ptz_landmark_map_home_set")
+        return _ViewDescSet(C.c_void_p(h), self.D, self.device_id, self.home_groups()["home_ptr"])
+
+    def home_groups(self):
+        """dict of home_ptr [n_ref + 1], home_lm [n_lm]: the landmarks of home r are home_lm[home_ptr[r]:home_ptr[r + 1]]."""
+        ptr, lm = np.zeros(len(self.ref_cams) + 1, dtype=np.int64), np.zeros(self.n_landmarks, dtype=np.int32)
+        _check(lib().ptz_landmark_map_home_groups(self.handle, _p(ptr), _p(lm) if len(lm) else None), "ptz_landmark_map_home_groups")
+        return dict(home_ptr=ptr, home_lm=lm)
+
     def close(self):
         if self.handle:
             lib().ptz_landmark_map_destroy(self.handle)
@@ -1637,6 +1654,7 @@ class LandmarkView:
         L.ptz_landmark_view_destroy.restype = None
         self.n_visible = int(L.ptz_landmark_view_n_visible(handle))
         self.device_ms = float(L.ptz_landmark_view_device_ms(handle))
+        self.kind = int(L.ptz_landmark_view_kind(handle))  # VIEW_PRIOR or VIEW_HOMES
 
     def arrays(self):
         """dict of numpy arrays: vis_ptr [n_query + 1], vis_lm [n_vis], vis_uv [n_vis, 2]."""
@@ -1691,6 +1709,68 @@ def landmark_visible(lmap, prior_cams, query_wh, factor_type=0, prior_R=None, **
     h = C.c_void_p()
     _check(lib().ptz_landmark_visible(lmap.handle, n, _p(pri) if n else None, _p(R) if n else None, _p(wh) if n else None, int(factor_type),
                                       C.byref(o), C.byref(h)), "ptz_landmark_visible")
+    return LandmarkView(h, n, lmap.D, lmap.device_id)
+
+
+# ---- landmark shortlist: probe votes for the map's homes (csrc/ptz_landmark_shortlist.h) --------------------------------------------
+VIEW_PRIOR, VIEW_HOMES = 0, 1
+
+
+def landmark_shortlist(lmap, query_set, query_img=None, **options):
+    """ptz_landmark_shortlist: desc_shortlist with the map's home set as the reference set -- the homes (cells of the map) worth
+    matching for each query image.  Options and the returned dict are desc_shortlist's; shortlist holds home indices."""
+    qi = np.arange(query_set.n_img, dtype=np.int32) if query_img is None else np.ascontiguousarray(query_img, dtype=np.int32)
+    if qi.ndim != 1:
+        raise ValueError("query_img: one image index per query")
+    sl = _shortlist_split(options)
+    options.setdefault("device_id", lmap.device_id)
+    o = desc_options(**options)
+    n, R, n_ref = len(qi), max(int(sl.max_refs), 1), len(lmap.ref_cams)
+    out = np.full((n, R), -1, dtype=np.int32)
+    ns = np.zeros(n, dtype=np.int32)
+    votes = np.zeros((n, n_ref), dtype=np.int32)
+    ms = C.c_double()
+    _check(lib().ptz_landmark_shortlist(lmap.handle, query_set.handle, n, _p(qi) if n else None, C.byref(o), C.byref(sl), _p(out) if n else None,
+                                        _p(ns) if n else None, _p(votes) if votes.size else None, C.byref(ms)), "ptz_landmark_shortlist")
+    return dict(shortlist=out, n_short=ns, votes=votes, device_ms=ms.value)
+
+
+def landmark_shortlist_workspace_bytes(lmap, query_set, n_query, **sl) -> int:
+    lib().ptz_landmark_shortlist_workspace_bytes.restype = C.c_int64
+    o = shortlist_options(**sl)
+    return int(lib().ptz_landmark_shortlist_workspace_bytes(lmap.handle, query_set.handle, int(n_query), C.byref(o)))
+
+
+def landmark_shortlist_device(lmap, query_set, n_query, d_shortlist, d_n_short, d_workspace, workspace_bytes, d_query_img=None, d_votes=None,
+                              stream=None, **options):
+    """ptz_landmark_shortlist_device: desc_shortlist_device over the map's home set; d_workspace needs
+    landmark_shortlist_workspace_bytes(...) bytes.  Enqueues on `stream` and returns without synchronising."""
+    sl = _shortlist_split(options)
+    options.setdefault("device_id", lmap.device_id)
+    o = desc_options(**options)
+    _check(lib().ptz_landmark_shortlist_device(lmap.handle, query_set.handle, int(n_query), _dptr(d_query_img), C.byref(o), C.byref(sl),
+                                               _dptr(d_shortlist), _dptr(d_n_short), _dptr(d_votes), _dptr(d_workspace),
+                                               C.c_int64(int(workspace_bytes)), C.c_void_p(stream) if stream else None),
+           "ptz_landmark_shortlist_device")
+
+
+def landmark_view_from_homes(lmap, shortlist, max_view_bytes=2 << 30, device=False, n_query=None, max_refs=None, stream=None):
+    """ptz_landmark_view_from_homes: the LandmarkView (kind VIEW_HOMES) of per-query lists of homes -- shortlist [n_query, R] with -1
+    in unused slots: every landmark whose home is on a query's list, in ascending landmark index; vis_uv is zeros.
+    device=True: ptz_landmark_view_from_homes_device -- shortlist is a device buffer (torch tensor or integer address) of
+    [n_query, max_refs] int32 written on `stream`; entries out of range are ignored there, and a ValueError / PTZ_EINVAL here."""
+    h = C.c_void_p()
+    if device:
+        n, R = int(n_query), int(max_refs)
+        _check(lib().ptz_landmark_view_from_homes_device(lmap.handle, n, R, _dptr(shortlist), C.c_int64(int(max_view_bytes)),
+                                                         C.c_void_p(stream) if stream else None, C.byref(h)), "ptz_landmark_view_from_homes_device")
+    else:
+        sl = np.ascontiguousarray(shortlist, dtype=np.int32)
+        if sl.ndim != 2 or sl.shape[1] < 1:
+            raise ValueError("shortlist: [n_query, R] with R >= 1")
+        n, R = sl.shape
+        _check(lib().ptz_landmark_view_from_homes(lmap.handle, n, R, _p(sl) if n else None, C.c_int64(int(max_view_bytes)), C.byref(h)),
+               "ptz_landmark_view_from_homes")
     return LandmarkView(h, n, lmap.D, lmap.device_id)
 
 
@@ -1750,7 +1830,8 @@ class Relocalizer:
                "ptz_relocalizer_create")
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
-            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, landmark_prior=None, **lm):
+            trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, landmark_prior=None,
+            landmark_shortlist=None, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
@@ -1769,7 +1850,16 @@ class Relocalizer:
         landmark_prior (with landmarks): None, or a dict with cams [n, 15] (a prior camera per query) and optionally radius_px (40),
         max_view_bytes: ptz_relocalizer_run_landmarks_tracked -- only the landmarks the prior sees are matched, by the guided matcher
         around their predicted pixels (guided_grid selects the kernel; guided_radius is ignored), the solve starts from the prior and
-        the gate on the assembled query is always on.  The result gains n_visible [n] and view_ms; view() downloads the view."""
+        the gate on the assembled query is always on.  The result gains n_visible [n] and view_ms; view() downloads the view.
+        landmark_shortlist (with landmarks): None, or a dict of shortlist_options fields (max_refs, n_probes, min_votes; {} for the
+        defaults): ptz_relocalizer_run_landmarks_shortlisted -- probe features vote for the map's homes, and the dense matcher sees
+        only the landmarks of the listed homes; the gate is not forced on.  The result gains shortlist [n, R] (home indices),
+        n_short [n], votes [n, n_ref], votes_ms, n_visible [n] and view_ms; view() downloads the view.  Exclusive with
+        landmark_prior, shortlist and prior."""
+        if landmark_shortlist is not None and landmarks is None:
+            raise ValueError("landmark_shortlist= votes for the homes of a map: it needs landmarks=")
+        if landmark_shortlist is not None and landmark_prior is not None:
+            raise ValueError("landmark_shortlist= and landmark_prior= are two ways to pick a query's landmarks: give one")
         if landmark_prior is not None and landmarks is None:
             raise ValueError("landmark_prior= predicts the landmarks of a map: it needs landmarks=")
         if prior is not None and shortlist is not None:
@@ -1830,6 +1920,15 @@ class Relocalizer:
                                                                C.byref(o), C.byref(po), C.byref(r), C.byref(vr)),
                    "ptz_relocalizer_run_landmarks_tracked")
             extra = dict(n_visible=nvis, view_ms=vr.view_ms)
+        elif landmarks is not None and landmark_shortlist is not None:
+            so = shortlist_options(**landmark_shortlist)
+            sr, vr = ShortlistResult(), LandmarkViewResult()
+            sl = np.full((n, max(int(so.max_refs), 1)), -1, dtype=np.int32)
+            ns, votes, nvis = np.zeros(n, dtype=np.int32), np.zeros((n, len(self.ref_cams)), dtype=np.int32), np.zeros(n, dtype=np.int32)
+            sr.shortlist, sr.n_short, sr.votes, vr.n_visible = vp(sl), vp(ns), vp(votes), vp(nvis)
+            _check(lib().ptz_relocalizer_run_landmarks_shortlisted(self.handle, landmarks.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(so),
+                                                                   C.byref(r), C.byref(sr), C.byref(vr)), "ptz_relocalizer_run_landmarks_shortlisted")
+            extra = dict(shortlist=sl, n_short=ns, votes=votes, votes_ms=sr.shortlist_ms, n_visible=nvis, view_ms=vr.view_ms)
         elif landmarks is not None:
             _check(lib().ptz_relocalizer_run_landmarks(self.handle, landmarks.handle, query_set.handle, n, _p(wh), C.byref(o), C.byref(r)),
                    "ptz_relocalizer_run_landmarks")
@@ -1873,7 +1972,7 @@ class Relocalizer:
         return dict(match_ptr=ptr, idx_a=ia, idx_b=ib, dist2=d2, uv_a=ua, uv_b=ub)
 
     def view(self):
-        """The view of the last run, if it had landmark_prior=: dict of vis_ptr [n + 1], vis_lm [n_vis], vis_uv [n_vis, 2]."""
+        """The view of the last run, if it had landmark_prior= or landmark_shortlist=: dict of vis_ptr [n + 1], vis_lm [n_vis], vis_uv [n_vis, 2]."""
         k = C.c_int64()
         _check(lib().ptz_relocalizer_view(self.handle, C.byref(k), None, None, None), "ptz_relocalizer_view")
         ptr, lm, uv = np.zeros(self._last_n + 1, dtype=np.int64), np.zeros(k.value, dtype=np.int32), np.zeros((k.value, 2), dtype=np.float32)

@@ -26,6 +26,11 @@
 // --prior_params / --sequence against the map: a test image with a prior camera goes through ptz_relocalizer_run_landmarks_tracked -- only
 // the landmarks the prior sees are matched, around their predicted pixels -- and the untracked path is the dense landmark run.  Every
 // record gains "tracked" and n_visible.
+// --landmark_shortlist R (with --landmarks; takes --shortlist_probes and --shortlist_min_votes) sends every test image that has no prior
+// -- all of them, the images without an entry in --landmark_prior_params, the untracked frames of --landmark_sequence -- through
+// ptz_relocalizer_run_landmarks_shortlisted: its probe features vote for the map's homes and only the landmarks of the R listed homes
+// are matched.  An image that run does not register is run once more against the whole map, so the fallback chain ends where it
+// ends without the flag.  Every record gains n_shortlist and n_visible (both 0 for an image the dense run answered).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -133,6 +138,9 @@ int main(int argc, char** argv)
                                       "against the landmarks that frame's camera sees (implies --inlier_matches)");
   parser.Add("landmark_prior_radius", '\0', "With --landmark_prior_params / --landmark_sequence: the margin of the predicted view and the guided "
                                             "matcher's radius in pixels (default 40)", false);
+  parser.Add("landmark_shortlist", '\0', "With --landmarks: match each test image without a prior against the landmarks of the R homes (cells "
+                                         "of the map) that most of its probe features vote for; takes --shortlist_probes and "
+                                         "--shortlist_min_votes; every record gains n_shortlist and n_visible", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -152,6 +160,11 @@ int main(int argc, char** argv)
              lm_tracking = lm_prior_file || lm_sequence;
   if (!landmarks && (lm_tracking || parser.Exist("landmark_prior_radius"))) {
     fprintf(stderr, "--landmark_prior_params, --landmark_sequence and --landmark_prior_radius need --landmarks\n");
+    return 1;
+  }
+  const bool lm_shortlisting = parser.Exist("landmark_shortlist");
+  if (!landmarks && lm_shortlisting) {
+    fprintf(stderr, "--landmark_shortlist needs --landmarks\n");
     return 1;
   }
   if (!lm_tracking && parser.Exist("landmark_prior_radius")) {
@@ -198,16 +211,16 @@ int main(int argc, char** argv)
   }
   ptz_shortlist_options sl;
   ptz_shortlist_options_default(&sl);
-  if (!shortlisting && (parser.Exist("shortlist_probes") || parser.Exist("shortlist_min_votes"))) {
-    fprintf(stderr, "--shortlist_probes and --shortlist_min_votes need --shortlist\n");
+  if (!shortlisting && !lm_shortlisting && (parser.Exist("shortlist_probes") || parser.Exist("shortlist_min_votes"))) {
+    fprintf(stderr, "--shortlist_probes and --shortlist_min_votes need --shortlist or --landmark_shortlist\n");
     return 1;
   }
-  if (shortlisting) {
-    sl.max_refs = atoi(parser.Get("shortlist").c_str());
+  if (shortlisting || lm_shortlisting) {
+    sl.max_refs = atoi(parser.Get(shortlisting ? "shortlist" : "landmark_shortlist").c_str());
     if (parser.Exist("shortlist_probes")) sl.n_probes = atoi(parser.Get("shortlist_probes").c_str());
     if (parser.Exist("shortlist_min_votes")) sl.min_votes = atoi(parser.Get("shortlist_min_votes").c_str());
     if (sl.max_refs < 1 || sl.n_probes < 1 || sl.min_votes < 0) {
-      fprintf(stderr, "--shortlist and --shortlist_probes must be at least 1, --shortlist_min_votes not negative\n");
+      fprintf(stderr, "--shortlist, --landmark_shortlist and --shortlist_probes must be at least 1, --shortlist_min_votes not negative\n");
       return 1;
     }
   }
@@ -405,8 +418,10 @@ int main(int argc, char** argv)
       }
     }
 
-    // one run over the test images idx (in that order): tracked from priors [15 per image], or by the path the other flags select
-    const auto run_block = [&](const std::vector<size_t>& idx, const double* priors) {
+    // one run over the test images idx (in that order): tracked from priors [15 per image], or by the path the other flags select;
+    // dense: against the whole map although --landmark_shortlist is given (the second run of an image the shortlisted one lost)
+    const auto run_block = [&](const std::vector<size_t>& idx, const double* priors, bool dense) {
+      const bool listing = lmap && lm_shortlisting && !priors && !dense;
       const int32_t nq = static_cast<int32_t>(idx.size());
       if (!ok || rc != PTZ_OK || nq == 0) return;
       std::vector<std::string> names;
@@ -428,7 +443,7 @@ int main(int argc, char** argv)
       rr.cam = cam.data(); rr.accepted = accepted.data(); rr.summaries = summaries.data(); rr.sel_ref = sel_ref.data(); rr.n_sel = n_sel.data();
       rr.n_matches = n_matches.data(); rr.n_inliers = n_inliers.data(); rr.trim_report = reports.data(); rr.cov = cov.data();
       rr.sigma0 = sigma0.data(); rr.cov_status = status.data();
-      std::vector<int32_t> n_short(nq, priors || shortlisting ? 0 : n_ref);
+      std::vector<int32_t> n_short(nq, priors || shortlisting || lm_shortlisting ? 0 : n_ref);
       ptz_shortlist_result sr;
       sr.shortlist = nullptr; sr.n_short = n_short.data(); sr.votes = nullptr; sr.shortlist_ms = 0;
       ptz_prior_result pr;
@@ -437,6 +452,7 @@ int main(int argc, char** argv)
       ptz_landmark_view_result vr;
       vr.n_visible = n_vis.data(); vr.view_ms = 0;
       rc = lmap && priors ? ptz_relocalizer_run_landmarks_tracked(rl, lmap, test_set, nq, wh.data(), priors, &ro, &lpo, &rr, &vr)
+           : listing ? ptz_relocalizer_run_landmarks_shortlisted(rl, lmap, test_set, nq, wh.data(), &ro, &sl, &rr, &sr, &vr)
            : lmap ? ptz_relocalizer_run_landmarks(rl, lmap, test_set, nq, wh.data(), &ro, &rr)
            : priors ? ptz_relocalizer_run_tracked(rl, test_set, nq, wh.data(), priors, &ro, &po, &rr, &pr)
            : shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
@@ -506,6 +522,16 @@ int main(int argc, char** argv)
       }
     };
 
+    // the images without a prior: by the path the flags select; with --landmark_shortlist the ones it loses once more, dense
+    const auto run_untracked = [&](const std::vector<size_t>& idx) {
+      run_block(idx, nullptr, false);
+      if (!lm_shortlisting || !ok || rc != PTZ_OK) return;
+      std::vector<size_t> lost;
+      for (const size_t i : idx)
+        if (!success_ids.count(static_cast<long>(i))) lost.push_back(i);
+      run_block(lost, nullptr, true);
+    };
+
     std::vector<size_t> all(test_fnames.size());
     for (size_t i = 0; i < all.size(); ++i) all[i] = i;
     if (sequence || lm_sequence) {
@@ -514,14 +540,14 @@ int main(int argc, char** argv)
       for (const size_t t : all) {
         const size_t mark = pairs_matches.size();
         if (!prev.empty()) {
-          run_block({t}, prev.data());
+          run_block({t}, prev.data(), false);
           if (ok && rc == PTZ_OK && !success_ids.count(static_cast<long>(t))) {
             pairs_matches.resize(mark);
             img_pairs_name.resize(mark);
             prev.clear();
           }
         }
-        if (prev.empty()) run_block({t}, nullptr);
+        if (prev.empty()) run_untracked({t});
         prev = success_ids.count(static_cast<long>(t)) ? test_cameras[t].ToVector() : std::vector<double>();
       }
     }
@@ -539,10 +565,10 @@ int main(int argc, char** argv)
         }
         else without.push_back(t);
       }
-      run_block(with, priors.data());
-      run_block(without, nullptr);
+      run_block(with, priors.data(), false);
+      run_untracked(without);
     }
-    else run_block(all, nullptr);
+    else run_untracked(all);
     if (ok && rc == PTZ_OK && parser.Exist("save_matches") && !WriteColmapMatches(parser.Get("save_matches"), pairs_matches, img_pairs_name)) {
       fprintf(stderr, "Error writing matches to %s. Exiting ...\n", parser.Get("save_matches").c_str());
       ok = false;
@@ -680,9 +706,9 @@ int main(int argc, char** argv)
         j["n_landmarks"] = Json::Int(n_landmarks);
         if (!trimming) j["n_matches"] = Json::Int(multi_n_matches[i]);
       }
-      if (shortlisting || tracking) j["n_shortlist"] = Json::Int(n_shortlist[i]);
+      if (shortlisting || tracking || lm_shortlisting) j["n_shortlist"] = Json::Int(n_shortlist[i]);
       if (tracking || lm_tracking) j["tracked"] = Json::Int(tracked[i]);
-      if (lm_tracking) j["n_visible"] = Json::Int(n_visible[i]);
+      if (lm_tracking || lm_shortlisting) j["n_visible"] = Json::Int(n_visible[i]);
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

@@ -281,6 +281,7 @@ extern "C" void ptz_landmark_map_destroy(ptz_landmark_map* m)
   if (!m) return;
   ptz::DeviceGuard g(m->device);
   ptz_desc_set_destroy(m->set);
+  ptz_desc_set_destroy(m->home_set);
   delete m;
 }
 

@@ -4,6 +4,7 @@
 // the matcher gathers uv_a from them and nobody reads it), so the distances stay on the matcher's kernels.
 #pragma once
 
+#include <mutex>
 #include <vector>
 
 #include "ptz_common.h"
@@ -22,6 +23,12 @@ struct ptz_landmark_map {
   std::vector<uint8_t> desc;
   ptz_desc_set* set = nullptr;
   double build_ms = 0;
+  // the HOME SET (ptz_landmark_shortlist.h): the landmarks grouped by home as a ptz_desc_set of n_ref images, built from the host
+  // copies on the first request (ptz_landmark_map_home_set) and the map's until it is destroyed
+  mutable std::mutex home_mutex;
+  mutable ptz_desc_set* home_set = nullptr;
+  mutable std::vector<int64_t> home_ptr;  // [n_ref + 1]
+  mutable std::vector<int32_t> home_lm;   // [n_lm]
 };
 
 // A landmark view (ptz_landmark_visible, ptz_landmark_prior.hip): per query the landmarks its prior camera sees, and their packed
@@ -29,6 +36,7 @@ struct ptz_landmark_map {
 // matcher runs on it as on any set.  Everything stays on the device; only vis_ptr has a host copy (the one read that sizes the set).
 struct ptz_landmark_view {
   int device = 0;
+  int32_t kind = PTZ_LANDMARK_VIEW_PRIOR;  // PTZ_LANDMARK_VIEW_PRIOR, or _HOMES: no prior cameras, no H, no predicted pixels (null)
   int32_t n_query = 0, n_lm = 0;
   int64_t n_vis = 0;
   ptz::PoolBlock blk;               // [prior_cams | H | vis_ptr]

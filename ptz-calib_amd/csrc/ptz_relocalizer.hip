@@ -11,6 +11,10 @@
 //      -- then the guided matcher over the pairs (view image q, query q) under identity H stands in place of stage 1, its idx_a is
 //      lifted from view-local to landmark indices in front of the landmark assembly, the prior enters the solve's initial camera,
 //      and stage 4 is forced on, as in the tracked run
+//      (ptz_relocalizer_run_landmarks_shortlisted) the vote pass over the map's home set, then the view of    ptz_landmark_shortlist_device
+//      the landmarks whose home is on a query's list, both from device arrays                          ptz_landmark_view_from_homes_device
+//      -- then the DENSE matcher of stage 1 runs over the pairs (view image q, query q), its idx_a is lifted as in the tracked
+//      landmark run, and nothing else differs from the landmark run: no prior, no forced gate
 //   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
@@ -57,7 +61,8 @@ __global__ void k_reloc_lost(int n_query, const int64_t* __restrict__ gate_ptr, 
   if (q < n_query && gate_ptr[q + 1] <= gate_ptr[q]) accepted[q] = 0;
 }
 
-// a tracked landmark run: the matcher's idx_a is local to the view image of its pair (= its query); the assembly wants landmarks.
+// a landmark run over a view (from a prior or from homes): the matcher's idx_a is local to the view image of its pair (= its
+// query); the assembly wants landmarks.
 // One wave per query; an index outside the view becomes -1, which neither votes nor is kept.
 __global__ void k_reloc_lift(int n_query, const int64_t* __restrict__ match_ptr, const int32_t* __restrict__ idx_a,
                              const int64_t* __restrict__ vis_ptr, const int32_t* __restrict__ vis_lm, int32_t* __restrict__ lifted)
@@ -94,7 +99,7 @@ struct ptz_relocalizer {
   int32_t gate_pairs = 0, gate_pm = 0;
   int64_t gate_matches = 0;
   ptz_desc_matches* table = nullptr;  // the last run's match table of its pairs (the guided one, if that pass ran)
-  ptz_landmark_view* view = nullptr;  // the last run's landmark view, if it was a tracked landmark run
+  ptz_landmark_view* view = nullptr;  // the last run's landmark view, if it was a tracked or a shortlisted landmark run
   std::vector<int32_t> pair_ref;      // the last run's pair list: the reference of each pair,
   std::vector<int64_t> query_ptr;     // and each query's range of it
   // the last run's block: the assembled matches stay until the next run
@@ -191,12 +196,21 @@ struct RelocLmPrior {
   ptz_landmark_view_result* res;
 };
 
+// the vote options of a shortlisted landmark run and what it reports of its stage 0
+struct RelocLmShort {
+  ptz_shortlist_options opt;
+  ptz_shortlist_result* sl_res;
+  ptz_landmark_view_result* res;
+};
+
 // all the runs: sl = pr = nullptr is ptz_relocalizer_run (every reference of every query), else stage 0 picks a query's references,
 // by votes (sl) or by the overlap with its prior camera (pr); lmap: the landmark run, whose one pair per query is (map, query);
-// lp (with lmap): the tracked landmark run, whose pair is (the query's view of the map, query)
+// lp (with lmap): the tracked landmark run, whose pair is (the query's view of the map, query); ls (with lmap): the shortlisted
+// landmark run, the same pair with the view of the listed homes
 static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set* query_set, int32_t n_query, const int32_t* query_wh,
                          const ptz_reloc_options* options, const ptz_shortlist_options* sl, ptz_reloc_result* res, ptz_shortlist_result* sl_res,
-                         const RelocPrior* pr = nullptr, const ptz_landmark_map* lmap = nullptr, const RelocLmPrior* lp = nullptr)
+                         const RelocPrior* pr = nullptr, const ptz_landmark_map* lmap = nullptr, const RelocLmPrior* lp = nullptr,
+                         const RelocLmShort* ls = nullptr)
 {
   using namespace ptz;
   if (!r || !query_set || n_query < 0 || !res || (n_query > 0 && !query_wh)) return PTZ_EINVAL;
@@ -222,12 +236,15 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   if (lp && (!lmap || !(std::isfinite(lp->opt.radius_px) && lp->opt.radius_px > 0) || lp->opt.max_view_bytes < 1 || (n_query > 0 && !lp->cams) ||
              prior_cams_check(n_query, lp->cams)))
     return PTZ_EINVAL;
+  if (ls && (!lmap || lp || shortlist_options_check(ls->opt))) return PTZ_EINVAL;
   if (lmap && o.guided_radius > 0.0) return PTZ_EUNSUPPORTED;  // no pair homography between a map and an image
   if (pr || lp) o.inlier_matches = 1;  // a lone admissible candidate passes the ratio test: the tracked run always gates the assembled query
   for (double& t : res->stage_ms) t = 0;
   if (sl_res) sl_res->shortlist_ms = 0;
   if (pr && pr->res) pr->res->prior_ms = 0;
   if (lp && lp->res) lp->res->view_ms = 0;
+  if (ls && ls->sl_res) ls->sl_res->shortlist_ms = 0;
+  if (ls && ls->res) ls->res->view_ms = 0;
   ptz_landmark_view_destroy(r->view);  // (whatever this run is, the last run's view goes)
   r->view = nullptr;
   if (n_query == 0) return PTZ_OK;
@@ -347,6 +364,42 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
           for (size_t q = 0; q < nq; ++q) lp->res->n_visible[q] = (int32_t)(r->view->vis_ptr[q + 1] - r->view->vis_ptr[q]);
       }
     }
+    else if (ls) {
+      // 0a. the vote pass over the map's home set; the lists stay on the device (sl_res downloads them for the caller)
+      const size_t R = (size_t)ls->opt.max_refs;
+      const int64_t ws = ptz_landmark_shortlist_workspace_bytes(lmap, query_set, n_query, &ls->opt);
+      if (ws <= 0) return PTZ_ENOMEM;  // (a home set that could not be built)
+      BlockLayout b;
+      const size_t o_sl = b.take(sizeof(int32_t) * R * nq), o_ns = b.take(sizeof(int32_t) * nq), o_votes = b.take(sizeof(int32_t) * nq * n_ref),
+                   o_ws = b.take((size_t)ws);
+      CallHeld t(st);
+      if (const int32_t rc = t.acquire(r->device, b.total())) return rc;
+      char* const p = t.base;
+      PTZ_HIP_TRY(hipEventRecord(t.ev[0], st));
+      if (const int32_t rc = ptz_landmark_shortlist_device(lmap, query_set, n_query, nullptr, &o.match, &ls->opt, (int32_t*)(p + o_sl),
+                                                           (int32_t*)(p + o_ns), (int32_t*)(p + o_votes), p + o_ws, ws, st))
+        return rc;
+      PTZ_HIP_TRY(hipEventRecord(t.ev[1], st));
+      if (ls->sl_res) {
+        ptz_shortlist_result* sr = ls->sl_res;
+        if (sr->shortlist) PTZ_HIP_TRY(hipMemcpyAsync(sr->shortlist, p + o_sl, sizeof(int32_t) * R * nq, hipMemcpyDeviceToHost, st));
+        if (sr->n_short) PTZ_HIP_TRY(hipMemcpyAsync(sr->n_short, p + o_ns, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+        if (sr->votes) PTZ_HIP_TRY(hipMemcpyAsync(sr->votes, p + o_votes, sizeof(int32_t) * nq * n_ref, hipMemcpyDeviceToHost, st));
+      }
+      // 0b. the view of the listed homes, on the same stream: image q of its set holds the landmarks query q is matched against
+      ptz_landmark_prior_options vo;
+      ptz_landmark_prior_options_default(&vo);
+      if (const int32_t rc = ptz_landmark_view_from_homes_device(lmap, n_query, (int32_t)R, (const int32_t*)(p + o_sl), vo.max_view_bytes, st, &r->view))
+        return rc;
+      PTZ_HIP_TRY(hipGetLastError());
+      for (int q = 0; q < n_query; ++q) ia[q] = q;
+      if (ls->sl_res) ls->sl_res->shortlist_ms = t.elapsed_ms();
+      if (ls->res) {
+        ls->res->view_ms = r->view->device_ms;
+        if (ls->res->n_visible)
+          for (size_t q = 0; q < nq; ++q) ls->res->n_visible[q] = (int32_t)(r->view->vis_ptr[q + 1] - r->view->vis_ptr[q]);
+      }
+    }
   }
   else {
     ia.resize((size_t)n_query * n_ref);
@@ -373,7 +426,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
     res->stage_ms[1] = ptz_desc_matches_device_ms(m);
   }
   else {
-    if (const int32_t rc = ptz_desc_match_pairs(lmap ? lmap->set : r->refs, query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
+    if (const int32_t rc = ptz_desc_match_pairs(ls ? r->view->set : (lmap ? lmap->set : r->refs), query_set, npair, ia.data(), ib.data(), &o.match, &m)) return rc;
     res->stage_ms[0] = ptz_desc_matches_device_ms(m);
   }
   int64_t nm = ptz_desc_matches_n_matches(m);
@@ -430,7 +483,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                o_found = b.take(sizeof(int32_t) * nq), o_mask = b.take(nmx), o_gptr = b.take(sizeof(int64_t) * (nq + 1)),
                o_ga = b.take(sizeof(float) * 2 * nmx), o_gb = b.take(sizeof(float) * 2 * nmx), o_kept = b.take(nmx),
                o_rep = b.take(sizeof(ptz_krt_trim_report) * nq), o_wst = b.take((size_t)ws_trim), o_cov = b.take(sizeof(double) * nf * nf * nq),
-               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq), o_lift = b.take(lp ? sizeof(int32_t) * nmx : 0);
+               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq), o_lift = b.take(lp || ls ? sizeof(int32_t) * nmx : 0);
   ptzpool::dev_release(r->device, r->blk);
   r->blk = nullptr; r->n_query = 0; r->kept = 0;
   if (ptzpool::dev_acquire(r->device, b.total(), (void**)&r->blk) != hipSuccess) return PTZ_ENOMEM;
@@ -442,7 +495,7 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   // 3. the assembly
   PTZ_HIP_TRY(hipEventRecord(ev.e[0], st));
   if (lmap) {  // the anchor takes slot 0 of sel (K = 1); n_sel is derived on the host
-    if (lp) {
+    if (lp || ls) {
       hipLaunchKernelGGL(k_reloc_lift, dim3((n_query + 3) / 4), dim3(256), 0, st, n_query, d_ptr, d_ia, r->view->d_vis_ptr, r->view->d_vis_lm,
                          (int32_t*)(d + o_lift));
       PTZ_HIP_TRY(hipGetLastError());
@@ -599,6 +652,18 @@ extern "C" int32_t ptz_relocalizer_run_landmarks_tracked(ptz_relocalizer* r, con
   ptz_landmark_prior_options_default(&p.opt);
   if (lp_opt) p.opt = *lp_opt;
   return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, nullptr, map, &p);
+}
+
+extern "C" int32_t ptz_relocalizer_run_landmarks_shortlisted(ptz_relocalizer* r, const ptz_landmark_map* map, const ptz_desc_set* query_set,
+                                                             int32_t n_query, const int32_t* query_wh, const ptz_reloc_options* options,
+                                                             const ptz_shortlist_options* sl_opt, ptz_reloc_result* res,
+                                                             ptz_shortlist_result* sl_res, ptz_landmark_view_result* view_res)
+{
+  if (!map) return PTZ_EINVAL;
+  RelocLmShort s = {{}, sl_res, view_res};
+  ptz_shortlist_options_default(&s.opt);
+  if (sl_opt) s.opt = *sl_opt;
+  return reloc_run(__func__, r, query_set, n_query, query_wh, options, nullptr, res, nullptr, nullptr, map, nullptr, &s);
 }
 
 extern "C" int32_t ptz_relocalizer_view(const ptz_relocalizer* r, int64_t* n_visible, int64_t* vis_ptr, int32_t* vis_lm, float* vis_uv)
