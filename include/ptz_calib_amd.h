@@ -268,6 +268,23 @@ int32_t ptz_chol_solve_batch(int32_t count, int32_t n, const double* A, const do
 int32_t ptz_debug_chol_solve(int32_t count, const int32_t* n, int32_t ld, const double* A, const double* rhs, double* x,
                              int32_t* fail, const int32_t* active, int32_t path, int32_t flags, int32_t device_id);
 
+/* Diagnostic for the tests of the Schur kernels (k_ray_prep, k_schur_f / k_schur / k_schur_w): the damped reduced camera system
+ * S y = b of the FIRST LM step of problem `index`, as the solver's own launches leave it.  The call runs the solver's prologue
+ * (state and LM reset, linearisation, control words, the step opened) and its first pass up to and including the system's
+ * construction, through the code the solver runs, in the full-size launch shape -- with the caller's Jacobi scales in place of the
+ * column norms: scale_c [n_cam][NC], scale_r [n_ray][3] in the caller's ray order, of problem `index` (NULL: 1.0; the other
+ * problems of the batch always get 1.0).  flags bit 0: the problem's block of the padded system starts as 0xFF bytes, so a tile
+ * that is read without having been cleared shows as NaN.  Outputs, in the cameras' numbering (camera i: rows i NC ..), the
+ * elimination order undone, tiles outside the structure reported as zero, the lower triangle mirrored: S [n][n], n = NC n_cam;
+ * rhs [n] = g_c - sum W E g_r; diag_c [n_cam][NC] (may be NULL) the clamped diagonal the LM term is made of; info [8] (may be NULL):
+ * kernel (0 k_schur_w, 1 k_schur, 2 k_schur_f), table in global memory, order np of the padded system, its 64-column tiles,
+ * 1 if the problem's elimination order is not the identity, the batch's largest observation count and run count of one camera,
+ * threads of the Schur workgroup.  The batch's state is left mid-step: a later solve starts over from the stored initial state.
+ * PTZ_EUNSUPPORTED: PTZRayDistDisp, annotations, shared intrinsics.  PTZ_EINVAL: no state, index out of range, NULL S / rhs, or
+ * a problem that ends at iteration zero (no step is opened). */
+int32_t ptz_debug_batch_reduced_system(ptz_ba_batch* b, int32_t index, const double* scale_c, const double* scale_r, int32_t flags,
+                                       double* S, double* rhs, double* diag_c, int32_t* info);
+
 /* Measured FP64 matrix-core rate of the device (v_mfma_f64_16x16x4_f64 from registers, every wave slot busy): the
  * number the reduced-camera solve is priced against in the roofline reports. */
 int32_t ptz_mfma_f64_peak(int32_t device_id, double* tflops);

@@ -52,7 +52,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_landmark_view_device_ms", "ptz_landmark_visible_workspace_bytes", "ptz_landmark_visible_device",
            "ptz_relocalizer_run_landmarks_tracked", "ptz_relocalizer_view", "ptz_landmark_map_home_set", "ptz_landmark_map_home_groups",
            "ptz_landmark_shortlist", "ptz_landmark_shortlist_workspace_bytes", "ptz_landmark_shortlist_device", "ptz_landmark_view_from_homes",
-           "ptz_landmark_view_from_homes_device", "ptz_landmark_view_kind", "ptz_relocalizer_run_landmarks_shortlisted"]
+           "ptz_landmark_view_from_homes_device", "ptz_landmark_view_kind", "ptz_relocalizer_run_landmarks_shortlisted",
+           "ptz_debug_batch_reduced_system"]
 
 
 class PtzError(RuntimeError):
@@ -284,6 +285,32 @@ class BaBatch:
         _check(lib().ptz_ba_batch_linearize(self.handle, index, C.byref(cost), _p(g_c), _p(U), _p(g_r), _p(V), _p(W)),
                "ptz_ba_batch_linearize")
         return dict(cost=cost.value, g_c=g_c, U=U, g_r=g_r, V=V, W=W, nc=nc)
+
+    REDUCED_INFO = ("kernel", "table_global", "np", "n_tiles", "reordered", "max_cam_obs", "max_cam_run", "threads")
+
+    def reduced_system(self, index=0, scale_c=None, scale_r=None, poison=True):
+        """ptz_debug_batch_reduced_system: the damped reduced camera system of problem `index`'s first LM step as the solver's own
+        launches build it, with the caller's Jacobi scales (scale_c [n_cam, NC], scale_r [n_ray, 3]; None: 1.0).  Returns
+        (S [n, n], b [n], diag_c [n_cam, NC], info: int32 [8], see REDUCED_INFO) in the cameras' numbering."""
+        if not 0 <= index < self.n:  # (the library refuses it before it reads anything)
+            one = np.zeros(1)
+            _check(lib().ptz_debug_batch_reduced_system(self.handle, int(index), None, None, 0, _p(one), _p(one), None, None),
+                   "ptz_debug_batch_reduced_system")
+        s = self.scenes[index]
+        nc = self.nc
+        n = s.n_cam * nc
+        if scale_c is not None:
+            scale_c = np.ascontiguousarray(scale_c, dtype=np.float64)
+            if scale_c.shape != (s.n_cam, nc):
+                raise ValueError("scale_c must be [n_cam, NC]")
+        if scale_r is not None:
+            scale_r = np.ascontiguousarray(scale_r, dtype=np.float64)
+            if scale_r.shape != (s.n_ray, 3):
+                raise ValueError("scale_r must be [n_ray, 3]")
+        S = np.zeros((n, n)); b = np.zeros(n); diag_c = np.zeros((s.n_cam, nc)); info = np.zeros(8, dtype=np.int32)
+        _check(lib().ptz_debug_batch_reduced_system(self.handle, int(index), _p(scale_c), _p(scale_r), 1 if poison else 0, _p(S), _p(b),
+                                                    _p(diag_c), _p(info)), "ptz_debug_batch_reduced_system")
+        return S, b, diag_c, info
 
     def covariance(self, gauge_cam=None, pixel_sigma=0.0, cov=None, sigma0=None):
         """ptz_ba_batch_covariance at the batch's current state (after a solve: the minimum-cost point).  gauge_cam: the anchor

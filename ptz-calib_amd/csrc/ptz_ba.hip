@@ -567,19 +567,15 @@ static void make_groups(ptz_ba_batch* b)
   }
 }
 
-// one LM pass of one group in launch shape `sh`, enqueued on b->stream; returns after enqueueing (no synchronisation).
-// A pass = one trust-region step and the bookkeeping that OPENS the next one (k_lm_pre last: the first iteration is opened by
-// solve_impl's prologue), so that launch shapes with and without launches of their own for LM control can follow one another.
-template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const PassShape& sh)
+// What a pass's kernels are given: the group's Dev with the launch shape's fields set.  fast / fuse: see enqueue_pass.
+template <int TYPE> Dev pass_dev(const ptz_ba_batch* b, const Dev& dgrp, const PassShape& sh, bool* fast_out = nullptr, bool* fuse_out = nullptr)
 {
-  constexpr int NC = Dims<TYPE>::NC;
   Dev d = dgrp;
   d.use_act = sh.compact ? 1 : 0;
   d.ray_block = sh.ray_block;
   d.chol.count = sh.slots;
   d.chol.act = sh.compact ? d.act : nullptr;
   d.chol.act_n = d.grp_ctl + 2;
-  const int path_slots = sh.path_slots > 0 ? sh.path_slots : sh.slots;
   if (!sh.fused) d.chol.L = nullptr;  // (the second matrix marks the one-launch-per-column path)
   // Scenes without annotation residuals and shared blocks: the camera-side linearisation of the CANDIDATE is evaluated before the
   // step is judged (k_lin_cam, Dev::spec_lin), and one control point per pass judges the step and opens the next iteration
@@ -593,8 +589,23 @@ template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const Pa
   const bool fuse = sh.fuse_ctl && fast;
   d.spec_lin = fast ? 1 : 0;
   d.fuse_ctl = fuse ? 1 : 0;
+  if (fast_out) *fast_out = fast;
+  if (fuse_out) *fuse_out = fuse;
+  return d;
+}
+
+// Which Schur kernel a launch took (ptz_debug_batch_reduced_system reports it): 0 k_schur_w, 1 k_schur, 2 k_schur_f
+struct SchurLaunch { int kernel = -1, threads = 0; };
+
+// The reduced camera system of the scenes of one pass, enqueued on b->stream: ray preparation (LM diagonal, E blocks, the system's
+// structural tiles cleared) and the Schur kernel of the batch.  `d` is pass_dev()'s.  One body for the solver's passes and for
+// ptz_debug_batch_reduced_system, which reads back what these launches leave.
+template <int TYPE> SchurLaunch enqueue_reduced_system(ptz_ba_batch* b, const Dev& d, const PassShape& sh)
+{
+  constexpr int NC = Dims<TYPE>::NC;
   const int B = sh.slots;
   hipStream_t st = b->stream;
+  SchurLaunch sl;
   const int schur_thr = schur_threads<TYPE>();
   const size_t schur_smem = schur_lds_bytes(b->schur_tg ? 0 : b->max_cam_obs, NC, d.chol.np, b->schur_w, schur_thr, Dims<TYPE>::NW, b->max_cam_ent,
                                             b->schur_f ? SCHUR_F_ROW : 0);
@@ -612,20 +623,39 @@ template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const Pa
   b->prof_end();
   b->prof_begin(P_SCHUR);
   if (b->schur_w) {
+    sl.kernel = 0; sl.threads = SCHUR_THREADS;
     if (b->schur_tg) LAUNCH((k_schur_w<TYPE, true>), dim3(b->max_cam, B), dim3(SCHUR_THREADS), schur_smem, d);
     else LAUNCH((k_schur_w<TYPE, false>), dim3(b->max_cam, B), dim3(SCHUR_THREADS), schur_smem, d);
   }
   else if (b->schur_f) {
     if constexpr (Dims<TYPE>::FACTOR == 0) {
+      sl.kernel = 2; sl.threads = 256;
       if (b->schur_tg) LAUNCH((k_schur_f<TYPE, true>), dim3(b->max_cam, B), dim3(256), schur_smem, d);
       else LAUNCH((k_schur_f<TYPE, false>), dim3(b->max_cam, B), dim3(256), schur_smem, d);
     }
   }
-  else if (b->schur_tg) LAUNCH((k_schur<TYPE, true>), dim3(b->max_cam, B), dim3(schur_thr), schur_smem, d);
-  else LAUNCH((k_schur<TYPE, false>), dim3(b->max_cam, B), dim3(schur_thr), schur_smem, d);
+  else {
+    sl.kernel = 1; sl.threads = schur_thr;
+    if (b->schur_tg) LAUNCH((k_schur<TYPE, true>), dim3(b->max_cam, B), dim3(schur_thr), schur_smem, d);
+    else LAUNCH((k_schur<TYPE, false>), dim3(b->max_cam, B), dim3(schur_thr), schur_smem, d);
+  }
   if (Dims<TYPE>::HAS3D) LAUNCH(k_schur_3d<TYPE>, dim3(B), dim3(64), 0, d);
   if (d.shared) LAUNCH(k_fold_system<TYPE>, dim3(B), dim3(1024), sizeof(double) * (size_t)(b->max_n + 4) + (size_t)(d.chol.np / CHOL_NB) * (d.chol.np / CHOL_NB), d);
   b->prof_end();
+  return sl;
+}
+
+// one LM pass of one group in launch shape `sh`, enqueued on b->stream; returns after enqueueing (no synchronisation).
+// A pass = one trust-region step and the bookkeeping that OPENS the next one (k_lm_pre last: the first iteration is opened by
+// solve_impl's prologue), so that launch shapes with and without launches of their own for LM control can follow one another.
+template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const PassShape& sh)
+{
+  bool fast = false, fuse = false;
+  const Dev d = pass_dev<TYPE>(b, dgrp, sh, &fast, &fuse);
+  const int path_slots = sh.path_slots > 0 ? sh.path_slots : sh.slots;
+  const int B = sh.slots;
+  hipStream_t st = b->stream;
+  enqueue_reduced_system<TYPE>(b, d, sh);
   chol_factor_solve_profiled(d.chol, d.yc, st, b, sh.fused, path_slots);
   if (d.shared) LAUNCH(k_group_expand<TYPE>, dim3(B), dim3(256), 0, d);
   if (!fuse) {
@@ -665,6 +695,43 @@ template <int TYPE> void enqueue_pass(ptz_ba_batch* b, const Dev& dgrp, const Pa
   b->prof_end();
 }
 
+// ---- the prologue of a solve, in the pieces ptz_debug_batch_reduced_system runs too ----
+// The scene groups and their control words on the host: nothing of this batch is in flight.  Leaves b->stream = stream 0.
+static void begin_solve(ptz_ba_batch* b)
+{
+  make_groups(b);
+  const int G = (int)b->dg.size();
+  b->stream = b->streams[0];
+  for (int i = 0; i < 4 * b->ctl_groups; ++i) __atomic_store_n(&b->h_ctl[i], 0, __ATOMIC_RELEASE);  // nothing of this batch is in flight
+  for (int g = 0; g < G; ++g) __atomic_store_n(&b->h_ctl[4 * g + 2], b->group_count[g], __ATOMIC_RELEASE);
+}
+
+// x <- initial state, scales <- 1, LM state reset (whole batch, stream 0)
+template <int TYPE> void enqueue_solve_init(ptz_ba_batch* b)
+{
+  constexpr int NC = Dims<TYPE>::NC;
+  const Dev& d = b->d;
+  const int B = b->n_scene;
+  const size_t n15 = (size_t)15 * b->total_cam, n3 = (size_t)3 * b->total_ray, nnc = (size_t)b->total_cam * NC;
+  const size_t most = std::max(std::max(n15, n3), std::max(std::max(nnc, (size_t)6 * B), d.dsp_x ? d.dsp_stride : (size_t)0));
+  LAUNCH(k_solve_init, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, d, (const double*)b->cam0, (const double*)b->ray0, (const double*)b->dsp0,
+         (const double*)b->tlw0, n15, n3, nnc);
+}
+
+// The groups' control words on the device; then iteration zero's books are closed and the first step is opened (every pass ends
+// with the same bookkeeping for the next)
+template <int TYPE> void enqueue_open_first_step(ptz_ba_batch* b)
+{
+  const int G = (int)b->dg.size();
+  for (int g = 0; g < G; ++g) hipLaunchKernelGGL(k_ctl_reset, dim3(1), dim3(64), 0, b->stream, b->dg[g]);
+  b->prof_begin(P_LMCTL);
+  for (int g = 0; g < G; ++g) {
+    LAUNCH(k_lm_pre<TYPE>, dim3(b->group_count[g]), dim3(LM_THREADS), 0, b->dg[g]);
+    if (b->shapes.size() > 1 && b->compaction) LAUNCH(k_compact, dim3(1), dim3(1024), 0, b->dg[g]);
+  }
+  b->prof_end();
+}
+
 template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
 {
   constexpr int NC = Dims<TYPE>::NC;
@@ -674,20 +741,11 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
   double t_enq = 0, t_sync = 0;
-  make_groups(b);
+  begin_solve(b);
   const int G = (int)b->dg.size();
   hipStream_t s0 = b->streams[0];
-  b->stream = s0;
-  for (int i = 0; i < 4 * b->ctl_groups; ++i) __atomic_store_n(&b->h_ctl[i], 0, __ATOMIC_RELEASE);  // nothing of this batch is in flight
-  for (int g = 0; g < G; ++g) __atomic_store_n(&b->h_ctl[4 * g + 2], b->group_count[g], __ATOMIC_RELEASE);
   PTZ_HIP_TRY(hipEventRecord(b->ev0, s0));
-  // x <- initial state, scales <- 1, LM state reset (whole batch, stream 0)
-  {
-    const size_t n15 = (size_t)15 * b->total_cam, n3 = (size_t)3 * b->total_ray, nnc = (size_t)b->total_cam * NC;
-    const size_t most = std::max(std::max(n15, n3), std::max(std::max(nnc, (size_t)6 * B), d.dsp_x ? d.dsp_stride : (size_t)0));
-    LAUNCH(k_solve_init, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, d, (const double*)b->cam0, (const double*)b->ray0, (const double*)b->dsp0,
-           (const double*)b->tlw0, n15, n3, nnc);
-  }
+  enqueue_solve_init<TYPE>(b);
   // IterationZero: evaluate, Jacobi scales from the column norms, re-evaluate scaled
   enqueue_linearize<TYPE>(b);
   if (b->opt.jacobi_scaling) {
@@ -695,14 +753,7 @@ template <int TYPE> int solve_impl(ptz_ba_batch* b, ptz_lm_summary* out)
     if (d.shared) LAUNCH(k_group_scale<TYPE>, dim3(b->max_grp * NC, B), dim3(64), 0, d);
     enqueue_linearize<TYPE>(b);
   }
-  for (int g = 0; g < G; ++g) hipLaunchKernelGGL(k_ctl_reset, dim3(1), dim3(64), 0, s0, b->dg[g]);
-  // iteration zero's books are closed and the first step is opened here; every pass ends with the same bookkeeping for the next
-  b->prof_begin(P_LMCTL);
-  for (int g = 0; g < G; ++g) {
-    LAUNCH(k_lm_pre<TYPE>, dim3(b->group_count[g]), dim3(LM_THREADS), 0, b->dg[g]);
-    if (b->shapes.size() > 1 && b->compaction) LAUNCH(k_compact, dim3(1), dim3(1024), 0, b->dg[g]);
-  }
-  b->prof_end();
+  enqueue_open_first_step<TYPE>(b);
   // fork: every group's stream continues after the common prologue
   PTZ_HIP_TRY(hipEventRecord(b->fork_ev[0], s0));
   for (int g = 1; g < G; ++g) PTZ_HIP_TRY(hipStreamWaitEvent(b->streams[g], b->fork_ev[0], 0));
@@ -2892,6 +2943,102 @@ int32_t ptz_debug_batch_structure_hash(ptz_ba_batch* b, uint64_t* hash)
   }
   *hash = h;
   return PTZ_OK;
+}
+
+extern "C++" {
+namespace {
+template <int TYPE>
+int32_t reduced_system_impl(ptz_ba_batch* b, int index, const double* scale_c, const double* scale_r, bool poison, double* S, double* rhs,
+                            double* diag_c, int32_t* info)
+{
+  constexpr int NC = Dims<TYPE>::NC;
+  const Dev& d = b->d;
+  const SceneDev& s = b->scenes[index];
+  const size_t np = d.chol.np, nt = np / CHOL_NB;
+  // ---- the solver's prologue (solve_impl) with the caller's Jacobi scales where k_jacobi_scale would write its own
+  begin_solve(b);
+  hipStream_t s0 = b->stream;
+  enqueue_solve_init<TYPE>(b);
+  if (scale_c) PTZ_HIP_TRY(copy_on(s0, d.scale_c + (size_t)s.cam_off * NC, scale_c, sizeof(double) * NC * s.n_cam, hipMemcpyHostToDevice));
+  if (scale_r) {
+    const int* perm = b->ray_perm.data() + s.ray_off;  // internal ray j -> the caller's ray index
+    std::vector<double> sr((size_t)s.n_ray * 3);
+    for (int j = 0; j < s.n_ray; ++j)
+      for (int k = 0; k < 3; ++k) sr[(size_t)j * 3 + k] = scale_r[(size_t)perm[j] * 3 + k];
+    PTZ_HIP_TRY(copy_on(s0, d.scale_r + (size_t)s.ray_off * 3, sr.data(), sizeof(double) * sr.size(), hipMemcpyHostToDevice));
+  }
+  enqueue_linearize<TYPE>(b);
+  enqueue_open_first_step<TYPE>(b);
+  // ---- the first pass of the scene's group up to the system, in shape 0 at its full extent
+  int g = 0;
+  while (g + 1 < (int)b->dg.size() && index >= b->group_first[g] + b->group_count[g]) ++g;
+  PassShape sh = b->shapes[0];
+  sh.slots = b->group_count[g];
+  sh.path_slots = sh.slots;
+  sh.compact = false;
+  const Dev dp = pass_dev<TYPE>(b, b->dg[g], sh);
+  double* A_dev = d.chol.A + (size_t)index * np * np;
+  if (poison) PTZ_HIP_TRY(hipMemsetAsync(A_dev, 0xFF, sizeof(double) * np * np, s0));
+  const SchurLaunch sl = enqueue_reduced_system<TYPE>(b, dp, sh);
+  {
+    const hipError_t we = stream_wait(s0);
+    b->release_staged();
+    PTZ_HIP_TRY(we);
+    PTZ_HIP_TRY(hipGetLastError());
+  }
+  b->prof_collect();
+  // ---- read back
+  LmState lm;
+  int active = 0;
+  PTZ_HIP_TRY(copy_on(s0, &lm, d.lm + index, sizeof(LmState), hipMemcpyDeviceToHost));
+  PTZ_HIP_TRY(copy_on(s0, &active, d.active + index, sizeof(int), hipMemcpyDeviceToHost));
+  if (!active) return PTZ_EINVAL;  // the scene ended at iteration zero (gradient tolerance): no step was opened, no system built
+  std::vector<double> A(np * np);
+  PTZ_HIP_TRY(copy_on(s0, A.data(), A_dev, sizeof(double) * np * np, hipMemcpyDeviceToHost));
+  std::vector<unsigned char> mask(nt * nt, 1);  // (PTZ_BA_DENSE_CHOL: no mask, every tile is cleared and read)
+  if (d.chol.tmask) PTZ_HIP_TRY(copy_on(s0, mask.data(), d.chol.tmask + (size_t)index * nt * nt, nt * nt, hipMemcpyDeviceToHost));
+  std::vector<int> tperm(nt);
+  for (size_t t = 0; t < nt; ++t) tperm[t] = (int)t;
+  if (d.tperm) PTZ_HIP_TRY(copy_on(s0, tperm.data(), d.tperm + (size_t)index * nt, sizeof(int) * nt, hipMemcpyDeviceToHost));
+  int reordered = 0;
+  for (size_t t = 0; t < nt; ++t) reordered |= tperm[t] != (int)t;
+  const int n = s.n;
+  auto col = [&](int c) { return (size_t)tperm[c / CHOL_NB] * CHOL_NB + c % CHOL_NB; };  // sys_col()
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c <= r; ++c) {
+      const size_t pr = col(r), pc = col(c), hi = std::max(pr, pc), lo = std::min(pr, pc);
+      const double v = mask[(hi / CHOL_NB) * nt + lo / CHOL_NB] ? A[hi * np + lo] : 0.0;
+      S[(size_t)r * n + c] = v;
+      S[(size_t)c * n + r] = v;
+    }
+  // the right-hand side is row n of the padded system where it stands (its tile, the first dense one, keeps its place in every
+  // order: plan_dissection), its columns follow the order
+  for (int c = 0; c < n; ++c) rhs[c] = A[(size_t)n * np + col(c)];
+  if (diag_c)
+    PTZ_HIP_TRY(copy_on(s0, diag_c, d.diag_c + ((size_t)lm.cur * d.lin_cams + s.cam_off) * NC, sizeof(double) * NC * s.n_cam, hipMemcpyDeviceToHost));
+  if (info) {
+    info[0] = sl.kernel; info[1] = b->schur_tg ? 1 : 0; info[2] = (int)np; info[3] = (int)nt; info[4] = reordered;
+    info[5] = b->max_cam_obs; info[6] = b->max_cam_run; info[7] = sl.threads;
+  }
+  return PTZ_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t ptz_debug_batch_reduced_system(ptz_ba_batch* b, int32_t index, const double* scale_c, const double* scale_r, int32_t flags, double* S,
+                                       double* rhs, double* diag_c, int32_t* info)
+{
+  if (!b || !b->has_state || index < 0 || index >= b->n_scene || !S || !rhs) return PTZ_EINVAL;
+  if (b->type < PTZ_BA_PTZRay || b->type > PTZ_BA_PTZRayFxfyDist || b->has3d || b->d.shared) return PTZ_EUNSUPPORTED;
+  clear_stale_error(__func__);
+  PTZ_DEVICE_GUARD(b->device);
+  if (int32_t rcp = ensure_host_ray_perm(b)) return rcp;
+  const bool poison = (flags & 1) != 0;
+  switch (b->type) {
+    case 0: return reduced_system_impl<0>(b, index, scale_c, scale_r, poison, S, rhs, diag_c, info);
+    case 1: return reduced_system_impl<1>(b, index, scale_c, scale_r, poison, S, rhs, diag_c, info);
+    default: return reduced_system_impl<2>(b, index, scale_c, scale_r, poison, S, rhs, diag_c, info);
+  }
 }
 
 void ptz_trim_cache(void) { ptzpool::trim(); }
