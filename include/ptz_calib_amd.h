@@ -426,6 +426,39 @@ int32_t ptz_match_gate_run(ptz_match_gate* g, int32_t n_pair, const int64_t* mat
                            uint8_t* mask /* or NULL */, int64_t* out_ptr, float* out_uv_a, float* out_uv_b,
                            int32_t* out_index /* or NULL */, double* device_ms);
 
+/* The rotation-and-focal gate: the same gating for ASSEMBLED relocalization queries, under the model such a query obeys.  uv_a of
+ * query p is a pixel of the pinhole cam_ref[15 p] = [fx, fy, cx, cy, ..] at the rig's centre (the anchor, or the virtual anchor of
+ * ptz_reloc_assemble / ptz_landmark_assemble; only these four entries are read), uv_b a pixel of the query, whose centre is
+ * (cam_cur[15 p + 2], cam_cur[15 p + 3]); the two are related by K_q R K_a^-1 with unknown f and R, which two matches fix in closed
+ * form.  `iters` two-match samples (1 .. 4096, 128 is the default of every caller here) give up to 2 iters hypotheses; the one with
+ * the most inliers at `thresh` pixels wins, ties to the lowest number.  The contract -- sampling, the closed form, the order of every
+ * operation -- is csrc/ptz_rotfocal.h, and the outputs are its bits whatever the batch and the launch shape.  No adaptive bound, no
+ * table, no per-query size limit (2^31 - 1 matches), no refinement: the solve consumes the mask.  The query's distortion and
+ * fx != fy do not enter the model; the threshold absorbs them.
+ * Outputs: d_found [n_pair] (1: a model with at least 3 inliers; 0: none; -1: a range outside [0, max_matches], nothing else is
+ * written for it), d_model [10 n_pair] or NULL (f, R row-major), d_H [9 n_pair] or NULL (K_q R K_a^-1 divided by its last entry;
+ * nine NaN where that entry's magnitude is not above 1e-300 -- what the guided matcher takes for "no admissible candidate"),
+ * d_mask [n_match] or NULL; model, H and mask bytes of a query whose found is not 1 are left as they were.  The compacted CSR
+ * (d_out_ptr, d_out_uv_a, d_out_uv_b, d_out_index or NULL) is ptz_match_gate_run_device's, by the same rule: a query passes with
+ * found = 1 and at least max(min_inliers, 4) mask ones.  Four kernels on `hip_stream`, no synchronisation.  The gate holds workspace
+ * only.  PTZ_EINVAL, before any device work: NULL gate / required arrays, negative extents, max_pairs <= 0, a threshold that is not
+ * finite and positive, min_inliers < 0, iters outside 1 .. 4096, a stream of another device; PTZ_ELIMIT: n_pair > max_pairs,
+ * max_matches beyond 2^31 - 1; n_pair = 0 is PTZ_OK. */
+typedef struct ptz_rotfocal_gate ptz_rotfocal_gate;
+int32_t ptz_rotfocal_gate_create(int32_t max_pairs, int64_t max_matches, int32_t device_id, ptz_rotfocal_gate** out);
+void ptz_rotfocal_gate_destroy(ptz_rotfocal_gate* g);
+int32_t ptz_rotfocal_gate_run_device(ptz_rotfocal_gate* g, int32_t n_pair, const int64_t* d_match_ptr, const float* d_uv_a,
+                                     const float* d_uv_b, const double* d_cam_ref, const double* d_cam_cur, double thresh,
+                                     int32_t min_inliers, int32_t iters, double* d_model /* or NULL */, double* d_H /* or NULL */,
+                                     int32_t* d_found, uint8_t* d_mask /* or NULL */, int64_t* d_out_ptr, float* d_out_uv_a,
+                                     float* d_out_uv_b, int32_t* d_out_index /* or NULL */, void* hip_stream);
+/* The same run on HOST arrays: upload, ptz_rotfocal_gate_run_device, download.  Also PTZ_EINVAL: match_ptr[0] != 0 or decreasing
+ * offsets; PTZ_ELIMIT: more matches than the gate's max_matches.  device_ms (or NULL): the four kernels, between events. */
+int32_t ptz_rotfocal_gate_run(ptz_rotfocal_gate* g, int32_t n_pair, const int64_t* match_ptr, const float* uv_a, const float* uv_b,
+                              const double* cam_ref, const double* cam_cur, double thresh, int32_t min_inliers, int32_t iters,
+                              double* model /* or NULL */, double* H /* or NULL */, int32_t* found, uint8_t* mask /* or NULL */,
+                              int64_t* out_ptr, float* out_uv_a, float* out_uv_b, int32_t* out_index /* or NULL */, double* device_ms);
+
 /* Gate, then solve, in one call:
  *   replaces the loop body of run_ptz_reloc.cc:68-118 for callers whose matches hold outliers -- upload, gate with
  *   src = uv_ref, dst = uv_cur, the LM of ptz_krt_solve_batch on the compacted CSR (ptz_krt_solve_batch_device's launch, same
@@ -929,6 +962,15 @@ int32_t ptz_reloc_assemble(int32_t n_query, int32_t n_pair, int32_t n_ref, const
  * ptz_desc_match_pairs_guided_grid_device: the same matches, hence the same outputs; any value but 0 and 1 is PTZ_EINVAL.
  * gate_max_pair_matches (2048, at most 4096): the pair size the gates' bound tables are built for; a pair (stage 2) or a query
  * (stage 4) with more matches does not pass.  The gate object is kept and grows with the runs.
+ * ptz_relocalizer_set_gate_model(r, gate_model, gate_iters): the model of stage 4 in every run on r that follows (a relocalizer
+ * starts with 0, 128; ptz_reloc_options keeps its layout).  gate_model 0: the homography gate.  1: the rotation-and-focal gate,
+ * ptz_rotfocal_gate_run_device with gate_iters samples on the assembled arrays and cam_ref / cam_cur as stage 3 (and the prior) left
+ * them on the device -- in all six runs; gate_max_pair_matches does not apply to it, and stage 2 stays the homography gate (a
+ * general pair model between two distorted images).  That a query the gate kept nothing of is not accepted in a tracked run is
+ * unchanged.  With gate_model = 0 every output is what it was before the call existed.  PTZ_EINVAL, nothing changed: a NULL
+ * relocalizer, a gate_model other than 0 and 1, gate_iters outside 1 .. 4096.
+ * ptz_relocalizer_gate_models downloads the last run's models of stage 4 (gate_model = 1 and a gated run, PTZ_EINVAL otherwise):
+ * model [10 n_query] (f, R row-major; zeros where found is not 1), found [n_query] (the estimator's flag), either may be NULL.
  * ptz_relocalizer_matches downloads the last run's assembled matches (tests): match_ptr [n_query + 1], uv_ref / uv_cur
  * [ptz_relocalizer_n_matches, 2], src (index in the matcher's table), any may be NULL.
  * ptz_relocalizer_table: the last run's match table of all pairs (the guided pass's, if it ran), the relocalizer's until its next run
@@ -975,6 +1017,8 @@ int32_t ptz_relocalizer_run(ptz_relocalizer* r, const ptz_desc_set* query_set, i
 const ptz_desc_matches* ptz_relocalizer_table(const ptz_relocalizer* r);
 int64_t ptz_relocalizer_n_matches(const ptz_relocalizer* r);
 int32_t ptz_relocalizer_matches(const ptz_relocalizer* r, int64_t* match_ptr, float* uv_ref, float* uv_cur, int32_t* src);
+int32_t ptz_relocalizer_set_gate_model(ptz_relocalizer* r, int32_t gate_model, int32_t gate_iters);
+int32_t ptz_relocalizer_gate_models(const ptz_relocalizer* r, double* model /* or NULL */, int32_t* found /* or NULL */);
 
 /* ---- reference shortlist: which references a query is worth matching against ----------------------------------------------------
  * A retrieval step in front of the matcher.  The contract is csrc/ptz_desc_shortlist.h, all integer but desc_ratio_ok's multiply:
@@ -1086,7 +1130,7 @@ int32_t ptz_reloc_prior_pairs_device(int32_t n_ref, const double* d_ref_cams, co
  * the gate kept nothing of (the solve on no matches converges where it stands and would say 1).  With a radius of tens of pixels
  * min_inliers = 6 is weak evidence: a wrong prior's lone candidates agree with SOME homography in a dozen matches by chance; callers
  * that rely on the signal raise options->min_inliers to a fraction of what a true overlap yields (tens).  ptz_relocalizer_pairs / _table / _matches work as after
- * any run.  Known limits: gate_max_pair_matches (at most 4096) bounds an assembled query; H ignores distortion; an overlap list is
+ * any run.  Known limits: gate_max_pair_matches (at most 4096) bounds an assembled query (gate_model = 0); H ignores distortion; an overlap list is
  * only as good as the prior. */
 typedef struct ptz_prior_result {
   int32_t* shortlist;
@@ -1193,7 +1237,7 @@ int32_t ptz_relocalizer_run_landmarks(ptz_relocalizer* r, const ptz_landmark_map
  * NULL), pointers nullable: n_visible [n_query], view_ms.  ptz_relocalizer_table returns the matcher's table: idx_a is view-local,
  * uv_a the predicted pixel.  ptz_relocalizer_view downloads the last such run's view (every pointer nullable; PTZ_EINVAL when the
  * last run was neither a tracked nor a shortlisted landmark run).  Validation is that of the two runs it combines.  Known limits: the prior's distortion is
- * ignored in the prediction; max_view_bytes; gate_max_pair_matches still bounds an assembled query; a view is only as good as the
+ * ignored in the prediction; max_view_bytes; gate_max_pair_matches still bounds an assembled query (gate_model = 0); a view is only as good as the
  * prior. */
 typedef struct ptz_landmark_prior_options {
   double radius_px;       /* 40: the margin of the visibility rule and the guided matcher's radius */

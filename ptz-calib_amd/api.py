@@ -53,7 +53,8 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_relocalizer_run_landmarks_tracked", "ptz_relocalizer_view", "ptz_landmark_map_home_set", "ptz_landmark_map_home_groups",
            "ptz_landmark_shortlist", "ptz_landmark_shortlist_workspace_bytes", "ptz_landmark_shortlist_device", "ptz_landmark_view_from_homes",
            "ptz_landmark_view_from_homes_device", "ptz_landmark_view_kind", "ptz_relocalizer_run_landmarks_shortlisted",
-           "ptz_debug_batch_reduced_system"]
+           "ptz_debug_batch_reduced_system", "ptz_rotfocal_gate_create", "ptz_rotfocal_gate_destroy", "ptz_rotfocal_gate_run_device",
+           "ptz_rotfocal_gate_run", "ptz_relocalizer_gate_models", "ptz_relocalizer_set_gate_model"]
 
 
 class PtzError(RuntimeError):
@@ -838,6 +839,70 @@ def gate_matches(match_ptr, uv_a, uv_b, ransac_thresh=4.0, min_inliers=0, max_pa
             g.close()
     k = int(out_ptr[-1])
     return dict(H=H, found=found, mask=mask, out_ptr=out_ptr, out_uv_a=oa[:k], out_uv_b=ob[:k], out_index=oi[:k], device_ms=ms.value)
+
+
+class RotFocalGate:
+    """ptz_rotfocal_gate: the two-point rotation-and-focal RANSAC gate of assembled relocalization queries (up to max_pairs queries,
+    max_matches matches; a query may have any number of them).  The contract is csrc/ptz_rotfocal.h."""
+
+    def __init__(self, max_pairs, max_matches, device_id=0):
+        self.max_pairs, self.max_matches = int(max_pairs), int(max_matches)
+        self.handle = C.c_void_p()
+        lib().ptz_rotfocal_gate_destroy.restype = None
+        _check(lib().ptz_rotfocal_gate_create(self.max_pairs, C.c_int64(self.max_matches), int(device_id), C.byref(self.handle)),
+               "ptz_rotfocal_gate_create")
+
+    def run_device(self, n_pair, d_match_ptr, d_uv_a, d_uv_b, d_cam_ref, d_cam_cur, d_found, d_out_ptr, d_out_uv_a, d_out_uv_b, d_model=None,
+                   d_H=None, d_mask=None, d_out_index=None, thresh=4.0, min_inliers=0, iters=128, stream=None):
+        """ptz_rotfocal_gate_run_device: every d_* is a device buffer (torch tensor or integer address).  Enqueues on `stream`
+        (integer hipStream_t handle, None = default stream) and returns without synchronising."""
+        _check(lib().ptz_rotfocal_gate_run_device(self.handle, int(n_pair), _dptr(d_match_ptr), _dptr(d_uv_a), _dptr(d_uv_b), _dptr(d_cam_ref),
+                                                  _dptr(d_cam_cur), C.c_double(thresh), int(min_inliers), int(iters), _dptr(d_model), _dptr(d_H),
+                                                  _dptr(d_found), _dptr(d_mask), _dptr(d_out_ptr), _dptr(d_out_uv_a), _dptr(d_out_uv_b),
+                                                  _dptr(d_out_index), C.c_void_p(stream) if stream else None), "ptz_rotfocal_gate_run_device")
+
+    def run(self, match_ptr, uv_a, uv_b, cam_ref, cam_cur, thresh=4.0, min_inliers=0, iters=128, fill=0):
+        """ptz_rotfocal_gate_run on host arrays.  Returns a dict of numpy arrays: model [n_pair, 10] (f, R row-major), H [n_pair, 3, 3],
+        found [n_pair], mask [n_match] (model, H and mask keep `fill` where found != 1), out_ptr [n_pair + 1], out_uv_a / out_uv_b
+        [n_kept, 2], out_index [n_kept], and device_ms."""
+        ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+        a = np.ascontiguousarray(uv_a, dtype=np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(uv_b, dtype=np.float32).reshape(-1, 2)
+        cr = np.ascontiguousarray(cam_ref, dtype=np.float64).reshape(-1, 15)
+        cc = np.ascontiguousarray(cam_cur, dtype=np.float64).reshape(-1, 15)
+        n, nm = len(ptr) - 1, len(a)
+        if len(cr) != n or len(cc) != n:
+            raise ValueError("cam_ref and cam_cur need one camera per query")
+        model, H = np.full((n, 10), float(fill)), np.full((n, 3, 3), float(fill))
+        found = np.zeros(n, dtype=np.int32)
+        mask = np.full(nm, fill, dtype=np.uint8)
+        out_ptr = np.zeros(n + 1, dtype=np.int64)
+        oa, ob = np.zeros((nm, 2), dtype=np.float32), np.zeros((nm, 2), dtype=np.float32)
+        oi = np.zeros(nm, dtype=np.int32)
+        ms = C.c_double()
+        _check(lib().ptz_rotfocal_gate_run(self.handle, n, _p(ptr), _p(a), _p(b), _p(cr), _p(cc), C.c_double(thresh), int(min_inliers), int(iters),
+                                           _p(model), _p(H), _p(found), _p(mask), _p(out_ptr), _p(oa), _p(ob), _p(oi), C.byref(ms)),
+               "ptz_rotfocal_gate_run")
+        k = int(out_ptr[-1])
+        return dict(model=model, H=H, found=found, mask=mask, out_ptr=out_ptr, out_uv_a=oa[:k], out_uv_b=ob[:k], out_index=oi[:k],
+                    device_ms=ms.value)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_rotfocal_gate_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def krt_solve_batch_gated(batch, max_reproj_error=100.0, ransac_thresh=4.0, min_inliers=0, **opt):
@@ -1858,7 +1923,7 @@ class Relocalizer:
 
     def run(self, query_set, query_wh, max_refs=1, factor_type=0, guided_radius=0.0, ransac_thresh=4.0, min_inliers=6, inlier_matches=False,
             trim=None, uncertainty=False, max_reproj_error=100.0, gate_max_pair_matches=2048, match=None, shortlist=None, prior=None, guided_grid=False, landmarks=None, landmark_prior=None,
-            landmark_shortlist=None, **lm):
+            landmark_shortlist=None, gate_model=0, gate_iters=128, **lm):
         """One run over the images of query_set (a DescSet with key points; query_wh [n_query, 2]).  trim: None, or a dict of
         krt_trim_options fields; match: a dict of desc_options fields; lm: LmOptions fields.  Returns a dict of per-query numpy
         arrays: cam, accepted, summaries (list of dicts), sel_ref [n, K], n_sel, n_matches, n_inliers, trim_report (list of dicts or
@@ -1882,7 +1947,9 @@ class Relocalizer:
         defaults): ptz_relocalizer_run_landmarks_shortlisted -- probe features vote for the map's homes, and the dense matcher sees
         only the landmarks of the listed homes; the gate is not forced on.  The result gains shortlist [n, R] (home indices),
         n_short [n], votes [n, n_ref], votes_ms, n_visible [n] and view_ms; view() downloads the view.  Exclusive with
-        landmark_prior, shortlist and prior."""
+        landmark_prior, shortlist and prior.
+        gate_model: 0, the homography gate on the assembled queries; 1, the rotation-and-focal gate (RotFocalGate) with gate_iters
+        samples (1 .. 4096), in every kind of run; set on the relocalizer before the run (ptz_relocalizer_set_gate_model) -- gate_max_pair_matches does not bound a query then, and gate_models() downloads f and R."""
         if landmark_shortlist is not None and landmarks is None:
             raise ValueError("landmark_shortlist= votes for the homes of a map: it needs landmarks=")
         if landmark_shortlist is not None and landmark_prior is not None:
@@ -1909,6 +1976,7 @@ class Relocalizer:
         o.trim, o.uncertainty, o.max_refs, o.factor_type = int(trim is not None), int(bool(uncertainty)), K, int(factor_type)
         o.max_reproj_error, o.gate_max_pair_matches = float(max_reproj_error), int(gate_max_pair_matches)
         o.guided_grid = int(guided_grid)
+        _check(lib().ptz_relocalizer_set_gate_model(self.handle, int(gate_model), int(gate_iters)), "ptz_relocalizer_set_gate_model")
         nf = krt_free_dim(factor_type)
         cam, acc = np.zeros((n, 15)), np.zeros(n, dtype=np.int32)
         summ, rep = (LmSummary * max(n, 1))(), (KrtTrimReport * max(n, 1))()
@@ -2005,6 +2073,14 @@ class Relocalizer:
         ptr, lm, uv = np.zeros(self._last_n + 1, dtype=np.int64), np.zeros(k.value, dtype=np.int32), np.zeros((k.value, 2), dtype=np.float32)
         _check(lib().ptz_relocalizer_view(self.handle, None, _p(ptr), _p(lm) if k.value else None, _p(uv) if k.value else None), "ptz_relocalizer_view")
         return dict(vis_ptr=ptr, vis_lm=lm, vis_uv=uv)
+
+    def gate_models(self):
+        """The models of the last run's gate on the assembled queries, if it ran with gate_model=1: dict of model [n, 10] (f, R row-major;
+        zeros where found != 1) and found [n]."""
+        n = self._last_n
+        model, found = np.zeros((n, 10)), np.zeros(n, dtype=np.int32)
+        _check(lib().ptz_relocalizer_gate_models(self.handle, _p(model), _p(found)), "ptz_relocalizer_gate_models")
+        return dict(model=model, found=found)
 
     def matches(self):
         """The last run's assembled matches (tests): dict of match_ptr, uv_ref, uv_cur, src."""

@@ -17,6 +17,10 @@
 // untracked (--shortlist if given, else all pairs), and a tracked frame that is lost is run again untracked -- one frame per run and
 // therefore latency-bound.  --prior_radius, --prior_refs: the matcher's radius (40 px) and the list length (8).  Every record gains
 // "tracked" and n_shortlist.
+// --gate_model rotfocal [--gate_iters T] (not in the reference; needs --inlier_matches or a flag that implies it; implies --on_device) gates
+// a test image's assembled matches with the two-point rotation-and-focal gate (ptz_relocalizer_set_gate_model) in the place of the
+// homography gate, in whichever run the other flags select; the tracked runs' rule that half of a frame's guided matches lie on the
+// gate's model then counts that gate's mask; every record gains gate_model and gate_f, the gate's focal length.
 // --landmarks (not in the reference; with --landmark_min_views; implies --on_device) relocalizes against a landmark MAP instead of
 // reference images: the reference images are matched among themselves (MatchDescriptors, --match_ratio and --match_min), the host
 // TracksBuilder turns the matches into tracks as PTZRayOptimizer does, ptz_landmark_map_create makes one ray and one descriptor per
@@ -141,6 +145,10 @@ int main(int argc, char** argv)
   parser.Add("landmark_shortlist", '\0', "With --landmarks: match each test image without a prior against the landmarks of the R homes (cells "
                                          "of the map) that most of its probe features vote for; takes --shortlist_probes and "
                                          "--shortlist_min_votes; every record gains n_shortlist and n_visible", false);
+  parser.Add("gate_model", '\0', "With --inlier_matches (or a flag that implies it): the model of the gate on a test image's assembled matches: "
+                                 "homography (default) or rotfocal, the two-point rotation-and-focal gate (implies --on_device); with rotfocal "
+                                 "every record gains gate_model and gate_f", false);
+  parser.Add("gate_iters", '\0', "With --gate_model rotfocal: its samples, 1 .. 4096 (default 128)", false);
   parser.ParseCheck(argc, argv);
   const int min_inliers = parser.Exist("min_inliers") ? atoi(parser.Get("min_inliers").c_str()) : kDefaultMinInliers;
   if (min_inliers < 0) {
@@ -178,9 +186,24 @@ int main(int argc, char** argv)
     fprintf(stderr, "--landmark_prior_radius must be a positive number of pixels\n");
     return 1;
   }
-  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking || landmarks;
+  if (parser.Exist("gate_model") && parser.Get("gate_model") != "homography" && parser.Get("gate_model") != "rotfocal") {
+    fprintf(stderr, "--gate_model is homography or rotfocal\n");
+    return 1;
+  }
+  const bool rotfocal = parser.Exist("gate_model") && parser.Get("gate_model") == "rotfocal";
+  if (rotfocal && !(parser.Exist("inlier_matches") || tracking || lm_tracking)) {
+    fprintf(stderr, "--gate_model rotfocal needs --inlier_matches or a flag that implies it\n");
+    return 1;
+  }
+  const int gate_iters = parser.Exist("gate_iters") ? atoi(parser.Get("gate_iters").c_str()) : 128;
+  if (parser.Exist("gate_iters") && (!rotfocal || gate_iters < 1 || gate_iters > 4096)) {
+    fprintf(stderr, "--gate_iters needs --gate_model rotfocal and is 1 .. 4096\n");
+    return 1;
+  }
+  const bool on_device = parser.Exist("on_device") || parser.Exist("multi_ref") || shortlisting || tracking || landmarks || rotfocal;
   if (on_device && !parser.Exist("match_descriptors")) {
-    fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params, --sequence and --landmarks need --match_descriptors\n");
+    fprintf(stderr, "--on_device, --multi_ref, --shortlist, --prior_params, --sequence, --landmarks and --gate_model rotfocal need "
+                    "--match_descriptors\n");
     return 1;
   }
   if (landmarks && (parser.Exist("match_guided") || shortlisting || parser.Exist("multi_ref") || tracking || parser.Exist("save_matches"))) {
@@ -338,6 +361,7 @@ int main(int argc, char** argv)
   std::vector<Trimmed> trimmed(test_fnames.size());
   std::vector<int> multi_n_refs(test_fnames.size(), 0), multi_n_matches(test_fnames.size(), 0), n_shortlist(test_fnames.size(), 0);
   std::vector<int> tracked(test_fnames.size(), 0), n_visible(test_fnames.size(), 0);
+  std::vector<double> gate_f(test_fnames.size(), 0.0);  // --gate_model rotfocal: the gate's focal length of a test image
   int n_landmarks = 0;
   if (on_device && !test_fnames.empty()) {
     // the same options as the host path reads them, handed to the resident loop (ptz_relocalizer_run): pass 1 over all pairs, the
@@ -382,6 +406,7 @@ int main(int argc, char** argv)
     bool ok = n_ref > 0 && static_cast<size_t>(n_ref) == ref_cameras.size() && BuildDescSet(parser.Get("ref_features"), ref_fnames, ref_features, &ref_set);
     int32_t rc = PTZ_OK;
     if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
+    if (ok && rc == PTZ_OK && rotfocal) rc = ptz_relocalizer_set_gate_model(rl, 1, gate_iters);  // stage 4 of every run below
     ptz_landmark_map* lmap = nullptr;
     if (ok && rc == PTZ_OK && landmarks) {
       // the references among themselves, every pair once; the tracks of those matches; one landmark per track
@@ -458,6 +483,11 @@ int main(int argc, char** argv)
            : shortlisting ? ptz_relocalizer_run_shortlisted(rl, test_set, nq, wh.data(), &ro, &sl, &rr, &sr)
                           : ptz_relocalizer_run(rl, test_set, nq, wh.data(), &ro, &rr);
       for (int32_t q = 0; q < nq; ++q) n_shortlist[idx[q]] = n_short[q];
+      if (rc == PTZ_OK && rotfocal && gated) {
+        std::vector<double> models(10 * static_cast<size_t>(nq), 0.0);
+        rc = ptz_relocalizer_gate_models(rl, models.data(), nullptr);
+        for (int32_t q = 0; rc == PTZ_OK && q < nq; ++q) gate_f[idx[q]] = models[10 * static_cast<size_t>(q)];
+      }
       if (rc == PTZ_OK && parser.Exist("save_matches")) {
         // the table comes to the host once, for the file alone: blocks in the pairs' order, a pair without matches has none
         const ptz_desc_matches* t = ptz_relocalizer_table(rl);
@@ -678,7 +708,7 @@ int main(int argc, char** argv)
   std::vector<std::vector<Point3d>> pts3d(test_fnames.size());
   const std::string out_path = out_dir + "/" + cam_id + ".json";
   SaveRegisteredCam(test_cameras, success_ids, test_fnames, pixels, pts3d, out_path);
-  if (uncertainty || trimming || multi_ref > 0 || shortlisting || tracking || landmarks) {
+  if (uncertainty || trimming || multi_ref > 0 || shortlisting || tracking || landmarks || rotfocal) {
     // the keys go into the records SaveRegisteredCam wrote (the writer lays a parsed file out as it was: insertion order,
     // shortest round-trip numbers); a registered image whose covariance could not be computed keeps its record without them
     std::stringstream ss;
@@ -709,6 +739,10 @@ int main(int argc, char** argv)
       if (shortlisting || tracking || lm_shortlisting) j["n_shortlist"] = Json::Int(n_shortlist[i]);
       if (tracking || lm_tracking) j["tracked"] = Json::Int(tracked[i]);
       if (lm_tracking || lm_shortlisting) j["n_visible"] = Json::Int(n_visible[i]);
+      if (rotfocal) {
+        j["gate_model"] = Json::String("rotfocal");
+        j["gate_f"] = Json::Float(gate_f[i]);
+      }
       if (trimming) {
         j["rms_px"] = Json::Float(trimmed[i].rms);
         j["n_matches"] = Json::Int(trimmed[i].n_matches);

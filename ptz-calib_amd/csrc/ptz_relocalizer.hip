@@ -18,7 +18,8 @@
 //   1. the matcher over the run's pairs: every (reference, query) pair, or the shortlisted ones             ptz_desc_match_pairs
 //   2. optionally the gate on all pairs and the guided pass      ptz_match_gate_run_device, ptz_desc_match_pairs_guided_device
 //   3. the assembly                                              ptz_reloc_assemble_device
-//   4. optionally the gate on the assembled queries              ptz_match_gate_run_device
+//   4. optionally the gate on the assembled queries              ptz_match_gate_run_device, or after ptz_relocalizer_set_gate_model(r, 1, ..)
+//                                                                ptz_rotfocal_gate_run_device (cam_ref / cam_cur as stage 3 left them)
 //   5. the solve or the trimmed solve                            ptz_krt_solve_batch_device, ptz_krt_solve_batch_trimmed_device
 //   6. optionally the covariance                                 ptz_krt_covariance_batch_device
 // with every array between them on the device.  Nothing here computes: the stages are the library's own entry points, composed as
@@ -98,6 +99,10 @@ struct ptz_relocalizer {
   ptz_match_gate* gate = nullptr;  // grows with the runs: pairs, matches, matches of one pair
   int32_t gate_pairs = 0, gate_pm = 0;
   int64_t gate_matches = 0;
+  ptz_rotfocal_gate* rf_gate = nullptr;  // the rotation-and-focal gate of stage 4 (gate_model = 1): grows likewise
+  int32_t rf_pairs = 0;
+  int64_t rf_matches = 0;
+  int32_t gate_model = 0, gate_iters = 128;  // ptz_relocalizer_set_gate_model: the model of stage 4 in the runs that follow
   ptz_desc_matches* table = nullptr;  // the last run's match table of its pairs (the guided one, if that pass ran)
   ptz_landmark_view* view = nullptr;  // the last run's landmark view, if it was a tracked or a shortlisted landmark run
   std::vector<int32_t> pair_ref;      // the last run's pair list: the reference of each pair,
@@ -106,7 +111,8 @@ struct ptz_relocalizer {
   char* blk = nullptr;
   int32_t n_query = 0;
   int64_t kept = 0;
-  size_t o_optr = 0, o_oa = 0, o_ob = 0, o_osrc = 0;
+  size_t o_optr = 0, o_oa = 0, o_ob = 0, o_osrc = 0, o_model = 0, o_found = 0;
+  bool has_models = false;  // the last run gated its assembled queries with gate_model = 1
 };
 
 extern "C" void ptz_reloc_options_default(ptz_reloc_options* o)
@@ -164,6 +170,7 @@ extern "C" void ptz_relocalizer_destroy(ptz_relocalizer* r)
   ptz::DeviceGuard guard(r->device);
   if (r->st) { (void)ptz::stream_wait(r->st); ptzpool::stream_release(r->device, r->st); }
   ptz_match_gate_destroy(r->gate);
+  ptz_rotfocal_gate_destroy(r->rf_gate);
   ptz_desc_matches_destroy(r->table);
   ptz_landmark_view_destroy(r->view);
   ptzpool::dev_release(r->device, r->blk);
@@ -180,6 +187,16 @@ static int32_t reloc_gate_for(ptz_relocalizer* r, int32_t pairs, int64_t matches
   r->gate_matches = matches > r->gate_matches ? matches : r->gate_matches;
   r->gate_pm = pm > r->gate_pm ? pm : r->gate_pm;
   return ptz_match_gate_create(r->gate_pairs, r->gate_matches, r->gate_pm, r->device, &r->gate);
+}
+
+static int32_t reloc_rf_gate_for(ptz_relocalizer* r, int32_t pairs, int64_t matches)
+{
+  if (r->rf_gate && r->rf_pairs >= pairs && r->rf_matches >= matches) return PTZ_OK;
+  ptz_rotfocal_gate_destroy(r->rf_gate);
+  r->rf_gate = nullptr;
+  r->rf_pairs = pairs > r->rf_pairs ? pairs : r->rf_pairs;
+  r->rf_matches = matches > r->rf_matches ? matches : r->rf_matches;
+  return ptz_rotfocal_gate_create(r->rf_pairs, r->rf_matches, r->device, &r->rf_gate);
 }
 
 // the prior cameras of a tracked run and what it reports of its stage 0
@@ -483,9 +500,10 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
                o_found = b.take(sizeof(int32_t) * nq), o_mask = b.take(nmx), o_gptr = b.take(sizeof(int64_t) * (nq + 1)),
                o_ga = b.take(sizeof(float) * 2 * nmx), o_gb = b.take(sizeof(float) * 2 * nmx), o_kept = b.take(nmx),
                o_rep = b.take(sizeof(ptz_krt_trim_report) * nq), o_wst = b.take((size_t)ws_trim), o_cov = b.take(sizeof(double) * nf * nf * nq),
-               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq), o_lift = b.take(lp || ls ? sizeof(int32_t) * nmx : 0);
+               o_s0 = b.take(sizeof(double) * nq), o_cst = b.take(sizeof(int32_t) * nq), o_lift = b.take(lp || ls ? sizeof(int32_t) * nmx : 0),
+               o_model = b.take(sizeof(double) * 10 * nq);
   ptzpool::dev_release(r->device, r->blk);
-  r->blk = nullptr; r->n_query = 0; r->kept = 0;
+  r->blk = nullptr; r->n_query = 0; r->kept = 0; r->has_models = false;
   if (ptzpool::dev_acquire(r->device, b.total(), (void**)&r->blk) != hipSuccess) return PTZ_ENOMEM;
   char* d = r->blk;
   if (npair > 0) PTZ_HIP_TRY(hipMemcpyAsync(d + o_pref, ia.data(), sizeof(int32_t) * npair, hipMemcpyHostToDevice, st));
@@ -531,11 +549,21 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
 
   // 4. the gate on the assembled queries
   if (gated) {
-    if (const int32_t rc = reloc_gate_for(r, n_query, nm, o.gate_max_pair_matches)) return rc;
-    if (const int32_t rc = ptz_match_gate_run_device(r->gate, n_query, a_ptr, a_ref, a_cur, o.ransac_thresh, o.min_inliers, (double*)(d + o_H),
-                                                     (int32_t*)(d + o_found), d_mask, (int64_t*)(d + o_gptr), (float*)(d + o_ga),
-                                                     (float*)(d + o_gb), nullptr, st))
-      return rc;
+    if (r->gate_model == 1) {  // the assembled query's own model: f and R between the (virtual) anchor and the query, no size limit
+      if (const int32_t rc = reloc_rf_gate_for(r, n_query, nm)) return rc;
+      PTZ_HIP_TRY(hipMemsetAsync(d + o_model, 0, sizeof(double) * 10 * nq, st));
+      if (const int32_t rc = ptz_rotfocal_gate_run_device(r->rf_gate, n_query, a_ptr, a_ref, a_cur, a_cref, a_ccur, o.ransac_thresh, o.min_inliers,
+                                                          r->gate_iters, (double*)(d + o_model), nullptr, (int32_t*)(d + o_found), d_mask,
+                                                          (int64_t*)(d + o_gptr), (float*)(d + o_ga), (float*)(d + o_gb), nullptr, st))
+        return rc;
+    }
+    else {
+      if (const int32_t rc = reloc_gate_for(r, n_query, nm, o.gate_max_pair_matches)) return rc;
+      if (const int32_t rc = ptz_match_gate_run_device(r->gate, n_query, a_ptr, a_ref, a_cur, o.ransac_thresh, o.min_inliers, (double*)(d + o_H),
+                                                       (int32_t*)(d + o_found), d_mask, (int64_t*)(d + o_gptr), (float*)(d + o_ga),
+                                                       (float*)(d + o_gb), nullptr, st))
+        return rc;
+    }
     hipLaunchKernelGGL(k_reloc_universe, dim3((n_query + 3) / 4), dim3(256), 0, st, n_query, a_ptr, (const int64_t*)(d + o_gptr), d_mask);
     PTZ_HIP_TRY(hipGetLastError());
     PTZ_HIP_TRY(hipMemcpyAsync(gptr.data(), d + o_gptr, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, st));
@@ -605,7 +633,8 @@ static int32_t reloc_run(const char* who, ptz_relocalizer* r, const ptz_desc_set
   m = nullptr;
   r->pair_ref.swap(ia);
   r->query_ptr.swap(qptr);
-  r->o_optr = o_optr; r->o_oa = o_oa; r->o_ob = o_ob; r->o_osrc = o_osrc;
+  r->o_optr = o_optr; r->o_oa = o_oa; r->o_ob = o_ob; r->o_osrc = o_osrc; r->o_model = o_model; r->o_found = o_found;
+  r->has_models = gated && r->gate_model == 1;
   return PTZ_OK;
 }
 
@@ -679,6 +708,25 @@ extern "C" int32_t ptz_relocalizer_pairs(const ptz_relocalizer* r, int32_t* n_pa
   if (n_pair) *n_pair = (int32_t)r->pair_ref.size();
   if (pair_ref && !r->pair_ref.empty()) memcpy(pair_ref, r->pair_ref.data(), sizeof(int32_t) * r->pair_ref.size());
   if (query_ptr) memcpy(query_ptr, r->query_ptr.data(), sizeof(int64_t) * r->query_ptr.size());
+  return PTZ_OK;
+}
+
+extern "C" int32_t ptz_relocalizer_set_gate_model(ptz_relocalizer* r, int32_t gate_model, int32_t gate_iters)
+{
+  if (!r || (gate_model != 0 && gate_model != 1) || gate_iters < 1 || gate_iters > 4096) return PTZ_EINVAL;
+  r->gate_model = gate_model;
+  r->gate_iters = gate_iters;
+  return PTZ_OK;
+}
+
+extern "C" int32_t ptz_relocalizer_gate_models(const ptz_relocalizer* r, double* model, int32_t* found)
+{
+  using namespace ptz;
+  if (!r || !r->blk || r->n_query <= 0 || !r->has_models) return PTZ_EINVAL;
+  PTZ_DEVICE_GUARD(r->device);
+  if (model) PTZ_HIP_TRY(hipMemcpyAsync(model, r->blk + r->o_model, sizeof(double) * 10 * (size_t)r->n_query, hipMemcpyDeviceToHost, r->st));
+  if (found) PTZ_HIP_TRY(hipMemcpyAsync(found, r->blk + r->o_found, sizeof(int32_t) * (size_t)r->n_query, hipMemcpyDeviceToHost, r->st));
+  PTZ_HIP_TRY(stream_wait(r->st));
   return PTZ_OK;
 }
 

@@ -616,6 +616,39 @@ int32_t ptzh_find_homography(int32_t n, const float* src, const float* dst, doub
 }
 
 // KRTOptimizer through the C++ class: one query.  cam_cur15 in (initial, world) / out (refined, world).
+// KRTOptimizer with SetGateModel(model, iters): 1 = solved, 0 = Solve returned false, -1 = SetGateModel refused the arguments;
+// kept [n_match] (nullable): MatchResiduals' kept set after a solve; gate_f (nullable): the gate's focal length
+int32_t ptzh_krt_solve_gate_model(const double* cam_ref15, double* cam_cur15, int32_t n_match, const float* uv_ref, const float* uv_cur,
+                                  int32_t max_iter, double max_reproj_error, int32_t type, int32_t model, int32_t iters, ptz_lm_summary* summary,
+                                  uint8_t* kept, double* gate_f)
+{
+  Camera ref, cur;
+  ref.FromVector(std::vector<double>(cam_ref15, cam_ref15 + 15));
+  cur.FromVector(std::vector<double>(cam_cur15, cam_cur15 + 15));
+  std::vector<KeyPoint> kr(n_match), kc(n_match);
+  std::vector<DMatch> ms(n_match);
+  for (int m = 0; m < n_match; ++m) {
+    kr[m].pt = Point2f(uv_ref[2 * m], uv_ref[2 * m + 1]);
+    kc[m].pt = Point2f(uv_cur[2 * m], uv_cur[2 * m + 1]);
+    ms[m].queryIdx = m; ms[m].trainIdx = m;
+  }
+  KRTOptimizer opt(max_iter, max_reproj_error, static_cast<KRTOptimizer::FACTOR_TYPE>(type));
+  if (!opt.SetGateModel(model, iters)) return -1;
+  opt.SetInitParams(cur.K(), cur.R(), cur.t(), cur.dist());
+  opt.Add2d2dConstraints(ref, kr, kc, ms);
+  Mat33 K, R; Vec3 t; Vec5 dist;
+  const bool ok = opt.Solve(K, R, t, dist);
+  if (summary) *summary = opt.summary();
+  if (gate_f) *gate_f = opt.gate_f();
+  if (!ok) return 0;
+  const std::vector<double> v = Camera(K, R, t, dist).ToVector();
+  memcpy(cam_cur15, v.data(), sizeof(double) * 15);
+  std::vector<double> err;
+  std::vector<uint8_t> k;
+  if (kept && opt.MatchResiduals(err, k)) memcpy(kept, k.data(), k.size());
+  return 1;
+}
+
 int32_t ptzh_krt_solve(const double* cam_ref15, double* cam_cur15, int32_t n_match, const float* uv_ref, const float* uv_cur,
                        int32_t max_iter, double max_reproj_error, int32_t type, int32_t* num_iter, ptz_lm_summary* summary)
 {

@@ -45,9 +45,19 @@ void KRTOptimizer::Add2d3dConstraints(const std::vector<Point2f>& pts2d, const s
   }
 }
 
+bool KRTOptimizer::SetGateModel(int model, int iters)
+{
+  if ((model != 0 && model != 1) || iters < 1 || iters > 4096) return false;
+  gate_model_ = model;
+  gate_iters_ = iters;
+  return true;
+}
+
 bool KRTOptimizer::Solve(Mat33& K, Mat33& R, Vec3& t, Vec5& dist)
 {
   if (uv_ref_.empty()) return false;
+  gate_f_ = 0;
+  if (gate_model_ == 1) return SolveGated(K, R, t, dist);
   const int64_t match_ptr[2] = {0, static_cast<int64_t>(uv_ref_.size() / 2)};
   const int64_t point_ptr[2] = {0, static_cast<int64_t>(pts2d_.size() / 2)};
   const bool p3 = !pts2d_.empty();
@@ -71,6 +81,57 @@ bool KRTOptimizer::Solve(Mat33& K, Mat33& R, Vec3& t, Vec5& dist)
   num_iter_ = summary_.num_successful_steps;  // krt_optimizer.cc:396
   if (!accepted) return false;                // CheckResults, :504-533
   cam_curr_world_.FromVector(cur);            // ObtainRefinedCameraParams, :535-567 (done on the device, world frame)
+  solved_ = true;
+  K = cam_curr_world_.K();
+  dist = cam_curr_world_.dist();
+  R = cam_curr_world_.R();
+  t = cam_curr_world_.t();
+  return true;
+}
+
+// Solve() behind the rotation-and-focal gate: gate, then the plain solve on the compacted matches or the trimming loop over all of
+// them with the gate's kept set as its universe
+bool KRTOptimizer::SolveGated(Mat33& K, Mat33& R, Vec3& t, Vec5& dist)
+{
+  const int64_t n = static_cast<int64_t>(uv_ref_.size() / 2);
+  const int64_t match_ptr[2] = {0, n};
+  const int64_t point_ptr[2] = {0, static_cast<int64_t>(pts2d_.size() / 2)};
+  const bool p3 = !pts2d_.empty();
+  std::vector<double> ref = cam_ref_.ToVector(), cur = cam_curr_world_.ToVector();
+  ptz_rotfocal_gate* g = nullptr;
+  if (ptz_rotfocal_gate_create(1, n, device_id_, &g) != PTZ_OK) return false;
+  double model[10] = {0};
+  int32_t found = 0;
+  int64_t out_ptr[2] = {0, 0};
+  std::vector<float> oa(uv_ref_.size()), ob(uv_cur_.size());
+  kept_.assign(static_cast<size_t>(n), 0);
+  const int32_t rc = ptz_rotfocal_gate_run(g, 1, match_ptr, uv_ref_.data(), uv_cur_.data(), ref.data(), cur.data(), 4.0, 6, gate_iters_, model,
+                                           nullptr, &found, kept_.data(), out_ptr, oa.data(), ob.data(), nullptr, nullptr);
+  ptz_rotfocal_gate_destroy(g);
+  if (rc != PTZ_OK || found != 1 || out_ptr[1] <= 0) {  // (the mask bytes of a query that does not pass are not a kept set)
+    kept_.assign(static_cast<size_t>(n), 0);
+    return false;
+  }
+  gate_f_ = model[0];
+  ptz_lm_options opt;
+  ptz_lm_options_default(&opt);
+  opt.max_num_iterations = max_iter_;
+  opt.device_id = device_id_;
+  int32_t accepted = 0;
+  if (trimming_) {
+    const std::vector<uint8_t> universe = kept_;
+    if (ptz_krt_solve_batch_trimmed(1, match_ptr, uv_ref_.data(), uv_cur_.data(), p3 ? point_ptr : nullptr, pts2d_.data(), pts3d_.data(),
+                                    ref.data(), cur.data(), static_cast<int32_t>(factor_type_), max_reproj_error_, universe.data(), &trim_, &opt,
+                                    &summary_, &accepted, kept_.data(), &trim_report_, nullptr) != PTZ_OK)
+      return false;
+  }
+  else if (ptz_krt_solve_batch_2d3d(1, out_ptr, oa.data(), ob.data(), p3 ? point_ptr : nullptr, pts2d_.data(), pts3d_.data(), ref.data(),
+                                    cur.data(), static_cast<int32_t>(factor_type_), max_reproj_error_, &opt, &summary_, &accepted,
+                                    nullptr) != PTZ_OK)
+    return false;
+  num_iter_ = summary_.num_successful_steps;
+  if (!accepted) return false;
+  cam_curr_world_.FromVector(cur);
   solved_ = true;
   K = cam_curr_world_.K();
   dist = cam_curr_world_.dist();

@@ -39,6 +39,13 @@ class KRTOptimizer {
   // After a Solve() that returned true: |e_m| of every match at the refined camera in the order of Add2d2dConstraints (-1: skipped by
   // the border guard; ptz_krt_residuals_batch) and the matches of the last solve (all 1 without trimming).  false otherwise.
   bool MatchResiduals(std::vector<double>& err_px, std::vector<uint8_t>& kept) const;
+  // The gate in front of Solve() over the 2D-2D matches.  model 0: none, as before.  model 1: the rotation-and-focal gate
+  // (ptz_rotfocal_gate_run with one query: `iters` two-match samples, 4 px, at least 6 inliers; the reference camera given to
+  // Add2d2dConstraints is the anchor, the initial camera's principal point the query's centre) -- Solve() runs on the matches it keeps
+  // (with trimming they are the loop's universe), returns false where it keeps none, and Covariance() / MatchResiduals() report the
+  // kept set.  Any other model, or iters outside 1 .. 4096: false, nothing changed.
+  bool SetGateModel(int model, int iters = 128);
+  double gate_f() const { return gate_f_; }  // the gate's focal length of the last Solve() (0 without one)
   void SetFixedFocal() { set_fixed_focal_ = true; }  // a flag nobody reads, as in the reference (krt_optimizer.cc:502)
   int num_iter_ = 0;
 
@@ -46,6 +53,7 @@ class KRTOptimizer {
   void SetDevice(int device_id) { device_id_ = device_id; }
 
  private:
+  bool SolveGated(Mat33& K, Mat33& R, Vec3& t, Vec5& dist);
   Camera cam_curr_world_, cam_ref_;
   std::vector<float> uv_ref_, uv_cur_, pts2d_;
   std::vector<double> pts3d_;
@@ -58,7 +66,9 @@ class KRTOptimizer {
   bool trimming_ = false;
   ptz_krt_trim_options trim_{};
   ptz_krt_trim_report trim_report_{};
-  std::vector<uint8_t> kept_;  // of the last trimmed Solve(); empty without trimming
+  std::vector<uint8_t> kept_;  // of the last trimmed or gated Solve(); empty without either
+  int gate_model_ = 0, gate_iters_ = 128;
+  double gate_f_ = 0;
 };
 
 }  // namespace ptzcalib
