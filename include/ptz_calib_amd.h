@@ -42,6 +42,7 @@ extern "C" {
                                the C++ classes report it on stderr and return false. */
 #define PTZ_ENOOBS (-6)     /* ptz_ba_batch_create_views: a view none of whose tracks has a candidate observation -- no residual block, not a problem
                                (the reference's Solve returns false there, ptzray_optimizer.cc:517); every other malformed view is PTZ_EINVAL */
+#define PTZ_EINTERNAL (-7)  /* a bounded device loop reached its step cap (ptz_tracks_*): a bug in the library, reported and never waited for */
 
 /* enum FACTOR_TYPE { PTZRay, PTZRayDist, PTZRayFxfyDist, PTZRayDistDisp }  (ptzray_optimizer.h:110) */
 #define PTZ_BA_PTZRay 0
@@ -1320,6 +1321,66 @@ int32_t ptz_relocalizer_run_landmarks_shortlisted(ptz_relocalizer* r, const ptz_
                                                   int32_t n_query, const int32_t* query_wh, const ptz_reloc_options* options,
                                                   const ptz_shortlist_options* sl_opt, ptz_reloc_result* result,
                                                   ptz_shortlist_result* sl_result, ptz_landmark_view_result* view_result);
+
+/* ---- feature tracks on the device: connected components of the match table ---------------------------------------------------------
+ * The tracks the landmark map is built from, without the host: the matches of a set of images among themselves are the edges of a
+ * graph over the features, a track is a connected component that holds no image twice.  The contract is csrc/ptz_tracks.h, all
+ * integer:
+ *   node       feature `feat` of image `img` is node feat_ptr[img] + feat (image-major); fewer than 2^31 features in all (PTZ_ELIMIT)
+ *   edge       match m of pair p, match_ptr[p] <= m < match_ptr[p + 1]: (img_a[p], idx_a[m]) - (img_b[p], idx_b[m]), the layout of
+ *              ptz_desc_matches.  Duplicate edges, a pair listed twice or reversed, img_a == img_b and an edge from a node to itself
+ *              are all allowed.
+ *   label      of a matched node: the smallest node of its connected component.  Unmatched features belong to nothing.
+ *   track      a component in which no image occurs twice and that has at least min_len nodes (min_len >= 2, else PTZ_EINVAL):
+ *              what Build + Filter(min_len) + ExportFlat of host/tracks.cc keep
+ *   order      tracks in ascending label, the views of a track in ascending node, which is ascending image
+ *   outputs    trk_ptr [n_track + 1]; per view trk_img, trk_feat, trk_node, trk_uv (the set's key point of the node; zeros where
+ *              there are none); counts [4]: matched nodes, components, components dropped for a repeated image, components dropped
+ *              as short (a component with both defects counts as repeated)
+ * The result depends on the SET of edges only: not on the order of pairs or matches, on which side of a pair is a, on the launch
+ * shape or on the run.  As arrays it equals the host builder's tracks sorted by the node of their first view.
+ * ptz_tracks_build (host arrays: upload, run).  PTZ_EINVAL, before any device work: NULL out / feat_ptr, n_img < 0, feat_ptr that
+ * does not start at 0 or decreases, n_pair < 0, match_ptr that does not start at 0 or decreases, missing arrays, an image or a
+ * feature index out of range, min_len < 2, device_id < 0; PTZ_ELIMIT: 2^31 features or matches and above.
+ * ptz_tracks_from_matches: the resident form, for the table of ptz_desc_match_pairs(set, set, ...) over the pairs (img_a[p],
+ * img_b[p]) -- HOST arrays of the table's n_pair, uploaded; everything else is read where it lies (the table's device arrays, the
+ * set's offsets and key points) and nothing is downloaded but the sizes, the counts and the error word.  PTZ_EINVAL: NULL
+ * arguments, a table of another device, an image out of range, min_len < 2.
+ * ptz_tracks_build_device: raw DEVICE pointers on the device that owns d_trk_ptr, enqueued on `hip_stream`, no synchronisation
+ * inside.  d_feat_ptr [n_img + 1] and n_feat = its last entry (the host's copy); d_kp [n_feat] float2 or NULL.  Nothing on the
+ * device is validated: an edge with an image or a feature out of range is ignored.  Outputs: d_trk_ptr with room for n_feat / 2 +
+ * 2 entries; d_trk_img / d_trk_feat / d_trk_node with room for n_feat entries and d_trk_uv for 2 n_feat (or NULL); d_sizes [8]
+ * int64: n_track, n_view, the four counts, the error word (non-zero: PTZ_EINTERNAL for the caller to report), 0.  d_workspace:
+ * 256-byte aligned, at least ptz_tracks_workspace_bytes(n_feat) bytes; whatever it holds before is never read.
+ * PTZ_EINTERNAL: a walk up a parent chain or a retry loop reached its cap of n_feat steps.  Every loop of every kernel is
+ * bounded and no kernel waits for another workgroup, so a bug ends as this code.
+ * ptz_tracks_download / _device_ptrs: every pointer nullable.  ptz_tracks_device_ms: the launches, between events.
+ * ptz_landmark_map_create_from_tracks is ptz_landmark_map_create on the tracks' device (the set's), the three track arrays copied
+ * device to device instead of uploaded: the same launches, the same map.  lm_track indexes the device's track order.
+ * Known limits: tracks are rebuilt from the whole table every time; the bundle adjustment is not fed from device tracks (its
+ * observation order follows the track order). */
+typedef struct ptz_tracks ptz_tracks;
+int32_t ptz_tracks_build(int32_t n_img, const int64_t* feat_ptr, int32_t n_pair, const int32_t* img_a, const int32_t* img_b,
+                         const int64_t* match_ptr, const int32_t* idx_a, const int32_t* idx_b, int32_t min_len, int32_t device_id,
+                         ptz_tracks** out);
+int32_t ptz_tracks_from_matches(const ptz_desc_set* set, const ptz_desc_matches* matches, const int32_t* img_a, const int32_t* img_b,
+                                int32_t min_len, ptz_tracks** out);
+int64_t ptz_tracks_workspace_bytes(int64_t n_feat);
+int32_t ptz_tracks_build_device(int32_t n_img, const int64_t* d_feat_ptr, int64_t n_feat, const float* d_kp /* or NULL */, int32_t n_pair,
+                                const int32_t* d_img_a, const int32_t* d_img_b, const int64_t* d_match_ptr, int64_t n_match,
+                                const int32_t* d_idx_a, const int32_t* d_idx_b, int32_t min_len, int64_t* d_trk_ptr, int32_t* d_trk_img,
+                                int32_t* d_trk_feat, int32_t* d_trk_node, float* d_trk_uv /* or NULL */, int64_t* d_sizes,
+                                void* d_workspace, int64_t workspace_bytes, void* hip_stream);
+void ptz_tracks_destroy(ptz_tracks* t);
+int32_t ptz_tracks_n_tracks(const ptz_tracks* t);
+int64_t ptz_tracks_n_views(const ptz_tracks* t);
+int32_t ptz_tracks_counts(const ptz_tracks* t, int64_t* counts /* [4] */);
+int32_t ptz_tracks_download(const ptz_tracks* t, int64_t* trk_ptr, int32_t* trk_img, int32_t* trk_feat, int32_t* trk_node, float* trk_uv);
+int32_t ptz_tracks_device_ptrs(const ptz_tracks* t, const int64_t** d_trk_ptr, const int32_t** d_trk_img, const int32_t** d_trk_feat,
+                               const int32_t** d_trk_node, const float** d_trk_uv);
+double ptz_tracks_device_ms(const ptz_tracks* t);
+int32_t ptz_landmark_map_create_from_tracks(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, const ptz_tracks* tracks,
+                                            int32_t factor_type, int32_t min_views, ptz_landmark_map** out);
 
 #ifdef __cplusplus
 }

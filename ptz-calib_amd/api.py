@@ -18,7 +18,8 @@ BA_PTZRay, BA_PTZRayDist, BA_PTZRayFxfyDist, BA_PTZRayDistDisp = 0, 1, 2, 3
 KRT_F, KRT_FDist, KRT_Fxfy, KRT_FxfyDist = 0, 1, 2, 3
 COV_OK, COV_DOF, COV_SINGULAR, COV_SKIPPED = 0, 1, 2, 3
 PROF_SLOTS = 16
-_ERR = {-1: "PTZ_EINVAL", -2: "PTZ_ENODEVICE", -3: "PTZ_ENOMEM", -4: "PTZ_EUNSUPPORTED", -5: "PTZ_ELIMIT", -6: "PTZ_ENOOBS"}
+_ERR = {-1: "PTZ_EINVAL", -2: "PTZ_ENODEVICE", -3: "PTZ_ENOMEM", -4: "PTZ_EUNSUPPORTED", -5: "PTZ_ELIMIT", -6: "PTZ_ENOOBS",
+        -7: "PTZ_EINTERNAL"}
 
 EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_batch_create", "ptz_ba_batch_destroy",
            "ptz_ba_batch_set_state", "ptz_ba_batch_solve", "ptz_ba_batch_get_state", "ptz_ba_batch_last_solve_ms",
@@ -54,7 +55,10 @@ EXPORTS = ["ptz_lm_options_default", "ptz_version", "ptz_device_count", "ptz_ba_
            "ptz_landmark_shortlist", "ptz_landmark_shortlist_workspace_bytes", "ptz_landmark_shortlist_device", "ptz_landmark_view_from_homes",
            "ptz_landmark_view_from_homes_device", "ptz_landmark_view_kind", "ptz_relocalizer_run_landmarks_shortlisted",
            "ptz_debug_batch_reduced_system", "ptz_rotfocal_gate_create", "ptz_rotfocal_gate_destroy", "ptz_rotfocal_gate_run_device",
-           "ptz_rotfocal_gate_run", "ptz_relocalizer_gate_models", "ptz_relocalizer_set_gate_model"]
+           "ptz_rotfocal_gate_run", "ptz_relocalizer_gate_models", "ptz_relocalizer_set_gate_model", "ptz_tracks_build",
+           "ptz_tracks_from_matches", "ptz_tracks_workspace_bytes", "ptz_tracks_build_device", "ptz_tracks_destroy", "ptz_tracks_n_tracks",
+           "ptz_tracks_n_views", "ptz_tracks_counts", "ptz_tracks_download", "ptz_tracks_device_ptrs", "ptz_tracks_device_ms",
+           "ptz_landmark_map_create_from_tracks"]
 
 
 class PtzError(RuntimeError):
@@ -1623,6 +1627,23 @@ class LandmarkMap:
         self.n_landmarks = int(L.ptz_landmark_map_n_landmarks(self.handle))
         self.build_ms = float(L.ptz_landmark_map_build_ms(self.handle))
 
+    @classmethod
+    def from_tracks(cls, ref_set, ref_cams, tracks, factor_type=0, min_views=1):
+        """ptz_landmark_map_create_from_tracks: the same map from the device arrays of a Tracks of ref_set; lm_track indexes its order."""
+        self = cls.__new__(cls)
+        self.ref_cams = np.ascontiguousarray(ref_cams, dtype=np.float64).reshape(-1, 15)
+        self.device_id, self.D, self.factor_type = ref_set.device_id, ref_set.D, int(factor_type)
+        self.handle = C.c_void_p()
+        L = lib()
+        L.ptz_landmark_map_destroy.restype = None
+        L.ptz_landmark_map_build_ms.restype = C.c_double
+        L.ptz_landmark_map_desc_set.restype = C.c_void_p
+        _check(L.ptz_landmark_map_create_from_tracks(ref_set.handle, _p(self.ref_cams), len(self.ref_cams), tracks.handle, self.factor_type,
+                                                     int(min_views), C.byref(self.handle)), "ptz_landmark_map_create_from_tracks")
+        self.n_landmarks = int(L.ptz_landmark_map_n_landmarks(self.handle))
+        self.build_ms = float(L.ptz_landmark_map_build_ms(self.handle))
+        return self
+
     def arrays(self):
         """dict of numpy arrays: lm_track / lm_home / lm_views [n_lm], lm_ray [n_lm, 3], lm_desc [n_lm, D]."""
         n = self.n_landmarks
@@ -1666,6 +1687,100 @@ class LandmarkMap:
             self.close()
         except Exception:
             pass
+
+
+class Tracks:
+    """ptz_tracks: the feature tracks of a match table, resident on the device until closed (csrc/ptz_tracks.h): tracks in
+    ascending smallest node, the views of a track in ascending image."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        L = lib()
+        L.ptz_tracks_destroy.restype = None
+        L.ptz_tracks_n_views.restype = C.c_int64
+        L.ptz_tracks_device_ms.restype = C.c_double
+        self.n_tracks = int(L.ptz_tracks_n_tracks(handle))
+        self.n_views = int(L.ptz_tracks_n_views(handle))
+        self.device_ms = float(L.ptz_tracks_device_ms(handle))
+
+    def download(self):
+        """(trk_ptr [n_track + 1], trk_img, trk_feat, trk_node [n_view], trk_uv [n_view, 2])."""
+        ptr = np.zeros(self.n_tracks + 1, dtype=np.int64)
+        img, feat, node = (np.zeros(self.n_views, dtype=np.int32) for _ in range(3))
+        uv = np.zeros((self.n_views, 2), dtype=np.float32)
+        _check(lib().ptz_tracks_download(self.handle, _p(ptr), _p(img), _p(feat), _p(node), _p(uv)), "ptz_tracks_download")
+        return ptr, img, feat, node, uv
+
+    def counts(self):
+        """int64 [4]: matched nodes, components, components dropped for a repeated image, components dropped as short."""
+        c = np.zeros(4, dtype=np.int64)
+        _check(lib().ptz_tracks_counts(self.handle, _p(c)), "ptz_tracks_counts")
+        return c
+
+    def device_ptrs(self):
+        """Integer device addresses (trk_ptr, trk_img, trk_feat, trk_node, trk_uv), the tracks' until they are closed."""
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().ptz_tracks_device_ptrs(self.handle, *[C.byref(x) for x in p]), "ptz_tracks_device_ptrs")
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self.handle:
+            lib().ptz_tracks_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tracks_build(feat_ptr, img_a, img_b, match_ptr, idx_a, idx_b, min_len=2, device_id=0) -> Tracks:
+    """ptz_tracks_build: the tracks of the match table (img_a / img_b [n_pair], match_ptr [n_pair + 1], idx_a / idx_b [n_match]) over
+    the images of feat_ptr [n_img + 1], from host arrays.  An index out of range is PTZ_EINVAL."""
+    fp = np.ascontiguousarray(feat_ptr, dtype=np.int64)
+    ia, ib = np.ascontiguousarray(img_a, dtype=np.int32), np.ascontiguousarray(img_b, dtype=np.int32)
+    ptr = np.ascontiguousarray(match_ptr, dtype=np.int64)
+    xa, xb = np.ascontiguousarray(idx_a, dtype=np.int32), np.ascontiguousarray(idx_b, dtype=np.int32)
+    if len(fp) < 1 or ia.shape != ib.shape or xa.shape != xb.shape or (len(ia) and (len(ptr) != len(ia) + 1 or int(ptr[-1]) != len(xa))):
+        raise ValueError("feat_ptr, the pair lists, match_ptr and the index lists disagree on their extents")
+    h = C.c_void_p()
+    _check(lib().ptz_tracks_build(len(fp) - 1, _p(fp), len(ia), _p(ia) if len(ia) else None, _p(ib) if len(ib) else None,
+                                  _p(ptr) if len(ia) else None, _p(xa) if len(xa) else None, _p(xb) if len(xb) else None, int(min_len),
+                                  int(device_id), C.byref(h)), "ptz_tracks_build")
+    return Tracks(h)
+
+
+def tracks_from_matches(desc_set, matches, img_a, img_b, min_len=2) -> Tracks:
+    """ptz_tracks_from_matches: the tracks of a resident table (match_descriptors(set, set, img_a, img_b, resident=True)) of the set's
+    images among themselves; nothing but the sizes comes back to the host."""
+    ia, ib = np.ascontiguousarray(img_a, dtype=np.int32), np.ascontiguousarray(img_b, dtype=np.int32)
+    if ia.shape != ib.shape or ia.ndim != 1 or len(ia) != matches.n_pairs:
+        raise ValueError("img_a and img_b: the table's pair lists")
+    h = C.c_void_p()
+    _check(lib().ptz_tracks_from_matches(desc_set.handle, matches.handle, _p(ia) if len(ia) else None, _p(ib) if len(ib) else None, int(min_len),
+                                         C.byref(h)), "ptz_tracks_from_matches")
+    return Tracks(h)
+
+
+def tracks_workspace_bytes(n_feat) -> int:
+    lib().ptz_tracks_workspace_bytes.restype = C.c_int64
+    return int(lib().ptz_tracks_workspace_bytes(C.c_int64(n_feat)))
+
+
+def tracks_build_device(n_img, d_feat_ptr, n_feat, d_kp, n_pair, d_img_a, d_img_b, d_match_ptr, n_match, d_idx_a, d_idx_b, min_len, d_trk_ptr,
+                        d_trk_img, d_trk_feat, d_trk_node, d_trk_uv, d_sizes, d_workspace, workspace_bytes, stream=None):
+    """ptz_tracks_build_device: raw device buffers (torch tensors or addresses), enqueued on `stream`, nothing waited for."""
+    _check(lib().ptz_tracks_build_device(int(n_img), _dptr(d_feat_ptr), C.c_int64(n_feat), _dptr(d_kp), int(n_pair), _dptr(d_img_a), _dptr(d_img_b),
+                                         _dptr(d_match_ptr), C.c_int64(n_match), _dptr(d_idx_a), _dptr(d_idx_b), int(min_len), _dptr(d_trk_ptr),
+                                         _dptr(d_trk_img), _dptr(d_trk_feat), _dptr(d_trk_node), _dptr(d_trk_uv), _dptr(d_sizes),
+                                         _dptr(d_workspace), C.c_int64(workspace_bytes), _dptr(stream)), "ptz_tracks_build_device")
 
 
 def landmark_assemble_workspace_bytes(n_query, n_match) -> int:

@@ -35,6 +35,10 @@
 // ptz_relocalizer_run_landmarks_shortlisted: its probe features vote for the map's homes and only the landmarks of the R listed homes
 // are matched.  An image that run does not register is run once more against the whole map, so the fallback chain ends where it
 // ends without the flag.  Every record gains n_shortlist and n_visible (both 0 for an image the dense run answered).
+// --device_tracks (with --landmarks) keeps the map's tracks on the device: the references are matched among themselves by
+// ptz_desc_match_pairs on the resident reference set, ptz_tracks_from_matches turns the resident table into tracks and
+// ptz_landmark_map_create_from_tracks reads them where they lie -- no match, track or offset crosses the bus.  The landmarks are
+// those of the host route in the order of their tracks' smallest features, so the records agree to rounding, not to the bit.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -136,6 +140,8 @@ int main(int argc, char** argv)
                               "n_landmarks and n_matches");
   parser.Add("landmark_min_views", '\0', "With --landmarks: reference images a track needs to become a landmark (default 2; the tracks come from "
                                          "matches between reference images, so they have two views at least and 1 acts as 2)", false);
+  parser.AddFlag("device_tracks", "With --landmarks: build the map's tracks on the device from the resident match table of the reference "
+                                  "images (ptz_tracks_from_matches) instead of downloading it for the host TracksBuilder");
   parser.Add("landmark_prior_params", '\0', "With --landmarks: prior cameras of test images (a parameters file keyed by image name); an image "
                                             "with an entry is matched against the landmarks its prior sees only (implies --inlier_matches)", false);
   parser.AddFlag("landmark_sequence", "With --landmarks: the test images are frames in name order; a frame after a registered one is relocalized "
@@ -213,6 +219,11 @@ int main(int argc, char** argv)
   }
   if (!landmarks && parser.Exist("landmark_min_views")) {
     fprintf(stderr, "--landmark_min_views needs --landmarks\n");
+    return 1;
+  }
+  const bool device_tracks = parser.Exist("device_tracks");
+  if (!landmarks && device_tracks) {
+    fprintf(stderr, "--device_tracks needs --landmarks\n");
     return 1;
   }
   const int landmark_min_views = parser.Exist("landmark_min_views") ? atoi(parser.Get("landmark_min_views").c_str()) : 2;
@@ -408,7 +419,26 @@ int main(int argc, char** argv)
     if (ok) rc = ptz_relocalizer_create(ref_set, ref_cams.data(), n_ref, 0, &rl);
     if (ok && rc == PTZ_OK && rotfocal) rc = ptz_relocalizer_set_gate_model(rl, 1, gate_iters);  // stage 4 of every run below
     ptz_landmark_map* lmap = nullptr;
-    if (ok && rc == PTZ_OK && landmarks) {
+    if (ok && rc == PTZ_OK && landmarks && device_tracks) {
+      // the same pairs on the resident set, the table, the tracks and the map without leaving the device
+      std::vector<int32_t> ia, ib;
+      for (int32_t r = 0; r < n_ref; ++r)
+        for (int32_t s = r + 1; s < n_ref; ++s) { ia.push_back(r); ib.push_back(s); }
+      ptz_desc_options mo;
+      ptz_desc_options_default(&mo);
+      mo.ratio = ro.match.ratio;
+      mo.min_matches = ro.match.min_matches;
+      ptz_desc_matches* table = nullptr;
+      ptz_tracks* tracks = nullptr;
+      rc = ptz_desc_match_pairs(ref_set, ref_set, static_cast<int32_t>(ia.size()), ia.data(), ib.data(), &mo, &table);
+      if (rc == PTZ_OK) rc = ptz_tracks_from_matches(ref_set, table, ia.data(), ib.data(), std::max(landmark_min_views, 2), &tracks);
+      if (rc == PTZ_OK) rc = ptz_landmark_map_create_from_tracks(ref_set, ref_cams.data(), n_ref, tracks, ro.factor_type, landmark_min_views, &lmap);
+      if (rc == PTZ_OK) fprintf(stderr, "Landmark map: %d landmarks from %zu tracks of %d reference images\n", ptz_landmark_map_n_landmarks(lmap),
+                                static_cast<size_t>(ptz_tracks_n_tracks(tracks)), n_ref);
+      ptz_tracks_destroy(tracks);
+      ptz_desc_matches_destroy(table);
+    }
+    else if (ok && rc == PTZ_OK && landmarks) {
       // the references among themselves, every pair once; the tracks of those matches; one landmark per track
       DescMatchOptions mo;
       mo.ratio = ro.match.ratio;

@@ -24,6 +24,7 @@
 #include "ptz_gate_compact.h"
 #include "ptz_host_batch.h"
 #include "ptz_landmark_map.h"
+#include "ptz_tracks_obj.h"
 
 namespace ptz {
 namespace {
@@ -285,20 +286,28 @@ extern "C" void ptz_landmark_map_destroy(ptz_landmark_map* m)
   delete m;
 }
 
-extern "C" int32_t ptz_landmark_map_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t n_track,
-                                           const int64_t* trk_ptr, const int32_t* trk_img, const int32_t* trk_feat, int32_t factor_type,
-                                           int32_t min_views, int32_t device_id, ptz_landmark_map** out)
+namespace ptz {
+namespace {
+
+// The body of ptz_landmark_map_create.  The three track arrays are the caller's host arrays (kind = hipMemcpyHostToDevice, trk_ptr
+// checked here) or a ptz_tracks' device arrays on the set's device (hipMemcpyDeviceToDevice, n_view the tracks' own): the copies
+// differ, the launches do not.
+int32_t lm_map_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t n_track, int64_t n_view, const int64_t* trk_ptr,
+                      const int32_t* trk_img, const int32_t* trk_feat, hipMemcpyKind kind, int32_t factor_type, int32_t min_views,
+                      int32_t device_id, ptz_landmark_map** out)
 {
-  using namespace ptz;
   if (!out) return PTZ_EINVAL;
   *out = nullptr;
   // validation first, device second
   if (!ref_set || !ref_cams || n_ref < 1 || n_track < 0 || !trk_ptr || min_views < 1 || device_id < 0) return PTZ_EINVAL;
   if (ref_set->n_img != n_ref || ref_set->device != device_id) return PTZ_EINVAL;
-  if (trk_ptr[0] != 0) return PTZ_EINVAL;
-  for (int t = 0; t < n_track; ++t)
-    if (trk_ptr[t + 1] < trk_ptr[t]) return PTZ_EINVAL;
-  const int64_t n_view = trk_ptr[n_track];
+  if (kind == hipMemcpyHostToDevice) {
+    if (trk_ptr[0] != 0) return PTZ_EINVAL;
+    for (int t = 0; t < n_track; ++t)
+      if (trk_ptr[t + 1] < trk_ptr[t]) return PTZ_EINVAL;
+    n_view = trk_ptr[n_track];
+  }
+  if (n_view < 0) return PTZ_EINVAL;
   if (n_view > 0 && (!trk_img || !trk_feat)) return PTZ_EINVAL;
   if (ref_set->n_feat > 0 && !ref_set->d_kp) return PTZ_EINVAL;  // a set without key points has no rays
   if (!lm_known_factor(factor_type)) return PTZ_EUNSUPPORTED;
@@ -335,10 +344,10 @@ extern "C" int32_t ptz_landmark_map_create(const ptz_desc_set* ref_set, const do
   const std::vector<int32_t> ones(nc, 1);
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_cams, ref_cams, sizeof(double) * 15 * n_ref, hipMemcpyHostToDevice, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_R, R.data(), sizeof(double) * 9 * n_ref, hipMemcpyHostToDevice, h.st));
-  PTZ_HIP_TRY(hipMemcpyAsync(d + o_tptr, trk_ptr, sizeof(int64_t) * ((size_t)n_track + 1), hipMemcpyHostToDevice, h.st));
+  PTZ_HIP_TRY(hipMemcpyAsync(d + o_tptr, trk_ptr, sizeof(int64_t) * ((size_t)n_track + 1), kind, h.st));
   if (n_view > 0) {
-    PTZ_HIP_TRY(hipMemcpyAsync(d + o_timg, trk_img, sizeof(int32_t) * n_view, hipMemcpyHostToDevice, h.st));
-    PTZ_HIP_TRY(hipMemcpyAsync(d + o_tfeat, trk_feat, sizeof(int32_t) * n_view, hipMemcpyHostToDevice, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(d + o_timg, trk_img, sizeof(int32_t) * n_view, kind, h.st));
+    PTZ_HIP_TRY(hipMemcpyAsync(d + o_tfeat, trk_feat, sizeof(int32_t) * n_view, kind, h.st));
   }
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_cptr, cptr.data(), sizeof(int64_t) * (nc + 1), hipMemcpyHostToDevice, h.st));
   PTZ_HIP_TRY(hipMemcpyAsync(d + o_ones, ones.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, h.st));
@@ -388,6 +397,27 @@ extern "C" int32_t ptz_landmark_map_create(const ptz_desc_set* ref_set, const do
   if (const int32_t rc = ptz_desc_set_create(1, fp, nl ? map->desc.data() : nullptr, D, kp.data(), device_id, &map->set)) return rc;
   *out = map.release();
   return PTZ_OK;
+}
+
+}  // namespace
+}  // namespace ptz
+
+extern "C" int32_t ptz_landmark_map_create(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, int32_t n_track,
+                                           const int64_t* trk_ptr, const int32_t* trk_img, const int32_t* trk_feat, int32_t factor_type,
+                                           int32_t min_views, int32_t device_id, ptz_landmark_map** out)
+{
+  return ptz::lm_map_create(ref_set, ref_cams, n_ref, n_track, 0, trk_ptr, trk_img, trk_feat, hipMemcpyHostToDevice, factor_type, min_views, device_id,
+                            out);
+}
+
+extern "C" int32_t ptz_landmark_map_create_from_tracks(const ptz_desc_set* ref_set, const double* ref_cams, int32_t n_ref, const ptz_tracks* tracks,
+                                                       int32_t factor_type, int32_t min_views, ptz_landmark_map** out)
+{
+  if (!out) return PTZ_EINVAL;
+  *out = nullptr;
+  if (!tracks || !ref_set || tracks->device != ref_set->device || tracks->n_img != ref_set->n_img || tracks->n_feat != ref_set->n_feat) return PTZ_EINVAL;
+  return ptz::lm_map_create(ref_set, ref_cams, n_ref, tracks->n_track, tracks->n_view, tracks->d_trk_ptr, tracks->d_trk_img, tracks->d_trk_feat,
+                            hipMemcpyDeviceToDevice, factor_type, min_views, ref_set->device, out);
 }
 
 extern "C" int32_t ptz_landmark_map_n_landmarks(const ptz_landmark_map* m) { return m ? m->n_lm : 0; }
