@@ -91,7 +91,9 @@ struct ptz_ba_batch {
   int ray_block = RAY_BLOCK;
   bool schur_tg = false;         // a camera with more observations than k_schur's LDS table holds: table in global memory
   bool schur_w = false;          // PTZ_BA_SCHUR_W=1: round 2's Schur kernel over materialised W rows (kept for A/B measurements)
-  bool schur_f = false;          // PTZRay, table in LDS: k_schur_f (factored 8-double rows, three workgroups per compute unit; PTZ_BA_SCHUR_F=0: k_schur)
+  bool schur_f = false;          // PTZRay, table in LDS: k_schur_f (factored 8-double rows, four workgroups per compute unit; PTZ_BA_SCHUR_F=0: k_schur)
+  bool schur_wg4 = true;         // PTZ_BA_SCHUR_WG4=0: k_schur_f held at three workgroups per compute unit by its LDS request
+  int schur_lds_ent = 0;         // entries of the camera list the Schur kernel stages in LDS (k_schur: max_cam_ent; k_schur_f: none)
   bool gtab = false;             // camera tables too large for LDS: the GTAB instantiations read them from global memory
   int n_group_hint(int n) const { if (const char* e = getenv("PTZ_BA_STREAMS")) return std::max(1, atoi(e)); return n >= 32 ? 2 : 1; }
   int max_cam = 0, max_ray = 0, max_chunk = 0, max_pair = 0, max_n = 0, max_cam_obs = 0, max_cam_ent = 0, max_cam_pair = 0, max_cam_run = 0;
@@ -325,7 +327,11 @@ inline int fill_and_schedule(int nt, const unsigned char* mask, const int* perm,
 // threads of a k_schur workgroup = the most runs a camera's entries are cut into (ptz_ba_kernels.h schur_threads<TYPE>())
 inline int schur_threads_of(int factor_type) { (void)factor_type; return 256; }
 
-// NW: camera columns with a 2D-2D Jacobian (Dims<TYPE>::NW); max_ent: entries of the largest camera
+// LDS a k_schur_f<TYPE, false> workgroup may ask for and still be resident four times per compute unit (160 KB / 4: 561 rows at C4)
+constexpr size_t SCHUR_F_WG4_LDS = 160 * 1024 / 4;
+
+// NW: camera columns with a 2D-2D Jacobian (Dims<TYPE>::NW); max_ent: entries of the largest camera's list where the kernel
+// stages it in LDS (k_schur; 0 for k_schur_f, which reads its runs from global memory)
 inline size_t schur_lds_bytes(int max_obs, int NC, int np, bool legacy, int threads, int NW = 0, int max_ent = 0, int row = 0)
 {
   // legacy (k_schur_w): T rows of the largest camera, the reduction strip, the scene's tile order (one int per 64 columns)
@@ -336,6 +342,15 @@ inline size_t schur_lds_bytes(int max_obs, int NC, int np, bool legacy, int thre
   const size_t table = (size_t)max_obs * (row > 0 ? row : ((NW * 3 + 3) | 1)), sums = (size_t)threads * ((NW * NW) | 1);  // row > 0: k_schur_f's factored rows
   return sizeof(double) * ((size_t)(threads / 64) * (NW + NW * (NW + 1) / 2) + (size_t)(np / CHOL_NB + 2) / 2 + std::max(table, sums) + 2) +
          2 * (size_t)((max_ent + 3) & ~3);
+}
+
+// The dynamic LDS a batch's Schur launches ask for (the pass launches and the residency line of PTZ_BA_DEBUG_TIMING): the batch's
+// kernel and table home, and PTZ_BA_SCHUR_WG4=0 -- k_schur_f<TYPE, false> is resident four times per compute unit up to
+// SCHUR_F_WG4_LDS bytes, the switch asks for 1 KB more
+inline size_t schur_launch_lds(const ptz_ba_batch* b, int NC, int NW, int np, int threads)
+{
+  const size_t smem = schur_lds_bytes(b->schur_tg ? 0 : b->max_cam_obs, NC, np, b->schur_w, threads, NW, b->schur_lds_ent, b->schur_f ? SCHUR_F_ROW : 0);
+  return b->schur_f && !b->schur_tg && !b->schur_wg4 ? std::max(smem, SCHUR_F_WG4_LDS + 1024) : smem;
 }
 
 // Every host <-> device copy of a batch goes through a stream of its own and waits for THAT stream only.  hipMemcpy / hipMemset
@@ -607,8 +622,7 @@ template <int TYPE> SchurLaunch enqueue_reduced_system(ptz_ba_batch* b, const De
   hipStream_t st = b->stream;
   SchurLaunch sl;
   const int schur_thr = schur_threads<TYPE>();
-  const size_t schur_smem = schur_lds_bytes(b->schur_tg ? 0 : b->max_cam_obs, NC, d.chol.np, b->schur_w, schur_thr, Dims<TYPE>::NW, b->max_cam_ent,
-                                            b->schur_f ? SCHUR_F_ROW : 0);
+  const size_t schur_smem = schur_launch_lds(b, NC, Dims<TYPE>::NW, d.chol.np, schur_thr);
   b->prof_begin(P_RAYPREP);
   {
     const int nt = d.chol.np / CHOL_NB;
@@ -2273,24 +2287,38 @@ int32_t create_schur_limits(ptz_ba_batch* b, const CreateCtx& c)
   // (also when a view has more runs than a workgroup has threads -- more pairs than that: the several rounds k_schur then needs
   // cannot reuse the table's LDS space for their sums)
   const int NW2d = NC - ((c.has3d && type != PTZ_BA_PTZRayFxfyDist) ? 1 : 0);  // Dims<TYPE>::NW
-  b->d.schur_ent_cap = b->max_cam_ent;
-  for (auto& dgp : b->dg) dgp.schur_ent_cap = b->max_cam_ent;
-  // PTZRay: the factored rows of k_schur_f (8 doubles per observation instead of 15: three workgroups per compute unit, and
-  // the LDS table holds views of ~2000 observations); PTZ_BA_SCHUR_F=0 keeps k_schur (A/B measurements)
+  // PTZRay: the factored rows of k_schur_f (8 doubles per observation instead of 15, and no copy of the entry list: four
+  // workgroups per compute unit for views of up to ~560 observations, three beyond, and the LDS table holds views of ~2000
+  // observations); PTZ_BA_SCHUR_F=0 keeps k_schur (A/B measurements)
   b->schur_f = type == PTZ_BA_PTZRay && !b->schur_w && env_flag("PTZ_BA_SCHUR_F", true);
   const int frow = b->schur_f ? SCHUR_F_ROW : 0;
   b->d.e_fold = b->schur_f ? 1 : 0;
   for (auto& dgp : b->dg) dgp.e_fold = b->d.e_fold;
-  b->schur_tg = schur_lds_bytes(b->max_cam_obs, NC, b->d.chol.np, b->schur_w, schur_threads_of(type), NW2d, b->max_cam_ent, frow) > 160 * 1024 ||
+  // k_schur stages a camera's entry list in LDS; k_schur_f reads its runs from global memory
+  b->schur_lds_ent = b->schur_f ? 0 : b->max_cam_ent;
+  b->d.schur_ent_cap = b->schur_lds_ent;
+  for (auto& dgp : b->dg) dgp.schur_ent_cap = b->schur_lds_ent;
+  // PTZ_BA_SCHUR_WG4=0: k_schur_f's launches ask for more LDS than a quarter of a compute unit's, which holds the same binary
+  // at three workgroups per compute unit (A/B measurements: what the occupancy gives, apart from the restructured loads)
+  b->schur_wg4 = env_flag("PTZ_BA_SCHUR_WG4", true);
+  b->schur_tg = schur_lds_bytes(b->max_cam_obs, NC, b->d.chol.np, b->schur_w, schur_threads_of(type), NW2d, b->schur_lds_ent, frow) > 160 * 1024 ||
                 (!b->schur_w && b->max_cam_run > schur_threads_of(type));
   // a view with more pair entries than the LDS copy of its list holds (~60 000)
-  if (!b->schur_w && schur_lds_bytes(0, NC, b->d.chol.np, false, schur_threads_of(type), NW2d, b->max_cam_ent, frow) > 160 * 1024) return PTZ_ELIMIT;
+  if (!b->schur_w && schur_lds_bytes(0, NC, b->d.chol.np, false, schur_threads_of(type), NW2d, b->schur_lds_ent, frow) > 160 * 1024) return PTZ_ELIMIT;
   b->schur_tg = env_flag("PTZ_BA_SCHUR_GLOBAL_T", b->schur_tg);
   if (b->schur_tg) {
     PTZ_TRY(b->alloc(&b->d.Tbuf, (size_t)b->total_obs * ((NC * 3 + 3) | 1)));
     for (auto& dgp : b->dg) dgp.Tbuf = b->d.Tbuf;
   }
   if (b->shapes[0].eval_smem > 160 * 1024 || b->shapes[0].lin_smem > 160 * 1024) return PTZ_ELIMIT;
+  if (c.dbg_t && b->schur_f && !b->schur_tg) {  // PTZ_BA_DEBUG_TIMING: the residency the runtime reports for the batch's k_schur_f launches
+    const size_t smem = schur_launch_lds(b, NC, NW2d, b->d.chol.np, schur_threads_of(type));
+    int wg = 0;
+    const hipError_t e = c.has3d ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, k_schur_f<4, false>, 256, smem)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, k_schur_f<0, false>, 256, smem);
+    fprintf(stderr, "[ptz_ba] k_schur_f: %zu bytes of LDS for views of up to %d observations, %d workgroups per compute unit%s\n", smem, b->max_cam_obs,
+            wg, e == hipSuccess ? "" : " (occupancy query failed)");
+  }
   return PTZ_OK;
 }
 

@@ -1873,14 +1873,19 @@ __global__ __launch_bounds__(schur_threads<TYPE>(), schur_threads<TYPE>() == 512
 //     T'_a MR_b^T G_b = (F_i B_i)^T { Graw_a^T [P'z^-1 Q_a (Rji(0:1) - (x_b, y_b) Rji(2))^T] Graw_b } f_j F_j
 // (F = diag(1, f, f, f), B = blockdiag(1, Jl) diag(s)): the braces are what a run sums -- 8 doubles of LDS per entry (64 bytes
 // instead of 120) and about the same ~90 FP64 operations -- and everything outside them is constant over a camera pair and is
-// applied to the pair's sum in phase 3.  Table 514 x 9 doubles = 37 KB: three workgroups per compute unit.
+// applied to the pair's sum in phase 3.  Table 551 x 9 doubles = 39.7 KB: four workgroups per compute unit (see the residency note
+// at the kernel).
 // Same sums in a fixed order (bits independent of batch, launch shape, scene group: the tests that hold k_schur to that hold this
 // kernel); its blocks differ from k_schur's in the last bits (regrouped products).  PTZRay only (with or without annotations);
 // the other factor types and views beyond the LDS table keep k_schur.
 // TG: the table in global memory (d.Tbuf) for views beyond the LDS table, and several rounds of runs for views with more runs than
 // threads -- the same arithmetic in the same order (a scene keeps its bits in a batch that needs them).
+// Residency: the table in LDS (TG false) runs FOUR workgroups per compute unit -- at most 128 VGPRs (two record buffers, below) and
+// at most 40 960 bytes of LDS, which holds views of up to 561 observations now that a camera's entry list is no longer staged in
+// LDS: phase 2 reads each thread's run straight from d.ent, four entries at a time, two chunks deep (one in use, the next on its way).  Larger views get three
+// workgroups, as does PTZ_BA_SCHUR_WG4=0 (the launch then asks for more LDS than a quarter of the compute unit's).
 template <int TYPE, bool TG>
-__global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
+__global__ __launch_bounds__(256, TG ? 3 : 4) void k_schur_f(Dev d)
 {
   constexpr int THREADS = 256;
   constexpr int NC = Dims<TYPE>::NC, NW = Dims<TYPE>::NW, CBS = Dims<TYPE>::CBS;
@@ -1915,15 +1920,18 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
     return r;
   };
   auto oclamp = [&](int q) { return max(o0 + min(q, no - 1), 0); };
-  constexpr int PF = 3;
-  int gid[PF];
+  // Three trips are fetched ahead (half of C4's views have 513..551 observations) into TWO record buffers: the third trip's
+  // ray id is requested with the others, its record goes into the first buffer once trip 0 has been processed, ahead of trip
+  // 1's arithmetic.  (Three buffers are 72 VGPRs and hold the kernel at three waves per SIMD.)
+  constexpr int PF = 2, TRIPS = 3;
+  int gid[TRIPS];
   Rec rcs[PF];
 #ifdef PTZ_SCHUR_STAMPS  // (probe builds: the waits make the stamps mean "arrived"; they cost nothing the loads do not wait for anyway)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   SC_STAMP(13);
 #endif
 #pragma unroll
-  for (int t = 0; t < PF; ++t) gid[t] = d.cam_ray[oclamp((int)threadIdx.x + t * THREADS)];
+  for (int t = 0; t < TRIPS; ++t) gid[t] = d.cam_ray[oclamp((int)threadIdx.x + t * THREADS)];
 #ifdef PTZ_SCHUR_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   SC_STAMP(14);
@@ -1935,32 +1943,26 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
 #endif
   constexpr int DIAG_NE = NC * (NC + 1) / 2;
   const int dt = (int)threadIdx.x - (THREADS - 64);
-  int dp = 0, dq = 0;
-  double dv = 0, dDc = 0;
-  if (dt >= 0 && dt < DIAG_NE) {
-    dp = (int)((sqrtf(8.0f * dt + 1.0f) - 1.0f) * 0.5f);
-    while ((dp + 1) * (dp + 2) / 2 <= dt) ++dp;
-    while (dp * (dp + 1) / 2 > dt) --dp;
-    dq = dt - dp * (dp + 1) / 2;
-    dv = U_[(size_t)(s.cam_off + ci) * NC * NC + dp * NC + dq];
-    if (dp == dq) dDc = diagc_[(size_t)(s.cam_off + ci) * NC + dp];
-  }
-  else if (dt >= DIAG_NE && dt < DIAG_NE + NC) dv = gc_[(size_t)(s.cam_off + ci) * NC + (dt - DIAG_NE)];
   const int* cpair = d.cam_pair + s.cam_off + s.idx;
   const int pr0 = cpair[ci], npr = cpair[ci + 1] - pr0;
   constexpr int PS = (NW * NW) | 1;
   const int ntl = d.chol.np / CHOL_NB;
   double* strip = lds;                                         // [waves][NW + NU]
   int* tord = reinterpret_cast<int*>(strip + (THREADS / 64) * (NW + NU));
-  unsigned short* eslot = reinterpret_cast<unsigned short*>(strip + (THREADS / 64) * (NW + NU) + (ntl + 2) / 2);
   const int* crun = d.cam_run + s.cam_off + s.idx;
   const int run0 = crun[ci], nrun = crun[ci + 1] - run0;
   const uint2* runs = d.run_rec + s.run_off + run0;
-  const int* ppt = d.pair_ptr + s.pair_off + s.idx + pr0;
-  const int ent0 = npr > 0 ? ppt[0] : 0;
-  const int nent = npr > 0 ? ppt[npr] - ent0 : 0;
-  double* tab = reinterpret_cast<double*>(eslot + ((d.schur_ent_cap + 3) & ~3));  // the table [no][TS], later the run sums [THREADS][PS]
+  double* tab = strip + (THREADS / 64) * (NW + NU) + (ntl + 2) / 2;  // the table [no][TS], later the run sums [THREADS][PS]
   double* T = TG ? d.Tbuf + (size_t)o0 * TS : tab;
+  // A run's entries, read from d.ent in register chunks of EC (low 16 bits: the observation's row of the table).  Positions are
+  // clamped to the run's last entry, so a chunk never reads beyond the run, and every value it holds is a row of this camera.
+  constexpr int EC = 4;
+  auto load_chunk = [&](unsigned (&c)[EC], const uint2& run, int k0) {
+    const int last = (int)(run.y >> 16) - 1;
+#pragma unroll
+    for (int u = 0; u < EC; ++u) c[u] = d.ent[run.x + (unsigned)max(min(k0 + u, last), 0)];
+  };
+  unsigned ecur[EC] = {0u, 0u, 0u, 0u}, enxt[EC] = {0u, 0u, 0u, 0u};
   double* part = tab;
   auto scol = [&](int c) { return tord[c / CHOL_NB] * CHOL_NB + c % CHOL_NB; };
   const double* camtab = cur_camblk(d, st) + (size_t)s.cam_off * CBS;
@@ -2043,15 +2045,17 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
       Tq[6] = x; Tq[7] = y;
     };
     if ((int)threadIdx.x < nrun) rr = runs[threadIdx.x];
-    const int cjx = npr > 0 ? pcj[rr.y & 0xffffu] : 0;
+    int cjx = 0;
     SC_STAMP(8);
 #pragma unroll
-    for (int t = 0; t < PF; ++t) {
+    for (int t = 0; t < TRIPS; ++t) {
       const int q = (int)threadIdx.x + t * THREADS;
-      if (q < no) process(rcs[t], q);
+      if (q < no) process(rcs[t % PF], q);
+      if (t == PF - 1) cjx = npr > 0 ? pcj[rr.y & 0xffffu] : 0;  // the run's partner camera, once the record buffers are no longer both held
+      if (t + PF < TRIPS && no > (t + PF) * THREADS) rcs[t % PF] = load_rec(gid[t + PF]);  // (uniform) the buffer just freed takes the next trip
       SC_STAMP(9 + t);
     }
-    for (int q = (int)threadIdx.x + PF * THREADS; q < no; q += THREADS) process(load_rec(d.cam_ray[o0 + q]), q);
+    for (int q = (int)threadIdx.x + TRIPS * THREADS; q < no; q += THREADS) process(load_rec(d.cam_ray[o0 + q]), q);
     {  // Rji = R_j R_i^T of this thread's run (on its way during the reductions and the barrier below)
       const double* cbj = camtab + (size_t)cjx * CBS;
       double Rj[9];
@@ -2065,9 +2069,10 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
     int tord_v[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) { const int t = (int)threadIdx.x + u * THREADS; tord_v[u] = d.tperm ? d.tperm[(size_t)sc * ntl + min(t, ntl - 1)] : t; }
-    unsigned ent_v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) ent_v[u] = d.ent[ent0 + max(min(u * THREADS + (int)threadIdx.x, nent - 1), 0)];
+    if ((int)threadIdx.x < nrun) {  // the first two chunks of this thread's run: on their way during the reductions and the barrier
+      load_chunk(ecur, rr, 0);
+      load_chunk(enxt, rr, EC);
+    }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     constexpr int NV = NW + NU;
     constexpr int PAD = 16;
@@ -2112,19 +2117,23 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
 #pragma unroll
     for (int u = 0; u < 2; ++u) { const int t = (int)threadIdx.x + u * THREADS; if (t < ntl) tord[t] = tord_v[u]; }
     for (int t = (int)threadIdx.x + 2 * THREADS; t < ntl; t += THREADS) tord[t] = d.tperm ? d.tperm[(size_t)sc * ntl + t] : t;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int e = u * THREADS + (int)threadIdx.x; if (e < nent) eslot[e] = (unsigned short)(ent_v[u] & 0xffffu); }
-    for (int e0 = 8 * THREADS; e0 < nent; e0 += 8 * THREADS) {
-      unsigned v8[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v8[u] = d.ent[ent0 + min(e0 + u * THREADS + (int)threadIdx.x, nent - 1)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int e = e0 + u * THREADS + (int)threadIdx.x; if (e < nent) eslot[e] = (unsigned short)(v8[u] & 0xffffu); }
-    }
     SC_STAMP(12);
     __syncthreads();
   }
   SC_STAMP(1);
+  // the camera's own block and right-hand side, used at the very end: requested here, not with the gathers at the top, because
+  // the trips of phase 1 with their two record buffers are the kernel's register peak
+  int dp = 0, dq = 0;
+  double dv = 0, dDc = 0;
+  if (dt >= 0 && dt < DIAG_NE) {
+    dp = (int)((sqrtf(8.0f * dt + 1.0f) - 1.0f) * 0.5f);
+    while ((dp + 1) * (dp + 2) / 2 <= dt) ++dp;
+    while (dp * (dp + 1) / 2 > dt) --dp;
+    dq = dt - dp * (dp + 1) / 2;
+    dv = U_[(size_t)(s.cam_off + ci) * NC * NC + dp * NC + dq];
+    if (dp == dq) dDc = diagc_[(size_t)(s.cam_off + ci) * NC + dp];
+  }
+  else if (dt >= DIAG_NE && dt < DIAG_NE + NC) dv = gc_[(size_t)(s.cam_off + ci) * NC + (dt - DIAG_NE)];
   const int np = d.chol.np;
   double* A = d.chol.A + (size_t)sc * np * np;
   auto schur_diag_finish = [&]() {
@@ -2153,6 +2162,10 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
   // ---- phase 2: one run of entries per thread.  Views whose table is in LDS have at most THREADS runs: ONE round, after which
   // the table is dead and its space takes the run sums; with the table in global memory the runs may need several rounds, and a
   // pair that continues from the previous round adds to what that round stored.
+  // The run's entries come from global memory two chunks deep (one in use, enxt on its way): the table row of entry k + 1 is
+  // requested before entry k's arithmetic, with its index already in a register, and when a chunk's last entry is reached the
+  // next chunk takes its place and the one after that is requested -- four entries of arithmetic ahead of its first use.  The
+  // loop body is ONE block of arithmetic, as it was when the list was staged in LDS (the compiler contracts it the same way).
   const int* prun = d.pair_run + s.pair_off + s.idx + pr0;
   SC_STAMP(2);
   for (int base = 0; base < (TG ? nrun : min(nrun, 1)); base += THREADS) {
@@ -2171,12 +2184,18 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
         for (int rw = 0; rw < 3; ++rw)
 #pragma unroll
           for (int c = 0; c < 3; ++c) Rji[3 * rw + c] = Rj[3 * rw] * Ri[3 * c] + Rj[3 * rw + 1] * Ri[3 * c + 1] + Rj[3 * rw + 2] * Ri[3 * c + 2];
+        load_chunk(ecur, rr, 0);
+        load_chunk(enxt, rr, EC);
       }
       const int cnt = (int)(rr.y >> 16);
-      const unsigned short* es = eslot + ((int)rr.x - ent0);
+      // the chunk in use, its four rows packed into 64 bits and shifted out 16 bits per entry
+      auto pack = [](const unsigned (&c)[EC]) {
+        return (unsigned long long)((c[0] & 0xffffu) | (c[1] << 16)) | ((unsigned long long)((c[2] & 0xffffu) | (c[3] << 16)) << 32);
+      };
+      unsigned long long rows = pack(ecur);
       double Tn[8];
       {
-        const double* Ta = T + (size_t)es[0] * TS;
+        const double* Ta = T + (size_t)((unsigned)rows & 0xffffu) * TS;
 #pragma unroll
         for (int k = 0; k < 8; ++k) Tn[k] = Ta[k];
       }
@@ -2184,8 +2203,16 @@ __global__ __launch_bounds__(256, 3) void k_schur_f(Dev d)
         double Tc[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) Tc[i] = Tn[i];
+        // The row requested next is entry k + 1's while the run lasts.  Behind the run's last entry the request is never used and
+        // names SOME row of this camera: the last entry again inside a chunk (chunks are clamped), an entry of an earlier chunk
+        // when the run ends on a chunk's edge (enxt was not reloaded).  Every value a chunk ever held is a row of this camera.
+        rows >>= 16;
+        if ((k & (EC - 1)) == EC - 1) {  // (the same k in every lane still in the loop) the chunk is used up: the next one arrived entries ago; request the one after it
+          rows = pack(enxt);
+          if (k + 1 + EC < cnt) load_chunk(enxt, rr, k + 1 + EC);
+        }
         {
-          const double* Ta = T + (size_t)es[min(k + 1, cnt - 1)] * TS;
+          const double* Ta = T + (size_t)((unsigned)rows & 0xffffu) * TS;
 #pragma unroll
           for (int i = 0; i < 8; ++i) Tn[i] = Ta[i];
         }
